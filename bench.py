@@ -2,7 +2,18 @@
 """bench.py -- featuremetric residual+Jacobian throughput on the synthetic 1M-observation BA
 problem (BASELINE.json config 3: 200 cams / 200k points / 1M obs, 128-ch fp16 16x16 patches).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: it builds the scene, settles the clocks, runs the W warm-up steps, times the K steps,
+writes the last step's records if --dump-outputs is given, and prints the line.  --full adds everything else this script
+measures after the headline (clocks / power, k_jac, the Gram-matrix evaluation, LM iterations/s and the 8-GPU model, cost maps,
+the CPU baselines, keypoint adjustment, the drop-in API calls, the per-rank table) and writes bench_detail.json.
+
+--dump-outputs DIR: after the timed steps, the records of the last step (the n_obs x 8 float64 array pxr_ba_eval hands its
+caller, include/pixsfm_hip.h) go to DIR as .npy files: a fixed, seeded sample of 2^18 rows (`records_sample.npy`) with its
+row indices (`records_sample_index.npy`) and the column sums over every row (`records_column_sum.npy`), all float64.  The
+scene is seeded, so the same arguments give the same inputs in every run.  With several ranks each rank writes its own
+shard's files, suffixed `.rank<r>`.
 
 A "step" = one fused residual+Jacobian evaluation (pxr_ba_eval, with_jacobian=1) of every
 observation owned by the rank: projection, bicubic interpolation of the patch stencil,
@@ -21,7 +32,7 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set -- re-p
 exits non-zero if any rank failed (the others are stopped: a rank left alone in a collective would hang).
 
 Rank 0 prints ONE JSON line; see DESIGN.md section "Measurement" for the roofline and
-cpu_baseline definitions.  Besides the contract's fields it carries `lm` / `lm_no_inner` (LM iterations/s
+cpu_baseline definitions.  With --full it carries, besides the contract's fields, `lm` / `lm_no_inner` (LM iterations/s
 on the same problem), `ka` (BASELINE configs[1]) and `costmap` (the reference's low-memory strategy on the
 same scene: cost-map extraction + cost-map BA).
 """
@@ -318,7 +329,14 @@ def parse_args(argv=None):
     ap.add_argument("--watchdog-s", type=float, default=float(os.environ.get("PXR_BENCH_WATCHDOG_S", "420")),
                     help="several ranks only: if the legs after the headline measurement (LM, KA) do not finish within this many seconds "
                          "-- a collective that never returns -- rank 0 prints the line with what it has and every rank exits 0; 0 disables")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg (telemetry, k_jac, Gram-matrix evaluation, LM, scaling model, cost maps, "
+                         "CPU baselines, KA, drop-in API calls) and write --detail-out; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records to DIR as .npy (a seeded sample of rows, their indices, column sums)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.preset == "aachen":
         args.cams, args.points, args.obs_per_point, args.patch_size = 4000, 1_000_000, 5, 8
         args.no_ka = args.no_api_e2e = args.no_cpu_baseline = True
@@ -825,7 +843,8 @@ def compact_line(full):
         out["gpu_over_cpu"] = _r(full["value"] / cb["value"], 4) if cb.get("value") else None
     if "like_for_like" in full:
         out["like_for_like"] = full["like_for_like"]
-    out["initial_cost"] = _r(full.get("initial_cost"), 10)
+    if full.get("initial_cost") is not None:
+        out["initial_cost"] = _r(full["initial_cost"], 10)
     if "collective" in full:
         out["collective"] = full["collective"][:60]
     if "ranks" in full:
@@ -870,7 +889,8 @@ def compact_line(full):
                 ph = ae[k].get("phases_s", {})
                 top = sorted(ph.items(), key=lambda kv: -kv[1])[:4]
                 out["api_e2e"][k] = {"wall_s": _r(ae[k].get("wall_s"), 4), "phases_s": {a: _r(b, 3) for a, b in top}}
-    out["detail"] = full.get("detail_file")
+    if full.get("detail_file") is not None:
+        out["detail"] = full["detail_file"]
     if "watchdog" in full:
         out["watchdog"] = full["watchdog"]
     # ---- the tail: clocks, then both LM figures (metric 2) ----
@@ -917,6 +937,29 @@ def write_detail(full, path):
     except OSError as e:
         print("bench.py: could not write %s (%r)" % (path, e), file=sys.stderr)
         return None
+
+
+DUMP_SAMPLE_ROWS = 1 << 18          # 2^18 records x 64 B = 16.8 MB: the dump stays far below 64 MB at any scene size
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(job, ba, out_dir):
+    """--dump-outputs: what the timed path handed its caller in the last step -- the n_obs x 8 float64 records of pxr_ba_eval
+    (still in ba.rec: nothing runs on it after the timed loop) -- as a fixed, seeded sample of rows, their indices, and the column
+    sums over all rows.  Every rank writes its own shard's files (suffix .rank<r> when there are several)."""
+    import numpy as np
+    job.ctx.sync()
+    rec = ba.rec.download()
+    n = rec.shape[0]
+    if n > DUMP_SAMPLE_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_ROWS, replace=False))
+    else:
+        idx = np.arange(n)
+    suffix = ".rank%d" % job.rank if job.world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("records_sample", rec[idx]), ("records_sample_index", idx.astype(np.float64)),
+                      ("records_column_sum", rec.sum(axis=0))):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def make_scene(job):
@@ -1129,6 +1172,15 @@ def main():
 
     dt, kernel_ms = run_eval(job, ba, cfg)
     n_obs_total = int(job.reduce(float(n_obs_local)))
+    if args.dump_outputs:
+        dump_outputs(job, ba, args.dump_outputs)
+    if not args.full:
+        result_line = None
+        if rank == 0:
+            line = compact_line(headline(job, args, dt, kernel_ms, n_obs_total, n_obs_local, total_points, None, None))
+            result_line = json.dumps(line, separators=(",", ":"))
+        finish(job, result_line)
+        return
     per_rank = gather_ranks(job, n_obs_local, kernel_ms)
     cost = job.reduce(ba.cost(make_loss("cauchy", [0.25])))         # cost of the whole (sharded) problem
     per_rank_now = per_rank
@@ -1205,9 +1257,13 @@ def main():
                 result_line = json.dumps(line, separators=(",", ":"))
                 if len(result_line) <= LINE_BUDGET_BYTES:
                     break
-    # The JSON line must be the last thing on stdout: native libraries (RCCL's version banner, ...) write to the C
-    # stdio buffer of every rank, which would otherwise be flushed at exit -- after the line.  Flush it now, wait for
-    # all ranks, tear the process group down, then print.
+    finish(job, result_line)
+
+
+def finish(job, result_line):
+    """The JSON line must be the last thing on stdout: native libraries (RCCL's version banner, ...) write to the C
+    stdio buffer of every rank, which would otherwise be flushed at exit -- after the line.  Flush it now, wait for
+    all ranks, tear the process group down, then print."""
     import ctypes
     libc = ctypes.CDLL(None)
     libc.fflush(None)

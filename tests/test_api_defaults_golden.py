@@ -38,18 +38,6 @@ def test_default_configurations_equal_the_reference():
     assert not problems, "\n".join(problems)
 
 
-def test_reference_defaults_live_when_present():
-    import importlib.util
-    import pytest
-    if not os.path.isdir("/root/reference/pixsfm"):
-        pytest.skip("reference tree absent")
-    spec = importlib.util.spec_from_file_location("make_golden_defaults", os.path.join(HERE, "golden", "make_golden_defaults.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    live = json.loads(json.dumps(m.collect(), default=str, sort_keys=True))
-    assert live == json.load(open(os.path.join(HERE, "golden", "default_conf_ref.json")))
-
-
 def test_option_structs_default_like_the_cxx_structs():
     """The optimizer / extractor classes stand for the reference's C++ option structs (constructed from a possibly PARTIAL dict
     by make_dataclass): a key the caller leaves out takes the STRUCT's default, which differs from the Python-level default_conf

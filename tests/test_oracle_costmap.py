@@ -2,36 +2,40 @@
 
 The reference has no test or golden vector for CostMapExtractor, so:
   * the two storage-type rounding rules the extraction leans on are pinned bit-exactly against the reference's
-    OWN vendored half.hpp compiled from its own source (oracle/ref_half_shim.cc -> oracle/_ref/libpxo_ref_half.so): half - half, and dtype(double) of SetEntry;
+    OWN vendored half.hpp compiled from its own source (oracle/ref_half_shim.cc -> oracle/_ref/libpxo_ref_half.so; where that is not
+    built, its outputs for the same inputs, tests/golden/half_ref_outputs.npz): half - half, and dtype(double) of SetEntry;
   * the vectorised restatement is checked against an independent per-texel loop that follows
     costmap_extractor.h:242-357 statement by statement;
   * the 3-channel, reference-free residual block (costmap_bundle_optimizer.h:104-119) is checked by finite differences.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import half_ref
 import pxo
 import pxo_costmap
 
 
-def _ref():
-    r = pxo.ref()
-    if r is None or not hasattr(r, "pxo_ref_half_sub"):
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
-    return r
-
-
-def test_half_subtraction_rule_matches_reference_half_hpp():
-    r = _ref()
+def half_sub_inputs():
     rng = np.random.default_rng(1)
     n = 300000
     a = (rng.normal(size=n) * 10.0 ** rng.uniform(-7, 4, n)).astype(np.float16)
     b = (rng.normal(size=n) * 10.0 ** rng.uniform(-7, 4, n)).astype(np.float16)
     b[:1000] = a[:1000]                                    # exact cancellation
-    out = np.empty_like(a)
-    r.pxo_ref_half_sub(a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.c_int64(n))
+    return a, b
+
+
+def half_from_double_inputs():
+    rng = np.random.default_rng(2)
+    v = rng.normal(size=400000) * 10.0 ** rng.uniform(-9, 4, 400000)
+    h = rng.normal(size=2000).astype(np.float16)
+    ties = h.astype(np.float64) + np.spacing(h).astype(np.float64) / 2       # exact half-way points and their neighbours
+    return (np.concatenate([v, ties, ties * (1 + 2e-16), ties * (1 - 2e-16), ties * (1 + 1e-9)]),)
+
+
+def test_half_subtraction_rule_matches_reference_half_hpp():
+    a, b = half_sub_inputs()
+    out = half_ref.run("sub", (a, b), np.float16)          # half.hpp: live (oracle/_ref) or its stored output (tests/half_ref.py)
     mine = pxo_costmap.storage_diff(a, b)
     same = (out.view(np.uint16) == mine.view(np.uint16)) | ((out == 0) & (mine == 0))
     assert same.all()
@@ -40,14 +44,8 @@ def test_half_subtraction_rule_matches_reference_half_hpp():
 def test_set_entry_cast_rule_matches_reference_half_hpp():
     """dtype(value) for half goes through float (half.hpp has no constructor from double): two roundings.  A single
     correct rounding (numpy's float64 -> float16) differs on ~3e-5 of random inputs -- the test would catch it."""
-    r = _ref()
-    rng = np.random.default_rng(2)
-    v = rng.normal(size=400000) * 10.0 ** rng.uniform(-9, 4, 400000)
-    h = rng.normal(size=2000).astype(np.float16)
-    ties = h.astype(np.float64) + np.spacing(h).astype(np.float64) / 2       # exact half-way points and their neighbours
-    v = np.concatenate([v, ties, ties * (1 + 2e-16), ties * (1 - 2e-16), ties * (1 + 1e-9)])
-    out = np.empty(v.size, np.uint16)
-    r.pxo_ref_half_from_double(v.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.c_int64(v.size))
+    (v,) = half_from_double_inputs()
+    out = half_ref.run("from_double", (v,), np.uint16)
     assert np.array_equal(out, pxo_costmap.store(v, np.float16).view(np.uint16))
     assert (out != v.astype(np.float16).view(np.uint16)).any()
 

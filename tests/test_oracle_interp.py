@@ -120,13 +120,9 @@ def test_half_widening_matches_the_references_half_hpp():
     from its own source, oracle/ref_half_shim.cc) and by the oracle's pxo_half_to_float (what the interpolation reads fp16
     texels through; the reference's SIMD path uses F16C's _mm256_cvtph_ps, cubic_hermite_spline_simd.h:51-54, which is the
     same IEEE widening)."""
-    import ctypes as C
-    r = pxo.ref()
-    if r is None:
-        pytest.skip("oracle/_ref/libpxo_ref_half.so not built (needs /root/reference at build time)")
+    import half_ref
     bits = np.arange(65536, dtype=np.uint16)
-    want = np.empty(65536, np.float32)
-    r.pxo_ref_half_to_float(bits.ctypes.data_as(C.c_void_p), want.ctypes.data_as(C.c_void_p), C.c_int64(65536))
+    want = half_ref.run("to_float", (bits,), np.float32)      # live (oracle/_ref) or its stored output (tests/half_ref.py)
     got = np.array([pxo.lib().pxo_half_to_float(int(b)) for b in bits], dtype=np.float32)
     nan = np.isnan(want)
     assert np.array_equal(got[~nan].view(np.uint32), want[~nan].view(np.uint32)) and np.isnan(got[nan]).all()

@@ -1,8 +1,11 @@
 """CPU: the pybind surface of the reference's module (pixsfm/*/bindings.cc) against the `_pixsfm`-shaped package.
-  * live, when /root/reference is present: every class / function / attribute name the bindings define at module level exists
-    in the matching sub-module, and every method / property bound on a class exists on an instance of the stand-in;
+  * every class / function / attribute name the bindings define at module level exists in the matching sub-module, and every
+    method / property bound on a class exists on an instance of the stand-in -- the names as parsed from the bindings, stored in
+    tests/golden/shim_bindings_ref.json (tests/golden/make_golden_bindings.py); parsed live, and held to that file, where the
+    reference tree is present;
   * always: the semantics of the container helpers that are plain host code (FeaturePatch.to_corner / slice / get_entry,
     FeatureMap.shape, Graph.add_node / degrees / scores / edges, ...), restated from the sources cited in the classes."""
+import json
 import os
 import re
 
@@ -39,33 +42,59 @@ def _instances():
             "QueryBundleOptimizer": loc.QueryBundleOptimizer({}, None)}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree absent")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shim_bindings_ref.json")
+BINDERS = {"KeypointOptimizer": ["FeatureMetricKeypointOptimizer"], "ParallelSolve": ["FeatureMetricKeypointOptimizer"],
+           "BundleOptimizer": ["FeatureReferenceBundleOptimizer", "CostMapBundleOptimizer"],
+           "SingleQueryKeypointOptimizer": ["QueryKeypointOptimizer"], "SingleQueryBundleOptimizer": ["QueryBundleOptimizer"]}
+
+
+def bound_names(src):
+    """What one bindings.cc binds: module-level names; methods / properties per class named by a literal, per template-bound
+    container class ("Name" + type_suffix), and per optimizer binder function (void BindX(...) { ... })."""
+    src = re.sub(r"//[^\n]*", "", src)          # bindings that are commented out do not count
+    names = set(re.findall(r'py::(?:class|enum)_<[^;]*?>\(\s*\w+\s*,\s*\(?\s*"([A-Za-z_0-9]+)"', src, re.S))
+    names |= set(re.findall(r'\bm\.def\(\s*"([A-Za-z_0-9]+)"', src)) | set(re.findall(r'\bm\.attr\(\s*"([A-Za-z_0-9]+)"', src))
+    out = {"names": sorted(names), "classes": {}, "templated": {}, "binders": {}}
+    for m in re.finditer(r'py::class_<[^;]*?>\(\s*\w+\s*,\s*\(?\s*"([A-Za-z_0-9]+)"([^;]*);', src, re.S):
+        out["classes"].setdefault(m.group(1), set()).update(re.findall(DEF, m.group(2)))
+    for m in re.finditer(r'py::class_<[^;]*?>\(\s*m\s*,\s*\(\s*"([A-Za-z]+)"\s*\+\s*type_suffix\)[^;]*?\)([^;]*);', src, re.S):
+        out["templated"].setdefault(m.group(1), set()).update(re.findall(DEF, m.group(2)))
+    for m in re.finditer(r'void Bind(%s)\([^)]*\)\s*\{(.*?)\n\}' % "|".join(BINDERS), src, re.S):
+        out["binders"].setdefault(m.group(1), set()).update(re.findall(DEF, m.group(2)))
+    for k in ("classes", "templated", "binders"):
+        out[k] = {a: sorted(b) for a, b in sorted(out[k].items())}
+    return out
+
+
+def reference_bindings():
+    """{sub-module: bound_names(its bindings.cc)}: parsed live where the reference tree is present (and then equal to the stored
+    file), else the stored file."""
+    with open(GOLDEN) as fh:
+        stored = json.load(fh)
+    if os.path.isdir(REF):
+        live = {mod_name: bound_names(open(os.path.join(REF, rel)).read()) for mod_name, rel in BINDINGS.items()}
+        assert live == stored, "tests/golden/shim_bindings_ref.json is out of date (tests/golden/make_golden_bindings.py)"
+    return stored
+
+
 def test_every_bound_name_exists_in_the_shim():
     import importlib
     inst = _instances()
     problems = []
-    for mod_name, rel in BINDINGS.items():
-        src = re.sub(r"//[^\n]*", "", open(os.path.join(REF, rel)).read())          # bindings that are commented out do not count
+    for mod_name, b in reference_bindings().items():
         mod = importlib.import_module("pixsfm_amd._pixsfm." + mod_name)
-        names = set(re.findall(r'py::(?:class|enum)_<[^;]*?>\(\s*\w+\s*,\s*\(?\s*"([A-Za-z_0-9]+)"', src, re.S))
-        names |= set(re.findall(r'\bm\.def\(\s*"([A-Za-z_0-9]+)"', src)) | set(re.findall(r'\bm\.attr\(\s*"([A-Za-z_0-9]+)"', src))
-        problems += ["%s.%s" % (mod_name, n) for n in sorted(names) if not hasattr(mod, n)]
+        problems += ["%s.%s" % (mod_name, n) for n in b["names"] if not hasattr(mod, n)]
         # methods / properties: classes named by a literal, and the template binders of the feature containers and optimizers
-        for m in re.finditer(r'py::class_<[^;]*?>\(\s*\w+\s*,\s*\(?\s*"([A-Za-z_0-9]+)"([^;]*);', src, re.S):
-            if m.group(1) in inst:
-                problems += ["%s.%s.%s" % (mod_name, m.group(1), d) for d in sorted(set(re.findall(DEF, m.group(2))))
-                             if not d.startswith("__") and d not in NOT_OFFERED and not hasattr(inst[m.group(1)], d)]
-        for m in re.finditer(r'py::class_<[^;]*?>\(\s*m\s*,\s*\(\s*"([A-Za-z]+)"\s*\+\s*type_suffix\)[^;]*?\)([^;]*);', src, re.S):
-            if m.group(1) in inst:
-                problems += ["%s.%s.%s" % (mod_name, m.group(1), d) for d in sorted(set(re.findall(DEF, m.group(2))))
-                             if not d.startswith("__") and not hasattr(inst[m.group(1)], d)]
-        for m in re.finditer(r'void Bind(KeypointOptimizer|ParallelSolve|BundleOptimizer|SingleQueryKeypointOptimizer|SingleQueryBundleOptimizer)\([^)]*\)\s*\{(.*?)\n\}', src, re.S):
-            targets = {"KeypointOptimizer": ["FeatureMetricKeypointOptimizer"], "ParallelSolve": ["FeatureMetricKeypointOptimizer"],
-                       "BundleOptimizer": ["FeatureReferenceBundleOptimizer", "CostMapBundleOptimizer"],
-                       "SingleQueryKeypointOptimizer": ["QueryKeypointOptimizer"], "SingleQueryBundleOptimizer": ["QueryBundleOptimizer"]}[m.group(1)]
-            for t in targets:
-                problems += ["%s.%s.%s" % (mod_name, t, d) for d in sorted(set(re.findall(DEF, m.group(2))))
-                             if d not in NOT_OFFERED and not hasattr(inst[t], d)]
+        for cls, defs in b["classes"].items():
+            if cls in inst:
+                problems += ["%s.%s.%s" % (mod_name, cls, d) for d in defs
+                             if not d.startswith("__") and d not in NOT_OFFERED and not hasattr(inst[cls], d)]
+        for cls, defs in b["templated"].items():
+            if cls in inst:
+                problems += ["%s.%s.%s" % (mod_name, cls, d) for d in defs if not d.startswith("__") and not hasattr(inst[cls], d)]
+        for binder, defs in b["binders"].items():
+            for t in BINDERS[binder]:
+                problems += ["%s.%s.%s" % (mod_name, t, d) for d in defs if d not in NOT_OFFERED and not hasattr(inst[t], d)]
     assert not problems, "\n".join(problems)
 
 

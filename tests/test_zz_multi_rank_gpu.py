@@ -245,7 +245,7 @@ def _bench(n_gpus, extra_env=None, timeout=900):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env or {})
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n_gpus), "--steps", "3", "--warmup", "1", "--cams", "24",
-           "--points", "6000", "--lm-iters", "6", "--no-ka", "--no-costmap", "--no-cpu-baseline", "--no-api-e2e", "--no-telemetry"]
+           "--points", "6000", "--lm-iters", "6", "--full", "--no-ka", "--no-costmap", "--no-cpu-baseline", "--no-api-e2e", "--no-telemetry"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]

@@ -11,7 +11,7 @@ for mode in ("gram", "packed"):
     env = dict(os.environ)
     if mode == "packed":
         env["PXR_INNER_PACKED"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--points", pts, "--steps", "3", "--warmup", "1", "--no-ka", "--no-costmap",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--points", pts, "--steps", "3", "--warmup", "1", "--full", "--no-ka", "--no-costmap",
                         "--no-cpu-baseline", "--no-api-e2e", "--no-telemetry"], env=env, capture_output=True, text=True)
     if p.returncode != 0:
         print(mode, "FAILED", p.stderr[-2000:])

@@ -2,7 +2,7 @@
 # Builds csrc/pxr_ka.hip with -DPXR_KA_PROFILE into tools/debug/libpixsfm_hip_kaprof.so (the other objects are those of the
 # regular build): one workgroup of pxr_ka_solve (argument: its sub-problem index, default 0) prints how its wall time splits over the
 # phases of the LM loop, when it started and how long it ran.
-#   tools/ka_phase_probe.sh && PXR_HIP_LIB=tools/debug/libpixsfm_hip_kaprof.so python bench.py --no-cpu-baseline --no-costmap --lm-iters 0
+#   tools/ka_phase_probe.sh && PXR_HIP_LIB=tools/debug/libpixsfm_hip_kaprof.so python bench.py --full --no-cpu-baseline --no-costmap --lm-iters 0
 set -e
 cd "$(dirname "$0")/../pixel-perfect-sfm_amd/csrc"
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -I. -munsafe-fp-atomics -mllvm -amdgpu-spill-vgpr-to-agpr=0"

@@ -8,7 +8,7 @@ COMMIT=${2:-unknown}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-CMD="python $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-api-e2e --no-costmap --no-telemetry --no-ka-points"
+CMD="python $ROOT/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-api-e2e --no-costmap --no-telemetry --no-ka-points"
 CS=$ROOT/pixel-perfect-sfm_amd/csrc
 KERNELS="ba_eval_kernel ka_solve_kernel k_schur_lds k_inner_gram k_gram_build k_gram_eval k_jac k_img k_point k_chol_step"
 pass() {   # name, counters...

@@ -22,7 +22,7 @@ for path in sorted(glob.glob(os.path.join(src, "*_*.json"))):
         k["dispatches"][ps] = d.get("dispatches")
         k["mean"].update(d.get("mean", {}))
 json.dump({"measured_at_commit": commit,
-           "command": "rocprofv3 --pmc <one group per pass> --kernel-trace --output-format csv -- python bench.py --steps 5 --warmup 1 "
+           "command": "rocprofv3 --pmc <one group per pass> --kernel-trace --output-format csv -- python bench.py --steps 5 --warmup 1 --full "
                       "--no-cpu-baseline --no-api-e2e --no-costmap --no-telemetry  (tools/pmc_collect.sh; passes: FETCH_SIZE | WRITE_SIZE | "
                       "eight SQ counters | LDS / VMEM / SALU / TCC counters)",
            "note": "means per dispatch; FETCH_SIZE / WRITE_SIZE in KB as reported (gfx950: a wide coalesced read is tallied at half its "
