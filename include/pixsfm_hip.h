@@ -39,7 +39,7 @@ extern "C" {
 
 enum { PXR_OK = 0, PXR_EINVAL = -1, PXR_EHIP = -2, PXR_ENOMEM = -3, PXR_EUNSUPPORTED = -4,
        PXR_ENUMERIC = -5 };
-enum { PXR_F16 = 0, PXR_F32 = 1, PXR_F64 = 2 };
+enum { PXR_F16 = 0, PXR_F32 = 1, PXR_F64 = 2, PXR_U8 = 3 /* grey images (pxr_dsift_*) */ };
 /* COLMAP 3.8 camera model ids (CAMERA_MODEL_SWITCH_CASES, residuals/src/feature_reference.h:232) */
 enum { PXR_SIMPLE_PINHOLE = 0, PXR_PINHOLE = 1, PXR_SIMPLE_RADIAL = 2, PXR_RADIAL = 3,
        PXR_OPENCV = 4, PXR_OPENCV_FISHEYE = 5, PXR_FULL_OPENCV = 6, PXR_FOV = 7,
@@ -123,6 +123,23 @@ int pxr_arena_upload_gather(pxr_arena* a, int64_t first, int64_t count, const vo
  * ps) with their corners and scales; asynchronous on the context's stream. */
 int pxr_arena_extract(pxr_ctx* ctx, pxr_arena* a, int64_t first, int64_t n, const void* d_fmap,
                       int src_dtype, int h, int w, const double* d_keypoints, double image_w,
+                      double image_h, int l2_normalize);
+/* Dense SIFT, the reference's weight-free `dsift` model (pixsfm/features/models/dsift.py, pixsfm/configs/dsift.yaml):
+ * kornia >= 0.6.4 DenseSIFTDescriptor(num_ang_bins=8, num_spatial_bins=4, spatial_bin_size, rootsift, clipval, stride=1,
+ * padding=1) on the grey image (PIL convert("L"), to_tensor).  Definition restated in DESIGN.md §16.
+ * d_image: the grey image on the device, row-major h x w, image_dtype PXR_U8 (value / 255, as to_tensor) or PXR_F32.
+ * spatial_bin_size: even, 2 .. 8 (other values: PXR_EUNSUPPORTED); 128 channels (8 angle x 4 x 4 spatial bins).
+ * pxr_dsift_dense writes the model's output, d_out [128][h][w] fp32 (torch layout); asynchronous on the context's stream. */
+int pxr_dsift_dense(pxr_ctx* ctx, const void* d_image, int image_dtype, int h, int w, int spatial_bin_size, int rootsift,
+                    double clipval, float* d_out);
+/* The fused sparse producer: pxr_arena_extract (FeatureExtractor.tensor_to_fmap sparse branch, extractor.py:152-199) of the
+ * dense SIFT map of d_image, computed only on the patch windows.  The map is the image itself (h x w), so scale =
+ * (w / image_w, h / image_h) with (image_w, image_h) the ORIGINAL image size; corners, l2_normalize and the cast as in
+ * pxr_arena_extract; the arena must have C = 128 (else PXR_EUNSUPPORTED) and square patches of side ps <= 16 with
+ * h, w > ps.  Fills patches [first, first + n) bit-identical to pxr_dsift_dense followed by pxr_arena_extract;
+ * asynchronous on the context's stream. */
+int pxr_dsift_extract(pxr_ctx* ctx, pxr_arena* a, int64_t first, int64_t n, const void* d_image, int image_dtype, int h,
+                      int w, int spatial_bin_size, int rootsift, double clipval, const double* d_keypoints, double image_w,
                       double image_h, int l2_normalize);
 void* pxr_arena_data(pxr_arena* a);     /* device pointer of patch 0 */
 int32_t* pxr_arena_corners(pxr_arena* a); /* device int32[n][2] */

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("PXR_HIP_LIB") or os.path.join(HERE, "libpixsfm_hip.so
 KPAD = 12
 OBS_REC = 8
 F16, F32, F64 = 0, 1, 2
+U8 = 3            # grey images of the dense-SIFT producer (pxr_dsift_*)
 CAMERA_MODEL_IDS = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4, "OPENCV_FISHEYE": 5,
                     "FULL_OPENCV": 6, "FOV": 7, "SIMPLE_RADIAL_FISHEYE": 8, "RADIAL_FISHEYE": 9, "THIN_PRISM_FISHEYE": 10}
 LOSS_IDS = {"trivial": 0, "cauchy": 1, "huber": 2, "soft_l1": 3}
@@ -96,6 +97,9 @@ _SIGNATURES = {
     "pxr_arena_upload_gather": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pxr_arena_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "pxr_dsift_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "pxr_dsift_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_int]),
     "pxr_arena_data": (C.c_void_p, [C.c_void_p]),
     "pxr_arena_corners": (C.c_void_p, [C.c_void_p]),
     "pxr_arena_scales": (C.c_void_p, [C.c_void_p]),

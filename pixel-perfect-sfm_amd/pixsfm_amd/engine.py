@@ -281,6 +281,27 @@ class PatchArena:
         self.ctx.sync()          # the temporary keypoint upload may be released after this
         return n
 
+    def extract_dsift(self, first, grey, keypoints, image_size, spatial_bin_size=4, rootsift=True, clipval=0.2,
+                      l2_normalize=True):
+        """Fill patches [first, first + len(keypoints)) with dense SIFT descriptors of ONE grey image (the reference's `dsift`
+        model, pixsfm/features/models/dsift.py, followed by FeatureExtractor.tensor_to_fmap's sparse branch,
+        extractor.py:152-199) computed only on the patch windows (pxr_dsift_extract): the dense map is never formed.
+        grey: (h, w) uint8 (value / 255) or float32 image, a torch.cuda tensor / __cuda_array_interface__ object or a host
+        array (uploaded).  keypoints: (n, 2) COLMAP coordinates in the ORIGINAL image; image_size: its (width, height).
+        The arena needs C = 128.  Bit-identical to dsift_dense() followed by extract()."""
+        img = _grey_on_device(self.ctx, grey)
+        if isinstance(keypoints, DeviceArray):
+            d_kp, n = keypoints, keypoints.shape[0]
+        else:
+            kp = np.ascontiguousarray(keypoints, dtype=np.float64).reshape(-1, 2)
+            d_kp, n = self.ctx.to_device(kp, np.float64), len(kp)
+        check(self.ctx.lib.pxr_dsift_extract(self.ctx.handle, self.handle, int(first), int(n), img.ptr, img.dtype, img.h, img.w,
+                                             int(spatial_bin_size), int(bool(rootsift)), float(clipval), d_kp.ptr,
+                                             float(image_size[0]), float(image_size[1]), int(bool(l2_normalize))),
+              "pxr_dsift_extract")
+        self.ctx.sync()          # the temporary uploads may be released after this
+        return n
+
     def download(self, first=0, count=None):
         """(patches, corners, scales) of a range of the arena as numpy arrays (tests / debugging)."""
         count = self.n - first if count is None else count
@@ -319,6 +340,67 @@ class PatchArena:
             self.close()
         except Exception:
             pass
+
+
+class _Grey:
+    """A grey image on the device: pointer, pxr dtype, size (+ whatever keeps the memory alive)."""
+
+    def __init__(self, ptr, dtype, h, w, keep):
+        self.ptr, self.dtype, self.h, self.w, self.keep = C.c_void_p(ptr), dtype, int(h), int(w), keep
+
+
+def _grey_on_device(ctx, grey):
+    """(h, w) or (1, 1, h, w) uint8 / float32 grey image -> _Grey; host arrays are uploaded, device tensors used in place."""
+    cai = getattr(grey, "__cuda_array_interface__", None)
+    if cai is None:
+        a = np.asarray(grey)
+        if a.dtype not in (np.uint8, np.float32):
+            raise ValueError("grey image dtype %s not supported (uint8 / float32)" % a.dtype)
+        a = np.ascontiguousarray(a)
+        shape = a.shape
+        while len(shape) > 2 and shape[0] == 1:
+            shape = shape[1:]
+        if len(shape) != 2 or a.size == 0:
+            raise ValueError("grey image must be (h, w); got %r" % (a.shape,))
+        d = ctx.to_device(a)
+        return _Grey(d.ptr.value, _lib.U8 if a.dtype == np.uint8 else F32, shape[0], shape[1], d)
+    shape = tuple(cai["shape"])
+    while len(shape) > 2 and shape[0] == 1:
+        shape = shape[1:]
+    if len(shape) != 2 or 0 in shape:
+        raise ValueError("grey image must be (h, w); got %r" % (tuple(cai["shape"]),))
+    dt = {"|u1": _lib.U8, "<f4": F32}.get(cai["typestr"])
+    if dt is None:
+        raise ValueError("grey image dtype %s not supported (uint8 / float32)" % cai["typestr"])
+    if cai.get("strides") is not None:
+        item = 1 if dt == _lib.U8 else 4
+        full = tuple(cai["shape"])
+        if tuple(cai["strides"]) != tuple(int(np.prod(full[i + 1:])) * item for i in range(len(full))):
+            raise ValueError("grey image must be contiguous (call .contiguous())")
+    _sync_torch()
+    return _Grey(cai["data"][0], dt, shape[0], shape[1], grey)
+
+
+def _sync_torch():
+    """Work torch queued on its own stream (the upload of a tensor, say) completes before a kernel on the context's stream."""
+    import sys
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.cuda.is_initialized():
+        torch.cuda.current_stream().synchronize()
+
+
+def dsift_dense(ctx, grey, spatial_bin_size=4, rootsift=True, clipval=0.2):
+    """The reference's `dsift` model (pixsfm/features/models/dsift.py: kornia DenseSIFTDescriptor(8, 4, spatial_bin_size,
+    rootsift, clipval, stride=1, padding=1)) on ONE grey image, on the GPU (pxr_dsift_dense): a torch.cuda float32 tensor
+    (1, 128, h, w) on the context's device.  grey: (h, w) uint8 (value / 255, as to_tensor) or float32, device or host."""
+    import torch
+    img = _grey_on_device(ctx, grey)
+    out = torch.empty((1, 128, img.h, img.w), dtype=torch.float32, device="cuda:%d" % ctx.device)
+    _sync_torch()
+    check(ctx.lib.pxr_dsift_dense(ctx.handle, img.ptr, img.dtype, img.h, img.w, int(spatial_bin_size), int(bool(rootsift)),
+                                  float(clipval), C.c_void_p(out.data_ptr())), "pxr_dsift_dense")
+    ctx.sync()
+    return out
 
 
 def interpolate(ctx, arena, cfg, keypoints, patch_idx, jacobian=False):
