@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "pxr_device.h"
 #include "pxr_interp.h"
@@ -52,6 +53,128 @@ struct BaEvalArgs {
   int opr;            // observations a lane group walks (<= LPO): 4 from 200k observations on, LPO below (launch_eval) -- same arithmetic
                       // per observation, only the number of wavefronts in flight changes
 };
+
+// ---- fp16 arenas: the horizontal pass on the raw halves ----------------------------------------------------------------
+// fp16 -> fp32 is exact, so every spline_f32 op that reads a raw texel (t1, t2, t4, t5, t6, t7) can take the fp16 half straight
+// from the loaded dword: v_fma_mix_f32 widens it inside the FMA (op_sel_hi marks an fp16 source, op_sel picks its high half).
+// The ops and their order are spline_f32's -> h / hd bit-identical.  Left to itself hipcc folds only part of the widening into
+// fma_mix and converts the rest separately (120 v_cvt_f32_f16 per observation, ~12 % of the loop's issue cycles).
+// HI: the channel is the high half of its dword.  All three ops keep their constant in an SGPR (one scalar operand per VOP3).
+template <int HI>
+__device__ __forceinline__ float mix_fma_kh_nh(float k, uint32_t a, uint32_t b) {   // fma(k, a, -b), a and b fp16
+  float r;
+  if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,1,1] op_sel_hi:[0,1,1]" : "=v"(r) : "s"(k), "v"(a), "v"(b));
+  else asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "=v"(r) : "s"(k), "v"(a), "v"(b));
+  return r;
+}
+template <int HI>
+__device__ __forceinline__ float mix_fma_kh_h(float k, uint32_t a, uint32_t b) {    // fma(k, a, b), a and b fp16
+  float r;
+  if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,1] op_sel_hi:[0,1,1]" : "=v"(r) : "s"(k), "v"(a), "v"(b));
+  else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "=v"(r) : "s"(k), "v"(a), "v"(b));
+  return r;
+}
+template <int HI>
+__device__ __forceinline__ float mix_fma_ff_h(float x, float y, uint32_t b) {       // fma(x, y, b), b fp16
+  float r;
+  if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(y), "v"(b));
+  else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(y), "v"(b));
+  return r;
+}
+// spline_f32 (pxr_device.h) on the halves of w0..w3 that hold p0..p3
+template <int HI, bool WITH_D>
+__device__ __forceinline__ void spline_f16mix(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, const SplineCoefF32& k,
+                                              float& f, float& d) {
+  const float t1 = mix_fma_kh_nh<HI>(3.0f, w1, w0);
+  const float t2 = mix_fma_kh_nh<HI>(3.0f, w2, w3);
+  const float t4 = mix_fma_kh_nh<HI>(4.0f, w2, w3);
+  const float t5 = mix_fma_kh_nh<HI>(2.5f, w1, w0);
+  const float t6 = mix_fma_kh_h<HI>(-1.0f, w0, w2);
+  const float t3 = __fsub_rn(t1, t2);
+  const float b = __fmaf_rn(0.5f, t4, -t5);
+  const float t7 = mix_fma_ff_h<HI>(k.xhalf, t6, w1);
+  const float t8 = __fmaf_rn(k.xhalf, t3, b);
+  f = __fmaf_rn(k.x2, t8, t7);
+  if (WITH_D) {
+    const float t9 = __fmaf_rn(k.fourx, b, t6);
+    const float t10 = __fmul_rn(k.onefivex2, t3);
+    d = __fmaf_rn(0.5f, t9, t10);
+  }
+}
+__device__ __forceinline__ uint32_t dword(const uint4& t, int i) { return i == 0 ? t.x : i == 1 ? t.y : i == 2 ? t.z : t.w; }
+
+// PixelInterpolator::Evaluate L2 normalisation + chain rule (interpolation.h:648-666): a copy, op for op, of the normalisation in
+// interp8 (pxr_interp.h), which the KA, cost-map and Gram kernels share.  The two must stay identical -- a change to one is a change
+// to the other (the fp16 BA records are pinned to the oracle and to the other arenas' records by tests/test_ba_eval_gpu.py).
+template <int LPO, bool WITH_JAC>
+__device__ __forceinline__ void l2_normalize8(double f[8], double fr[8], double fc[8]) {
+  double ss = 0.0;
+#pragma unroll
+  for (int ch = 0; ch < 8; ++ch) ss = fma(f[ch], f[ch], ss);
+  ss = (LPO == 16) ? row16_sum(ss) : row8_sum(ss);
+  const double ninv = 1.0 / sqrt(ss);
+#pragma unroll
+  for (int ch = 0; ch < 8; ++ch) f[ch] *= ninv;
+  if (WITH_JAC) {
+    double dc = 0.0, dr = 0.0;
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) {
+      fc[ch] *= ninv; fr[ch] *= ninv;
+      dc = fma(f[ch], fc[ch], dc);
+      dr = fma(f[ch], fr[ch], dr);
+    }
+    if (LPO == 16) { dc = row16_sum(dc); dr = row16_sum(dr); }
+    else { dc = row8_sum(dc); dr = row8_sum(dr); }
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) {
+      fc[ch] = fma(-dc, f[ch], fc[ch]);
+      fr[ch] = fma(-dr, f[ch], fr[ch]);
+    }
+  }
+}
+
+// interp8 (pxr_interp.h) for an fp16 arena: the same stencil, the horizontal pass above, the shared vertical pass.  The 16 texel
+// addresses are one 64-bit base per observation plus 32-bit byte offsets (a patch is far below 4 GiB): no sign extension and no
+// 64-bit multiply per load (ba_eval_with_cost requires an fp16 patch of at most 4 GiB).  The texels are loaded non-temporally (`nt`): a step reads every patch once, and with the default
+// policy the 4 GB stencil stream pushed the references (read by every observation of a point) out of the L2.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+template <int LPO, bool WITH_JAC>
+__device__ __forceinline__ void interp8_f16(const _Float16* __restrict__ patch, int H, int W, int sub, double u, double v,
+                                            bool l2_normalize, double f[8], double fr[8], double fc[8]) {
+  constexpr uint32_t TEXEL_BYTES = LPO * 8 * sizeof(_Float16);
+  const StencilIndex si = stencil_index(H, W, u, v);
+  const char* base = reinterpret_cast<const char*>(patch + sub * 8);
+  uint32_t co[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) co[i] = (uint32_t)si.co[i] * TEXEL_BYTES;
+  uint4 tx[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const char* row = base + (uint32_t)si.ro[j] * TEXEL_BYTES;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + co[i]));
+      tx[j][i] = make_uint4(t.x, t.y, t.z, t.w);
+    }
+  }
+  float h[4][8], hd[4][8];
+  const SplineCoefF32 kh(si.dx);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const uint32_t w0 = dword(tx[j][0], w), w1 = dword(tx[j][1], w), w2 = dword(tx[j][2], w), w3 = dword(tx[j][3], w);
+      float dd = 0.f;
+      spline_f16mix<0, WITH_JAC>(w0, w1, w2, w3, kh, h[j][2 * w], dd);
+      hd[j][2 * w] = dd;
+      dd = 0.f;
+      spline_f16mix<1, WITH_JAC>(w0, w1, w2, w3, kh, h[j][2 * w + 1], dd);
+      hd[j][2 * w + 1] = dd;
+    }
+  }
+  interp8_vertical<float, WITH_JAC, false>(h, hd, si.dy, f, fr, fc);
+  if (l2_normalize) l2_normalize8<LPO, WITH_JAC>(f, fr, fc);
+}
 
 template <typename ST, int C, bool WITH_JAC, bool FLOAT_SIMD>
 __global__ __launch_bounds__(256) void ba_eval_kernel(const BaEvalArgs a) {
@@ -96,26 +219,38 @@ __global__ __launch_bounds__(256) void ba_eval_kernel(const BaEvalArgs a) {
   const ST* arena = reinterpret_cast<const ST*>(a.arena);
   const int row_base = lane & ~(LPO - 1);
 
+  // reference descriptor slice of this lane (8 doubles) and the point it belongs to: reloaded only when the observation's point
+  // differs from the one held.  Observations are point-sorted, so consecutive observations of a lane group mostly share one; a
+  // reload per observation re-read the 1 KiB reference from L2 or HBM every pass (the texel stream evicts it in between)
+  // (d_refs == NULL: no reference is subtracted -- the descriptor pass of the reference extraction)
+  double2 rf0 = make_double2(0, 0), rf1 = rf0, rf2 = rf0, rf3 = rf0;
+  int held = -1;
   for (int it = 0; it < opr; ++it) {
     if (obs0 + it >= n) break;   // uniform within the lane group
     const int src = row_base | it;
     const double u = shfl_f64(my_u, src), v = shfl_f64(my_v, src);
     const int64_t pi = shfl_i64(pidx, src);
     const int pti = __shfl(pt, src);
-    // reference descriptor slice of this lane: 8 doubles (issued before the texel math)
-    // (d_refs == NULL: no reference is subtracted -- the descriptor pass of the reference extraction)
-    double2 rf0 = make_double2(0, 0), rf1 = rf0, rf2 = rf0, rf3 = rf0;
-    if (a.v.d_refs) {
+    if (a.v.d_refs && pti != held) {   // issued before the texel math
       const double* refp = a.v.d_refs + (size_t)pti * C + sub * 8;
       rf0 = *reinterpret_cast<const double2*>(refp);
       rf1 = *reinterpret_cast<const double2*>(refp + 2);
       rf2 = *reinterpret_cast<const double2*>(refp + 4);
       rf3 = *reinterpret_cast<const double2*>(refp + 6);
+      held = pti;
     }
 
     double f[8], fr[8], fc[8];
-    interp8<ST, LPO, WITH_JAC, FLOAT_SIMD>(arena + (size_t)pi * patch_elems, a.H, a.W, C, sub, u, v,
-                                           a.l2_normalize != 0, f, fr, fc);
+    // use_float_simd keeps interp8: its fp32 vertical pass beside the mixed-precision horizontal one needs more registers than the
+    // kernel has (256 VGPRs + spills to AGPRs, one wavefront per SIMD instead of two), and the solver evaluates with it on every LM
+    // iteration (it skips the Gram cache).  The no-Jacobian kernel (the reference extraction's descriptor pass) takes interp8_f16
+    // although it drops from four to three wavefronts per SIMD (125 -> 138 VGPRs): 0.705 against 0.770 ms per 1M observations
+    // (0.759 on interp8 with the reference kept)
+    if constexpr (std::is_same<ST, _Float16>::value && !FLOAT_SIMD)
+      interp8_f16<LPO, WITH_JAC>(arena + (size_t)pi * patch_elems, a.H, a.W, sub, u, v, a.l2_normalize != 0, f, fr, fc);
+    else
+      interp8<ST, LPO, WITH_JAC, FLOAT_SIMD>(arena + (size_t)pi * patch_elems, a.H, a.W, C, sub, u, v,
+                                             a.l2_normalize != 0, f, fr, fc);
     const double ref[8] = {rf0.x, rf0.y, rf1.x, rf1.y, rf2.x, rf2.y, rf3.x, rf3.y};
     double r[8];
     double s = 0, gcc = 0, gcr = 0, grr = 0, bc = 0, br = 0;
@@ -297,7 +432,9 @@ static int launch_eval(pxr_ctx* ctx, const BaEvalArgs& a_in, bool with_jac, bool
   // s, then the row walks its 16 observations).  With 4 the launch has four times the wavefronts -- each with sixteen 16-byte
   // loads per lane in flight -- and a quarter of the projection lanes idle: measured on MI355X, alternating runs of the bench
   // (ms per step, 16 / 4 observations per group): 1M observations 0.802-0.813 / 0.768-0.793, 500k 0.404 / 0.388, 250k 0.206 /
-  // 0.202, 125k 0.1046 / 0.1066 (6 and 8 per group: worse than both below 250k).  PXR_BA_EVAL_OPR=<n> forces a value.
+  // 0.202, 125k 0.1046 / 0.1066 (6 and 8 per group: worse than both below 250k).  PXR_BA_EVAL_OPR=<n> forces a value.  Re-swept
+  // with the reference kept across a group's observations and nt stencil loads, 1M observations, ms per launch: 2 0.745, 3 0.715,
+  // 4 0.709, 5 0.711, 8 0.710, 16 0.732 -- 4 stays.
   static const int opr_knob = std::getenv("PXR_BA_EVAL_OPR") ? atoi(std::getenv("PXR_BA_EVAL_OPR")) : 0;
   a.opr = opr_knob > 0 ? std::min(opr_knob, LPO) : (a.v.n_obs >= 200000 ? std::min(4, LPO) : LPO);
   const int64_t obs_per_block = 4 * (64 / LPO) * a.opr;   // 4 waves x (64 / LPO groups x opr observations)
@@ -345,6 +482,9 @@ int pxr::ba_eval_with_cost(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* vi
   PXR_REQUIRE(view->n_obs >= 0, "pxr_ba_eval: negative n_obs");
   PXR_REQUIRE(arena->up == 1.0 || arena->C <= 4, "pxr_ba_eval: an upsampling factor is a property of cost maps (1 / 3 channels)");
   PXR_REQUIRE((d_gx == nullptr) == (d_gy == nullptr), "pxr_ba_eval: d_gx and d_gy must be given together");
+  // the fp16 path addresses the 16 texels with 32-bit byte offsets inside the patch (interp8_f16)
+  PXR_REQUIRE(arena->dtype != PXR_F16 || arena->C <= 4 || (uint64_t)arena->H * arena->W * arena->C * 2 <= (1ull << 32),
+              "pxr_ba_eval: an fp16 patch of %d x %d x %d exceeds 4 GiB", arena->H, arena->W, arena->C);
   PXR_REQUIRE(!(d_gx && !d_r), "pxr_ba_eval: d_gx/d_gy require d_r");
   if (view->n_obs == 0) return PXR_OK;
   PXR_HIP(hipSetDevice(ctx->device));
