@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """End-to-end example on a synthetic scene, written the way a pixsfm user drives the reference
 (pixsfm/keypoint_adjustment/main.py, pixsfm/bundle_adjustment/main.py): featuremetric keypoint adjustment, then
-featuremetric bundle adjustment, then the same BA through the low-memory cost-map strategy.
+featuremetric bundle adjustment, then the same BA through the low-memory cost-map strategy, then a classic geometric
+(reprojection-error) bundle adjustment of noisy keypoints -- the strategy the reference runs "for comparison".
 
     python examples/synthetic_refinement.py            # needs an MI355X and the built libpixsfm_hip.so
 """
@@ -62,7 +63,29 @@ def bundle_adjustment(strategy):
              s.termination_type))
 
 
+def mean_reprojection_error(rec):
+    from pixsfm_amd.api.bundle_adjustment import BundleAdjustmentSetup, _FlatBA, _geometric_dict
+    from pixsfm_amd.api.keypoint_adjustment import default_context
+    from pixsfm_amd.engine import GeometricBAProblem
+    setup = BundleAdjustmentSetup()
+    setup.add_images(rec.reg_image_ids())
+    return float(GeometricBAProblem(default_context(), _geometric_dict(_FlatBA(rec, setup, None, {}, extractor=True))).reprojection_errors().mean())
+
+
+def geometric_bundle_adjustment():
+    prob = synthetic.make_ba_problem(n_cams=12, n_points=1500, obs_per_point=5, seed=3, channels=1, patch_size=2)
+    noisy = prob["centers"] + np.random.default_rng(0).normal(0.0, 0.5, prob["centers"].shape)      # detections: 0.5 px of noise
+    rec, _ = reconstruction_from_flat(dict(prob, centers=noisy))
+    before = mean_reprojection_error(rec)
+    out = BundleAdjuster.create({"strategy": "geometric"}).refine(rec)            # no features needed
+    s = out["summary"]
+    print("BA (geometric): %d observations, mean reprojection error %.3f -> %.3f px, cost %.4g -> %.4g in %d iterations (%.1f ms), %s"
+          % (len(prob["obs_image"]), before, mean_reprojection_error(rec), s.initial_cost, s.final_cost, s.num_iterations,
+             s.total_time_in_seconds * 1e3, s.termination_type))
+
+
 if __name__ == "__main__":
     keypoint_adjustment()
     bundle_adjustment("feature_reference")
     bundle_adjustment("costmaps")
+    geometric_bundle_adjustment()

@@ -365,6 +365,30 @@ int pxr_ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, const 
                  const pxr_lm_options* options, pxr_allreduce_fn allreduce, void* allreduce_user,
                  pxr_lm_summary* summary);
 
+/* ---- geometric BA (strategy "geometric") ------------------------------------------------------
+ * The reprojection residual r = WorldToPixel(camera, q, t, X) - xy_observed of
+ * GeometricBundleOptimizer::AddResiduals (bundle_adjustment/src/geometric_bundle_optimizer.h:39-88; residuals/src/geometric.h
+ * -> [upstream COLMAP 3.8] BundleAdjustmentCostFunction / BundleAdjustmentConstantPoseCostFunction), two residuals per
+ * observation, no feature patches: view->d_obs_patch and view->d_refs are ignored and may be NULL.
+ * d_obs_xy [n_obs][2]: the observed keypoint of every observation, image pixels, COLMAP convention (device pointer).
+ *
+ * pxr_ba_geom_eval replaces the evaluation of those cost functions: per observation the record of pxr_ba_eval,
+ *   [rx^2 + ry^2, 1, 0, 1, rx, ry, x, y]   (gx = (1, 0), gy = (0, 1): the Jacobian of the block IS the projection Jacobian),
+ * and optionally the residual itself, d_res [n_obs][2] (NULL to skip).  pxr_ba_cost and pxr_ba_projection_jacobian work on
+ * such a view / such records unchanged. */
+int pxr_ba_geom_eval(pxr_ctx* ctx, const pxr_ba_view* view, const double* d_obs_xy, double* d_rec, double* d_res);
+
+/* Replaces GeometricBundleOptimizer::Run -> BundleOptimizer::SolveProblem -> ceres::Solve
+ * (geometric_bundle_optimizer.h:22-37, bundle_optimizer.h:172-245).  The same LM loop as pxr_ba_solve with the same meaning of
+ * the parameterisation arrays, options (PXR_LINEAR_AUTO by image count, inner iterations), summary, iteration callback,
+ * deterministic mode and collectives; a non-finite evaluation ends the solve with PXR_TERM_FAILURE at the last accepted point.
+ * The qvec / tvec / cam_params / xyz device arrays of `view` are updated IN PLACE. */
+int pxr_ba_solve_geometric(pxr_ctx* ctx, const pxr_ba_view* view, const double* d_obs_xy, const pxr_loss* loss,
+                           const uint8_t* h_pose_const, const uint8_t* h_tvec_const_mask,
+                           const uint16_t* h_cam_const_mask, const uint8_t* h_point_const,
+                           const pxr_lm_options* options, pxr_allreduce_fn allreduce, void* allreduce_user,
+                           pxr_lm_summary* summary);
+
 
 /* ---- BA reference extraction -----------------------------------------------------------
  * Replaces ReferenceExtractor::Run (bundle_adjustment/src/reference_extractor.h:125-318) +

@@ -1120,13 +1120,17 @@ static inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b -
 
 }  // namespace pxr
 
-extern "C" int pxr_ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, const pxr_interp_cfg* cfg,
-                            const pxr_loss* loss, const uint8_t* h_pose_const, const uint8_t* h_tvec_const_mask,
-                            const uint16_t* h_cam_const_mask, const uint8_t* h_point_const,
-                            const pxr_lm_options* opt, pxr_allreduce_fn allreduce, void* ar_user,
-                            pxr_lm_summary* sum) {
+// The LM loop of pxr_ba_solve and pxr_ba_solve_geometric.  d_obs_xy != NULL: the geometric problem -- the records come from
+// geom_eval and the inner iterations from k_inner_geom (pxr_ba_geom.hip), `arena` and `cfg` are not read, the Gram-matrix
+// cache and the Gram-matrix inner kernel are off.  Everything else is the same code for both.
+static int ba_solve_impl(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, const pxr_interp_cfg* cfg, const double* d_obs_xy,
+                         const pxr_loss* loss, const uint8_t* h_pose_const, const uint8_t* h_tvec_const_mask,
+                         const uint16_t* h_cam_const_mask, const uint8_t* h_point_const,
+                         const pxr_lm_options* opt, pxr_allreduce_fn allreduce, void* ar_user,
+                         pxr_lm_summary* sum) {
   using namespace pxr;
-  PXR_REQUIRE(ctx && arena && view && cfg && loss && opt && sum, "pxr_ba_solve: NULL argument");
+  const bool geom = d_obs_xy != nullptr;
+  PXR_REQUIRE(ctx && view && loss && opt && sum && (geom || (arena && cfg)), "pxr_ba_solve: NULL argument");
   PXR_REQUIRE(h_pose_const && h_tvec_const_mask && h_cam_const_mask && h_point_const,
               "pxr_ba_solve: NULL parameterisation array");
   PXR_REQUIRE(view->n_obs > 0, "pxr_ba_solve: problem has no residuals (bundle_optimizer.h:174-176)");
@@ -1546,12 +1550,12 @@ extern "C" int pxr_ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
   //  needs no care: with reference descriptors the functor ignores the bounds check, feature_reference.h:128-136.)
   // (InterpolationConfig.use_float_simd asks for the reference's ALL-fp32 splines: the Gram-matrix paths -- exact fp64 algebra -- would
   // silently compute something finer; a solve with that flag keeps the texel kernels, which have the fp32 arithmetic bit for bit)
-  bool gram_cache = ctx->gram_cache && gram_eval_supported(arena, view) && cfg->use_float_simd == 0;
+  bool gram_cache = !geom && ctx->gram_cache && gram_eval_supported(arena, view) && cfg->use_float_simd == 0;
   // The Gram-matrix kernel of the inner iterations keeps its matrices in the same cache from call to call (it writes back what
   // it builds), whether or not the LM loop evaluates from them: the same numbers as without a cache, fewer builds.  (That kernel
   // is built without the six extended camera models -- their forward-mode duals cost ~100 registers: a problem that uses one
   // keeps the packed kernel for every point.)
-  bool gram_inner = opt->use_inner_iterations != 0 && arena->dtype != PXR_F64 && (arena->C == 128 || arena->C == 64) && !getenv("PXR_INNER_OLD") &&
+  bool gram_inner = !geom && opt->use_inner_iterations != 0 && arena->dtype != PXR_F64 && (arena->C == 128 || arena->C == 64) && !getenv("PXR_INNER_OLD") &&
                     !getenv("PXR_INNER_PACKED") && cfg->use_float_simd == 0;
   for (int c = 0; c < n_cam; ++c) gram_inner = gram_inner && cam_model[c] <= PXR_OPENCV;
   bool inner_cache = gram_inner && gram_eval_supported(arena, view) && !getenv("PXR_INNER_NO_CACHE");
@@ -1563,6 +1567,8 @@ extern "C" int pxr_ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
     gram_cache = false; inner_cache = false;
     (void)set_error(PXR_OK, "");    // pxr_last_error() must not keep the allocation's message
   }
+  bool geom_ext = false;                // geometric problem with a camera model beyond OPENCV: k_inner_geom<true>
+  for (int c = 0; c < n_cam; ++c) geom_ext = geom_ext || cam_model[c] > PXR_OPENCV;
   setup_mark("Gram-matrix cache prepared");
   bool gram_warm = false;               // the cache holds every observation's matrices (after the first evaluation / inner call)
   int n_evaluations = 0;
@@ -1576,7 +1582,8 @@ extern "C" int pxr_ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
     // (the evaluation at the INITIAL point takes the exact-order kernel also with the cache on: the first trust-region step is
     // usually the largest of the solve -- at configs[2] 95 % of the projections leave their cell -- so matrices built there
     // would be built again at once, and 1.5 ms of builds cost more than 0.8 ms of texels)
-    if (gram_cache && n_evaluations > 0) { RC(gram_evaluate(ctx, arena, &v, cfg, gram, rec)); gram_warm = true; }
+    if (geom) RC(geom_eval(ctx, &v, d_obs_xy, rec, nullptr));
+    else if (gram_cache && n_evaluations > 0) { RC(gram_evaluate(ctx, arena, &v, cfg, gram, rec)); gram_warm = true; }
     else RC(ba_eval_with_cost(ctx, arena, &v, cfg, 1, rec, nullptr, nullptr, nullptr, nullptr, nullptr));
     ++n_evaluations;
     hipLaunchKernelGGL(k_cost_limbs, dim3(1024), dim3(256), 0, st, (const double*)rec, n_obs, *loss, slimb.p + 0 * PXR_LIMBS);
@@ -1902,9 +1909,12 @@ extern "C" int pxr_ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
         // point on ONE address -- 200 000 of them at configs[2] -- serialised for 0.5-1 ms of the 2-4 ms call:
         // profiles/r4_inner_cost_atomic.txt)
         PXR_HIP(hipMemsetAsync(det_part.p, 0, sizeof(double) * (size_t)n_pts, st));   // points without observations stay 0
-        RC(launch_inner_iterations(ctx, arena, &cand_view, cfg, loss, d_pt_ptr.p, d_pt_obs.p, d_pt_var.p, scal_sum + 4, gram_inner ? &inner_lists.l : nullptr,
-                                   det_part.p, (gram_cache || inner_cache) ? &gram : nullptr, gram_warm));
-        gram_warm = true;
+        if (geom) RC(launch_inner_geom(ctx, &cand_view, d_obs_xy, loss, d_pt_ptr.p, d_pt_obs.p, d_pt_var.p, scal_sum + 4, det_part.p, geom_ext));
+        else {
+          RC(launch_inner_iterations(ctx, arena, &cand_view, cfg, loss, d_pt_ptr.p, d_pt_obs.p, d_pt_var.p, scal_sum + 4, gram_inner ? &inner_lists.l : nullptr,
+                                     det_part.p, (gram_cache || inner_cache) ? &gram : nullptr, gram_warm));
+          gram_warm = true;
+        }
         hipLaunchKernelGGL(k_limb_accumulate, dim3(256), dim3(256), 0, st, (const double*)det_part.p, n_pts, slimb.p + 4 * PXR_LIMBS);
         PXR_HIP(hipMemsetAsync(scal_sum + 2, 0, sizeof(double), st));   // point part of |x - candidate|^2 after refinement
         PXR_HIP(hipMemsetAsync(slimb.p + 2 * PXR_LIMBS, 0, sizeof(long long) * PXR_LIMBS, st));
@@ -2003,4 +2013,24 @@ extern "C" int pxr_ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
   sum->final_cost = cost; sum->final_radius = radius;
   sum->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop0).count();
   return PXR_OK;
+}
+
+extern "C" int pxr_ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, const pxr_interp_cfg* cfg,
+                            const pxr_loss* loss, const uint8_t* h_pose_const, const uint8_t* h_tvec_const_mask,
+                            const uint16_t* h_cam_const_mask, const uint8_t* h_point_const,
+                            const pxr_lm_options* opt, pxr_allreduce_fn allreduce, void* ar_user,
+                            pxr_lm_summary* sum) {
+  PXR_REQUIRE(arena && cfg, "pxr_ba_solve: NULL argument");
+  return ba_solve_impl(ctx, arena, view, cfg, nullptr, loss, h_pose_const, h_tvec_const_mask, h_cam_const_mask, h_point_const, opt,
+                       allreduce, ar_user, sum);
+}
+
+extern "C" int pxr_ba_solve_geometric(pxr_ctx* ctx, const pxr_ba_view* view, const double* d_obs_xy, const pxr_loss* loss,
+                                      const uint8_t* h_pose_const, const uint8_t* h_tvec_const_mask,
+                                      const uint16_t* h_cam_const_mask, const uint8_t* h_point_const,
+                                      const pxr_lm_options* opt, pxr_allreduce_fn allreduce, void* ar_user,
+                                      pxr_lm_summary* sum) {
+  PXR_REQUIRE(d_obs_xy, "pxr_ba_solve_geometric: the observed keypoints are missing");
+  return ba_solve_impl(ctx, nullptr, view, nullptr, d_obs_xy, loss, h_pose_const, h_tvec_const_mask, h_cam_const_mask, h_point_const,
+                       opt, allreduce, ar_user, sum);
 }

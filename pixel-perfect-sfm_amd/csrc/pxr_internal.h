@@ -69,6 +69,12 @@ int comm_allreduce_sum_i64(pxr_ctx* ctx, long long* d_buf, int64_t count);
 int ba_eval_with_cost(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, const pxr_interp_cfg* cfg,
                       int with_jacobian, double* d_rec, double* d_r, double* d_gx, double* d_gy,
                       const pxr_loss* loss, double* d_cost_sum);
+// pxr_ba_geom.hip: the records of the reprojection residual r = WorldToPixel(...) - d_obs_xy[i] (d_res: r itself, or NULL), and
+// the inner iterations on it (the candidate's xyz refined in place; the cost at the unrefined candidate per point or summed)
+int geom_eval(pxr_ctx* ctx, const pxr_ba_view* view, const double* d_obs_xy, double* d_rec, double* d_res);
+int launch_inner_geom(pxr_ctx* ctx, const pxr_ba_view* view, const double* d_obs_xy, const pxr_loss* loss, const int64_t* d_pt_ptr,
+                      const int64_t* d_pt_obs, const int* d_pt_var, double* d_cost_before, double* d_cost_per_point,
+                      bool extended_models);
 // pxr_ba_inner.hip: the inner iterations' split of the points by track length (made once per solve)
 struct InnerLists {
   void* d_short = nullptr; int64_t n_short = 0; int maxo_short = 1;  // points with 1 .. 16 observations (Gram-matrix kernel): {point, length, first slot}

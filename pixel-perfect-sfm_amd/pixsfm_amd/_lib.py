@@ -112,6 +112,10 @@ _SIGNATURES = {
     "pxr_ba_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BaView), C.POINTER(InterpCfg), C.POINTER(Loss),
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LMOptions),
                                C.c_void_p, C.c_void_p, C.POINTER(LMSummary)]),
+    "pxr_ba_geom_eval": (C.c_int, [C.c_void_p, C.POINTER(BaView), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pxr_ba_solve_geometric": (C.c_int, [C.c_void_p, C.POINTER(BaView), C.c_void_p, C.POINTER(Loss),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LMOptions),
+                                         C.c_void_p, C.c_void_p, C.POINTER(LMSummary)]),
     "pxr_ba_compute_references": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BaView), C.POINTER(InterpCfg),
                                             C.POINTER(Loss), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pxr_costmap_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,

@@ -1,6 +1,6 @@
 """`_pixsfm._bundle_adjustment` (pixsfm/bundle_adjustment/bindings.cc:20-184)."""
 from ..api.bundle_adjustment import (BundleAdjustmentSetup, CostMapBundleOptimizer, CostMapExtractor,  # noqa: F401
-                                     FeatureReferenceBundleOptimizer, ReferenceExtractor)
+                                     FeatureReferenceBundleOptimizer, GeometricBundleOptimizer, ReferenceExtractor)
 
 
 from ._options import struct
@@ -31,4 +31,3 @@ def _outside(name, why):
 
 
 PatchWarpBundleOptimizer = _outside("PatchWarpBundleOptimizer", "N_NODES > 1 patch warping, DESIGN.md section 7")
-GeometricBundleOptimizer = _outside("GeometricBundleOptimizer", "reprojection-error BA is COLMAP's, not featuremetric")

@@ -3,8 +3,8 @@ pixsfm.keypoint_adjustment, pixsfm.bundle_adjustment, pixsfm._pixsfm._base/_feat
 from . import base, extract, features, localization, reconstruction  # noqa: F401
 from .bundle_adjustment import (BundleAdjuster, BundleAdjustmentSetup, CostMapBundleAdjuster,  # noqa: F401
                                 CostMapBundleOptimizer, CostMapExtractor, FeatureReferenceBundleAdjuster,
-                                FeatureReferenceBundleOptimizer, FeatureView, ReferenceExtractor,
-                                default_problem_setup)
+                                FeatureReferenceBundleOptimizer, FeatureView, GeometricBundleAdjuster,
+                                GeometricBundleOptimizer, ReferenceExtractor, default_problem_setup)
 from .keypoint_adjustment import (FeatureMetricKeypointAdjuster, FeatureMetricKeypointOptimizer,  # noqa: F401
                                   KeypointAdjuster, KeypointAdjustmentSetup,
                                   TopologicalReferenceKeypointAdjuster, TopologicalReferenceKeypointOptimizer,

@@ -15,7 +15,7 @@ from copy import deepcopy
 import numpy as np
 
 from .. import _lib
-from ..engine import BAProblem, lm_options, make_loss
+from ..engine import BAProblem, GeometricBAProblem, lm_options, make_loss
 from . import base, features
 from .keypoint_adjustment import Summary, default_context
 from .reconstruction import CAMERA_MODELS
@@ -266,7 +266,11 @@ class _SceneDump:
         fs = getattr(feature_view, "feature_set", None)
         self.has_patch = np.zeros(len(ids), np.uint8)
         self._patch_dicts = []
-        if fs is None:                           # any object with has_fpatch / fpatch (image_id, point2D_idx): asked one by one
+        if feature_view is None:                 # no features at all (geometric BA): every observation "has a patch"
+            self._patch_dicts = None
+            self.has_patch[:] = 1
+            images = []
+        elif fs is None:                         # any object with has_fpatch / fpatch (image_id, point2D_idx): asked one by one
             self._patch_dicts = None
             for k, i in enumerate(img_ids):
                 for j in range(counts[k]):
@@ -440,6 +444,21 @@ class _FlatBA:
                            feature_set=getattr(sc.feature_view, "feature_set", None))
 
     @property
+    def obs_xy(self):
+        """(n_obs, 2) the observed keypoint point2D.xy of every residual block (the geometric BA's measurements): one numpy gather
+        per image."""
+        out = np.empty((len(self._key_p2d), 2), np.float64)
+        sc, obs_image = self._scene, self._scene_obs_image
+        order = np.argsort(obs_image, kind="stable")
+        bounds = np.searchsorted(obs_image[order], np.arange(len(sc.img_ids) + 1))
+        for k, i in enumerate(sc.img_ids):
+            sel = order[bounds[k]:bounds[k + 1]]
+            if len(sel):
+                xy = np.array([p.xy for p in sc.reconstruction.images[i].points2D], np.float64).reshape(-1, 2)
+                out[sel] = xy[self._key_p2d[sel]]
+        return out
+
+    @property
     def obs_keys(self):
         """(image_id, point2D_idx) of every residual block."""
         if self._obs_keys is None:
@@ -458,6 +477,12 @@ class _FlatBA:
                     obs_patch=obs_patch, image_camera=self.image_camera,
                     qvec=self.qvec, tvec=self.tvec, cam_model=self.cam_model, cam_params=self.cam_params,
                     xyz=self.xyz, refs=refs)
+
+
+def _geometric_dict(flat):
+    """The problem dict of engine.GeometricBAProblem for a _FlatBA."""
+    return dict(obs_image=flat.obs_image, obs_point=flat.obs_point, obs_xy=flat.obs_xy, image_camera=flat.image_camera,
+                qvec=flat.qvec, tvec=flat.tvec, cam_model=flat.cam_model, cam_params=flat.cam_params, xyz=flat.xyz)
 
 
 class ReferenceExtractor:
@@ -688,6 +713,11 @@ class _PointSubset:
     def key_arrays(self, obs):
         return self.flat.key_arrays(self.obs[np.asarray(obs, dtype=np.int64)])
 
+    def geometric_dict(self):
+        f = self.flat
+        return dict(obs_image=self.obs_image, obs_point=self.obs_point, obs_xy=f.obs_xy[self.obs], image_camera=f.image_camera,
+                    qvec=f.qvec, tvec=f.tvec, cam_model=f.cam_model, cam_params=f.cam_params, xyz=self.xyz)
+
     def problem_dict(self, refs, patch_index):
         f = self.flat
         return dict(obs_image=self.obs_image, obs_point=self.obs_point, obs_patch=patch_index, image_camera=f.image_camera,
@@ -773,7 +803,6 @@ class FeatureReferenceBundleOptimizer:
         flat, ba = self._flat, self._ba
         if ba is None:
             return False                                                         # NumResiduals() == 0, :174-176
-        C = self._arena.C
         s = self.options['solver']
         lm = lm_options(max_iterations=s['max_num_iterations'], function_tolerance=s['function_tolerance'],
                         gradient_tolerance=s['gradient_tolerance'], parameter_tolerance=s['parameter_tolerance'],
@@ -799,17 +828,22 @@ class FeatureReferenceBundleOptimizer:
         from ._timing import phase
         try:
             with phase("solve"):
-                summ = ba.solve(self.interpolation.to_engine(), make_loss(self._loss['name'], self._loss['params']),
-                                flat.pose_const, flat.tvec_mask, flat.cam_mask, point_const, options=lm,
-                                allreduce=allreduce)
+                summ = self._solve(ba, make_loss(self._loss['name'], self._loss['params']), flat, point_const, lm, allreduce)
         finally:
             ba.ctx.set_iteration_callbacks(None)
         with phase("write_back"):
             self._write_back(reconstruction, flat, ba, lo if getattr(self, "_share", None) is not None else None,
                              n_loc if getattr(self, "_share", None) is not None else None)
-        self._summary = Summary(summ, num_residuals=len(flat.obs_image) * C)
+        self._summary = Summary(summ, num_residuals=len(flat.obs_image) * self._residuals_per_observation())
         self._summary.iterations = history
         return True
+
+    def _solve(self, ba, loss, flat, point_const, lm, allreduce):
+        return ba.solve(self.interpolation.to_engine(), loss, flat.pose_const, flat.tvec_mask, flat.cam_mask, point_const,
+                        options=lm, allreduce=allreduce)
+
+    def _residuals_per_observation(self):
+        return self._arena.C
 
     def _write_back(self, reconstruction, flat, ba, lo, n_loc):
         q, t, k, X = ba.params()
@@ -870,6 +904,51 @@ class CostMapBundleOptimizer(FeatureReferenceBundleOptimizer):
         return ok
 
 
+class GeometricBundleOptimizer(FeatureReferenceBundleOptimizer):
+    """_bundle_adjustment.GeometricBundleOptimizer(options, setup).run(reconstruction) (bindings.cc:155-162;
+    geometric_bundle_optimizer.h:17-88): classic bundle adjustment on the reprojection error of every point2D with a 3D
+    point -- no features, no interpolation.  The flat problem and the parameterisation are those of the featuremetric
+    optimiser (BundleOptimizer::SetUp / Parameterize*); the residual is WorldToPixel(...) - point2D.xy, solved by
+    pxr_ba_solve_geometric."""
+
+    def __init__(self, options=None, setup=None, ctx=None, allreduce=None):
+        super().__init__(options, setup, None, ctx=ctx, allreduce=allreduce)
+
+    def set_up(self, reconstruction, loss_function=None):
+        if reconstruction is None:
+            raise ValueError("reconstruction cannot be NULL.")                  # bundle_optimizer.h:117-118
+        if self._used:
+            raise ValueError("Cannot use the same BundleOptimizer multiple times")   # :120-121
+        self._used = True
+        ctx = self.ctx or default_context()
+        self._loss = loss_function or self.options['loss']
+        flat = _FlatBA(reconstruction, self.setup, None, self.options)
+        self._flat, self._ba, self._arena, self._share = flat, None, None, None
+        if len(flat.obs_image) == 0:
+            return
+        from .. import parallel
+        rank, world = parallel.world()
+        if world > 1:          # points sharded over the ranks with their observations and keypoints, cameras replicated
+            self._share = _rank_share(flat, rank, world)
+            self._share_lo = self._share.lo
+            if len(self._share.obs_image) == 0:
+                raise ValueError("rank %d received no observations: fewer points than ranks" % rank)
+            self._ba = GeometricBAProblem(ctx, self._share.geometric_dict())
+            return
+        self._ba = GeometricBAProblem(ctx, _geometric_dict(flat))
+
+    def _solve(self, ba, loss, flat, point_const, lm, allreduce):
+        return ba.solve(loss, flat.pose_const, flat.tvec_mask, flat.cam_mask, point_const, options=lm, allreduce=allreduce)
+
+    def _residuals_per_observation(self):
+        return 2
+
+    def run(self, reconstruction):
+        """Run = SetUp + SolveProblem (geometric_bundle_optimizer.h:22-37)."""
+        self.set_up(reconstruction, None)
+        return self.solve_problem(reconstruction)
+
+
 class BundleAdjuster:
     """pixsfm/bundle_adjustment/main.py:30-102."""
     default_conf = {
@@ -892,9 +971,10 @@ class BundleAdjuster:
     @classmethod
     def create(cls, conf):
         strategy = conf.get("strategy", cls.default_conf["strategy"])
-        strategies = {"feature_reference": FeatureReferenceBundleAdjuster, "costmaps": CostMapBundleAdjuster}   # main.py:67-73
+        strategies = {"feature_reference": FeatureReferenceBundleAdjuster, "costmaps": CostMapBundleAdjuster,
+                      "geometric": GeometricBundleAdjuster}                                                     # main.py:67-73
         if strategy not in strategies:
-            raise ValueError("strategy %r is outside the accelerated path (feature_reference, costmaps)" % strategy)
+            raise ValueError("strategy %r is outside the accelerated path (feature_reference, costmaps, geometric)" % strategy)
         return strategies[strategy](conf)
 
     def refine(self, reconstruction, feature_set, problem_setup=None):
@@ -970,3 +1050,23 @@ class CostMapBundleAdjuster(BundleAdjuster):
         solver = CostMapBundleOptimizer(deepcopy(self.conf['optimizer']), problem_setup, interp_conf)
         solver.run(reconstruction, costmap_view)
         return {"costmaps": costmap_fset, "references": references, "summary": solver.summary()}
+
+
+class GeometricBundleAdjuster(BundleAdjuster):
+    """main.py:289-312: classic bundle adjustment minimising the 2D distance between the reprojection of a 3D point and its
+    detection.  `refine(reconstruction, *args, problem_setup=None)`: problem_setup is keyword-only like in the reference;
+    whatever refine_multilevel passes positionally (a feature set, its problem_setup) is ignored."""
+    default_conf = deepcopy(BundleAdjuster.default_conf)
+    callbacks = []               # main.py:63: iteration callbacks handed to the optimizer's solver options (doc/FAQ.md:62-95)
+
+    def __init__(self, conf):
+        self.conf = base.merge_adjuster_conf(self.default_conf, conf)
+
+    def refine(self, reconstruction, *args, problem_setup=None):
+        if problem_setup is None:
+            problem_setup = default_problem_setup(reconstruction)
+        options = deepcopy(self.conf['optimizer'])
+        options['solver'] = {**options['solver'], 'callbacks': list(self.callbacks)}       # to_optim_ctr, main.py:307-308
+        solver = GeometricBundleOptimizer(options, problem_setup)
+        solver.run(reconstruction)
+        return {"summary": solver.summary()}

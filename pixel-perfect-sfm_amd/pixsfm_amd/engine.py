@@ -658,3 +658,105 @@ class BAProblem:
         check(self.ctx.lib.pxr_ba_cost(self.ctx.handle, self.rec.ptr, self.n_obs, C.byref(loss), C.byref(out)),
               "pxr_ba_cost")
         return out.value
+
+
+class GeometricBAProblem:
+    """Device-resident flat arrays of a geometric (reprojection-error) bundle-adjustment problem: the pxr_ba_view without a
+    patch arena plus the observed keypoints (GeometricBundleOptimizer::AddResiduals, geometric_bundle_optimizer.h:39-88).
+
+    problem: dict as for BAProblem without obs_patch / refs, plus obs_xy (n_obs x 2, image pixels, COLMAP convention).
+    """
+
+    def __init__(self, ctx, problem):
+        self.ctx = ctx
+        g = problem
+        self.n_obs = len(g["obs_image"])
+        self.n_images = len(g["image_camera"])
+        self.n_cameras = len(g["cam_model"])
+        self.n_points = len(g["xyz"])
+        obs_xy = np.ascontiguousarray(g["obs_xy"], dtype=np.float64).reshape(-1, 2)
+        if len(obs_xy) != self.n_obs:
+            raise ValueError("obs_xy must hold one keypoint per observation")
+        cam_params = np.zeros((self.n_cameras, KPAD))
+        cp = np.asarray(g["cam_params"], dtype=np.float64)
+        cam_params[:, :cp.shape[1]] = cp
+        self.d = {
+            "obs_image": ctx.to_device(g["obs_image"], np.int32),
+            "obs_point": ctx.to_device(g["obs_point"], np.int32),
+            "obs_xy": ctx.to_device(obs_xy, np.float64),
+            "image_camera": ctx.to_device(g["image_camera"], np.int32),
+            "qvec": ctx.to_device(g["qvec"], np.float64),
+            "tvec": ctx.to_device(g["tvec"], np.float64),
+            "cam_model": ctx.to_device(g["cam_model"], np.int32),
+            "cam_params": ctx.to_device(cam_params, np.float64),
+            "xyz": ctx.to_device(g["xyz"], np.float64),
+        }
+        self.rec = ctx.empty((self.n_obs, OBS_REC), np.float64)
+        self.res = ctx.empty((self.n_obs, 2), np.float64)
+        d = self.d
+        self.view = BaView(self.n_obs, d["obs_image"].ptr, d["obs_point"].ptr, None, self.n_images, d["image_camera"].ptr,
+                           d["qvec"].ptr, d["tvec"].ptr, self.n_cameras, d["cam_model"].ptr, d["cam_params"].ptr,
+                           self.n_points, d["xyz"].ptr, None)
+
+    def eval(self, residuals=True):
+        """Launch the reprojection-residual kernel (pxr_ba_geom_eval).  Returns device arrays (rec, res): the 8-double
+        records and the residuals (n_obs x 2; None with residuals=False: the records alone, what the solver asks for)."""
+        res = self.res if residuals else None
+        check(self.ctx.lib.pxr_ba_geom_eval(self.ctx.handle, C.byref(self.view), self.d["obs_xy"].ptr, self.rec.ptr,
+                                            res.ptr if res else None), "pxr_ba_geom_eval")
+        return self.rec, res
+
+    def reprojection_errors(self):
+        """Per-observation reprojection error in pixels at the current parameters (numpy, n_obs)."""
+        _, res = self.eval()
+        r = res.download()
+        return np.hypot(r[:, 0], r[:, 1])
+
+    def projection_jacobian(self, out=None):
+        """The 2 x (10+K) projection Jacobian of every observation -- here the Jacobian of the residual block itself."""
+        P = out if out is not None else self.ctx.empty((self.n_obs, 2, 10 + KPAD), np.float64)
+        check(self.ctx.lib.pxr_ba_projection_jacobian(self.ctx.handle, C.byref(self.view), P.ptr),
+              "pxr_ba_projection_jacobian")
+        return P
+
+    def solve(self, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, options=None, allreduce=None):
+        """Run the GPU LM (pxr_ba_solve_geometric); parameters are refined in place on the device.  Arguments as
+        BAProblem.solve without the interpolation configuration.  Returns the summary dict."""
+        ctx = self.ctx
+        pc = np.ascontiguousarray(pose_const, dtype=np.uint8)
+        tm = np.ascontiguousarray(tvec_const_mask, dtype=np.uint8)
+        cm = np.ascontiguousarray(cam_const_mask, dtype=np.uint16)
+        ptc = np.ascontiguousarray(point_const, dtype=np.uint8)
+        if len(pc) != self.n_images or len(tm) != self.n_images or len(cm) != self.n_cameras \
+                or len(ptc) != self.n_points:
+            raise ValueError("parameterisation arrays do not match the problem dimensions")
+        opts = options or lm_options()
+        summ = _lib.LMSummary()
+        cb = None
+        if allreduce is not None:
+            def _cb(user, ptr, count):
+                try:
+                    allreduce(ptr, count)
+                    return 0
+                except Exception as e:  # noqa: BLE001 -- must not unwind through C
+                    import sys
+                    print("all-reduce callback failed: %r" % (e,), file=sys.stderr)
+                    return 1
+            cb = _lib.ALLREDUCE_FN(_cb)
+        check(ctx.lib.pxr_ba_solve_geometric(ctx.handle, C.byref(self.view), self.d["obs_xy"].ptr, C.byref(loss),
+                                             pc.ctypes.data, tm.ctypes.data, cm.ctypes.data, ptc.ctypes.data,
+                                             C.byref(opts), C.cast(cb, C.c_void_p) if cb else None, None, C.byref(summ)),
+              "pxr_ba_solve_geometric")
+        return summ.as_dict()
+
+    def params(self):
+        """Download (qvec, tvec, cam_params, xyz)."""
+        d = self.d
+        return d["qvec"].download(), d["tvec"].download(), d["cam_params"].download(), d["xyz"].download()
+
+    def cost(self, loss):
+        """Sum of 0.5 rho(|r|^2) over the records of the last eval()."""
+        out = C.c_double()
+        check(self.ctx.lib.pxr_ba_cost(self.ctx.handle, self.rec.ptr, self.n_obs, C.byref(loss), C.byref(out)),
+              "pxr_ba_cost")
+        return out.value

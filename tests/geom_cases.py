@@ -1,0 +1,132 @@
+"""Geometric (reprojection-error) BA cases and the bridge that lets the featuremetric oracle check them.
+
+The oracle (oracle/pxo_solve.c) has no reprojection cost of its own.  It IS one when it is handed RAMP patches: give every
+observation a float64 patch whose texel (row j, column i) holds
+
+    ((x0 + i + .5) / sx - x_obs,  (y0 + j + .5) / sy - y_obs)          (FeaturePatch::ToImageCoordinates)
+
+zero references and l2_normalize=False.  Catmull-Rom interpolation reproduces linear functions exactly, so the oracle's
+featuremetric residual at a projection (x, y) is (x - x_obs, y - y_obs) -- the reprojection residual -- as long as the 4 x 4
+stencil stays inside the patch, i.e. the projection is at least 2 texels away from the border.  Every case handed out here is
+therefore checked: the reprojection errors at the initial parameters (make_case) and at the oracle's solution (oracle_solve)
+must be below patch_size / 2 - 3 pixels (13 px for 32 x 32 patches centred on the keypoint).  A case that violates the bound
+is a broken case: fix the case, never skip it.
+
+A track of n observations needs a scene of at least n cameras (a point is seen once per image).
+"""
+import numpy as np
+
+PATCH_SIZE = 32
+RAMP_LOSS = ("cauchy", 1.0)
+
+
+def margin(patch_size=PATCH_SIZE):
+    """Largest reprojection error (px, scale 1) for which the ramp equivalence holds."""
+    return patch_size / 2.0 - 3.0
+
+
+def ramp_patches(obs_xy, scales, patch_size=PATCH_SIZE, channels=2):
+    """(patches (n, ps, ps, channels) float64, corners (n, 2) int32): ramp patches centred on the observed keypoints.  Channels
+    beyond the second are zero (pxr_ba_eval wants 1, 3, 64 or 128 channels: use 3)."""
+    obs_xy = np.asarray(obs_xy, dtype=np.float64)
+    scales = np.asarray(scales, dtype=np.float64)
+    n = len(obs_xy)
+    corners = np.floor(obs_xy * scales - patch_size / 2.0).astype(np.int32)      # extractor.py:192-193
+    ii = np.arange(patch_size, dtype=np.float64)
+    xs = (corners[:, 0:1] + ii[None, :] + 0.5) / scales[:, 0:1] - obs_xy[:, 0:1]  # (n, ps): by column
+    ys = (corners[:, 1:2] + ii[None, :] + 0.5) / scales[:, 1:2] - obs_xy[:, 1:2]  # (n, ps): by row
+    patches = np.zeros((n, patch_size, patch_size, channels), dtype=np.float64)
+    patches[..., 0] = xs[:, None, :]
+    patches[..., 1] = ys[:, :, None]
+    return patches, corners
+
+
+def reprojection(prob, qvec=None, tvec=None, cam_params=None, xyz=None):
+    """(n_obs, 2) pxo.world_to_pixel of every observation at the given (default: the problem's) parameters."""
+    import pxo
+    q = prob["qvec"] if qvec is None else qvec
+    t = prob["tvec"] if tvec is None else tvec
+    k = prob["cam_params"] if cam_params is None else cam_params
+    X = prob["xyz"] if xyz is None else xyz
+    out = np.empty((len(prob["obs_image"]), 2))
+    for i, (im, pt) in enumerate(zip(prob["obs_image"], prob["obs_point"])):
+        cam = prob["image_camera"][im]
+        m = int(prob["cam_model"][cam])
+        K = pxo.lib().pxo_camera_num_params(m)
+        out[i] = pxo.world_to_pixel(m, np.asarray(k[cam])[:K], q[im], t[im], X[pt], jac=False)[0]
+    return out
+
+
+def reprojection_errors(prob, *params):
+    r = reprojection(prob, *params) - prob["obs_xy"]
+    return np.hypot(r[:, 0], r[:, 1])
+
+
+def assert_inside(prob, *params, what=""):
+    e = reprojection_errors(prob, *params)
+    ps = prob["patches"].shape[1] if "patches" in prob else PATCH_SIZE
+    assert np.isfinite(e).all() and e.max() < margin(ps), \
+        "broken case (%s): reprojection error %.2f px leaves the ramp's linear zone (%.1f px)" % (what, e.max(), margin(ps))
+    return e
+
+
+def as_ramp_problem(prob, obs_xy, patch_size=PATCH_SIZE, channels=2):
+    """A copy of a flat problem dict (synthetic.make_ba_problem layout) turned into its ramp form: obs_xy added, patches /
+    corners / obs_patch / refs replaced.  Checked at the initial parameters."""
+    out = {k: v for k, v in prob.items() if k not in ("patches", "corners", "refs", "obs_patch")}
+    n = len(prob["obs_image"])
+    out["obs_xy"] = np.ascontiguousarray(obs_xy, dtype=np.float64)
+    out["scales"] = np.ones((n, 2))
+    out["patches"], out["corners"] = ramp_patches(out["obs_xy"], out["scales"], patch_size, channels)
+    out["obs_patch"] = np.arange(n, dtype=np.int64)
+    out["refs"] = np.zeros((len(prob["xyz"]), channels))
+    assert_inside(out, what="initial parameters")
+    return out
+
+
+def make_case(n_cams=6, n_points=40, obs_per_point=4, seed=0, model=2, keypoint_noise=0.6, shared_camera=False, channels=2,
+              patch_size=PATCH_SIZE, ramp=True, **kw):
+    """A synthetic scene (perturbed poses / points as make_ba_problem makes them) whose observed keypoints are the true
+    projections plus seeded Gaussian noise of `keypoint_noise` px, in ramp form.  ramp=False: without the patches (a case that
+    is not handed to the oracle -- 16 KB per observation saved); the initial errors are checked all the same."""
+    from pixsfm_amd import synthetic
+    assert obs_per_point <= n_cams, "a track of n observations needs a scene of at least n cameras"
+    # (the featuremetric content of the generator is not used: the smallest it can render)
+    base = synthetic.make_ba_problem(n_cams=n_cams, n_points=n_points, obs_per_point=obs_per_point, seed=seed, model=model,
+                                     shared_camera=shared_camera, channels=1, patch_size=2, dtype=np.float64, **kw)
+    rng = np.random.default_rng(1000 + seed)
+    obs_xy = base["centers"] + rng.normal(0.0, keypoint_noise, base["centers"].shape)
+    if ramp:
+        return as_ramp_problem(base, obs_xy, patch_size, channels)
+    out = {k: v for k, v in base.items() if k not in ("patches", "corners", "scales", "refs", "obs_patch")}
+    out["obs_xy"] = obs_xy
+    assert_inside(out, what="initial parameters")
+    return out
+
+
+def geometric_dict(prob):
+    """What engine.GeometricBAProblem takes."""
+    return {k: prob[k] for k in ("obs_image", "obs_point", "obs_xy", "image_camera", "qvec", "tvec", "cam_model", "cam_params", "xyz")}
+
+
+def oracle_eval(prob, loss=RAMP_LOSS, want_J=False):
+    """(cost, r (n_obs, 2), J | None) of the oracle's featuremetric evaluation of the ramp problem."""
+    import pxo
+    cost, r, J = pxo.ba_eval_batch(prob, pxo.cfg(l2_normalize=False), pxo.loss(*loss), want_r=True, want_J=want_J)
+    return cost, r[:, :2], J
+
+
+def oracle_solve(prob, loss, gauge, **opt_kw):
+    """pxo.ba_solve on the ramp problem = the oracle's geometric BA.  Checked at its solution."""
+    import pxo
+    s, q, t, k, X = pxo.ba_solve(prob, pxo.cfg(l2_normalize=False), pxo.loss(*loss), *gauge, pxo.lm_options(**opt_kw))
+    assert_inside(prob, q, t, k, X, what="the oracle's solution")
+    return s, (q, t, k, X)
+
+
+def robust_cost(prob, loss, *params):
+    """1/2 sum rho(|r|^2) from pxo.world_to_pixel and pxo.loss_eval."""
+    import pxo
+    e = reprojection_errors(prob, *params)
+    ls = pxo.loss(*loss)
+    return 0.5 * sum(pxo.loss_eval(ls, float(s))[0] for s in e * e)
