@@ -389,6 +389,66 @@ int pxr_ba_solve_geometric(pxr_ctx* ctx, const pxr_ba_view* view, const double* 
                            const pxr_lm_options* options, pxr_allreduce_fn allreduce, void* allreduce_user,
                            pxr_lm_summary* summary);
 
+/* ---- track triangulation (known poses in, points and tracks out) ------------------------------
+ * The middle stage of the reference's pipeline between keypoint adjustment and bundle adjustment, which PixSfM.triangulation
+ * hands to COLMAP: pycolmap.triangulate_points as called by hloc.triangulation.main from pixsfm/refine_hloc.py:112-114.
+ * Tracks are given in CSR form over the observations (observations of one track are contiguous); images and cameras exactly
+ * as in pxr_ba_view.  All arrays are device pointers. */
+typedef struct {
+  int64_t n_tracks;
+  const int64_t* d_track_offsets; /* [n_tracks + 1] monotone, last = n_obs: track t owns observations [offsets[t], offsets[t+1]) */
+  int64_t n_obs;
+  const int32_t* d_obs_image;     /* [n_obs] index into qvec/tvec/image_camera */
+  const double* d_obs_xy;         /* [n_obs][2] the keypoints, image pixels, COLMAP convention */
+  int32_t n_images;
+  const int32_t* d_image_camera;  /* [n_images] */
+  const double* d_qvec;           /* [n_images][4] */
+  const double* d_tvec;           /* [n_images][3] */
+  int32_t n_cameras;
+  const int32_t* d_cam_model;     /* [n_cameras] PXR_* model id */
+  const double* d_cam_params;     /* [n_cameras][PXR_KPAD] */
+} pxr_tri_view;
+
+/* [upstream COLMAP 3.8] IncrementalTriangulator::Options / EstimateTriangulationOptions values that the reference inherits
+ * through hloc; max_hypotheses is this estimator's own bound (pairs are enumerated, not sampled). */
+typedef struct {
+  double min_tri_angle;     /* 1.5  degrees: smallest parallax of a hypothesis pair and of an accepted track        */
+  double max_angle_error;   /* 2.0  degrees: angular inlier threshold between a ray and the point                    */
+  double max_reproj_error;  /* 4.0  pixels: reprojection filter on the angular inliers                              */
+  int32_t min_track_len;    /* 2    final inliers a track needs (never fewer than 2)                                */
+  int32_t max_hypotheses;   /* 256  two-view hypotheses per track: all P = n (n - 1) / 2 pairs when P <= this, else
+                                    pair number floor(h P / max_hypotheses), h = 0 .. max_hypotheses - 1            */
+} pxr_tri_options;
+
+/* Replaces [upstream COLMAP 3.8] Camera::ImageToWorld (<Model>::ImageToWorld of the eleven models), batched: the normalised
+ * image point d_uv[i] whose projection under camera d_cam_index[i] (NULL: camera 0) is the pixel d_xy[i].  The pinholes are
+ * closed form; every other model runs Newton on WorldToImage(u, v) - (x, y) with the model's analytic 2 x 2 Jacobian from the
+ * pinhole normalisation, until the squared step is below 1e-20, 32 steps at most.  d_ok[i] (may be NULL) = 0 and d_uv[i] = NaN
+ * where the iteration does not converge, meets a singular Jacobian or a non-finite value, or the camera index is out of range. */
+int pxr_image_to_world(pxr_ctx* ctx, int64_t n, const int32_t* d_cam_index, int32_t n_cameras, const int32_t* d_cam_model,
+                       const double* d_cam_params, const double* d_xy, double* d_uv, uint8_t* d_ok);
+
+/* Replaces pycolmap.triangulate_points (hloc.triangulation.main, pixsfm/refine_hloc.py:112-114) for given tracks: every
+ * observation becomes a world-frame ray (unit bearing d, camera centre c; an observation that cannot be undistorted is left
+ * out), and every track is estimated on its own, deterministically:
+ *   solve(S) = (sum_S (I - d d^t))^-1 sum_S (I - d d^t) c;  cos_i(X) = d_i . (X - c_i) / |X - c_i|, inlier: cos_i >= cos(max_angle_error)
+ *   1. hypotheses X = solve({a, b}) over pairs a < b in lexicographic order (subsampled as in pxr_tri_options), skipped when
+ *      d_a . d_b > cos(min_tri_angle) or when a or b is not an inlier of X;  2. the one with the largest (inlier count,
+ *      -sum over inliers of (1 - cos_i), -index);  3. X' = solve(inliers), kept if it has at least as many inliers;
+ *   4. final set = angular inliers with pixel error <= max_reproj_error; if that removed any and >= 2 remain, X = solve(final set);
+ *   5. kept if the final set has >= max(2, min_track_len) members and two of them see X under >= min_tri_angle.
+ * Outputs: d_status[t] 0 = point written to d_xyz[t], 1 = fewer than two usable observations, 2 = no hypothesis survived,
+ * 3 = rejected in step 4 / 5; d_xyz[t] is left untouched unless status is 0; d_n_inliers[t] = size of the final set (0 unless
+ * status is 0); per observation d_obs_inlier (member of the final set; 0 unless status is 0) and d_obs_err (pixel error of
+ * every usable observation of a track with a point against the final X; NaN elsewhere).
+ * PXR_EINVAL (nothing launched on the tracks): offsets not monotone or not ending at n_obs, an image or camera index out of range.
+ * Synchronises the context's stream (the offsets are validated and the tracks ordered by length on the host). */
+int pxr_triangulate_tracks(pxr_ctx* ctx, const pxr_tri_view* view, const pxr_tri_options* options, double* d_xyz,
+                           int32_t* d_status, int32_t* d_n_inliers, uint8_t* d_obs_inlier, double* d_obs_err);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[4] = validation, rays, compaction, tracks. */
+int pxr_triangulate_tracks_timed(pxr_ctx* ctx, const pxr_tri_view* view, const pxr_tri_options* options, double* d_xyz,
+                                 int32_t* d_status, int32_t* d_n_inliers, uint8_t* d_obs_inlier, double* d_obs_err,
+                                 double* h_kernel_ms);
 
 /* ---- BA reference extraction -----------------------------------------------------------
  * Replaces ReferenceExtractor::Run (bundle_adjustment/src/reference_extractor.h:125-318) +

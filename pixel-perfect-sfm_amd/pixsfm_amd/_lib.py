@@ -76,6 +76,20 @@ class KaView(C.Structure):
                 ("d_unary_ref", C.c_void_p), ("d_unary_w", C.c_void_p), ("d_prob_unary_ptr", C.c_void_p),
                 ("d_prob_unary", C.c_void_p), ("d_prob_group", C.c_void_p)]
 
+
+class TriView(C.Structure):
+    """pxr_tri_view"""
+    _fields_ = [("n_tracks", C.c_int64), ("d_track_offsets", C.c_void_p), ("n_obs", C.c_int64), ("d_obs_image", C.c_void_p),
+                ("d_obs_xy", C.c_void_p), ("n_images", C.c_int32), ("d_image_camera", C.c_void_p), ("d_qvec", C.c_void_p),
+                ("d_tvec", C.c_void_p), ("n_cameras", C.c_int32), ("d_cam_model", C.c_void_p), ("d_cam_params", C.c_void_p)]
+
+
+class TriOptions(C.Structure):
+    """pxr_tri_options"""
+    _fields_ = [("min_tri_angle", C.c_double), ("max_angle_error", C.c_double), ("max_reproj_error", C.c_double),
+                ("min_track_len", C.c_int32), ("max_hypotheses", C.c_int32)]
+
+
 # every symbol include/pixsfm_hip.h declares (checked by tests/test_cabi_and_host.py)
 _SIGNATURES = {
     "pxr_version": (C.c_int, []),
@@ -116,6 +130,12 @@ _SIGNATURES = {
     "pxr_ba_solve_geometric": (C.c_int, [C.c_void_p, C.POINTER(BaView), C.c_void_p, C.POINTER(Loss),
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LMOptions),
                                          C.c_void_p, C.c_void_p, C.POINTER(LMSummary)]),
+    "pxr_image_to_world": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "pxr_triangulate_tracks": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.POINTER(TriOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "pxr_triangulate_tracks_timed": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.POINTER(TriOptions), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_ba_compute_references": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BaView), C.POINTER(InterpCfg),
                                             C.POINTER(Loss), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pxr_costmap_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,

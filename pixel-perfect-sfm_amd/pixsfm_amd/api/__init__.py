@@ -1,6 +1,6 @@
 """pixsfm-compatible Python surface of the accelerated KA/BA path (same class / method names as
 pixsfm.keypoint_adjustment, pixsfm.bundle_adjustment, pixsfm._pixsfm._base/_features)."""
-from . import base, extract, features, localization, reconstruction  # noqa: F401
+from . import base, extract, features, localization, reconstruction, triangulation  # noqa: F401
 from .bundle_adjustment import (BundleAdjuster, BundleAdjustmentSetup, CostMapBundleAdjuster,  # noqa: F401
                                 CostMapBundleOptimizer, CostMapExtractor, FeatureReferenceBundleAdjuster,
                                 FeatureReferenceBundleOptimizer, FeatureView, GeometricBundleAdjuster,
@@ -13,3 +13,4 @@ from .localization import (QueryBundleAdjuster, QueryBundleOptimizer, QueryKeypo
                            QueryKeypointOptimizer, find_feature_inliers, find_nearest_references)  # noqa: F401,E402
 from .extract import (FeatureExtractor, extract_patchdata_from_graph, features_from_graph,  # noqa: F401,E402
                       features_from_image_list, features_from_reconstruction)
+from .triangulation import TrackTriangulator  # noqa: F401,E402

@@ -760,3 +760,99 @@ class GeometricBAProblem:
         check(self.ctx.lib.pxr_ba_cost(self.ctx.handle, self.rec.ptr, self.n_obs, C.byref(loss), C.byref(out)),
               "pxr_ba_cost")
         return out.value
+
+
+def tri_options(min_tri_angle=1.5, max_angle_error=2.0, max_reproj_error=4.0, min_track_len=2, max_hypotheses=256):
+    """pxr_tri_options: the triangulator values the reference inherits from COLMAP through hloc (angles in degrees, the
+    reprojection error in pixels) and the bound on the two-view hypotheses per track."""
+    return _lib.TriOptions(float(min_tri_angle), float(max_angle_error), float(max_reproj_error), int(min_track_len),
+                           int(max_hypotheses))
+
+
+def _padded_cam_params(cam_params, n_cameras):
+    out = np.zeros((n_cameras, KPAD))
+    cp = np.asarray(cam_params, dtype=np.float64).reshape(n_cameras, -1)
+    out[:, :cp.shape[1]] = cp
+    return out
+
+
+def image_to_world(ctx, cam_model, cam_params, xy, cam_index=None):
+    """Camera::ImageToWorld, batched on the GPU (pxr_image_to_world): pixels xy (n, 2) -> normalised image points (n, 2) under
+    camera cam_index[i] (None: camera 0) of cam_model (n_cameras,) / cam_params (n_cameras, <= KPAD).  Returns (uv, ok) as
+    numpy arrays; uv is NaN where ok is False (no convergence, singular Jacobian, non-finite input)."""
+    cam_model = np.atleast_1d(np.asarray(cam_model, dtype=np.int32))
+    n_cameras = len(cam_model)
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    n = len(xy)
+    if cam_index is not None and len(cam_index) != n:
+        raise ValueError("cam_index must hold one camera per pixel")
+    if n == 0:
+        return np.empty((0, 2)), np.empty((0,), dtype=bool)
+    d_model = ctx.to_device(cam_model, np.int32)
+    d_params = ctx.to_device(_padded_cam_params(cam_params, n_cameras), np.float64)
+    d_xy = ctx.to_device(xy, np.float64)
+    d_idx = None if cam_index is None else ctx.to_device(cam_index, np.int32)
+    d_uv, d_ok = ctx.empty((n, 2), np.float64), ctx.empty((n,), np.uint8)
+    check(ctx.lib.pxr_image_to_world(ctx.handle, n, d_idx.ptr if d_idx else None, n_cameras, d_model.ptr, d_params.ptr, d_xy.ptr,
+                                     d_uv.ptr, d_ok.ptr), "pxr_image_to_world")
+    return d_uv.download(), d_ok.download().astype(bool)
+
+
+class TriangulationProblem:
+    """Device-resident flat arrays of a track-triangulation problem (pxr_tri_view): known poses and cameras, the keypoints
+    of every observation, tracks in CSR form over the observations.
+
+    problem: dict with track_offsets (n_tracks + 1), obs_image, obs_xy (n_obs x 2, image pixels, COLMAP convention),
+    image_camera, qvec, tvec, cam_model, cam_params (n_cams x <= KPAD).
+    """
+
+    def __init__(self, ctx, problem):
+        self.ctx = ctx
+        g = problem
+        offsets = np.ascontiguousarray(g["track_offsets"], dtype=np.int64).reshape(-1)
+        if len(offsets) < 1:
+            raise ValueError("track_offsets must hold n_tracks + 1 entries")
+        self.n_tracks = len(offsets) - 1
+        self.n_obs = len(g["obs_image"])
+        self.n_images = len(g["image_camera"])
+        self.n_cameras = len(g["cam_model"])
+        obs_xy = np.ascontiguousarray(g["obs_xy"], dtype=np.float64).reshape(-1, 2)
+        if len(obs_xy) != self.n_obs:
+            raise ValueError("obs_xy must hold one keypoint per observation")
+        self.d = {
+            "track_offsets": ctx.to_device(offsets, np.int64),
+            "obs_image": ctx.to_device(np.asarray(g["obs_image"]).reshape(-1), np.int32),
+            "obs_xy": ctx.to_device(obs_xy, np.float64),
+            "image_camera": ctx.to_device(g["image_camera"], np.int32),
+            "qvec": ctx.to_device(np.asarray(g["qvec"], dtype=np.float64).reshape(-1, 4), np.float64),
+            "tvec": ctx.to_device(np.asarray(g["tvec"], dtype=np.float64).reshape(-1, 3), np.float64),
+            "cam_model": ctx.to_device(g["cam_model"], np.int32),
+            "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
+        }
+        d = self.d
+        self.view = _lib.TriView(self.n_tracks, d["track_offsets"].ptr, self.n_obs, d["obs_image"].ptr, d["obs_xy"].ptr,
+                                 self.n_images, d["image_camera"].ptr, d["qvec"].ptr, d["tvec"].ptr, self.n_cameras,
+                                 d["cam_model"].ptr, d["cam_params"].ptr)
+        self.kernel_ms = None
+
+    def triangulate(self, xyz=None, timed=False, **options):
+        """Run the kernels (pxr_triangulate_tracks) with tri_options(**options).  Returns the device arrays
+        (xyz (n_tracks, 3), status (n_tracks,) int32, n_inliers (n_tracks,) int32, obs_inlier (n_obs,) uint8,
+        obs_err (n_obs,) float64).  xyz: a (n_tracks, 3) host array the output starts from -- rows of tracks without a point
+        keep it (default: NaN).  timed: also keep the kernels' HIP-event times in self.kernel_ms
+        {"check", "rays", "compact", "tracks"} (milliseconds)."""
+        ctx = self.ctx
+        opts = tri_options(**options)
+        init = np.full((self.n_tracks, 3), np.nan) if xyz is None else np.asarray(xyz, dtype=np.float64).reshape(self.n_tracks, 3)
+        d_xyz = ctx.to_device(init, np.float64)
+        d_status, d_ninl = ctx.empty((self.n_tracks,), np.int32), ctx.empty((self.n_tracks,), np.int32)
+        d_inl, d_err = ctx.empty((self.n_obs,), np.uint8), ctx.empty((self.n_obs,), np.float64)
+        if timed:
+            ms = (C.c_double * 4)()
+            check(ctx.lib.pxr_triangulate_tracks_timed(ctx.handle, C.byref(self.view), C.byref(opts), d_xyz.ptr, d_status.ptr,
+                                                       d_ninl.ptr, d_inl.ptr, d_err.ptr, ms), "pxr_triangulate_tracks_timed")
+            self.kernel_ms = dict(zip(("check", "rays", "compact", "tracks"), (float(x) for x in ms)))
+        else:
+            check(ctx.lib.pxr_triangulate_tracks(ctx.handle, C.byref(self.view), C.byref(opts), d_xyz.ptr, d_status.ptr,
+                                                 d_ninl.ptr, d_inl.ptr, d_err.ptr), "pxr_triangulate_tracks")
+        return d_xyz, d_status, d_ninl, d_inl, d_err
