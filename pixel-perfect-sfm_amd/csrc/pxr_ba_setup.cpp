@@ -13,11 +13,12 @@
 #include <thread>
 #include <vector>
 
+#include "pxr_ba_structure.h"
 #include "pxr_internal.h"
 
 namespace {
-// [upstream COLMAP 3.8 camera_models.h] number of parameters and the focal / principal point / extra parameter groups
-const int kNumParams[11] = {3, 4, 4, 5, 8, 8, 12, 5, 4, 5, 12};
+// [upstream COLMAP 3.8 camera_models.h] the focal / principal point / extra parameter groups
+using pxr::kNumParams;
 int focal_mask(int m) { return (m == 1 || m == 4 || m == 5 || m == 6 || m == 7 || m == 10) ? 0b11 : 0b1; }
 int pp_mask(int m) { return (m == 1 || m == 4 || m == 5 || m == 6 || m == 7 || m == 10) ? 0b1100 : 0b110; }
 int extra_mask(int m) { return ((1 << kNumParams[m]) - 1) & ~(focal_mask(m) | pp_mask(m)); }
