@@ -450,6 +450,68 @@ int pxr_triangulate_tracks_timed(pxr_ctx* ctx, const pxr_tri_view* view, const p
                                  int32_t* d_status, int32_t* d_n_inliers, uint8_t* d_obs_inlier, double* d_obs_err,
                                  double* h_kernel_ms);
 
+/* ---- absolute pose estimation (2D-3D correspondences in, one pose per query out) ---------------
+ * The middle stage of the reference's QueryLocalizer.localize between query keypoint adjustment and query bundle adjustment:
+ * pycolmap.absolute_pose_estimation (pixsfm/localization/main.py:458).  A batch of queries in CSR form over the correspondences
+ * (correspondences of one query are contiguous), laid out like pxr_tri_view.  All arrays are device pointers.
+ *
+ * [upstream COLMAP 3.8] AbsolutePoseEstimationOptions / RANSACOptions / AbsolutePoseRefinementOptions values as pycolmap 0.x
+ * exposes them, with the one override the reference makes (QueryLocalizer.default_conf.PnP.estimation.ransac.max_error = 12);
+ * round_size, seed and lo_rounds are this estimator's own. */
+#define PXR_ABSPOSE_LDS_CORR 1024 /* correspondences of a query the estimator stages on chip; a longer query reads the rest from memory */
+typedef struct {
+  double max_error;             /* 12.0     pixels: inlier threshold                                                      */
+  double min_inlier_ratio;      /* 0.01     success needs n_inliers >= max(min_num_inliers, ceil(min_inlier_ratio n))      */
+  double confidence;            /* 0.99999  of the stop rule                                                              */
+  double refine_loss_scale;     /* 1.0      pixels: Cauchy scale of the refinement                                        */
+  uint64_t seed;                /* 0        of the sample hash                                                            */
+  int32_t min_num_inliers;      /* 4                                                                                      */
+  int32_t min_num_trials;       /* 64       lower clamp of the stop rule                                                  */
+  int32_t max_num_trials;       /* 4096     upper clamp of the stop rule, rounded up to a multiple of round_size          */
+  int32_t round_size;           /* 64       samples per round: the stop rule is evaluated at round boundaries only        */
+  int32_t refine_max_iterations;/* 100      Levenberg-Marquardt iterations per refinement                                 */
+  int32_t lo_rounds;            /* 4        at most this many refine / re-classify repetitions                            */
+} pxr_abspose_options;
+/* Writes the defaults above. */
+void pxr_abspose_default_options(pxr_abspose_options* options);
+
+/* Replaces pycolmap.absolute_pose_estimation for a batch of queries.  This is NOT COLMAP's LO-RANSAC: the estimator has no
+ * random state and reproduces bit for bit; a query alone and the same query inside any batch give the same bits (DESIGN.md
+ * section 19).  Query q owns correspondences [d_query_offsets[q], d_query_offsets[q+1]): pixel d_xy[i] (COLMAP convention) of
+ * camera d_query_camera[q] sees the point d_xyz[i].  Per query:
+ *   1. every pixel goes through ImageToWorld (pxr_image_to_world); a correspondence that cannot be undistorted or holds a
+ *      non-finite coordinate is unusable for the whole call; n = the usable ones, in order; n < 4: status 1.
+ *   2. sample h = 0, 1, ... is three distinct indices: draw d = mix(mix(seed + G (h + 1)) + G (d + 1)) mod n, d = 0, 1, ..., with
+ *      mix = the output function of splitmix64 and G = 0x9E3779B97F4A7C15 (64-bit wrap-around), a repeated index drawn again;
+ *      the three are used in ascending order.  Neither q nor the batch enters.
+ *   3. P3P (Grunert's quartic, Ferrari's real roots in the order (+,+) (+,-) (-,+) (-,-), three Newton steps each) gives up to four
+ *      poses with positive distances; a degenerate sample gives none.  Each is scored over all n in the normalised image plane:
+ *      err = |(u, v) - (X/Z, Y/Z)|^2, inlier iff Z > 0 and err <= (max_error / mean focal)^2; the largest key
+ *      (inlier count, -sum min(err, thr^2), -h, -root) wins.
+ *   4. after each round of round_size samples: stop once samples done >= clamp(log(1 - confidence) / log(1 - w^3),
+ *      min_num_trials, max_num_trials), w = best count / n.  No pose at all: status 2.
+ *   5. local optimisation: Levenberg-Marquardt on the pixel residuals of the inliers through the full camera model (Cauchy
+ *      weights rho'(|r|^2) of scale refine_loss_scale, pose on the quaternion manifold, intrinsics constant, step norm <= 1e-12
+ *      or refine_max_iterations), then all n classified by pixel error <= max_error; repeated until the set stands still or
+ *      lo_rounds; a refined pose with fewer inliers than the one before it is dropped.  The final set is pixel error <=
+ *      max_error under the pose that stays.
+ *   6. n_inliers < max(min_num_inliers, ceil(min_inlier_ratio n)): status 3.
+ * Outputs: d_status[q] 0 = pose written to d_qvec[q] (unit, w >= 0) / d_tvec[q], which are left untouched otherwise;
+ * d_n_inliers[q] (0 unless status is 0); d_n_trials[q] samples drawn; per correspondence d_inlier (0 unless status is 0) and
+ * d_err (pixel error under the final pose of the usable correspondences of a status-0 query; NaN elsewhere and behind the camera).
+ * PXR_EINVAL (nothing launched): offsets not starting at 0, not monotone or not ending at n_corr, a camera index out of range.
+ * Synchronises the context's stream (offsets and cameras are validated and the queries ordered by size on the host). */
+int pxr_absolute_pose(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_query_offsets, int64_t n_corr, const double* d_xy,
+                      const double* d_xyz, const int32_t* d_query_camera, int32_t n_cameras, const int32_t* d_cam_model,
+                      const double* d_cam_params, const pxr_abspose_options* options, double* d_qvec, double* d_tvec,
+                      int32_t* d_status, int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[4] = records, compaction, hypotheses, refinement. */
+int pxr_absolute_pose_timed(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_query_offsets, int64_t n_corr, const double* d_xy,
+                            const double* d_xyz, const int32_t* d_query_camera, int32_t n_cameras, const int32_t* d_cam_model,
+                            const double* d_cam_params, const pxr_abspose_options* options, double* d_qvec, double* d_tvec,
+                            int32_t* d_status, int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err,
+                            double* h_kernel_ms);
+
 /* ---- BA reference extraction -----------------------------------------------------------
  * Replaces ReferenceExtractor::Run (bundle_adjustment/src/reference_extractor.h:125-318) +
  * RobustMeanIRLS (base/src/irls_optim.h:24-71) for N_NODES = 1: per point, descriptors of all

@@ -90,6 +90,16 @@ class TriOptions(C.Structure):
                 ("min_track_len", C.c_int32), ("max_hypotheses", C.c_int32)]
 
 
+class AbsposeOptions(C.Structure):
+    """pxr_abspose_options"""
+    _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
+                ("refine_loss_scale", C.c_double), ("seed", C.c_uint64), ("min_num_inliers", C.c_int32),
+                ("min_num_trials", C.c_int32), ("max_num_trials", C.c_int32), ("round_size", C.c_int32),
+                ("refine_max_iterations", C.c_int32), ("lo_rounds", C.c_int32)]
+
+
+ABSPOSE_LDS_CORR = 1024      # PXR_ABSPOSE_LDS_CORR
+
 # every symbol include/pixsfm_hip.h declares (checked by tests/test_cabi_and_host.py)
 _SIGNATURES = {
     "pxr_version": (C.c_int, []),
@@ -136,6 +146,13 @@ _SIGNATURES = {
                                          C.c_void_p, C.c_void_p]),
     "pxr_triangulate_tracks_timed": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.POINTER(TriOptions), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "pxr_abspose_default_options": (None, [C.POINTER(AbsposeOptions)]),
+    "pxr_absolute_pose": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.POINTER(AbsposeOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pxr_absolute_pose_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.POINTER(AbsposeOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_ba_compute_references": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BaView), C.POINTER(InterpCfg),
                                             C.POINTER(Loss), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pxr_costmap_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,

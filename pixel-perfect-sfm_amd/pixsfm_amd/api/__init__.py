@@ -10,7 +10,10 @@ from .keypoint_adjustment import (FeatureMetricKeypointAdjuster, FeatureMetricKe
                                   TopologicalReferenceKeypointAdjuster, TopologicalReferenceKeypointOptimizer,
                                   build_matching_graph, find_problem_labels)
 from .localization import (QueryBundleAdjuster, QueryBundleOptimizer, QueryKeypointAdjuster,  # noqa: F401,E402
-                           QueryKeypointOptimizer, find_feature_inliers, find_nearest_references)  # noqa: F401,E402
+                           QueryKeypointOptimizer, QueryLocalizer, absolute_pose_estimation,  # noqa: F401,E402
+                           absolute_pose_estimation_batch, compute_reprojection_errors, find_feature_inliers,  # noqa: F401,E402
+                           find_nearest_references, find_unique_inliers, find_unique_min_by_group,  # noqa: F401,E402
+                           find_unique_min_reproj_inliers)  # noqa: F401,E402
 from .extract import (FeatureExtractor, extract_patchdata_from_graph, features_from_graph,  # noqa: F401,E402
                       features_from_image_list, features_from_reconstruction)
 from .triangulation import TrackTriangulator  # noqa: F401,E402

@@ -14,14 +14,24 @@ point2D_idxs)` (main.py:194-258; src/single_query_bundle_optimizer.h:91-222, que
 the quaternion manifold, intrinsics constant unless refine_* says otherwise.  It runs on pxr_ba_solve
 with every (correspondence, reference descriptor) pair as its own constant point.
 
-PnP / retrieval / QueryLocalizer orchestration (main.py:261-560) stay outside the accelerated path
-(control plane).
+`absolute_pose_estimation(points2D, points3D, camera, estimation_options, refinement_options)` stands in for
+pycolmap.absolute_pose_estimation (main.py:458), which is not installable here: a batched, deterministic P3P estimator with
+local optimisation on the GPU (pxr_absolute_pose; DESIGN.md section 19 -- NOT COLMAP's LO-RANSAC).
+`absolute_pose_estimation_batch` runs many queries in one launch.
+
+`QueryLocalizer(reconstruction, conf, dense_features=..., references=...).localize(...)` is main.py:261-499 step by step:
+query features, the references of the query (nearest / robust_mean / all_observations), QKA, PnP, unique inliers
+(find_unique_inliers, find_unique_min_by_group, find_unique_min_reproj_inliers, compute_reprojection_errors: main.py:38-86),
+QBA, the final inlier recount.  Retrieval and matching, which produce the 2D-3D pairs, stay outside (SURVEY section 8:
+control plane).
 """
+from collections import OrderedDict
 from copy import deepcopy
+from pathlib import Path
 
 import numpy as np
 
-from ..engine import BAProblem, lm_options, make_loss, nearest_references
+from ..engine import AbsolutePoseProblem, BAProblem, lm_options, make_loss, nearest_references
 from ..ka_engine import KAProblem
 from . import base, features
 from .keypoint_adjustment import default_context
@@ -432,3 +442,324 @@ class QueryBundleAdjuster:
         for level in resolve_level_indices(self.conf['level_indices'], len(fmaps)):
             self.refine(qvec, tvec, camera, points3D, fmaps[level], references[level], inliers=inliers,
                         point2D_idxs=point2D_idxs)
+
+
+# ---- PnP ---------------------------------------------------------------------------------------------------------------------------
+# pycolmap 0.x: AbsolutePoseEstimationOptions {estimate_focal_length, num_focal_length_samples, min_focal_length_ratio,
+# max_focal_length_ratio, ransac: RANSACOptions}, AbsolutePoseRefinementOptions {gradient_tolerance, max_num_iterations,
+# loss_function_scale, refine_focal_length, refine_extra_params, print_summary}
+_RANSAC_KEYS = {"max_error": "max_error", "min_inlier_ratio": "min_inlier_ratio", "confidence": "confidence",
+                "min_num_trials": "min_num_trials", "max_num_trials": "max_num_trials",
+                # the estimator's own
+                "min_num_inliers": "min_num_inliers", "round_size": "round_size", "seed": "seed", "lo_rounds": "lo_rounds"}
+_REFINEMENT_KEYS = {"max_num_iterations": "refine_max_iterations", "loss_function_scale": "refine_loss_scale"}
+
+
+def abspose_engine_options(estimation_options=None, refinement_options=None):
+    """The keyword arguments of engine.abspose_options for the option dicts QueryLocalizer passes to
+    pycolmap.absolute_pose_estimation.  Unknown keys raise ValueError; refining intrinsics raises NotImplementedError."""
+    out = {}
+    est = dict(estimation_options or {})
+    if est.pop("estimate_focal_length", False):
+        raise NotImplementedError("estimate_focal_length: the estimator takes the camera as given; refine intrinsics in the "
+                                  "query bundle adjustment (QBA.optimizer.refine_focal_length)")
+    ransac = est.pop("ransac", None) or {}
+    if est:
+        raise ValueError("unknown estimation option(s) %s" % sorted(est))
+    for k, v in dict(ransac).items():
+        if k not in _RANSAC_KEYS:
+            raise ValueError("unknown RANSAC option %r" % (k,))
+        out[_RANSAC_KEYS[k]] = v
+    ref = dict(refinement_options or {})
+    for k in ("refine_focal_length", "refine_extra_params"):
+        if ref.pop(k, False):
+            raise NotImplementedError("%s: the pose refinement keeps the intrinsics constant; refine them in the query bundle "
+                                      "adjustment (QBA.optimizer.%s)" % (k, k))
+    ref.pop("print_summary", None)
+    ref.pop("gradient_tolerance", None)       # the refinement stops on its step norm
+    for k, v in ref.items():
+        if k not in _REFINEMENT_KEYS:
+            raise ValueError("unknown refinement option %r" % (k,))
+        out[_REFINEMENT_KEYS[k]] = v
+    return out
+
+
+def absolute_pose_estimation_batch(queries, estimation_options=None, refinement_options=None, ctx=None):
+    """Many queries in ONE launch: `queries` = [(points2D (n, 2), points3D (n, 3), camera), ...].  Returns one dict per query
+    as absolute_pose_estimation does."""
+    opts = abspose_engine_options(estimation_options, refinement_options)
+    queries = list(queries)
+    if not queries:
+        return []
+    xy = [np.asarray(q[0], dtype=np.float64).reshape(-1, 2) for q in queries]
+    xyz = [np.asarray(q[1], dtype=np.float64).reshape(-1, 3) for q in queries]
+    for a, b in zip(xy, xyz):
+        if len(a) != len(b):
+            raise ValueError("points2D and points3D must have the same length")
+    cams = [q[2] for q in queries]
+    params = np.zeros((len(cams), 12))
+    for i, c in enumerate(cams):
+        params[i, :len(c.params)] = c.params
+    off = np.concatenate([[0], np.cumsum([len(a) for a in xy])]).astype(np.int64)
+    prob = dict(query_offsets=off, xy=np.concatenate(xy), xyz=np.concatenate(xyz), query_camera=np.arange(len(cams), dtype=np.int32),
+                cam_model=np.array([c.model_id for c in cams], np.int32), cam_params=params)
+    ctx = ctx or default_context()
+    d_q, d_t, d_status, d_ninl, _, d_inl, _ = AbsolutePoseProblem(ctx, prob).estimate(**opts)
+    q, t, status, ninl, inl = d_q.download(), d_t.download(), d_status.download(), d_ninl.download(), d_inl.download()
+    out = []
+    for i in range(len(queries)):
+        if status[i] != 0:
+            out.append({"success": False})
+        else:
+            out.append({"success": True, "qvec": q[i].copy(), "tvec": t[i].copy(), "num_inliers": int(ninl[i]),
+                        "inliers": [bool(x) for x in inl[off[i]:off[i + 1]]]})
+    return out
+
+
+def absolute_pose_estimation(points2D, points3D, camera, estimation_options=None, refinement_options=None, ctx=None):
+    """pycolmap.absolute_pose_estimation's shape: {"success", "qvec", "tvec", "num_inliers", "inliers"}, or {"success": False}."""
+    return absolute_pose_estimation_batch([(points2D, points3D, camera)], estimation_options, refinement_options, ctx=ctx)[0]
+
+
+# ---- unique inliers (main.py:38-86) --------------------------------------------------------------------------------------------------
+def _world_to_image(model_id, k, u, v):
+    r2 = u * u + v * v
+    if model_id == 0:
+        return np.stack([k[0] * u + k[1], k[0] * v + k[2]], 1)
+    if model_id == 1:
+        return np.stack([k[0] * u + k[2], k[1] * v + k[3]], 1)
+    if model_id in (2, 3):
+        rad = k[3] * r2 + (k[4] * r2 * r2 if model_id == 3 else 0.0)
+        return np.stack([k[0] * u * (1 + rad) + k[1], k[0] * v * (1 + rad) + k[2]], 1)
+    if model_id == 4:
+        rad = k[4] * r2 + k[5] * r2 * r2
+        du = u * rad + 2 * k[6] * u * v + k[7] * (r2 + 2 * u * u)
+        dv = v * rad + 2 * k[7] * u * v + k[6] * (r2 + 2 * v * v)
+        return np.stack([k[0] * (u + du) + k[2], k[1] * (v + dv) + k[3]], 1)
+    raise NotImplementedError("compute_reprojection_errors: camera model %d without a camera.world_to_image" % model_id)
+
+
+def compute_reprojection_errors(pnp_points2D, pnp_points3D, qvec, tvec, camera):
+    """main.py:80-86: |camera.world_to_image(R X + t) - p2D| per correspondence, as a list."""
+    X = np.asarray([getattr(p, "xyz", p) for p in pnp_points3D], dtype=np.float64).reshape(-1, 3)
+    p2D = np.asarray(pnp_points2D, dtype=np.float64).reshape(-1, 2)
+    q = np.asarray(qvec, dtype=np.float64).reshape(4)
+    w, x, y, z = q / np.linalg.norm(q)
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                  [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                  [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    p = X @ R.T + np.asarray(tvec, dtype=np.float64).reshape(3)
+    with np.errstate(all="ignore"):
+        uv = p[:, :2] / p[:, 2:]
+        if hasattr(camera, "world_to_image"):
+            proj = np.asarray(camera.world_to_image(list(uv)), dtype=np.float64).reshape(-1, 2)
+        else:
+            proj = _world_to_image(camera.model_id, np.asarray(camera.params, dtype=np.float64), uv[:, 0], uv[:, 1])
+        return list(np.linalg.norm(proj - p2D, axis=1))
+
+
+def find_unique_inliers(idxs, pre_inliers=None):
+    """main.py:38-47: the first (pre-)inlier of every index."""
+    idxs = np.asarray(list(idxs))
+    n = len(idxs)
+    out = np.zeros(n, bool)
+    if n == 0:
+        return []
+    pre = np.ones(n, bool) if pre_inliers is None else np.asarray(list(pre_inliers), dtype=bool)
+    live = np.flatnonzero(pre)
+    _, first = np.unique(idxs[live], return_index=True)
+    out[live[first]] = True
+    return [bool(x) for x in out]
+
+
+def find_unique_min_by_group(errors, idxs, pre_inliers=None):
+    """main.py:50-62: per index, the (pre-)inlier of smallest error (the first of equals)."""
+    idxs, errors = np.asarray(list(idxs)), np.asarray(list(errors), dtype=np.float64)
+    assert len(idxs) == len(errors)
+    n = len(idxs)
+    out = np.zeros(n, bool)
+    if n == 0:
+        return []
+    pre = np.ones(n, bool) if pre_inliers is None else np.asarray(list(pre_inliers), dtype=bool)
+    live = np.flatnonzero(pre)
+    if len(live):
+        _, group = np.unique(idxs[live], return_inverse=True)
+        order = np.lexsort((live, errors[live], group))          # by group, then error, then position
+        g = group[order]
+        out[live[order[np.concatenate([[True], g[1:] != g[:-1]])]]] = True
+    return [bool(x) for x in out]
+
+
+def find_unique_min_reproj_inliers(pnp_points3D_id, qvec, tvec, camera, pnp_points2D, rec, pre_inliers=None, point2D_idxs=None):
+    """main.py:65-77: one correspondence per 3D point, then one per keypoint, each the one of smallest reprojection error."""
+    p3Ds = [rec.points3D[p3D_id] for p3D_id in pnp_points3D_id]
+    errors = compute_reprojection_errors(pnp_points2D, p3Ds, qvec, tvec, camera)
+    inliers = pre_inliers
+    for idxs in [pnp_points3D_id, point2D_idxs]:
+        if idxs is None:
+            continue
+        inliers = find_unique_min_by_group(errors, idxs, pre_inliers=inliers)
+    return inliers
+
+
+# ---- QueryLocalizer (main.py:261-537) ----------------------------------------------------------------------------------------------
+_INHERIT = "${..interpolation}"
+
+
+def _extractor_default_conf():
+    from .extract import FeatureExtractor
+    return deepcopy(FeatureExtractor.default_conf)
+
+
+class QueryLocalizer:
+    """pixsfm/localization/main.py:261-537.  Option 1: QueryLocalizer(reconstruction, conf, references=references); option 2:
+    QueryLocalizer(reconstruction, conf, dense_features=feature_manager) extracts the references of every 3D point from the
+    manager's feature sets; a Path for dense_features is read through the H5 cache reader if it exists.  Extracting (and
+    caching) new map features is outside: the cache writer is."""
+
+    default_conf = {
+        "dense_features": _extractor_default_conf(),
+        "overwrite_features_sparse": None,
+        "interpolation": base.interpolation_default_conf,
+        "target_reference": "nearest",
+        "unique_inliers": "min_error",
+        "references": {"loss": {"name": "cauchy", "params": [0.25]}, "iters": 100, "keep_observations": True,
+                       "compute_offsets3D": False, "num_threads": -1},
+        "max_tracks_per_problem": 50,
+        "QKA": {**QueryKeypointAdjuster.default_conf, "interpolation": _INHERIT},
+        "PnP": {"estimation": {"ransac": {"max_error": 12}}, "refinement": {}},
+        "QBA": {**QueryBundleAdjuster.default_conf, "interpolation": _INHERIT},
+    }
+
+    def __init__(self, reconstruction, conf=None, dense_features=None, references=None, extractor=None, ctx=None):
+        conf = deepcopy(dict(conf or {}))
+        conf = conf.get("localization", conf)
+        pnp = conf.pop("PnP", None) or {}
+        dense = conf.pop("dense_features", None)
+        merged = base.merge_conf({k: v for k, v in self.default_conf.items() if k not in ("PnP", "dense_features")}, conf)
+        merged["dense_features"] = {**deepcopy(self.default_conf["dense_features"]), **(dense or {})}
+        merged["PnP"] = {"estimation": {"ransac": {**self.default_conf["PnP"]["estimation"]["ransac"],
+                                                   **((pnp.get("estimation") or {}).get("ransac") or {})},
+                                        **{k: v for k, v in (pnp.get("estimation") or {}).items() if k != "ransac"}},
+                         "refinement": dict(pnp.get("refinement") or {})}
+        extra = set(pnp) - {"estimation", "refinement"}
+        if extra:
+            raise ValueError("unknown configuration key(s) %s in PnP" % sorted(extra))
+        for part in ("QKA", "QBA"):                                # "${..interpolation}"
+            if merged[part]["interpolation"] == _INHERIT:
+                merged[part]["interpolation"] = deepcopy(merged["interpolation"])
+        self.conf = merged
+        abspose_engine_options(merged["PnP"]["estimation"], merged["PnP"]["refinement"])       # fail early on what PnP cannot take
+        if merged["target_reference"] not in ("nearest", "robust_mean", "all_observations", "full"):
+            raise ValueError("unknown target_reference %r" % (merged["target_reference"],))
+        if merged["QKA"]["stack_correspondences"] and merged["target_reference"] not in ("nearest", "robust_mean"):
+            raise ValueError("Stacked QKA requires a np.ndarray reference for each 2D-3D correspondence. Consider setting "
+                             "target_references to 'nearest' or 'robust_mean'.")
+        self.ctx = ctx
+        self.query_keypoint_adjuster = QueryKeypointAdjuster(merged["QKA"], ctx=ctx)
+        self.query_bundle_adjuster = QueryBundleAdjuster(merged["QBA"], ctx=ctx)
+        self.extractor = extractor
+        self.target_reference_funcs = {"nearest": self.get_nearest_references, "robust_mean": self.get_robust_mean_references,
+                                       "all_observations": self.get_all_references, "full": self.get_full_references}
+        self.get_query_references = self.target_reference_funcs[merged["target_reference"]]
+        self.references = references
+        self.reconstruction = reconstruction
+        if self.references is None and (merged["QKA"]["apply"] or merged["QBA"]["apply"]):
+            from .bundle_adjustment import ReferenceExtractor, find_problem_labels
+            if isinstance(dense_features, (str, Path)):
+                path = Path(dense_features)
+                dense_features = features.load_features_from_cache(path, ctx=ctx) if path.exists() else None
+            if dense_features is None:
+                raise ValueError("QueryLocalizer needs `references` or the map's `dense_features` (a FeatureManager, or the path "
+                                 "of an existing feature cache): extracting and caching new map features is outside the "
+                                 "accelerated path (no cache writer)")
+            self.reference_extractor = ReferenceExtractor(merged["references"], merged["interpolation"], ctx=ctx)
+            labels = find_problem_labels(reconstruction, merged["max_tracks_per_problem"])
+            self.references = [self.reference_extractor.run(labels, reconstruction, dense_features.fset(i))
+                               for i in range(dense_features.num_levels)]
+
+    def localize(self, keypoints, pnp_point2D_idxs, pnp_points3D_id, query_camera, image_path=None, query_fmaps=None):
+        assert len(pnp_point2D_idxs) == len(pnp_points3D_id)
+        conf = self.conf
+        require_feats = conf["QKA"]["apply"] or conf["QBA"]["apply"]
+        assert image_path is not None or query_fmaps is not None or not require_feats
+        if len(pnp_point2D_idxs) == 0:
+            return {"success": False}
+        pnp_point2D_idxs = [int(i) for i in pnp_point2D_idxs]
+        pnp_points3D = [self.reconstruction.points3D[p3D_id].xyz for p3D_id in pnp_points3D_id]
+        keypoints = np.array(keypoints, dtype=np.float64)
+
+        # Extract Features
+        if query_fmaps is None and require_feats:
+            if self.extractor is None:
+                from .extract import FeatureExtractor
+                self.extractor = FeatureExtractor(conf["dense_features"], ctx=self.ctx)
+            required_kp_ids = list(OrderedDict.fromkeys(pnp_point2D_idxs))
+            query_fmaps = self.extractor(image_path, keypoints=keypoints[required_kp_ids], as_dict=False,
+                                         keypoint_ids=required_kp_ids, overwrite_sparse=conf["overwrite_features_sparse"])
+
+        # Get references for this query
+        pnp_points2D = keypoints[pnp_point2D_idxs]
+        query_references = None
+        if require_feats:
+            query_references = self.get_query_references(pnp_points3D_id, query_fmaps, pnp_points2D, pnp_point2D_idxs)
+            assert len(query_fmaps) == len(query_references)
+
+        # Run QKA
+        if conf["QKA"]["apply"]:
+            self.query_keypoint_adjuster.refine_multilevel(pnp_points2D, query_fmaps, query_references,
+                                                           point2D_idxs=pnp_point2D_idxs)
+
+        # Run PnP
+        pose_dict = absolute_pose_estimation(pnp_points2D, pnp_points3D, query_camera,
+                                             estimation_options=conf["PnP"]["estimation"],
+                                             refinement_options=conf["PnP"]["refinement"], ctx=self.ctx)
+        if not pose_dict["success"]:
+            return pose_dict
+
+        # For QBA we optionally select unique 2D-3D correspondences
+        inliers = pose_dict["inliers"]
+        if conf["unique_inliers"]:                  # None and False: keep all
+            if conf["unique_inliers"] == "random":
+                inliers = find_unique_inliers(pnp_points3D_id, pre_inliers=inliers)
+            elif conf["unique_inliers"] == "min_error":
+                inliers = find_unique_min_reproj_inliers(pnp_points3D_id, pose_dict["qvec"], pose_dict["tvec"], query_camera,
+                                                         pnp_points2D, self.reconstruction, pre_inliers=inliers,
+                                                         point2D_idxs=pnp_point2D_idxs)
+            else:
+                import warnings
+                warnings.warn("Unknown unique_inlier method %s." % (conf["unique_inliers"],))
+        self.last_qba_inliers = list(inliers)
+
+        # Run QBA
+        if conf["QBA"]["apply"]:
+            self.query_bundle_adjuster.refine_multilevel(pose_dict["qvec"], pose_dict["tvec"], query_camera, pnp_points3D,
+                                                         query_fmaps, query_references, inliers=inliers,
+                                                         point2D_idxs=pnp_point2D_idxs)
+
+        # We recompute the inliers from the final pose
+        errors = compute_reprojection_errors(pnp_points2D, pnp_points3D, pose_dict["qvec"], pose_dict["tvec"], query_camera)
+        max_error = conf["PnP"]["estimation"]["ransac"]["max_error"]
+        pose_dict["inliers"] = [bool(err < max_error) for err in errors]
+        pose_dict["num_inliers"] = sum(pose_dict["inliers"])
+        return pose_dict
+
+    def get_nearest_references(self, pnp_points3D_id, query_fmaps, pnp_points2D, patch_idxs):
+        return [find_nearest_references(query_fmaps[level], refs, pnp_points2D, pnp_points3D_id, self.conf["interpolation"],
+                                        patch_idxs=patch_idxs, ctx=self.ctx) for level, refs in enumerate(self.references)]
+
+    def get_robust_mean_references(self, pnp_points3D_id, *args):
+        return [[np.asarray(refs[p3D_id].descriptor) for p3D_id in pnp_points3D_id] for refs in self.references]
+
+    def get_all_references(self, pnp_points3D_id, *args):
+        q_references = [[] for _ in self.references]
+        for level, refs in enumerate(self.references):
+            for p3D_id in pnp_points3D_id:
+                if not refs[p3D_id].has_observations():
+                    raise RuntimeError("Missing descriptors for observations.\nAssure that references.keep_observations==True.")
+                q_references[level].append(list(refs[p3D_id].observations))
+        return q_references
+
+    def get_full_references(self, pnp_points3D_id, *args):
+        raise NotImplementedError("target_reference 'full' feeds the patch-warp cost, which is outside the accelerated path; "
+                                  "use 'nearest', 'robust_mean' or 'all_observations'")

@@ -856,3 +856,69 @@ class TriangulationProblem:
             check(ctx.lib.pxr_triangulate_tracks(ctx.handle, C.byref(self.view), C.byref(opts), d_xyz.ptr, d_status.ptr,
                                                  d_ninl.ptr, d_inl.ptr, d_err.ptr), "pxr_triangulate_tracks")
         return d_xyz, d_status, d_ninl, d_inl, d_err
+
+
+def abspose_options(max_error=12.0, min_inlier_ratio=0.01, min_num_inliers=4, confidence=0.99999, min_num_trials=64,
+                    max_num_trials=4096, round_size=64, seed=0, refine_max_iterations=100, refine_loss_scale=1.0, lo_rounds=4):
+    """pxr_abspose_options: pycolmap 0.x / COLMAP 3.8's AbsolutePoseEstimationOptions and AbsolutePoseRefinementOptions values
+    with the reference's max_error of 12 px, and the estimator's own round_size, seed and lo_rounds."""
+    return _lib.AbsposeOptions(float(max_error), float(min_inlier_ratio), float(confidence), float(refine_loss_scale), int(seed),
+                               int(min_num_inliers), int(min_num_trials), int(max_num_trials), int(round_size),
+                               int(refine_max_iterations), int(lo_rounds))
+
+
+class AbsolutePoseProblem:
+    """Device-resident flat arrays of a batch of absolute-pose queries (pxr_absolute_pose): the 2D-3D correspondences of
+    every query in CSR form, one camera per query.
+
+    problem: dict with query_offsets (n_queries + 1), xy (n_corr x 2, image pixels, COLMAP convention), xyz (n_corr x 3),
+    query_camera (n_queries), cam_model, cam_params (n_cams x <= KPAD).
+    """
+
+    def __init__(self, ctx, problem):
+        self.ctx = ctx
+        g = problem
+        offsets = np.ascontiguousarray(g["query_offsets"], dtype=np.int64).reshape(-1)
+        if len(offsets) < 1:
+            raise ValueError("query_offsets must hold n_queries + 1 entries")
+        self.n_queries = len(offsets) - 1
+        xy = np.ascontiguousarray(g["xy"], dtype=np.float64).reshape(-1, 2)
+        xyz = np.ascontiguousarray(g["xyz"], dtype=np.float64).reshape(-1, 3)
+        if len(xy) != len(xyz):
+            raise ValueError("xy and xyz must hold one row per correspondence")
+        self.n_corr = len(xy)
+        self.n_cameras = len(g["cam_model"])
+        if len(np.asarray(g["query_camera"]).reshape(-1)) != self.n_queries:
+            raise ValueError("query_camera must hold one camera per query")
+        self.d = {
+            "query_offsets": ctx.to_device(offsets, np.int64),
+            "xy": ctx.to_device(xy, np.float64),
+            "xyz": ctx.to_device(xyz, np.float64),
+            "query_camera": ctx.to_device(np.asarray(g["query_camera"]).reshape(-1), np.int32),
+            "cam_model": ctx.to_device(g["cam_model"], np.int32),
+            "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
+        }
+        self.kernel_ms = None
+
+    def estimate(self, qvec=None, tvec=None, timed=False, **options):
+        """Run the kernels (pxr_absolute_pose) with abspose_options(**options).  Returns the device arrays (qvec (n_queries, 4),
+        tvec (n_queries, 3), status, n_inliers, n_trials (n_queries,) int32, inlier (n_corr,) uint8, err (n_corr,) float64).
+        qvec / tvec: host arrays the outputs start from -- rows of queries without a pose keep them (default: NaN).  timed: also
+        keep the kernels' HIP-event times in self.kernel_ms {"records", "compact", "hypotheses", "refine"} (milliseconds)."""
+        ctx, d, T, N = self.ctx, self.d, self.n_queries, self.n_corr
+        opts = abspose_options(**options)
+        q0 = np.full((T, 4), np.nan) if qvec is None else np.asarray(qvec, dtype=np.float64).reshape(T, 4)
+        t0 = np.full((T, 3), np.nan) if tvec is None else np.asarray(tvec, dtype=np.float64).reshape(T, 3)
+        d_q, d_t = ctx.to_device(q0, np.float64), ctx.to_device(t0, np.float64)
+        d_status, d_ninl, d_ntr = ctx.empty((T,), np.int32), ctx.empty((T,), np.int32), ctx.empty((T,), np.int32)
+        d_inl, d_err = ctx.empty((N,), np.uint8), ctx.empty((N,), np.float64)
+        args = (ctx.handle, T, d["query_offsets"].ptr, N, d["xy"].ptr, d["xyz"].ptr, d["query_camera"].ptr, self.n_cameras,
+                d["cam_model"].ptr, d["cam_params"].ptr, C.byref(opts), d_q.ptr, d_t.ptr, d_status.ptr, d_ninl.ptr, d_ntr.ptr,
+                d_inl.ptr, d_err.ptr)
+        if timed:
+            ms = (C.c_double * 4)()
+            check(ctx.lib.pxr_absolute_pose_timed(*args, ms), "pxr_absolute_pose_timed")
+            self.kernel_ms = dict(zip(("records", "compact", "hypotheses", "refine"), (float(x) for x in ms)))
+        else:
+            check(ctx.lib.pxr_absolute_pose(*args), "pxr_absolute_pose")
+        return d_q, d_t, d_status, d_ninl, d_ntr, d_inl, d_err
