@@ -41,8 +41,7 @@ inline int struct_error(const StructError& e) { return set_error(PXR_EINVAL, e.f
 
 // the environment knobs of a solve, read once per call (tests flip them between solves of one process)
 struct SolveKnobs {
-  bool arena, setup_host, verbose, spin_wait, inner_old, inner_packed, inner_no_cache, schur_lds, phase_timing;
-  int schur_ctiles;             // 0: not set
+  bool arena, setup_host, verbose, spin_wait, inner_packed, inner_no_cache, inner_no_prebuild, schur_lds, phase_timing;
   SolveKnobs();
 };
 

@@ -11,15 +11,13 @@
 //
 // Mappings.  fp16 / fp32 feature patches (C = 64, 128), tracks of <= 16 observations, the five hand-derived camera models:
 // k_inner_gram_packed -- the nested LM on the Gram matrices of the observations' stencils, up to four points per wavefront in
-// lockstep, four lanes per observation (described at the kernel; k_inner_gram is its one-point-per-wavefront predecessor,
-// kept as an A/B knob).  Longer tracks and extended camera models: k_inner_packed -- the descriptor interpolated at every
+// lockstep, four lanes per observation (described at the kernel).  Longer tracks and extended camera models: k_inner_packed -- the descriptor interpolated at every
 // round, 16 observations per wavefront trip, four lanes each.  fp64 storage and cost maps (C = 1, 3): k_inner_points -- one
 // point per wavefront (eight for cost maps), an observation per row of C / 8 lanes, the whole nested LM in registers.  All
 // return the cost at the (unrefined) candidate, so the outer loop needs no separate evaluation for Ceres' inner-iteration
 // bookkeeping.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 #include <vector>
 #include <algorithm>
@@ -42,7 +40,7 @@ struct InnerArgs {
   double* cost_before;         // += sum of 0.5 rho at the unrefined candidate
   double* cost_pt;             // deterministic mode (else NULL): [n_points] the per-point costs instead, summed in index order by the caller
   double* gram_G;              // the solve's Gram-matrix cache (pxr_ba_gram.hip; NULL: none): [n_obs][176] and the cells they were
-  int2* gram_cell;             // built for -- k_inner_gram copies a matrix instead of building it where the cell matches, and
+  int2* gram_cell;             // built for -- k_inner_gram_packed copies a matrix instead of building it where the cell matches, and
   int gram_warm;               // writes back what it builds; gram_warm = 0: nothing cached yet (the first call of a solve)
 };
 
@@ -723,368 +721,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // and D = T d (16) every sum is a quadratic / linear form in the weights:  f.f = w^t G w,  f.fc = w^t G wc, ...,  f.d = w.D.
 // G and D are built ONCE per observation -- sixteen texels x C channels cross HBM once, the contraction over the channels is
 // 32 v_mfma_f64_16x16x4 (A = B = one texel value per lane, fp64 accumulators: fp16 products are exact, the sums carry full
-// double precision) -- and stay in LDS (2 KB per observation) while the point iterates.  One wavefront = one point; an
-// observation takes 8 lanes, each with two rows of its G: a round is 88 fused multiply-adds and nine 8-lane reductions per
-// lane instead of 2 048 texel loads' worth of splines.  The nested LM moves a point by a fraction of a texel, so the 4 x 4
-// cell rarely changes between rounds; when it does (floor(u), floor(v) differ from the cached cell) that observation's Gram
-// matrix is rebuilt.
+// double precision) -- and stay in LDS (1.3 KB per observation) while the point iterates: a round is a few hundred fused
+// multiply-adds per lane instead of 2 048 texel loads' worth of splines.  The nested LM moves a point by a fraction of a
+// texel, so the 4 x 4 cell rarely changes between rounds; when it does (floor(u), floor(v) differ from the cached cell) that
+// observation's Gram matrix is rebuilt.
 //
 // Arithmetic: the reference interpolates with an fp32 horizontal pass (cubic_hermite_spline_simd.h); here the whole bicubic
 // is exact-in-fp64 algebra on the Gram matrix, so a round's cost differs from the exact-order kernels' by ~1e-7 relative
 // (the fp32 pass's own rounding) -- inside the nested LM's 1e-6 tolerances, and like k_inner_packed's channel-sum
 // normalisation it only steers Ceres' heuristic refinement: the outer loop re-evaluates the refined candidate with the
 // exact-order kernel.  Points with more than IG_MAXO observations take k_inner_packed (the host splits the points).
-#ifndef PXR_GRAM_WAVES
-#define PXR_GRAM_WAVES 2     // wavefronts per SIMD the kernel is compiled for (tools/inner_gram_probe.sh builds the others)
-#endif
-constexpr int IG_MAXO = 16;   // observations per point whose Gram matrices fit the wavefront's LDS (two trips of 8)
+//
+// Mapping: a wavefront takes up to four points whose observations fill at most sixteen slots (the host packs consecutive short
+// tracks: three 5-observation tracks per wavefront), an observation takes FOUR lanes -- lane R works on block row R of its Gram
+// matrix, rows 4 R .. 4 R + 3 -- and the points iterate in lockstep like in k_inner_packed: one round costs the same ~800 wave
+// instructions whether it serves one point or four (one point per wavefront repeated the projection, the weights, the
+// robustifier and the owner's trust-region step for five observations on 40 lanes: ~3 900 wave instructions per point,
+// profiles/r4_hot_kernels_pmc.json; docs/DESIGN_HISTORY.md, "Variants removed").  The nine sums are bilinear forms per 4 x 4
+// block:  B(a, b) = sum_ir sum_cc a[ir] G[4 R + ir][4 Cb + cc] b[cc]  with a, b the horizontal weights or their derivatives,
+// scaled by the vertical weights of block row R and block column Cb; a block below the diagonal is the transposed stored block,
+// i.e. the stored block's form with a and b swapped.
+constexpr int IG_MAXO = 16;   // observations per point whose Gram matrices fit the wavefront's LDS (one wavefront's sixteen slots)
 constexpr int IG_OBS = 32;    // doubles of an observation record: IP_OBS + the cell its Gram matrix was built for
-#ifndef PXR_GRAM_GSTRIDE
-#define PXR_GRAM_GSTRIDE 160      // doubles between two observations' Gram matrices in LDS (>= 160; padding rotates the banks)
-#endif
-constexpr int IG_GSTRIDE = PXR_GRAM_GSTRIDE;
-static_assert(IG_GSTRIDE >= IG_GDOUBLES, "ten 4 x 4 blocks per observation");   // (164 / 168 / 176: same 3.45 ms -- the 30 % LDS bank conflicts of the counters are not what bounds the kernel)
-
-// one entry of the host's list of points for k_inner_gram
-struct GramPoint { int p, len; int64_t o0; };
-// per observation of a listed point: what the staging needs without walking obs -> image -> camera
+// per observation slot of the kernel's table: what the staging needs without walking obs -> image -> camera
 struct GramSlot { int img, cam; int64_t patch; int64_t obs; };
-// The kernel's table: entry e = {GramPoint, GramSlot[maxo]} at e * gram_entry_bytes(maxo) -- addressed by the workgroup index
-// alone, so the list entry and its slots arrive in ONE round trip; the slots beyond the track's length repeat its last
-// observation (a lane may read its slot before it knows the length).
-__host__ __device__ inline size_t gram_entry_bytes(int maxo) { return sizeof(GramPoint) + sizeof(GramSlot) * (size_t)maxo; }
-__global__ __launch_bounds__(256) void k_gram_table(int64_t n_list, int maxo, const GramPoint* __restrict__ pt_list, const int64_t* __restrict__ pt_obs,
-                                                    const int32_t* __restrict__ obs_image, const int64_t* __restrict__ obs_patch,
-                                                    const int32_t* __restrict__ image_camera, char* __restrict__ table) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t e = t / (maxo + 1);
-  const int q = (int)(t % (maxo + 1)) - 1;                 // -1: the header
-  if (e >= n_list) return;
-  const GramPoint gp = pt_list[e];
-  char* ent = table + (size_t)e * gram_entry_bytes(maxo);
-  if (q < 0) { *reinterpret_cast<GramPoint*>(ent) = gp; return; }
-  const int64_t i = pt_obs[gp.o0 + min(q, gp.len - 1)];
-  const int img = obs_image[i];
-  reinterpret_cast<GramSlot*>(ent + sizeof(GramPoint))[q] = GramSlot{img, image_camera[img], obs_patch[i], i};
-}
-
-// dynamic LDS of k_inner_gram for points of at most `maxo` observations, in doubles
-__host__ __device__ inline size_t gram_lds_doubles(int maxo, int C) {
-  return (size_t)maxo * (IG_GSTRIDE + 16 + IG_OBS) + C + (sizeof(InnerOwner) + 7) / 8;
-}
-
-template <typename ST, int C>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PXR_GRAM_WAVES, PXR_GRAM_WAVES))) void k_inner_gram(const InnerArgs a, const char* __restrict__ table, const int maxo) {
-  static_assert(C == 128 || C == 64, "feature patches");
-  extern __shared__ __align__(16) double gsh[];
-  double* const Gs = gsh;                                  // [maxo][160]
-  double* const Ds = Gs + (size_t)maxo * IG_GSTRIDE;      // [maxo][16]
-  double* const obs = Ds + (size_t)maxo * 16;              // [maxo][IG_OBS]: R (9) t (3) k (12) sx sy corner (2) model patch cell (2)
-  double* const refd = obs + (size_t)maxo * IG_OBS;        // [C] reference descriptor
-  InnerOwner& S = *reinterpret_cast<InnerOwner*>(refd + C);
-  const int lane = threadIdx.x;
-#ifdef PXR_INNER_PROFILE   // tools/inner_phase_probe.sh: two wavefronts print how their shader-clock cycles split over the phases
-  long long gq_t = __builtin_amdgcn_s_memtime(), gq_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int gq_rounds = 0, gq_builds = 0;
-#define GQ_MARK(k) do { const long long n_ = __builtin_amdgcn_s_memtime(); gq_acc[k] += n_ - gq_t; gq_t = n_; } while (0)
-#else
-#define GQ_MARK(k) do { } while (0)
-#endif
-  const char* const ent = table + (size_t)blockIdx.x * gram_entry_bytes(maxo);
-  const GramSlot* const slots = reinterpret_cast<const GramSlot*>(ent + sizeof(GramPoint));   // this point's
-  const GramPoint gp = *reinterpret_cast<const GramPoint*>(ent);
-  const int64_t p = gp.p;
-  const int L = gp.len;                                    // 1 .. maxo (the host's lists)
-  const bool variable = a.pt_var[p] != 0;
-  bool active = variable, first = true;                    // (meaningful on lane 0, the owner)
-  const ST* arena = reinterpret_cast<const ST*>(a.arena);
-  const size_t patch_elems = (size_t)a.H * a.W * C;
-  const bool l2 = a.l2_normalize != 0;
-
-  // ---- staging: reference, observation records (rotation matrix of the unit quaternion), cached Gram matrices, owner state.
-  //      Two dependent round trips -- the table entry (list entry + slots, addressed by the workgroup index), then what the
-  //      slots address, everything of it in flight together (the copies of the cached matrices are requested before the
-  //      parameters and stored after them: the loads return in order).
-  const int sq = lane >> 2, part = lane & 3;
-  const GramSlot sl = slots[min(sq, maxo - 1)];            // (slots beyond the track's length repeat its last observation)
-  double refv[C / 64];
-#pragma unroll
-  for (int j = 0; j < C / 64; ++j) refv[j] = a.v.d_refs ? a.v.d_refs[(size_t)p * C + lane + 64 * j] : 0.0;
-  // The solve keeps every observation's Gram matrix for the cell of its last evaluation / inner call (pxr_ba_gram.hip): copy
-  // the 1 408 bytes instead of reading 4 KB of texels and running 32 MFMAs.  Speculative -- the first round rebuilds the few
-  // whose projection at the candidate left that cell.  Eight observations per batch (unconditional loads at clamped slots:
-  // scalars, not a scratch array).
-  const bool warm = a.gram_G != nullptr && a.gram_warm != 0;
-  const int hi = lane < 24 ? lane : 23;
-  double2 va0, va1, va2, va3, va4, va5, va6, va7, vb0, vb1, vb2, vb3, vb4, vb5, vb6, vb7;
-#define IG_FETCH(Q0, J, VA, VB)                                                                                             \
-  {                                                                                                                         \
-    const int64_t oi = __shfl((int)sl.obs, 4 * min(Q0 + J, L - 1));      /* (observation indices fit 31 bits) */              \
-    const double2* g = reinterpret_cast<const double2*>(a.gram_G + (size_t)oi * (IG_GDOUBLES + 16));                         \
-    VA = g[lane]; VB = g[64 + hi];                                                                                          \
-  }
-#define IG_PUT(Q0, J, VA, VB)                                                                                               \
-  if (Q0 + J < L) {                                                                                                         \
-    double2* Gd = reinterpret_cast<double2*>(Gs + (size_t)(Q0 + J) * IG_GSTRIDE);                                           \
-    Gd[lane] = VA;                                              /* doubles 0 .. 127 of G */                                 \
-    if (lane < 16) Gd[64 + lane] = VB;                          /* 128 .. 159 */                                            \
-    else if (lane < 24) reinterpret_cast<double2*>(Ds + (size_t)(Q0 + J) * 16)[lane - 16] = VB;   /* D */                   \
-  }
-#define IG_FETCH8(Q0) IG_FETCH(Q0, 0, va0, vb0) IG_FETCH(Q0, 1, va1, vb1) IG_FETCH(Q0, 2, va2, vb2) IG_FETCH(Q0, 3, va3, vb3) \
-                      IG_FETCH(Q0, 4, va4, vb4) IG_FETCH(Q0, 5, va5, vb5) IG_FETCH(Q0, 6, va6, vb6) IG_FETCH(Q0, 7, va7, vb7)
-#define IG_PUT8(Q0) IG_PUT(Q0, 0, va0, vb0) IG_PUT(Q0, 1, va1, vb1) IG_PUT(Q0, 2, va2, vb2) IG_PUT(Q0, 3, va3, vb3) \
-                    IG_PUT(Q0, 4, va4, vb4) IG_PUT(Q0, 5, va5, vb5) IG_PUT(Q0, 6, va6, vb6) IG_PUT(Q0, 7, va7, vb7)
-  if (warm) { IG_FETCH8(0) }
-  if (sq < L) {
-    double* ob = obs + (size_t)sq * IG_OBS;
-    const int img = sl.img, cam = sl.cam;
-    const int64_t pi = sl.patch;
-    if (part == 0) {
-      double R[9];
-      quat_to_rotation(a.v.d_qvec + 4 * (size_t)img, R);
-#pragma unroll
-      for (int m = 0; m < 9; ++m) ob[m] = R[m];
-#pragma unroll
-      for (int m = 0; m < 3; ++m) ob[9 + m] = a.v.d_tvec[3 * (size_t)img + m];
-    } else if (part == 1) {
-#pragma unroll
-      for (int m = 0; m < 6; ++m) ob[12 + m] = a.v.d_cam_params[(size_t)cam * PXR_KPAD + m];
-    } else if (part == 2) {
-#pragma unroll
-      for (int m = 6; m < PXR_KPAD; ++m) ob[12 + m] = a.v.d_cam_params[(size_t)cam * PXR_KPAD + m];
-    } else {
-      ob[24] = a.scales[2 * pi]; ob[25] = a.scales[2 * pi + 1];
-      ob[26] = (double)a.corners[2 * pi]; ob[27] = (double)a.corners[2 * pi + 1];
-      ob[28] = (double)a.v.d_cam_model[cam]; ob[29] = (double)pi;
-      // the cell its Gram matrix was built for: none yet -- or the cached matrix's
-      int2 cc = make_int2(-1000000, -1000000);
-      if (warm) cc = a.gram_cell[sl.obs];
-      ob[30] = (double)cc.x; ob[31] = (double)cc.y;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < C / 64; ++j) refd[lane + 64 * j] = refv[j];
-  if (warm) {
-    IG_PUT8(0)
-#pragma unroll 1
-    for (int q0 = 8; q0 < L; q0 += 8) { IG_FETCH8(q0) IG_PUT8(q0) }
-  }
-#undef IG_FETCH
-#undef IG_PUT
-#undef IG_FETCH8
-#undef IG_PUT8
-  if (lane == 0) {
-#pragma unroll
-    for (int m = 0; m < 3; ++m) { S.X[m] = a.v.d_xyz[3 * p + m]; S.Xc[m] = S.X[m]; }
-    S.live = 1; S.radius = 1e4; S.decrease_factor = 2.0; S.invalid = 0; S.it = 0; S.reuse_diag = 0; S.mcc = 0.0;
-  }
-  __syncthreads();
-  {   // d.d of the reference
-    double r2 = 0.0;
-    for (int ch = lane; ch < C; ch += 64) r2 = fma(refd[ch], refd[ch], r2);
-    r2 = rows_sum<16>(row16_sum(r2));
-    if (lane == 0) S.r2 = r2;
-  }
-
-  // 8 lanes per observation, lane `sub` works on rows 2 sub, 2 sub + 1 of its Gram matrix; trip k: observations 8k .. 8k + 7
-  const int sidx = lane >> 3, sub = lane & 7, ri = sub >> 1, ci = 2 * (sub & 1);
-  GQ_MARK(0);
-
-  while (true) {
-    __syncthreads();
-    double rs[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};       // this lane's observations: cost, H (6), g (3) (lanes with sub == 0)
-#pragma unroll 1
-    for (int k = 0; 8 * k < L; ++k) {
-      const int q = 8 * k + sidx;
-      const bool act = q < L;
-      double* ob = obs + (size_t)(act ? q : L - 1) * IG_OBS;
-      // WorldToPixel (base/src/projection.h:60-75) and d(x,y)/dX = d(x,y)/d(u,v) d(u,v)/dp R, on every lane of the observation
-      double R[9];
-#pragma unroll
-      for (int m = 0; m < 9; ++m) R[m] = ob[m];
-      const double sx = ob[24], sy = ob[25], cx = ob[26], cy = ob[27];
-      const int model = (int)ob[28];
-      const double X0 = S.Xc[0], X1 = S.Xc[1], X2 = S.Xc[2];
-      const double p0 = fma(R[0], X0, fma(R[1], X1, fma(R[2], X2, ob[9])));
-      const double p1 = fma(R[3], X0, fma(R[4], X1, fma(R[5], X2, ob[10])));
-      const double p2 = fma(R[6], X0, fma(R[7], X1, fma(R[8], X2, ob[11])));
-      const double iz = inner_rcp(p2), un = p0 * iz, vn = p1 * iz;
-      double x, y, Juv[2][2];
-      camera_model_jac<false, false>(model, ob + 12, un, vn, x, y, Juv, nullptr);   // (no extended models here: the host's routing)
-      double PX[2][3];
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const double A0 = Juv[r][0] * iz, A1 = Juv[r][1] * iz, A2 = -(Juv[r][0] * un + Juv[r][1] * vn) * iz;
-#pragma unroll
-        for (int m = 0; m < 3; ++m) PX[r][m] = A0 * R[m] + A1 * R[3 + m] + A2 * R[6 + m];
-      }
-      const double u = x * sx - 0.5 - cx, v = y * sy - 0.5 - cy;   // FeaturePatch::ToPixelCoordinates (featurepatch.h:250-255)
-      const double rf = floor(v), cf = floor(u);
-      const int row = texel_index(rf, a.H), col = texel_index(cf, a.W);
-      // -- (re)build the Gram matrices of this trip's observations whose cell moved: wave-uniform control flow, all 64 lanes;
-      //    the texels of the next one are requested before the MFMA chain of the current one --
-      const bool need = act && ((double)row != ob[30] || (double)col != ob[31]);
-      unsigned long long todo = __ballot(need);
-      GQ_MARK(1);
-      if (todo != 0ull) {
-        const int64_t pi = (int64_t)ob[29];
-        const int pi_lo = (int)(pi & 0xffffffffll), pi_hi = (int)(pi >> 32);
-        auto request = [&](GramTexels<ST, C>& tx, int src_lane) {
-          const int row_t = __builtin_amdgcn_readlane(row, src_lane), col_t = __builtin_amdgcn_readlane(col, src_lane);
-          const int64_t pi_t = ((int64_t)__builtin_amdgcn_readlane(pi_hi, src_lane) << 32) | (unsigned)__builtin_amdgcn_readlane(pi_lo, src_lane);
-          tx.load(arena + (size_t)pi_t * patch_elems, a.H, a.W, row_t, col_t);
-        };
-        // a ring of three stencils in flight: a build's MFMA chain (~1 us) is shorter than the latency of its texels (~2 us under
-        // load; with one stencil ahead every build waited for its loads: 6 000 cycles per build, profiles/r4_inner_gram_probe.txt)
-        auto take = [&](GramTexels<ST, C>& tx) -> int {    // request the next observation's texels; -1: none left
-          if (todo == 0ull) return -1;
-          const int src = __ffsll((long long)todo) - 1;
-          todo &= ~(0xffull << (src & ~7));
-          request(tx, src);
-          return src;
-        };
-        GramTexels<ST, C> t0, t1, t2;
-        int s0 = take(t0), s1 = take(t1), s2 = take(t2);
-        while (true) {
-          if (s0 < 0) break;
-          gram_contract<ST, C>(t0, refd, Gs + (size_t)(8 * k + (s0 >> 3)) * IG_GSTRIDE, Ds + (size_t)(8 * k + (s0 >> 3)) * 16);
-          s0 = take(t0);
-          if (s1 < 0) break;
-          gram_contract<ST, C>(t1, refd, Gs + (size_t)(8 * k + (s1 >> 3)) * IG_GSTRIDE, Ds + (size_t)(8 * k + (s1 >> 3)) * 16);
-          s1 = take(t1);
-          if (s2 < 0) break;
-          gram_contract<ST, C>(t2, refd, Gs + (size_t)(8 * k + (s2 >> 3)) * IG_GSTRIDE, Ds + (size_t)(8 * k + (s2 >> 3)) * 16);
-          s2 = take(t2);
-        }
-        if (need && sub == 0) { ob[30] = (double)row; ob[31] = (double)col; }
-        __syncthreads();                                 // the Gram matrices written by all lanes -> visible to their readers
-        if (a.gram_G) {
-          // ... and kept for the next call (and for the LM loop's evaluation, pxr_ba_gram.hip): an observation belongs to
-          // one point, a point to one wavefront -- nobody else touches these 1 408 bytes
-          unsigned long long wb = __ballot(need);
-          while (wb != 0ull) {
-            const int src = __ffsll((long long)wb) - 1;
-            wb &= ~(0xffull << (src & ~7));
-            const int slot = 8 * k + (src >> 3);
-            const int64_t oi = slots[slot].obs;
-            double2* g = reinterpret_cast<double2*>(a.gram_G + (size_t)oi * (IG_GDOUBLES + 16));
-            const double2* Gd = reinterpret_cast<const double2*>(Gs + (size_t)slot * IG_GSTRIDE);
-            g[lane] = Gd[lane];
-            if (lane < 16) g[64 + lane] = Gd[64 + lane];
-            else if (lane < 24) g[64 + lane] = reinterpret_cast<const double2*>(Ds + (size_t)slot * 16)[lane - 16];
-            const int2 cl = make_int2(__builtin_amdgcn_readlane(row, src), __builtin_amdgcn_readlane(col, src));
-            if (lane == 0) a.gram_cell[oi] = cl;
-          }
-        }
-#ifdef PXR_INNER_PROFILE
-        gq_builds += __popcll(__ballot(need)) / 8;
-#endif
-        GQ_MARK(2);
-      }
-      if (act) {
-        double wu[4], dwu[4], wv[4], dwv[4];
-        catmull_rom_weights(u - cf, wu, dwu);
-        catmull_rom_weights(v - rf, wv, dwv);
-        double ya[3], yb[3];                              // (G w, G wc, G wr) at rows 2 sub and 2 sub + 1
-        gram_rows_times_weights(Gs + (size_t)q * IG_GSTRIDE, sub, wu, dwu, wv, dwv, ya, yb);
-        const double2 d2 = *reinterpret_cast<const double2*>(Ds + (size_t)q * 16 + 2 * sub);
-        const double wvo = pick4(wv, ri), dwvo = pick4(dwv, ri);
-        const double wua = ci == 0 ? wu[0] : wu[2], wub = ci == 0 ? wu[1] : wu[3];
-        const double dwua = ci == 0 ? dwu[0] : dwu[2], dwub = ci == 0 ? dwu[1] : dwu[3];
-        const double oma = wvo * wua, omb = wvo * wub, omca = wvo * dwua, omcb = wvo * dwub, omra = dwvo * wua, omrb = dwvo * wub;
-        const double Sgg = row8_sum(fma(oma, ya[0], omb * yb[0])), Sgc = row8_sum(fma(oma, ya[1], omb * yb[1]));
-        const double Sgr = row8_sum(fma(oma, ya[2], omb * yb[2]));
-        const double Scc = row8_sum(fma(omca, ya[1], omcb * yb[1])), Scr = row8_sum(fma(omca, ya[2], omcb * yb[2]));
-        const double Srr = row8_sum(fma(omra, ya[2], omrb * yb[2]));
-        const double Sfd = row8_sum(fma(oma, d2.x, omb * d2.y)), Scd = row8_sum(fma(omca, d2.x, omcb * d2.y));
-        const double Srd = row8_sum(fma(omra, d2.x, omrb * d2.y));
-        double s, gcc, gcr, grr, bc, br;
-        if (l2) {
-          const double ninv = inner_rsqrt(Sgg), n2inv = ninv * ninv;
-          const double pc = Sgc * n2inv, pr = Sgr * n2inv;
-          s = fmax(0.0, 1.0 - 2.0 * Sfd * ninv + S.r2);
-          gcc = (Scc - Sgc * pc) * n2inv; gcr = (Scr - Sgc * pr) * n2inv; grr = (Srr - Sgr * pr) * n2inv;
-          bc = -(Scd - Sfd * pc) * ninv; br = -(Srd - Sfd * pr) * ninv;
-        } else {          // r = f - d
-          s = fmax(0.0, Sgg - 2.0 * Sfd + S.r2);
-          gcc = Scc; gcr = Scr; grr = Srr; bc = Sgc - Scd; br = Sgr - Srd;
-        }
-        double rho[3];
-        inner_loss(a.loss.type, a.loss.a, s, rho);
-        double cq = 0.5 * rho[0];
-        if (a.check_bounds && !a.v.d_refs && !(u > 0.0 && u < (double)a.W && v > 0.0 && v < (double)a.H)) cq = __builtin_nan("");
-        gcc *= sx * sx; gcr *= sx * sy; grr *= sy * sy; bc *= sx; br *= sy;
-        double kappa = 0.0;   // Ceres' corrector (corrector.cc): alpha = 1 - sqrt(1 + 2 s rho'' / rho')
-        if (s != 0.0 && rho[2] > 0.0) {
-          const double D = 1.0 + 2.0 * s * rho[2] * inner_rcp(rho[1]);
-          const double alpha = 1.0 - sqrt(D);
-          kappa = (2.0 * alpha - alpha * alpha) * inner_rcp(s);
-        }
-        const double w8 = rho[1];
-        const double m00 = w8 * (gcc - kappa * bc * bc), m01 = w8 * (gcr - kappa * bc * br), m11 = w8 * (grr - kappa * br * br);
-        const double b0 = w8 * bc, b1 = w8 * br;
-        double me0[3], me1[3];
-#pragma unroll
-        for (int m = 0; m < 3; ++m) { me0[m] = m00 * PX[0][m] + m01 * PX[1][m]; me1[m] = m01 * PX[0][m] + m11 * PX[1][m]; }
-        if (sub == 0) {
-          rs[0] += cq;
-          rs[1] += PX[0][0] * me0[0] + PX[1][0] * me1[0];
-          rs[2] += PX[0][0] * me0[1] + PX[1][0] * me1[1];
-          rs[3] += PX[0][0] * me0[2] + PX[1][0] * me1[2];
-          rs[4] += PX[0][1] * me0[1] + PX[1][1] * me1[1];
-          rs[5] += PX[0][1] * me0[2] + PX[1][1] * me1[2];
-          rs[6] += PX[0][2] * me0[2] + PX[1][2] * me1[2];
-#pragma unroll
-          for (int m = 0; m < 3; ++m) rs[7 + m] += PX[0][m] * b0 + PX[1][m] * b1;
-        }
-      }
-    }
-    // -- the owner (lane 0): the sum over the observations (a fixed tree over lanes 0, 8, .., 56; no LDS round trip), then
-    //    Ceres' trust-region bookkeeping --
-    GQ_MARK(3);
-#pragma unroll
-    for (int m = 0; m < 10; ++m) {
-      rs[m] += __shfl_xor(rs[m], 8); rs[m] += __shfl_xor(rs[m], 16); rs[m] += __shfl_xor(rs[m], 32);
-    }
-    GQ_MARK(4);
-    if (lane == 0) {
-      const double Hc[6] = {rs[1], rs[2], rs[3], rs[4], rs[5], rs[6]}, gc[3] = {rs[7], rs[8], rs[9]};
-      inner_owner_update(S, rs[0], Hc, gc, first, true, active, a.cost_before, a.cost_pt ? a.cost_pt + p : nullptr);
-    }
-    first = false;
-    GQ_MARK(5);
-#ifdef PXR_INNER_PROFILE
-    ++gq_rounds;
-#endif
-    if (__builtin_amdgcn_readfirstlane((int)active) == 0) break;
-  }
-#ifdef PXR_INNER_PROFILE
-  if ((blockIdx.x == 1000 || blockIdx.x == 150000) && lane == 0)
-    printf("[inner gram profile, wavefront %d, 100 MHz ticks x 10 ns] rounds %d builds %d  staging %lld  projection %lld  gram builds %lld  evaluation %lld  reduce %lld  owner LM %lld\n",
-           (int)blockIdx.x, gq_rounds, gq_builds, gq_acc[0], gq_acc[1], gq_acc[2], gq_acc[3], gq_acc[4], gq_acc[5]);
-#endif
-  if (variable && lane == 0) { a.xyz_out[3 * p] = S.X[0]; a.xyz_out[3 * p + 1] = S.X[1]; a.xyz_out[3 * p + 2] = S.X[2]; }
-}
-
-// ---- feature patches, fourth mapping: the Gram-matrix evaluation in the packed kernel's lockstep ------------------------------
-// k_inner_gram is bound by its vector instruction count (profiles/r4_hot_kernels_pmc.json: ~3 900 wave instructions per point,
-// the SIMDs 75 % busy issuing them): one point per wavefront repeats the projection, the weights, the robustifier and the
-// owner's trust-region step for five observations on 40 lanes.  Here a wavefront takes up to four points whose observations
-// fill at most sixteen slots (the host packs consecutive short tracks: three 5-observation tracks per wavefront), an
-// observation takes FOUR lanes -- lane R works on block row R of its Gram matrix, rows 4 R .. 4 R + 3 -- and the points
-// iterate in lockstep like in k_inner_packed: one round costs the same ~800 wave instructions whether it serves one point
-// or four.  The nine sums are bilinear forms per 4 x 4 block:  B(a, b) = sum_ir sum_cc a[ir] G[4 R + ir][4 Cb + cc] b[cc]  with
-// a, b the horizontal weights or their derivatives, scaled by the vertical weights of block row R and block column Cb; a block
-// below the diagonal is the transposed stored block, i.e. the stored block's form with a and b swapped.
 struct GramWave { int npts, pad; int p[IP_MAXPTS]; int st[IP_MAXPTS + 1]; int pad2; };   // points, first slot of each (st[npts] = slots used)
 static_assert(sizeof(GramWave) == 48, "table layout");
 constexpr int GW_SLOTS = 16;
 __host__ __device__ inline size_t gram_wave_bytes() { return sizeof(GramWave) + sizeof(GramSlot) * GW_SLOTS; }
-#ifndef PXR_GW_GPAD
-#define PXR_GW_GPAD 4          // doubles of padding between two slots' matrices: 1 280-byte slots put the same block of all sixteen on the same banks (0 / 2 / 4 / 6: 1.71 / 1.59 / 1.58 / 1.59 ms per call)
-#endif
+constexpr int GW_GPAD = 4;     // doubles of padding between two slots' matrices: 1 280-byte slots put the same block of all sixteen on the same banks (0 / 2 / 4 / 6: 1.71 / 1.59 / 1.58 / 1.59 ms per call)
 struct GramWaveLds {
-  double G[GW_SLOTS][IG_GDOUBLES + PXR_GW_GPAD];
+  double G[GW_SLOTS][IG_GDOUBLES + GW_GPAD];
   double D[GW_SLOTS][16];
   double obs[GW_SLOTS][IG_OBS];      // R (9) t (3) k (12) sx sy corner (2) model patch cell (2)
   double res[GW_SLOTS][10];
@@ -1449,12 +1116,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
 // Enqueue the inner iterations on the candidate parameters `view` (xyz refined in place);
 // *d_cost_before (device double, caller-zeroed) receives the cost at the unrefined candidate.
-// lists (may be NULL): the points with at most IG_MAXO observations (Gram-matrix kernel) and the others (packed kernel), made
-// once per solve by make_inner_lists.
+// lists: the points with at most IG_MAXO observations (Gram-matrix kernel) and the others (packed kernel), made once per solve
+// by make_inner_lists; NULL: the packed kernel (descriptor interpolated at every round) for every point.
+// prebuild: rebuild the stale matrices of the cache before the Gram-matrix kernel starts (false: inside it, a test's cross-check).
 int launch_inner_iterations(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, const pxr_interp_cfg* cfg,
                             const pxr_loss* loss, const int64_t* d_pt_ptr, const int64_t* d_pt_obs,
                             const int* d_pt_var, double* d_cost_before, const InnerLists* lists, double* d_cost_per_point,
-                            const GramCache* gram, bool gram_warm) {
+                            const GramCache* gram, bool gram_warm, bool prebuild) {
   if (arena->C != 128 && arena->C != 64 && arena->C != 3 && arena->C != 1)
     return set_error(PXR_EUNSUPPORTED, "inner iterations: CHANNELS=%d not supported (128, 64; cost maps: 3, 1)", arena->C);
   InnerArgs a;
@@ -1485,9 +1153,6 @@ int launch_inner_iterations(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
     else if (arena->C == 128) MACRO(float, 128, __VA_ARGS__);                           \
     else MACRO(float, 64, __VA_ARGS__);                                                 \
   } while (0)
-#define INNER_GRAM(ST, CC, NBLK, MAXO)                                                                                    \
-  hipLaunchKernelGGL((k_inner_gram<ST, CC>), dim3(NBLK), dim3(64), sizeof(double) * gram_lds_doubles(MAXO, CC), ctx->stream, a, \
-                     static_cast<const char*>(lists->d_slots), MAXO)
 #define INNER_GRAM_PACKED(ST, CC, NBLK) \
   hipLaunchKernelGGL((k_inner_gram_packed<ST, CC>), dim3(NBLK), dim3(64), 0, ctx->stream, a, static_cast<const char*>(lists->d_waves))
   if (arena->C <= 4) {
@@ -1497,16 +1162,8 @@ int launch_inner_iterations(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
     else if (arena->dtype == PXR_F32) INNER_LAUNCH(k_inner_points, float, 1);
     else if (arena->C == 3) INNER_LAUNCH(k_inner_points, double, 3);
     else INNER_LAUNCH(k_inner_points, double, 1);
-  } else if (getenv("PXR_INNER_OLD")) {   // A/B knob (tools/fuzz_solve_vs_oracle.py): the one-point-per-wavefront kernel for every storage type
-    if (arena->dtype == PXR_F16 && arena->C == 128) INNER_LAUNCH(k_inner_points, _Float16, 128);
-    else if (arena->dtype == PXR_F16) INNER_LAUNCH(k_inner_points, _Float16, 64);
-    else if (arena->dtype == PXR_F32 && arena->C == 128) INNER_LAUNCH(k_inner_points, float, 128);
-    else if (arena->dtype == PXR_F32) INNER_LAUNCH(k_inner_points, float, 64);
-    else if (arena->C == 128) INNER_LAUNCH(k_inner_points, double, 128);
-    else INNER_LAUNCH(k_inner_points, double, 64);
   } else if (arena->dtype != PXR_F64) {
-    // PXR_INNER_PACKED: A/B knob -- the round-3 kernel (descriptor interpolated at every round) for every point
-    if (lists == nullptr || getenv("PXR_INNER_PACKED")) {
+    if (lists == nullptr) {
       // packed kernel: points per wavefront from the mean track length (16 observation slots per trip)
       const int64_t per16 = view->n_obs > 0 ? (16 * view->n_points) / view->n_obs : 1;
       const int ppw = (int)(per16 < 1 ? 1 : (per16 > IP_MAXPTS ? IP_MAXPTS : per16));
@@ -1515,11 +1172,9 @@ int launch_inner_iterations(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
       INNER_BY_STORAGE(INNER_PACKED, pblocks, ppw, no_list);
     } else {
       // Gram-matrix kernel for the points whose observations' Gram matrices fit a wavefront's LDS, packed kernel (one point per
-      // wavefront) for the long tracks
-      // short tracks: up to four points (sixteen observation slots) per wavefront in lockstep; PXR_INNER_GRAM1=1 is the A/B knob
-      // for the one-point-per-wavefront kernel
+      // wavefront) for the long tracks; short tracks: up to four points (sixteen observation slots) per wavefront in lockstep
       if (lists->n_waves > 0) {
-        if (gram && !getenv("PXR_INNER_NO_PREBUILD")) {
+        if (gram && prebuild) {
           // the matrices the kernel will find stale are rebuilt before it starts (k_gram_flag_slots); after that the cache is warm
           PXR_HIP(hipMemsetAsync(gram->list, 0, sizeof(int) * (size_t)view->n_obs, ctx->stream));
           const int64_t n_thr = lists->n_waves * GW_SLOTS;
@@ -1530,14 +1185,12 @@ int launch_inner_iterations(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
         }
         INNER_BY_STORAGE(INNER_GRAM_PACKED, (unsigned)lists->n_waves);
       }
-      else if (lists->n_short > 0 && lists->d_slots) INNER_BY_STORAGE(INNER_GRAM, (unsigned)lists->n_short, lists->maxo_short);
       if (lists->n_long > 0) INNER_BY_STORAGE(INNER_PACKED, (unsigned)lists->n_long, 1, lists->d_long);
     }
   } else if (arena->dtype == PXR_F64 && arena->C == 128) INNER_LAUNCH(k_inner_points, double, 128);
   else INNER_LAUNCH(k_inner_points, double, 64);
 #undef INNER_LAUNCH
 #undef INNER_PACKED
-#undef INNER_GRAM
 #undef INNER_GRAM_PACKED
 #undef INNER_BY_STORAGE
   return hip_check(hipGetLastError(), "k_inner_points launch");
@@ -1550,16 +1203,11 @@ size_t inner_wave_stage_bytes(int64_t n_pts) { return sizeof(GramWave) * (size_t
 int make_inner_lists(pxr_ctx* ctx, const int64_t* pt_ptr, int64_t n, void* h_wave_stage, size_t wave_stage_bytes, const pxr_ba_view* view,
                      const int64_t* d_pt_ptr, const int64_t* d_pt_obs, InnerLists* out) {
   hipStream_t st = ctx->stream;
-  const bool one_point_kernel = getenv("PXR_INNER_GRAM1") != nullptr;      // (A/B knob: k_inner_gram's tables instead of the packed kernel's)
-  std::vector<GramPoint> shorts;
   std::vector<GramWave> waves_pageable;
   GramWave* wv = wave_stage_bytes >= inner_wave_stage_bytes(n) ? static_cast<GramWave*>(h_wave_stage) : nullptr;
   int64_t n_wv = 0;
   std::vector<int> longs;
-  int maxo = 1;
-  const int max_pts = getenv("PXR_INNER_GRAM_PPW") ? std::max(1, std::min(IP_MAXPTS, atoi(getenv("PXR_INNER_GRAM_PPW")))) : IP_MAXPTS;   // (A/B knob)
-  if (one_point_kernel) shorts.reserve((size_t)n); else if (!wv) waves_pageable.reserve((size_t)n / 2 + 1);
-  int64_t n_short = 0;
+  if (!wv) waves_pageable.reserve((size_t)n / 2 + 1);
   GramWave cur{};                                           // consecutive short points are packed: <= 4 points, <= 16 observations
   auto flush = [&]() {
     if (cur.npts > 0) { if (wv) wv[n_wv] = cur; else waves_pageable.push_back(cur); ++n_wv; }
@@ -1569,9 +1217,7 @@ int make_inner_lists(pxr_ctx* ctx, const int64_t* pt_ptr, int64_t n, void* h_wav
     const int64_t len = pt_ptr[p + 1] - pt_ptr[p];
     if (len <= 0) continue;
     if (len <= IG_MAXO) {
-      ++n_short; maxo = std::max(maxo, (int)len);
-      if (one_point_kernel) { shorts.push_back(GramPoint{(int)p, (int)len, pt_ptr[p]}); continue; }
-      if (cur.npts == max_pts || cur.st[cur.npts] + (int)len > GW_SLOTS) flush();
+      if (cur.npts == IP_MAXPTS || cur.st[cur.npts] + (int)len > GW_SLOTS) flush();
       cur.p[cur.npts] = (int)p;
       cur.st[cur.npts + 1] = cur.st[cur.npts] + (int)len;
       ++cur.npts;
@@ -1580,19 +1226,7 @@ int make_inner_lists(pxr_ctx* ctx, const int64_t* pt_ptr, int64_t n, void* h_wav
   flush();
   const GramWave* const waves = wv ? wv : waves_pageable.data();
   out->n_waves = n_wv; out->d_waves = nullptr; out->d_wave_heads = nullptr;
-  out->n_short = n_short; out->n_long = (int64_t)longs.size(); out->maxo_short = maxo;
-  out->d_short = nullptr; out->d_long = nullptr; out->d_slots = nullptr;
-  if (!shorts.empty()) {
-    out->d_short = solve_scratch(sizeof(GramPoint) * shorts.size(), &out->own_short);
-    if (!out->d_short) return set_error(PXR_ENOMEM, "hipMalloc(inner lists)");
-    if (int rc = hip_check(hipMemcpyAsync(out->d_short, shorts.data(), sizeof(GramPoint) * shorts.size(), hipMemcpyHostToDevice, st), "H2D")) return rc;
-    out->d_slots = solve_scratch(gram_entry_bytes(maxo) * shorts.size(), &out->own_slots);
-    if (!out->d_slots) return set_error(PXR_ENOMEM, "hipMalloc(inner table)");
-    const int64_t n_thr = (int64_t)shorts.size() * (maxo + 1);
-    hipLaunchKernelGGL(k_gram_table, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, st, (int64_t)shorts.size(), maxo,
-                       static_cast<const GramPoint*>(out->d_short), d_pt_obs, view->d_obs_image, view->d_obs_patch, view->d_image_camera,
-                       static_cast<char*>(out->d_slots));
-  }
+  out->n_long = (int64_t)longs.size(); out->d_long = nullptr;
   if (n_wv > 0) {            // one allocation: the headers as the host packed them, then the table the kernel reads
     const size_t heads = (sizeof(GramWave) * (size_t)n_wv + 255) & ~(size_t)255;
     char* d_all = static_cast<char*>(solve_scratch(heads + gram_wave_bytes() * (size_t)n_wv, &out->own_heads));
@@ -1612,11 +1246,9 @@ int make_inner_lists(pxr_ctx* ctx, const int64_t* pt_ptr, int64_t n, void* h_wav
   return hip_check(hipStreamSynchronize(st), "inner lists upload");    // the host vectors go out of scope
 }
 void free_inner_lists(InnerLists* l) {
-  if (l->d_short && l->own_short) (void)hipFree(l->d_short);
   if (l->d_long && l->own_long) (void)hipFree(l->d_long);
-  if (l->d_slots && l->own_slots) (void)hipFree(l->d_slots);
   if (l->d_wave_heads && l->own_heads) (void)hipFree(l->d_wave_heads);      // (d_waves lies inside it)
-  l->d_short = nullptr; l->d_long = nullptr; l->d_slots = nullptr; l->d_waves = nullptr; l->d_wave_heads = nullptr;
+  l->d_long = nullptr; l->d_waves = nullptr; l->d_wave_heads = nullptr;
 }
 
 }  // namespace pxr

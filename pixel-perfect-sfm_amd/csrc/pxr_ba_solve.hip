@@ -937,12 +937,10 @@ SolveKnobs::SolveKnobs() {
   setup_host = std::getenv("PXR_BA_SETUP_HOST") != nullptr;
   verbose = std::getenv("PXR_VERBOSE") != nullptr;
   spin_wait = std::getenv("PXR_BLOCKING_WAIT") == nullptr;
-  inner_old = std::getenv("PXR_INNER_OLD") != nullptr;
   inner_packed = std::getenv("PXR_INNER_PACKED") != nullptr;
   inner_no_cache = std::getenv("PXR_INNER_NO_CACHE") != nullptr;
+  inner_no_prebuild = std::getenv("PXR_INNER_NO_PREBUILD") != nullptr;
   schur_lds = std::getenv("PXR_SCHUR_GLOBAL_ATOMICS") == nullptr;
-  e = std::getenv("PXR_SCHUR_CTILES");                     // A/B knob (profiles/r6_schur_tiles.txt)
-  schur_ctiles = e ? std::max(1, std::atoi(e)) : 0;
   phase_timing = std::getenv("PXR_PHASE_TIMING") != nullptr;   // adds a stream sync per phase
 }
 
@@ -956,7 +954,7 @@ size_t inner_wave_stage_bytes(int64_t n_pts);        // pxr_ba_inner.hip: host r
 int launch_inner_iterations(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, const pxr_interp_cfg* cfg,
                             const pxr_loss* loss, const int64_t* d_pt_ptr, const int64_t* d_pt_obs,
                             const int* d_pt_var, double* d_cost_before, const InnerLists* lists, double* d_cost_per_point,
-                            const GramCache* gram, bool gram_warm);
+                            const GramCache* gram, bool gram_warm, bool prebuild);
 int make_inner_lists(pxr_ctx* ctx, const int64_t* h_pt_ptr, int64_t n_pts, void* h_wave_stage, size_t wave_stage_bytes, const pxr_ba_view* view, const int64_t* d_pt_ptr, const int64_t* d_pt_obs,
                      InnerLists* out);
 void free_inner_lists(InnerLists* l);
@@ -1399,7 +1397,7 @@ int LmSolve::setup() {
   // it builds), whether or not the LM loop evaluates from them: the same numbers as without a cache, fewer builds.  (That kernel
   // is built without the six extended camera models -- their forward-mode duals cost ~100 registers: a problem that uses one
   // keeps the packed kernel for every point.)
-  gram_inner = !m.geom && opt->use_inner_iterations != 0 && arena->dtype != PXR_F64 && (arena->C == 128 || arena->C == 64) && !knobs.inner_old &&
+  gram_inner = !m.geom && opt->use_inner_iterations != 0 && arena->dtype != PXR_F64 && (arena->C == 128 || arena->C == 64) &&
                !knobs.inner_packed && cfg->use_float_simd == 0;
   for (int c = 0; c < n_cam; ++c) gram_inner = gram_inner && sx.cam_model[c] <= PXR_OPENCV;
   inner_cache = gram_inner && gram_eval_supported(arena, view) && !knobs.inner_no_cache;
@@ -1454,7 +1452,6 @@ int LmSolve::setup() {
   // LDS-privatised Schur contraction: column tile so that DC x CT doubles fit in 128 KiB of LDS
   CT = n_c > 0 ? std::min(n_c, (int)((128 * 1024 / 8 - DC) / DC)) : 1;
   n_ctiles = n_c > 0 ? (n_c + CT - 1) / CT : 1;
-  if (knobs.schur_ctiles) n_ctiles = std::max(n_ctiles, std::min(std::max(1, n_c), knobs.schur_ctiles));
   CT = n_c > 0 ? (n_c + n_ctiles - 1) / n_ctiles : 1;       // balance the tiles
   schur_shmem = sizeof(double) * ((size_t)DC * CT + DC + 3 * 1024);   // tile, right-hand side, the lane groups' Y rows
   if (knobs.schur_lds && n_c > 0)
@@ -1530,7 +1527,7 @@ int LmSolve::candidate(double inv_radius, double inexact_correction, Candidate* 
     if (m.geom) RC(launch_inner_geom(ctx, &cand_view, d_obs_xy, loss, sx.d_pt_ptr.p, sx.d_pt_obs.p, sx.d_pt_var.p, scal_sum + SCAL_COST_BEFORE_INNER, ws.det_part.p, geom_ext));
     else {
       RC(launch_inner_iterations(ctx, arena, &cand_view, cfg, loss, sx.d_pt_ptr.p, sx.d_pt_obs.p, sx.d_pt_var.p, scal_sum + SCAL_COST_BEFORE_INNER, gram_inner ? &inner_lists.l : nullptr,
-                                 ws.det_part.p, (gram_cache || inner_cache) ? &gram : nullptr, gram_warm));
+                                 ws.det_part.p, (gram_cache || inner_cache) ? &gram : nullptr, gram_warm, !knobs.inner_no_prebuild));
       gram_warm = true;
     }
     hipLaunchKernelGGL(k_limb_accumulate, dim3(256), dim3(256), 0, st, (const double*)ws.det_part.p, n_pts, slimb + SCAL_COST_BEFORE_INNER * PXR_LIMBS);

@@ -77,12 +77,10 @@ int launch_inner_geom(pxr_ctx* ctx, const pxr_ba_view* view, const double* d_obs
                       bool extended_models);
 // pxr_ba_inner.hip: the inner iterations' split of the points by track length (made once per solve)
 struct InnerLists {
-  void* d_short = nullptr; int64_t n_short = 0; int maxo_short = 1;  // points with 1 .. 16 observations (Gram-matrix kernel): {point, length, first slot}
-  int* d_long = nullptr; int64_t n_long = 0;                          // the others (packed kernel, one point per wavefront)
-  void* d_slots = nullptr;                                            // the Gram-matrix kernel's table: per listed point {point, length, first slot} + {image, camera, patch, observation} x maxo_short
-  void* d_waves = nullptr; int64_t n_waves = 0;                       // the packed Gram-matrix kernel's table: per wavefront {<= 4 points, first slots} + 16 observation slots
+  void* d_waves = nullptr; int64_t n_waves = 0;                       // points with 1 .. 16 observations (Gram-matrix kernel): per wavefront {<= 4 points, first slots} + 16 observation slots
   void* d_wave_heads = nullptr;
-  bool own_short = true, own_long = true, own_slots = true, own_heads = true;   // false: carved out of the solve's arena (solve_scratch), not freed
+  int* d_long = nullptr; int64_t n_long = 0;                          // the others (packed kernel, one point per wavefront)
+  bool own_long = true, own_heads = true;   // false: carved out of the solve's arena (solve_scratch), not freed
 };
 // pxr_ba_solve.hip: `bytes` of device memory for the duration of the running pxr_ba_solve -- from the context's arena when it has
 // room (*owned = false), else from hipMalloc (*owned = true: the caller frees it)

@@ -1,6 +1,7 @@
-"""One SHA-256 per case over the result of a BA solve: the refined q, t, k, X and the non-timing fields of the summary.
+"""One SHA-256 per case over the result of a solve.  BA: the refined q, t, k, X and the non-timing fields of the summary; keypoint
+adjustment (the ka_* cases): the refined keypoints and the non-timing fields of every sub-problem's summary.
 
-A refactor of the LM driver must leave every line of this output unchanged: run it before and after on the same machine and
+A refactor of the LM driver or of the KA solve must leave every line of this output unchanged: run it before and after on the same machine and
 compare.  Only the public engine API is used, and the seeded generators the tests use (pixsfm_amd.synthetic, tests/geom_cases).
 
   python tools/ba_solve_fingerprint.py            # prints "<case> <sha256>" per line
@@ -76,6 +77,52 @@ def geometric(prob, g, **opts):
         ctx.close()
 
 
+KA_FIELDS = ("iterations", "num_successful", "termination", "initial_cost", "final_cost", "linear_iterations")
+
+
+def keypoint(prob, env, bound, l2_normalize=True, loss_a=0.25):
+    """a deterministic pxr_ka_solve of one of tests/test_ka_gpu.py's problems"""
+    from pixsfm_amd.engine import Context, PatchArena, interp_cfg, lm_options, make_loss
+    from pixsfm_amd.ka_engine import KAProblem
+    ctx = arena = None
+    try:
+        os.environ.update(env)
+        ctx = Context(0)
+        assert ctx.deterministic
+        arena = PatchArena.from_numpy(ctx, prob["patches"], prob["corners"], prob["scales"])
+        ka = KAProblem(ctx, arena, prob)
+        total, per = ka.solve(interp_cfg(l2_normalize=l2_normalize), make_loss("cauchy", [loss_a]), bound=bound,
+                              options=lm_options(parameter_tolerance=1e-5), per_problem=True)
+        h = hashlib.sha256(np.ascontiguousarray(ka.keypoints(), dtype=np.float64).tobytes())
+        for s in per:
+            for f in KA_FIELDS:
+                h.update(np.float64(s[f]).tobytes() if isinstance(s[f], float) else np.int64(s[f]).tobytes())
+        return h.hexdigest()
+    finally:
+        for k in env:
+            os.environ.pop(k, None)
+        if arena is not None:
+            arena.close()
+        if ctx is not None:
+            ctx.close()
+
+
+def ka_cases():
+    from pixsfm_amd import synthetic_ka
+    # 30 sub-problems on a grid of 5 resident workgroups, active bounds (test_two_phase_launch_gives_the_one_phase_results_bit_for_bit)
+    many = synthetic_ka.make_ka_problem(n_tracks=90, track_len=5, seed=17, max_kps_per_problem=15, sigma=1.5)
+    yield "ka_one_launch", lambda: keypoint(many, {"PXR_KA_TWO_LAUNCH": "0", "PXR_KA_TWO_PHASE_RESIDENT": "5"}, 1.5)
+    yield "ka_two_launches_resident_5", lambda: keypoint(many, {"PXR_KA_TWO_LAUNCH": "2", "PXR_KA_TWO_PHASE_RESIDENT": "5"}, 1.5)
+    # raw features 300x unit norm: the fixed-point grid is rescaled between launches (test_two_launches_with_a_fixed_point_rescale_in_between)
+    raw = dict(synthetic_ka.make_ka_problem(n_tracks=90, track_len=5, seed=23, max_kps_per_problem=15, sigma=1.5))
+    raw["patches"] = (raw["patches"].astype(np.float32) * 300.0).astype(np.float16)
+    yield "ka_rescale_300x", lambda: keypoint(raw, {"PXR_KA_TWO_LAUNCH": "2", "PXR_KA_TWO_PHASE_RESIDENT": "5"}, 3.0,
+                                              l2_normalize=False, loss_a=0.25 * 300.0)
+    # one label group of 300 keypoints as chunks of whole tracks (test_chunked_label_group_takes_the_decisions_of_one_problem)
+    group = synthetic_ka.make_ka_problem(n_tracks=60, track_len=5, seed=21, max_kps_per_problem=100000, sigma=1.5)
+    yield "ka_chunked_label_group", lambda: keypoint(dict(group, node_track=group["track_of_node"]), {}, 1.5)
+
+
 def cases():
     import geom_cases
     from pixsfm_amd import synthetic
@@ -101,6 +148,7 @@ def cases():
     yield "unordered_observations", lambda: featuremetric(shuffled, g, max_iterations=it, use_inner_iterations=True)
     yield "forced_collective", lambda: featuremetric(small, g, forced=True, max_iterations=it, use_inner_iterations=True)
     yield "forced_collective_iterative", lambda: featuremetric(shared, gauge(shared), forced=True, max_iterations=it, **TIGHT_CG)
+    yield from ka_cases()
 
 
 if __name__ == "__main__":
