@@ -62,17 +62,18 @@ struct KaArgs {
   double det_scale;            // 0: floating-point atomics; 2^k: deterministic fixed-point accumulation of H and g (pxr_device.h)
   double* prob_scale;          // deterministic mode, [n_problems]: every sub-problem's grid (det_scale until its overflow guard asks for a coarser one)
   uint8_t* prob_done;          // deterministic mode, [n_problems]: the sub-problem finished (a repeated launch skips it)
-  int* slot_of_node;           // [n_nodes] position of the node inside its sub-problem (the index of its LDS metadata)
-  int stream_slots;            // > 0: the line-search probes run as ka_probe_stream (every sub-problem has at most this many nodes, <= 64,
-                               // all its residual blocks in the LDS cache, no unary terms); its LDS region follows the LM state
-  int stream_off;              // doubles from sh_A to that region
-  double* prob_state = nullptr;     // [n_problems][KA_STATE]: LM state parked by a sub-problem that stopped with KA_TERM_RESCALE after an accepted step, or after its first iteration (KA_TERM_PARKED)
-  int* sched = nullptr;             // two-phase launch (ka_solve_kernel_sched): [0] arrivals at the grid barrier, [1] release flag, [2] entries of the list, [3] next entry to take
-  int* sched_list = nullptr;        // [n_problems] the parked sub-problems, those with a keypoint on a bound first
+  // Reserved: 16 bytes here and 16 behind prob_state, where the arguments of two deleted experiments sat (docs/DESIGN_HISTORY.md,
+  // "Variants removed").  The offsets of the fields below decide how the compiler groups the scalar loads of the kernel arguments,
+  // and through them the register allocation of the four deterministic capped kernels: with any other layout tried they come out
+  // with another schedule and 32 B less scratch per lane.  Held so that the kernels stay the measured ones; drop them together with
+  // a timing run of the deterministic solve.
+  long long reserved0_[2] = {0, 0};
+  double* prob_state = nullptr;     // [n_problems][KA_STATE]: LM state parked by a sub-problem that stopped with KA_TERM_RESCALE after an accepted step, or after `park_iters` iterations (KA_TERM_PARKED)
+  long long reserved1_[2] = {0, 0};
   uint8_t* prob_heavy = nullptr;    // [n_problems] set when a sub-problem is parked with a keypoint ON its bound
-  int phase = 0;                    // the plain kernels (ka_solve_kernel_occ2): 0 the whole solve, 1 park after `park_iters` LM iterations, 2 resume the parked ones
+  int phase = 0;                    // 0 the whole solve, 1 park after `park_iters` LM iterations, 2 resume the parked ones
   int park_iters = 1;
-  const int* order = nullptr;       // phase 2: sub-problem of workgroup b (-1: none), the ones parked on a bound first
+  const int* order = nullptr;       // phase 2: sub-problem of workgroup b (-1: none), the ones parked on a bound first (written by ka_order_kernel)
   // ---- label groups that span several workgroups (round 6) -----------------------------------------------------------------
   // A label group of the caller (ONE ceres::Problem of the reference: one trust region, one line search, one termination) may
   // be handed over as several CHUNKS -- consecutive sub-problems that share no variable (whole tracks each): pxr_ka_view.
@@ -123,8 +124,8 @@ __device__ __noinline__ void ka_group_sum4(const KaGroup g, unsigned gen, double
 }
 constexpr int KA_STATE = 12;           // has_state, radius, iterations, accepted steps, initial cost, stencils, decrease factor, invalid steps,
                                        // cost, next fixed-point grid, reuse_diag, FULL (the linearisation itself was parked too)
-constexpr int KA_TERM_RESCALE = 100;
-constexpr int KA_TERM_PARKED = 101;    // internal: stopped after its first LM iteration (phase 1 of ka_solve_kernel_sched), resumes in phase 2   // internal termination code: the sub-problem's fixed-point grid did not fit, launch again
+constexpr int KA_TERM_RESCALE = 100;   // internal termination code: the sub-problem's fixed-point grid did not fit, launch again
+constexpr int KA_TERM_PARKED = 101;    // internal: stopped after `park_iters` LM iterations (launch 1 of the two-launch schedule), resumes in launch 2
 
 // Channel layout of a node over lanes: 8 channels per lane (one 16-byte fp16 load) for the CNN feature sizes, and the
 // whole descriptor in ONE lane for CHANNELS < 8 -- the reference instantiates (128, 1) and (1, 1)
@@ -583,198 +584,6 @@ __device__ void ka_plus(const KaArgs& a, const KaProb& p, double alpha) {
   __syncthreads();
 }
 
-// EXPERIMENT, compiled in with -DPXR_KA_STREAM_PROBE only (tools/variant_build.sh; off in the shipped library).  Measured at
-// configs[1], round 5 (profiles/r5_ka_stream_probe.txt): a probe of a long line search takes 11.5 us instead of 15.8 us and the
-// slowest sub-problem 2.2 ms instead of 2.5-2.8 ms -- but the whole solve 5.9-6.2 ms instead of 5.4 ms: the solve kernel sits at
-// its 256-register cap, the out-of-line call (or, inlined, the second interpolation core) raises its spilled registers from 43 to
-// 195-261 and every other phase of every sub-problem pays for them.  Kept as the starting point for a kernel whose phases are
-// separate functions; bit-for-bit the same accepted steps (5852) and final cost to 1e-15.
-#ifdef PXR_KA_STREAM_PROBE
-// ---- the line-search probe as ONE streamed pass (cost only) ----------------------------------------------------------------
-// A probe of the projected Armijo search ([upstream] trust_region_minimizer.cc DoLineSearch) needs the cost at
-// P(x + alpha delta) and nothing else.  The general form (ka_plus + ka_nodes + ka_terms) is a chain of round trips: candidate
-// keypoints to global memory, two trips of node interpolations, descriptors to the L2-resident scratch, four trips of residual
-// blocks reading them back, the loss.  A sub-problem whose search direction runs into an active bound fails all twenty probes
-// of its line search ([upstream] max_num_line_search_step_size_iterations) in several LM iterations -- ~125 probes per solve
-// against ~5 for the others (tools/_ka_iter_hist.py) -- and those sub-problems are the tail of the launch.  Here the probe
-// stays on the CU:
-//   * FOUR lanes per node, every node of the sub-problem at once (<= 64), the descriptor in C / 32 steps of 32 channels: lane
-//     `sub` interpolates channels 32 k + 8 sub .. + 7 with the arithmetic of interp8 / interp8x2_value (the four lanes read 64
-//     consecutive bytes of every texel); with fp16 storage the texels of step k + 1 are requested before step k is computed;
-//   * a step's 32 channels of every node go to LDS (rows of 34 doubles: consecutive nodes start 16 bytes apart in the bank
-//     row), every residual block -- one lane each -- adds the step's part of f_a . f_b; |f|^2 accumulates with the node;
-//   * |f_a / |f_a| - f_b / |f_b||^2 = |f_a|^2 n_a^2 + |f_b|^2 n_b^2 - 2 (f_a . f_b) n_a n_b,  n = 1 / |f|  (a constant node's
-//     descriptor is the normalised one the linearisation left in the scratch: n = 1).  Fixed-order sums: every run alike.  The
-//     difference from the channel-wise form is the rounding of three fp64 dot products, ~1e-16 of |f|^2 = 1.
-// Only PixelInterpolator's L2-normalised descriptors (interpolation.h:642-677) take this path; the candidate keypoints are
-// written (ka_plus) once the search has settled.
-constexpr int KA_SCH = 32, KA_SROW = KA_SCH + 2, KA_STREAM_MAX = KA_NT / 4;
-struct KaStream {                  // LDS
-  double* buf;                     // [slots][KA_SROW] the current step's channels of every node
-  double* self;                    // [slots] |f|^2 n^2
-  double* ninv;                    // [slots] n
-  double* kp;                      // [slots][2] the sub-problem's current keypoints
-  const unsigned char* eslot;      // [edges][2] node slots of the cached residual blocks' endpoints
-};
-
-// (LDS pointers carry their address space here: out of line the compiler cannot infer it and would issue FLAT loads -- a quarter
-// of the ds_read rate -- for the 128 row reads per lane and probe)
-#define KA_LDS __attribute__((address_space(3)))
-#define KA_GLOBAL __attribute__((address_space(1)))
-// workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global load (vmcnt(0)), i.e. for
-// the texels of the NEXT step that are meant to stay in flight across the exchange (measured: 23 us per probe with it, slower
-// than the general form's 16)
-__device__ __forceinline__ void ka_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#ifdef PXR_KA_STREAM_FORCEINLINE     // A/B knob (tools/variant_build.sh)
-#define KA_STREAM_INLINE __forceinline__
-#else
-#define KA_STREAM_INLINE __attribute__((noinline))
-#endif
-// (everything by value: a reference to the kernel's KaArgs / KaProb would force both structures into scratch memory for the whole
-// kernel -- 1.4 KB per lane, every later field access a scratch load)
-struct KaStreamCall {
-  const KA_GLOBAL void* arena; const KA_GLOBAL double* desc;
-  int H, W, loss_type, slots_max, nslots, ne;
-  double loss_a;
-  KA_LDS double* buf;                       // the region of KaStream: buf | self | ninv | kp
-  const KA_LDS unsigned char* eslot;
-  const KA_LDS double *delta, *lo, *hi;     // (the LM state is in LDS whenever this path is on)
-  const KA_LDS KaNodeMeta* cnode; const KA_LDS KaEdgeMeta* cedge;
-  KA_LDS double* sh4;
-};
-template <typename ST, int C, bool FS>
-__device__ KA_STREAM_INLINE double ka_probe_stream(const KaStreamCall sc, double alpha) {
-  static_assert(C % KA_SCH == 0, "whole steps");
-  constexpr int NSTEP = C / KA_SCH;
-  typedef typename Texel8<ST>::work_t HT;
-  typedef double ldouble2 __attribute__((ext_vector_type(2)));
-  KA_LDS double* const buf = sc.buf;
-  KA_LDS double* const self = buf + sc.slots_max * KA_SROW;
-  KA_LDS double* const sninv = self + sc.slots_max;
-  const KA_LDS double* const skp = sninv + sc.slots_max;
-  const KA_LDS unsigned char* const eslot = sc.eslot;
-  const KA_LDS double* const delta = sc.delta;
-  const KA_LDS double* const lo = sc.lo;
-  const KA_LDS double* const hi = sc.hi;
-  const KA_LDS KaNodeMeta* const cnode = sc.cnode;
-  const KA_LDS KaEdgeMeta* const cedge = sc.cedge;
-  const int tid = threadIdx.x, sub = tid & 3;
-  const int nslots = sc.nslots, ne = sc.ne;
-  const int slot = min(tid >> 2, nslots - 1);    // (idle lanes shadow the last node: valid addresses, nothing stored)
-  const int64_t m_node = cnode[slot].node, m_pi = cnode[slot].pi, m_id = cnode[slot].id;
-  const double m_sx = cnode[slot].sx, m_sy = cnode[slot].sy, m_cx = cnode[slot].cx, m_cy = cnode[slot].cy;
-  const int m_v = cnode[slot].v;
-  const bool active = (tid >> 2) < nslots && m_node >= 0, moving = active && m_v >= 0;
-  const int vv = max(m_v, 0);
-  // ParameterBlock::Plus [upstream]: the projected candidate, the expression of ka_plus
-  const double x0 = skp[2 * slot], y0 = skp[2 * slot + 1];
-  const double xc = fmin(fmax(x0 + alpha * delta[vv], lo[vv]), hi[vv]);
-  const double yc = fmin(fmax(y0 + alpha * delta[vv + 1], lo[vv + 1]), hi[vv + 1]);
-  const double kx = m_v >= 0 ? xc : x0, ky = m_v >= 0 ? yc : y0;
-  const double u = kx * m_sx - 0.5 - m_cx, v = ky * m_sy - 0.5 - m_cy;        // featurepatch.h:250-255
-  const KA_GLOBAL ST* const gpatch = (const KA_GLOBAL ST*)sc.arena + (size_t)m_pi * sc.H * sc.W * C;
-  const StencilIndex si = stencil_index(sc.H, sc.W, u, v);
-  // (global address space spelled out as well: a FLAT load counts on lgkmcnt too, so every LDS wait of the exchange would wait
-  // for the texels of the next step -- 23 us per probe instead of 9)
-  typedef unsigned int gu4 __attribute__((ext_vector_type(4)));
-  typedef float gf4 __attribute__((ext_vector_type(4)));
-  const KA_GLOBAL ldouble2* const cdesc = (const KA_GLOBAL ldouble2*)(sc.desc + (size_t)m_id * 3 * C + sub * 8);
-  Texel8<ST> tx[4][4];
-  ldouble2 cf[4];
-  // every lane requests both -- its texels and the scratch row of its node -- and selects afterwards (a conditional load is a
-  // branch and a wait per element)
-  auto request = [&](int k) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const KA_GLOBAL ST* q = gpatch + (size_t)(si.ro[j] + si.co[i]) * C + k * KA_SCH + sub * 8;
-        if constexpr (sizeof(ST) == 2) {
-          const gu4 w = *(const KA_GLOBAL gu4*)q;
-          tx[j][i].raw = make_uint4(w.x, w.y, w.z, w.w);
-        } else {
-          const gf4 w0 = *(const KA_GLOBAL gf4*)q, w1 = *(const KA_GLOBAL gf4*)(q + 4);
-          tx[j][i].a = make_float4(w0.x, w0.y, w0.z, w0.w); tx[j][i].b = make_float4(w1.x, w1.y, w1.z, w1.w);
-        }
-      }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) cf[q] = cdesc[k * (KA_SCH / 2) + q];
-  };
-#define KA_STREAM_REQUEST(K) request(K)
-  KA_STREAM_REQUEST(0);
-  // this lane's residual blocks: tid and tid + KA_NT (at most KA_EDGE_CACHE = 2 KA_NT of them)
-  const int e0 = tid, e1 = tid + KA_NT;
-  const int sa0 = e0 < ne ? eslot[2 * e0] : 0, sb0 = e0 < ne ? eslot[2 * e0 + 1] : 0;
-  const int sa1 = e1 < ne ? eslot[2 * e1] : 0, sb1 = e1 < ne ? eslot[2 * e1 + 1] : 0;
-  double nrm2 = 0.0, dot0 = 0.0, dot1 = 0.0;
-#pragma unroll
-  for (int k = 0; k < NSTEP; ++k) {
-    HT h[4][8], hd[4][8];
-    double f[8], fr[8], fc[8];
-    interp8_horizontal<ST, false, FS>(tx, si.dx, h, hd);
-    ldouble2 cfk[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) cfk[q] = cf[q];
-    // step k + 1 is requested as soon as the horizontal pass has consumed step k's texels: in flight behind the vertical pass,
-    // the LDS exchange and its barriers (two steps' texels in registers cost the kernel 130 more spilled registers)
-    if (k + 1 < NSTEP) KA_STREAM_REQUEST(k + 1);
-    interp8_vertical<HT, false, FS>(h, hd, si.dy, f, fr, fc);
-    if (!moving) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { f[2 * q] = cfk[q].x; f[2 * q + 1] = cfk[q].y; }
-    }
-    double s8 = 0.0;
-#pragma unroll
-    for (int ch = 0; ch < 8; ++ch) s8 = fma(f[ch], f[ch], s8);
-    s8 += dpp_f64<0xB1>(s8);   // quad_perm [1,0,3,2]
-    s8 += dpp_f64<0x4E>(s8);   // quad_perm [2,3,0,1]
-    nrm2 += s8;
-    if (active) {
-      KA_LDS ldouble2* row = (KA_LDS ldouble2*)(buf + slot * KA_SROW + sub * 8);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { ldouble2 w2; w2.x = f[2 * q]; w2.y = f[2 * q + 1]; row[q] = w2; }
-    }
-    ka_lds_barrier();
-    if (e0 < ne) {
-      const KA_LDS ldouble2* ra = (const KA_LDS ldouble2*)(buf + sa0 * KA_SROW);
-      const KA_LDS ldouble2* rb = (const KA_LDS ldouble2*)(buf + sb0 * KA_SROW);
-      double d0 = 0.0, d1 = 0.0;
-#pragma unroll
-      for (int q = 0; q < KA_SCH / 2; ++q) { const ldouble2 x = ra[q], y = rb[q]; d0 = fma(x.x, y.x, d0); d1 = fma(x.y, y.y, d1); }
-      dot0 += d0 + d1;
-    }
-    if (e1 < ne) {
-      const KA_LDS ldouble2* ra = (const KA_LDS ldouble2*)(buf + sa1 * KA_SROW);
-      const KA_LDS ldouble2* rb = (const KA_LDS ldouble2*)(buf + sb1 * KA_SROW);
-      double d0 = 0.0, d1 = 0.0;
-#pragma unroll
-      for (int q = 0; q < KA_SCH / 2; ++q) { const ldouble2 x = ra[q], y = rb[q]; d0 = fma(x.x, y.x, d0); d1 = fma(x.y, y.y, d1); }
-      dot1 += d0 + d1;
-    }
-    ka_lds_barrier();
-  }
-#undef KA_STREAM_REQUEST
-  if (active && sub == 0) {
-    const double ninv = moving ? 1.0 / sqrt(nrm2) : 1.0;
-    sninv[slot] = ninv; self[slot] = nrm2 * ninv * ninv;
-  }
-  __syncthreads();
-  double cost = 0.0, rho[3];
-  if (e0 < ne) {
-    const double sq = self[sa0] + self[sb0] - 2.0 * dot0 * sninv[sa0] * sninv[sb0];
-    loss_eval(sc.loss_type, sc.loss_a, cedge[e0].w, sq < 0.0 ? 0.0 : sq, rho);      // (a NaN stays a NaN)
-    cost += 0.5 * rho[0];
-  }
-  if (e1 < ne) {
-    const double sq = self[sa1] + self[sb1] - 2.0 * dot1 * sninv[sa1] * sninv[sb1];
-    loss_eval(sc.loss_type, sc.loss_a, cedge[e1].w, sq < 0.0 ? 0.0 : sq, rho);
-    cost += 0.5 * rho[0];
-  }
-  return block_sum(cost, (double*)sc.sh4);
-}
-
-#endif   // PXR_KA_STREAM_PROBE
-
 // ---- Cholesky solves of one component block (n x n row-major lower, in place; b -> solution) ----
 // whole workgroup (any n).  Returns false on a non-positive pivot (block-uniform).
 __device__ bool ka_chol_block(double* A, int n, double* b) {
@@ -972,9 +781,6 @@ __global__ __launch_bounds__(KA_NT) void ka_setup_kernel(const KaArgs a, KaInfo*
   for (int i = tid; i < nloc; i += blockDim.x) {
     const int64_t node = a.v.d_prob_nodes[p.np0 + i];
     a.label[node] = (a.used[node] && a.v.d_node_const[node] != 1) ? i : -1;
-#ifdef PXR_KA_STREAM_PROBE
-    a.slot_of_node[node] = i;
-#endif
     cnt[i] = 0;
   }
   __syncthreads();
@@ -1106,7 +912,8 @@ __device__ __attribute__((noinline)) double ka_finish_fixed_point(double* Hm, do
   return ideal;
 }
 
-// phase 0: the whole solve; 1: at most ONE LM iteration, then the LM state is parked (KA_TERM_PARKED); 2: resume a parked sub-problem
+// phase 0: the whole solve; 1: at most `park_iters` LM iterations, then the LM state is parked (KA_TERM_PARKED); 2: resume a parked
+// sub-problem (launches 1 and 2 of the two-launch schedule: pxr_ka_solve)
 template <typename ST, int C, bool DET>
 __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __restrict__ info, double* sh_A, const int prob, const int phase) {
 #ifdef PXR_KA_PROFILE
@@ -1153,9 +960,6 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
   __shared__ KaEdgeMeta sh_edges[KA_EDGE_CACHE];
   __shared__ double sh_sq[KA_EDGE_CACHE];
   __shared__ double sh_kpc[2 * KA_NODE_CACHE], sh_kp0[2 * KA_NODE_CACHE];
-#ifdef PXR_KA_STREAM_PROBE
-  __shared__ unsigned char sh_eslot[2 * KA_EDGE_CACHE];     // node slots of the cached residual blocks' endpoints (ka_probe_stream)
-#endif
   for (int64_t i = p.np0 + tid; i < p.np1 && i - p.np0 < KA_NODE_CACHE; i += blockDim.x) {
     const int64_t node = a.v.d_prob_nodes[i];
     const int64_t pi = a.v.d_node_patch[node];
@@ -1170,10 +974,6 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
     KaEdgeMeta m;
     m.n1 = a.v.d_edge_src[e]; m.n2 = a.v.d_edge_dst[e]; m.v1 = a.var_of_node[m.n1]; m.v2 = a.var_of_node[m.n2]; m.w = a.v.d_edge_w[e];
     sh_edges[i - p.ne0] = m;
-#ifdef PXR_KA_STREAM_PROBE
-    sh_eslot[2 * (i - p.ne0)] = (unsigned char)a.slot_of_node[m.n1];       // (meaningful in sub-problems of <= 64 nodes: the
-    sh_eslot[2 * (i - p.ne0) + 1] = (unsigned char)a.slot_of_node[m.n2];   // only ones that read it)
-#endif
   }
   p.cnode = sh_nodes; p.cedge = sh_edges; p.csq = sh_sq; p.ckp = sh_kpc; p.ckp0 = sh_kp0;
   __syncthreads();
@@ -1204,30 +1004,6 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
     __syncthreads();
   }
   const pxr_lm_options& opt = a.opt;
-  // the line-search probes as one streamed pass (ka_probe_stream) when the launch was sized for it and this sub-problem fits
-  bool use_stream = false;
-#ifdef PXR_KA_STREAM_PROBE
-  KaStream strm{};
-  KaStreamCall scall{};
-  if constexpr (C % KA_SCH == 0 && sizeof(ST) <= 4) {
-    if (a.stream_slots > 0 && p.np1 - p.np0 <= a.stream_slots && p.ne1 - p.ne0 <= KA_EDGE_CACHE && p.nu1 == p.nu0) {
-      use_stream = true;
-      strm.buf = sh_A + a.stream_off; strm.self = strm.buf + (size_t)a.stream_slots * KA_SROW;
-      strm.ninv = strm.self + a.stream_slots; strm.kp = strm.ninv + a.stream_slots; strm.eslot = sh_eslot;
-      scall.arena = (const KA_GLOBAL void*)a.arena; scall.desc = (const KA_GLOBAL double*)a.desc;
-      scall.H = a.H; scall.W = a.W; scall.loss_type = a.loss.type; scall.loss_a = a.loss.a; scall.slots_max = a.stream_slots;
-      scall.nslots = (int)(p.np1 - p.np0); scall.ne = (int)(p.ne1 - p.ne0);
-      scall.buf = (KA_LDS double*)strm.buf; scall.eslot = (const KA_LDS unsigned char*)sh_eslot;
-      scall.delta = (const KA_LDS double*)p.delta; scall.lo = (const KA_LDS double*)p.lo; scall.hi = (const KA_LDS double*)p.hi;
-      scall.cnode = (const KA_LDS KaNodeMeta*)sh_nodes; scall.cedge = (const KA_LDS KaEdgeMeta*)sh_edges; scall.sh4 = (KA_LDS double*)sh4;
-      for (int i = tid; i < (int)(p.np1 - p.np0); i += blockDim.x) {
-        const int64_t node = sh_nodes[i].id;
-        strm.kp[2 * i] = a.v.d_kp[2 * node]; strm.kp[2 * i + 1] = a.v.d_kp[2 * node + 1];
-      }
-      __syncthreads();
-    }
-  }
-#endif
 
   // evaluate cost + normal equations at the CURRENT keypoints, then scale: H <- S H S, g <- S g
   // node stencils interpolated over the solve (a linearisation evaluates every node, a line-search probe the variable ones):
@@ -1283,18 +1059,8 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
     KA_T(2);
     return c;
   };
-  auto cost_at_candidate = [&](double alpha, bool long_search) -> double {
+  auto cost_at_candidate = [&](double alpha) -> double {
     stencils += nodes_var;
-#ifdef PXR_KA_STREAM_PROBE
-    if constexpr (C % KA_SCH == 0 && sizeof(ST) <= 4) {
-      if (use_stream && long_search) {
-        KA_T(7);
-        const double c = fsimd ? ka_probe_stream<ST, C, true>(scall, alpha) : ka_probe_stream<ST, C, false>(scall, alpha);
-        KA_T(3);
-        return c;
-      }
-    }
-#endif
     ka_plus(a, p, alpha);
     KA_T(7);
     ka_nodes<ST, C, false>(a, p, a.kp_cand, fsimd, true);
@@ -1317,7 +1083,7 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
   // parked in prob_state / the global scale vector (it used to start over with a fresh trust region).
   const double* const pst = a.prob_state + (size_t)prob * KA_STATE;
   const bool resumed = pst[0] != 0.0;
-  const bool resumed_full = resumed && pst[11] != 0.0;      // parked by phase 1 of the two-phase launch WITH its linearisation
+  const bool resumed_full = resumed && pst[11] != 0.0;      // parked by launch 1 of the two-launch schedule WITH its linearisation
   if (resumed) {
     const double* scale_g = a.vec + 2 * vstride + vb;
     for (int e = tid; e < n; e += blockDim.x) p.scale[e] = scale_g[e];
@@ -1363,8 +1129,8 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
   const int park_at = sm.iterations + a.park_iters;
   while (true) {
     if (phase == 1 && sm.iterations >= park_at && sm.iterations < opt.max_iterations && !(radius < opt.min_radius)) {
-      // phase 1 of the two-phase launch: one LM iteration done, the sub-problem goes on in phase 2 -- those that already sit on a
-      // bound (the ones that will run the twenty-probe line searches) first
+      // launch 1 of the two-launch schedule: `park_iters` LM iterations done, the sub-problem goes on in launch 2 -- those that
+      // already sit on a bound (the ones that will run the twenty-probe line searches) first
       sm.termination = KA_TERM_PARKED;
       double* scale_g = a.vec + 2 * vstride + vb;
       int on_bound = 0;
@@ -1481,12 +1247,7 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
       double xc = 1.0, xp = 0.0, fp = 0.0;
       bool have_prev = false, success = false;
       int iters = 0;
-#ifdef PXR_KA_STREAM_FROM       // (experiment: the streamed probe only from this probe of a search on -- 6.7 ms, worse than always: 6.1)
-      constexpr int kStreamFrom = PXR_KA_STREAM_FROM;
-#else
-      constexpr int kStreamFrom = 0;
-#endif
-      double fc = cost_at_candidate(xc, kStreamFrom <= 0);
+      double fc = cost_at_candidate(xc);
       const double f_full = fc;
       while (true) {
 #ifdef PXR_KA_TRACE_LS      // tools/ka_phase_probe.sh: the line search of the reporting sub-problem, probe by probe
@@ -1502,21 +1263,18 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
         if (nx < 1e-9) break;
         if (isfinite(fc)) { xp = xc; fp = fc; have_prev = true; }
         xc = nx;
-        fc = cost_at_candidate(xc, iters >= kStreamFrom);
+        fc = cost_at_candidate(xc);
       }
-      // (the streamed probes do not write the candidate keypoints: once, here)
       if (success) {
         if (xc != 1.0) {
           for (int e = tid; e < n; e += blockDim.x) p.delta[e] *= xc;
           __syncthreads();
           ka_plus(a, p, 1.0);
-        } else if (use_stream) {
-          ka_plus(a, p, 1.0);
         }
         cand = fc;
       } else {
         cand = f_full;
-        if (xc != 1.0 || use_stream) ka_plus(a, p, 1.0);
+        if (xc != 1.0) ka_plus(a, p, 1.0);
       }
     }
     KA_T(9);
@@ -1545,9 +1303,6 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
         const double nx = a.kp_cand[2 * node], ny = a.kp_cand[2 * node + 1];
         a.v.d_kp[2 * node] = nx; a.v.d_kp[2 * node + 1] = ny;
         if (i - p.np0 < KA_NODE_CACHE) { sh_kp0[2 * (i - p.np0)] = nx; sh_kp0[2 * (i - p.np0) + 1] = ny; }
-#ifdef PXR_KA_STREAM_PROBE
-        if (use_stream) { strm.kp[2 * (i - p.np0)] = nx; strm.kp[2 * (i - p.np0) + 1] = ny; }
-#endif
       }
       __syncthreads();
       cost = linearize(false);
@@ -1595,13 +1350,11 @@ __device__ __forceinline__ void ka_solve_body(const KaArgs& a, const KaInfo* __r
 // Two entry points over the same body.  The fp16 / fp32 instantiations need ~284 VGPRs unconstrained,
 // i.e. one wavefront per SIMD; capped at 256 (two wavefronts per SIMD, ~60 registers spilled to
 // scratch) the whole config-2 solve drops from 12.7 to 9.6 ms.  The fp64-storage instantiations keep the
-// compiler's own budget: capped, they spill ~950 registers.  (A tighter cap of 3 waves/SIMD produced
-// wrong steps on ROCm 7.2 and is not used.)
+// compiler's own budget: capped, they spill ~950 registers.  (A tighter cap of 3 waves/SIMD was tried:
+// correct, but slower -- 8.79 against 8.23 ms, docs/DESIGN_HISTORY.md "Variants removed".)
+constexpr int KA_WAVES = 2;
 template <typename ST, int C, bool DET>
-#ifndef PXR_KA_WAVES   // debugging knob of tools/ka_occupancy_probe.sh (the 3-waves build that gave wrong steps)
-#define PXR_KA_WAVES 2
-#endif
-__global__ __launch_bounds__(KA_NT) __attribute__((amdgpu_waves_per_eu(PXR_KA_WAVES, PXR_KA_WAVES))) void ka_solve_kernel_occ2(const KaArgs a, const KaInfo* __restrict__ info) {
+__global__ __launch_bounds__(KA_NT) __attribute__((amdgpu_waves_per_eu(KA_WAVES, KA_WAVES))) void ka_solve_kernel_occ2(const KaArgs a, const KaInfo* __restrict__ info) {
   extern __shared__ __align__(16) double sh_A[];      // lds_elems doubles (damped blocks) when the sub-problem fits
   int prob = (int)blockIdx.x;
   if (a.order) { prob = a.order[blockIdx.x]; if (prob < 0) return; }          // (phase 2 of the two-launch schedule)
@@ -1622,74 +1375,6 @@ __global__ __launch_bounds__(1024) void ka_order_kernel(const KaArgs a, int* __r
   for (int i = cnt + (int)threadIdx.x; i < np; i += blockDim.x) order[i] = -1;
 }
 
-// ---- the two-phase launch (round 6; an experiment, off by default: see pxr_ka_solve) ----------------------------------------------
-// One workgroup per sub-problem and dispatch in index order make the launch as long as its tail: the ~6 % of the sub-problems
-// that sit on an active bound run ~125 line-search probes (2.5-3.3 ms each), the others ~5 (0.65-0.9 ms), and the launch ends when
-// the LAST-dispatched heavy one does -- 5.3 ms at configs[1] against 4.1 ms of work per resident workgroup.  Which sub-problems are
-// heavy shows after ONE LM iteration: a keypoint whose unconstrained step crosses its bound is clamped onto it.  So a PERSISTENT
-// grid (as many workgroups as the launch keeps resident) first runs iteration 1 of every sub-problem and parks its LM state, meets
-// at a grid barrier whose last arrival lists the parked sub-problems -- those with a keypoint on a bound first --, and then takes
-// them from that list: the long chains start at once, the short ones fill the gaps.  Sub-problems are independent and every one
-// goes through the same arithmetic as in the one-phase launch (a parked one re-linearises at the point it stopped at: the same
-// H and g bit for bit in the deterministic mode), so the results do not depend on the order.
-template <typename ST, int C, bool DET>
-__global__ __launch_bounds__(KA_NT) __attribute__((amdgpu_waves_per_eu(PXR_KA_WAVES, PXR_KA_WAVES))) void ka_solve_kernel_sched(const KaArgs a, const KaInfo* __restrict__ info) {
-  extern __shared__ __align__(16) double sh_A[];
-  __shared__ int sh_take, sh_last, sh_cnt[2];
-  const int np = a.v.n_problems, tid = threadIdx.x;
-  // ONE call site of the solve body for both phases (two inlined copies of it: 531 spilled registers instead of 68, and a
-  // launch of 7.1 ms instead of 5.3)
-  int phase = 1, next = blockIdx.x, count = 0;
-  while (true) {
-    int prob;
-    if (phase == 1) {
-      if (next < np) { prob = next; next += gridDim.x; }
-      else {
-        // grid barrier (every workgroup of the grid is resident: the host sized it from the occupancy); the last arrival lists
-        // the parked sub-problems, those with a keypoint on a bound first
-        if (tid == 0) {
-          __threadfence();
-          sh_last = __hip_atomic_fetch_add(a.sched + 0, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-          sh_cnt[0] = 0; sh_cnt[1] = 0;
-        }
-        __syncthreads();
-        if (sh_last) {
-          __atomic_thread_fence(__ATOMIC_ACQUIRE);
-          for (int pass = 0; pass < 2; ++pass) {
-            for (int i = tid; i < np; i += blockDim.x) {
-              const bool parked = __hip_atomic_load(&a.summaries[i].termination, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == KA_TERM_PARKED;
-              const bool heavy = __hip_atomic_load(a.prob_heavy + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-              if (parked && heavy == (pass == 0)) a.sched_list[atomicAdd(&sh_cnt[0], 1)] = i;
-            }
-            __syncthreads();
-          }
-          if (tid == 0) {
-            a.sched[2] = sh_cnt[0];
-            __threadfence();
-            __hip_atomic_store(a.sched + 1, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        } else if (tid == 0) {
-          while (__hip_atomic_load(a.sched + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(2);
-          __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        }
-        __syncthreads();
-        count = __hip_atomic_load(a.sched + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (a.stream_off == -1) count = 0;          // PXR_KA_PHASE1_ONLY=1 (a timing experiment: phase 1 and the barrier alone)
-        phase = 2;
-        continue;
-      }
-    } else {
-      if (tid == 0) sh_take = atomicAdd(a.sched + 3, 1);
-      __syncthreads();
-      const int k = sh_take;
-      __syncthreads();
-      if (k >= count) break;
-      prob = __hip_atomic_load(a.sched_list + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    ka_solve_body<ST, C, DET>(a, info, sh_A, __builtin_amdgcn_readfirstlane(prob), phase);
-    __syncthreads();
-  }
-}
 template <typename ST, int C, bool DET>
 __global__ __launch_bounds__(KA_NT) void ka_solve_kernel(const KaArgs a, const KaInfo* __restrict__ info) {
   extern __shared__ __align__(16) double sh_A[];
@@ -1742,20 +1427,129 @@ __global__ __launch_bounds__(256) void ka_eval_kernel(const KaArgs a, bool fsimd
   }
 }
 
-static int fill_args(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* view, const pxr_interp_cfg* cfg,
-                     const pxr_loss* loss, KaArgs& a) {
+static void fill_args(pxr_arena* arena, const pxr_ka_view* view, const pxr_interp_cfg* cfg, const pxr_loss* loss, KaArgs& a) {
   a.v = *view;
   a.arena = arena->d_data; a.corners = arena->d_corners; a.scales = arena->d_scales;
   a.H = arena->H; a.W = arena->W; a.l2_normalize = cfg->l2_normalize; a.float_simd = cfg->use_float_simd; a.check_bounds = cfg->check_bounds; a.loss = *loss;
-  return PXR_OK;
 }
 
-template <typename T>
-struct KaBuf {
-  T* p = nullptr;
-  int alloc(size_t n) { return hip_check(hipMalloc((void**)&p, sizeof(T) * (n ? n : 1)), "hipMalloc(KA scratch)"); }
-  ~KaBuf() { if (p) (void)hipFree(p); }
+// ---- which kernels serve an arena: (storage type, channel count, accumulation mode) -> entry points --------------------------------
+struct KaKernels {
+  void (*eval)(const KaArgs, bool, double*, double*, double*, double*);
+  int eval_edges_per_block;
+  void (*solve)(const KaArgs, const KaInfo*);
+  bool occ2;             // the solve kernel is the register-capped one (fp16 / fp32 storage, 64 / 128 channels): the only one that parks and resumes
 };
+template <typename ST, int C>
+static KaKernels ka_kernels_of(bool det) {
+  constexpr bool occ2 = sizeof(ST) <= 4 && C >= 64;
+  KaKernels k{ka_eval_kernel<ST, C>, 256 / KaLay<C>::LPO, nullptr, occ2};
+  if constexpr (occ2) k.solve = det ? ka_solve_kernel_occ2<ST, C, true> : ka_solve_kernel_occ2<ST, C, false>;
+  else k.solve = det ? ka_solve_kernel<ST, C, true> : ka_solve_kernel<ST, C, false>;
+  return k;
+}
+static int ka_kernels(const char* who, const pxr_arena* arena, bool det, KaKernels* out) {
+  static const struct { int dtype, C; KaKernels (*of)(bool); } table[] = {
+      {PXR_F16, 128, ka_kernels_of<_Float16, 128>}, {PXR_F16, 64, ka_kernels_of<_Float16, 64>}, {PXR_F16, 1, ka_kernels_of<_Float16, 1>},
+      {PXR_F32, 128, ka_kernels_of<float, 128>},    {PXR_F32, 64, ka_kernels_of<float, 64>},    {PXR_F32, 1, ka_kernels_of<float, 1>},
+      {PXR_F64, 128, ka_kernels_of<double, 128>},   {PXR_F64, 64, ka_kernels_of<double, 64>},   {PXR_F64, 1, ka_kernels_of<double, 1>}};
+  for (const auto& row : table)
+    if (row.dtype == arena->dtype && row.C == arena->C) { *out = row.of(det); return PXR_OK; }
+  return set_error(PXR_EUNSUPPORTED, "%s: CHANNELS=%d not supported (128, 64, 1)", who, arena->C);
+}
+
+// the environment knobs of a KA solve, read once per call (tests flip them between solves on one context)
+struct KaKnobs {
+  bool two_launch;       // PXR_KA_TWO_LAUNCH=0 switches the two-launch schedule off ...
+  int park_iters;        // ... =N > 0 parks after N LM iterations (2 unless set)
+  int resident;          // PXR_KA_TWO_PHASE_RESIDENT: the workgroups one launch is taken to keep resident (0: two per CU); tests force a small one
+  bool verbose;          // PXR_VERBOSE
+  KaKnobs() {
+    const char* e = std::getenv("PXR_KA_TWO_LAUNCH");
+    two_launch = !(e && e[0] == '0');
+    park_iters = e && atoi(e) > 0 ? atoi(e) : 2;
+    e = std::getenv("PXR_KA_TWO_PHASE_RESIDENT");
+    resident = e ? std::max(1, atoi(e)) : 0;
+    verbose = std::getenv("PXR_VERBOSE") != nullptr;
+  }
+};
+
+// the scratch of a solve, carved out of the context's grow-only workspace (no hipMalloc per call once it has reached its
+// high-water mark): the offsets and the pointers that go with them
+struct KaWorkspace {
+  size_t desc, cand, vec, var, label, ipos, irow, comp, used, hptr, sum, info, pscale, pdone, pstate, order, heavy, gfirst, gsize, gpart, gcnt;
+  size_t bytes = 0;
+  KaWorkspace(size_t nn, size_t np, int C) {
+    auto carve = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
+    desc = carve(sizeof(double) * nn * 3 * C); cand = carve(sizeof(double) * nn * 2);
+    vec = carve(sizeof(double) * nn * 2 * 9);
+    var = carve(sizeof(int) * nn); label = carve(sizeof(int) * nn); ipos = carve(sizeof(int) * nn * 4);
+    irow = carve(sizeof(int) * nn * 6); comp = carve(sizeof(int) * nn); used = carve(nn);
+    hptr = carve(sizeof(int64_t) * (np + 1)); sum = carve(sizeof(pxr_lm_summary) * np);
+    info = carve(sizeof(KaInfo) * np);
+    pscale = carve(sizeof(double) * np); pdone = carve(np);
+    pstate = carve(sizeof(double) * KA_STATE * np);
+    order = carve(sizeof(int) * np); heavy = carve(np);
+    gfirst = carve(sizeof(int) * np); gsize = carve(sizeof(int) * np);
+    gpart = carve(sizeof(double) * 2 * 4 * np); gcnt = carve(sizeof(unsigned) * KA_GRP_CNT_STRIDE * np);
+  }
+  // what the host itself writes or hands to a kernel next to KaArgs
+  int64_t* d_hptr = nullptr; KaInfo* d_info = nullptr; int* d_order = nullptr; int *d_gfirst = nullptr, *d_gsize = nullptr;
+  void wire(char* ws, bool grouped, KaArgs& a) {
+    a.desc = (double*)(ws + desc); a.kp_cand = (double*)(ws + cand); a.vec = (double*)(ws + vec);
+    a.var_of_node = (int*)(ws + var); a.label = (int*)(ws + label); a.ipos = (int*)(ws + ipos);
+    a.irow = (int*)(ws + irow); a.comp_v0 = (int*)(ws + comp); a.used = (uint8_t*)(ws + used);
+    d_hptr = (int64_t*)(ws + hptr); a.prob_h_ptr = d_hptr; a.summaries = (pxr_lm_summary*)(ws + sum);
+    d_info = (KaInfo*)(ws + info);
+    a.prob_scale = (double*)(ws + pscale); a.prob_done = (uint8_t*)(ws + pdone);
+    a.prob_state = (double*)(ws + pstate);
+    d_order = (int*)(ws + order); a.prob_heavy = (uint8_t*)(ws + heavy);
+    d_gfirst = (int*)(ws + gfirst); d_gsize = (int*)(ws + gsize);
+    if (grouped) { a.grp_first = d_gfirst; a.grp_size = d_gsize; a.grp_part = (double*)(ws + gpart); a.grp_cnt = (unsigned*)(ws + gcnt); }
+  }
+};
+
+// One pass of the solve kernel over every sub-problem, timed between the context's two events.
+// The two-launch schedule (`two_launch`, the default when there are more sub-problems than resident workgroups): the launch is as
+// long as its tail -- the ~7 % of the sub-problems that run twenty-probe line searches against an active bound take 2.5-3.3 ms,
+// the others 0.65-0.9, and dispatch in index order starts some of the long ones last (with the heaviest first the same kernel
+// needs 3.4 instead of 5.3 ms at configs[1]: profiles/r6_ka_schedule.txt).  Which ones are heavy shows after TWO LM iterations
+// (a keypoint clamped onto its bound: 131 of 137 caught).  So: launch 1 runs two iterations of every sub-problem and parks the
+// complete LM state (nothing is evaluated twice), a one-workgroup kernel lists the parked ones -- on a bound first --, launch 2
+// resumes them in that order.  Same arithmetic per sub-problem: identical bits (tests/test_ka_gpu.py::test_two_phase_launch_*).
+// 5.36 -> 4.97 ms at configs[1].
+static int ka_launch_solve(pxr_ctx* ctx, const KaKernels& k, const KaArgs& a, const KaWorkspace& w, size_t shmem, int grp_max,
+                           bool two_launch, const KaKnobs& knobs) {
+  hipStream_t st = ctx->stream;
+  const int np = a.v.n_problems;
+  const void* kfn = reinterpret_cast<const void*>(k.solve);
+  PXR_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  if (grp_max > 1) {   // every member of a group must be resident at the same time (ka_group_sum4 spins)
+    int per_cu = 0;
+    PXR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, KA_NT, shmem));
+    const int resident = per_cu * ctx->num_cus;
+    if (grp_max > resident * 7 / 8)
+      return set_error(PXR_EUNSUPPORTED, "pxr_ka_solve: a label group of %d chunks exceeds what one launch keeps resident (%d workgroups): use smaller groups", grp_max, resident);
+    PXR_HIP(hipMemsetAsync(a.grp_cnt, 0, sizeof(unsigned) * KA_GRP_CNT_STRIDE * np, st));
+  }
+  if (knobs.verbose)
+    fprintf(stderr, "[pxr_ka_solve] %d sub-problems, %zu B of dynamic LDS, %s\n", np, shmem,
+            !two_launch ? "one launch" : k.occ2 ? "two launches" : "one launch (this kernel does not park)");
+  PXR_HIP(hipEventRecord(ctx->ev_start, st));
+  if (two_launch && k.occ2) {
+    PXR_HIP(hipMemsetAsync(a.prob_heavy, 0, np, st));
+    KaArgs a1 = a; a1.phase = 1; a1.park_iters = knobs.park_iters;
+    hipLaunchKernelGGL(k.solve, dim3(np), dim3(KA_NT), shmem, st, a1, w.d_info);
+    hipLaunchKernelGGL(ka_order_kernel, dim3(1), dim3(1024), 0, st, a, w.d_order);
+    KaArgs a2 = a; a2.phase = 2; a2.order = w.d_order;
+    hipLaunchKernelGGL(k.solve, dim3(np), dim3(KA_NT), shmem, st, a2, w.d_info);
+  } else {
+    hipLaunchKernelGGL(k.solve, dim3(np), dim3(KA_NT), shmem, st, a, w.d_info);
+  }
+  PXR_HIP(hipEventRecord(ctx->ev_stop, st));
+  PXR_HIP(hipGetLastError());
+  return PXR_OK;
+}
 
 }  // namespace pxr
 
@@ -1767,22 +1561,11 @@ extern "C" int pxr_ka_eval(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* vi
   if (view->n_edges == 0) return PXR_OK;
   PXR_HIP(hipSetDevice(ctx->device));
   KaArgs a{};
-  fill_args(ctx, arena, view, cfg, loss, a);
-  const bool fs = cfg->use_float_simd != 0;
-#define KA_EVAL_LAUNCH(ST, CC)                                                                                   \
-  hipLaunchKernelGGL((ka_eval_kernel<ST, CC>), dim3((unsigned)((view->n_edges + (256 / KaLay<CC>::LPO) - 1) / (256 / KaLay<CC>::LPO))), \
-                     dim3(256), 0, ctx->stream, a, fs, d_cost, d_r, d_J1, d_J2)
-  if (arena->dtype == PXR_F16 && arena->C == 128) KA_EVAL_LAUNCH(_Float16, 128);
-  else if (arena->dtype == PXR_F16 && arena->C == 64) KA_EVAL_LAUNCH(_Float16, 64);
-  else if (arena->dtype == PXR_F32 && arena->C == 128) KA_EVAL_LAUNCH(float, 128);
-  else if (arena->dtype == PXR_F32 && arena->C == 64) KA_EVAL_LAUNCH(float, 64);
-  else if (arena->dtype == PXR_F64 && arena->C == 128) KA_EVAL_LAUNCH(double, 128);
-  else if (arena->dtype == PXR_F64 && arena->C == 64) KA_EVAL_LAUNCH(double, 64);
-  else if (arena->dtype == PXR_F16 && arena->C == 1) KA_EVAL_LAUNCH(_Float16, 1);
-  else if (arena->dtype == PXR_F32 && arena->C == 1) KA_EVAL_LAUNCH(float, 1);
-  else if (arena->dtype == PXR_F64 && arena->C == 1) KA_EVAL_LAUNCH(double, 1);
-  else return set_error(PXR_EUNSUPPORTED, "pxr_ka_eval: CHANNELS=%d not supported (128, 64, 1)", arena->C);
-#undef KA_EVAL_LAUNCH
+  fill_args(arena, view, cfg, loss, a);
+  KaKernels k;
+  if (int rc = ka_kernels("pxr_ka_eval", arena, false, &k)) return rc;
+  hipLaunchKernelGGL(k.eval, dim3((unsigned)((view->n_edges + k.eval_edges_per_block - 1) / k.eval_edges_per_block)), dim3(256), 0,
+                     ctx->stream, a, cfg->use_float_simd != 0, d_cost, d_r, d_J1, d_J2);
   return hip_check(hipGetLastError(), "ka_eval_kernel launch");
 }
 
@@ -1798,9 +1581,9 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
   const int np = view->n_problems;
   memset(total, 0, sizeof(*total));
   if (np == 0) return PXR_OK;
-  std::vector<int64_t> node_ptr(np + 1), edge_ptr(np + 1), h_ptr(np + 1, 0);
+  const KaKnobs knobs;
+  std::vector<int64_t> node_ptr(np + 1), h_ptr(np + 1, 0);
   PXR_HIP(hipMemcpyAsync(node_ptr.data(), view->d_prob_node_ptr, sizeof(int64_t) * (np + 1), hipMemcpyDeviceToHost, st));
-  PXR_HIP(hipMemcpyAsync(edge_ptr.data(), view->d_prob_edge_ptr, sizeof(int64_t) * (np + 1), hipMemcpyDeviceToHost, st));
   PXR_HIP(hipStreamSynchronize(st));
   PXR_REQUIRE(node_ptr[0] == 0 && node_ptr[np] <= view->n_nodes, "pxr_ka_solve: every node belongs to at most one sub-problem");
   for (int i = 0; i < np; ++i) {
@@ -1808,8 +1591,6 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
     PXR_REQUIRE(nmax >= 0 && nmax < 46000, "pxr_ka_solve: sub-problem too large (< 23000 nodes each)");
   }
   const auto t0 = std::chrono::steady_clock::now();
-  // every scratch array is carved out of the context's grow-only workspaces (no hipMalloc per call
-  // once they have reached their high-water mark)
   auto grow = [&](void** buf, size_t* have, size_t want) -> int {
     if (want <= *have) return PXR_OK;
     PXR_HIP(hipStreamSynchronize(st));
@@ -1825,16 +1606,6 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
     *have = want;
     return PXR_OK;
   };
-  const size_t nn = (size_t)view->n_nodes;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_desc = carve(sizeof(double) * nn * 3 * arena->C), o_cand = carve(sizeof(double) * nn * 2);
-  const size_t o_vec = carve(sizeof(double) * nn * 2 * 9);
-  const size_t o_var = carve(sizeof(int) * nn), o_label = carve(sizeof(int) * nn), o_ipos = carve(sizeof(int) * nn * 4);
-  const size_t o_irow = carve(sizeof(int) * nn * 6), o_comp = carve(sizeof(int) * nn), o_used = carve(nn);
-  const size_t o_hptr = carve(sizeof(int64_t) * (np + 1)), o_sum = carve(sizeof(pxr_lm_summary) * np);
-  const size_t o_info = carve(sizeof(KaInfo) * np);
-  const size_t o_pscale = carve(sizeof(double) * np), o_pdone = carve(np), o_slot = carve(sizeof(int) * nn);
   // label groups spanning several workgroups (pxr_ka_view.d_prob_group)
   std::vector<int> grp_first, grp_size;
   int grp_max = 1;
@@ -1852,48 +1623,33 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
       i = j;
     }
   }
-  const size_t o_pstate = carve(sizeof(double) * KA_STATE * np);
-  const size_t o_sched = carve(sizeof(int) * 4), o_slist = carve(sizeof(int) * np), o_heavy = carve(np);
-  const size_t o_gfirst = carve(sizeof(int) * np), o_gsize = carve(sizeof(int) * np);
-  const size_t o_gpart = carve(sizeof(double) * 2 * 4 * np), o_gcnt = carve(sizeof(unsigned) * KA_GRP_CNT_STRIDE * np);
-  if (int rc = grow(&ctx->d_workspace, &ctx->workspace_bytes, off)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  int64_t* d_hptr = (int64_t*)(ws + o_hptr);
-  pxr_lm_summary* d_sum = (pxr_lm_summary*)(ws + o_sum);
-  KaInfo* d_info = (KaInfo*)(ws + o_info);
-  PXR_HIP(hipMemsetAsync(ws + o_used, 0, nn, st));
+  KaWorkspace w((size_t)view->n_nodes, (size_t)np, arena->C);
+  if (int rc = grow(&ctx->d_workspace, &ctx->workspace_bytes, w.bytes)) return rc;
   KaArgs a{};
-  fill_args(ctx, arena, view, cfg, loss, a);
+  fill_args(arena, view, cfg, loss, a);
+  w.wire(static_cast<char*>(ctx->d_workspace), grp_max > 1, a);
   a.bound = bound; a.opt = *options;
+  PXR_HIP(hipMemsetAsync(a.used, 0, (size_t)view->n_nodes, st));
+  PXR_HIP(hipMemsetAsync(a.prob_state, 0, sizeof(double) * KA_STATE * np, st));
   // deterministic mode: H and g of a sub-problem in fixed point; the start grid 2^-38 suits unit-norm 128-channel descriptors
   // (bound = max(trace, sqrt(2 trace cost)) ~ 1e4 .. 1e5 at configs[1]), the kernel adapts it per sub-problem and linearisation
   a.det_scale = ctx->deterministic ? 274877906944.0 : 0.0;      // 2^38 (see the grid rule in ka_solve_body)
-  a.prob_scale = (double*)(ws + o_pscale); a.prob_done = (uint8_t*)(ws + o_pdone);
-  a.prob_state = (double*)(ws + o_pstate);
-  PXR_HIP(hipMemsetAsync(a.prob_state, 0, sizeof(double) * KA_STATE * np, st));
-  a.sched = (int*)(ws + o_sched); a.sched_list = (int*)(ws + o_slist); a.prob_heavy = (uint8_t*)(ws + o_heavy);
   if (a.det_scale != 0.0) {
     std::vector<double> init((size_t)np, a.det_scale);
     PXR_HIP(hipMemcpyAsync(a.prob_scale, init.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
     PXR_HIP(hipMemsetAsync(a.prob_done, 0, np, st));
     PXR_HIP(hipStreamSynchronize(st));       // (`init` leaves scope)
   }
-  a.desc = (double*)(ws + o_desc); a.kp_cand = (double*)(ws + o_cand); a.vec = (double*)(ws + o_vec);
-  a.var_of_node = (int*)(ws + o_var); a.label = (int*)(ws + o_label); a.ipos = (int*)(ws + o_ipos);
-  a.irow = (int*)(ws + o_irow); a.comp_v0 = (int*)(ws + o_comp); a.used = (uint8_t*)(ws + o_used);
-  a.prob_h_ptr = d_hptr; a.summaries = d_sum; a.slot_of_node = (int*)(ws + o_slot);
   if (grp_max > 1) {
-    a.grp_first = (const int*)(ws + o_gfirst); a.grp_size = (const int*)(ws + o_gsize);
-    a.grp_part = (double*)(ws + o_gpart); a.grp_cnt = (unsigned*)(ws + o_gcnt);
-    PXR_HIP(hipMemcpyAsync(ws + o_gfirst, grp_first.data(), sizeof(int) * np, hipMemcpyHostToDevice, st));
-    PXR_HIP(hipMemcpyAsync(ws + o_gsize, grp_size.data(), sizeof(int) * np, hipMemcpyHostToDevice, st));
+    PXR_HIP(hipMemcpyAsync(w.d_gfirst, grp_first.data(), sizeof(int) * np, hipMemcpyHostToDevice, st));
+    PXR_HIP(hipMemcpyAsync(w.d_gsize, grp_size.data(), sizeof(int) * np, hipMemcpyHostToDevice, st));
     PXR_HIP(hipStreamSynchronize(st));
   }
   // 1. components, unknown layout, bounds; the block sizes come back to size the matrices exactly
-  hipLaunchKernelGGL(ka_setup_kernel, dim3(np), dim3(KA_NT), 0, st, a, d_info);
+  hipLaunchKernelGGL(ka_setup_kernel, dim3(np), dim3(KA_NT), 0, st, a, w.d_info);
   PXR_HIP(hipGetLastError());
   std::vector<KaInfo> infos(np);
-  PXR_HIP(hipMemcpyAsync(infos.data(), d_info, sizeof(KaInfo) * np, hipMemcpyDeviceToHost, st));
+  PXR_HIP(hipMemcpyAsync(infos.data(), w.d_info, sizeof(KaInfo) * np, hipMemcpyDeviceToHost, st));
   PXR_HIP(hipStreamSynchronize(st));
   int64_t largest = 1;
   for (int i = 0; i < np; ++i) {
@@ -1914,113 +1670,22 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
   n_max = (n_max + 1) & ~1;                                           // the int arrays start 8-byte aligned
   const size_t state_bytes = sizeof(double) * ((size_t)2 * lds_elems + (size_t)8 * n_max) + sizeof(int) * (size_t)4 * n_max;
   a.lds_state_n = (!need_aglob && state_bytes <= (size_t)56 * 1024) ? n_max : 0;
-  PXR_HIP(hipMemcpyAsync(d_hptr, h_ptr.data(), sizeof(int64_t) * (np + 1), hipMemcpyHostToDevice, st));
-  size_t shmem = a.lds_state_n > 0 ? state_bytes : sizeof(double) * (size_t)lds_elems;
-  // the streamed line-search probe (ka_probe_stream): L2-normalised 64 / 128-channel descriptors in fp16 / fp32 storage, no unary
-  // terms, every sub-problem of at most 64 nodes with all its residual blocks in the LDS cache, and its LDS region next to the
-  // LM state inside the two-workgroups-per-CU budget; PXR_KA_STREAM=0 is the A/B knob
-  a.stream_slots = 0; a.stream_off = 0;
-#ifdef PXR_KA_STREAM_PROBE
-  {
-    int64_t nodes_max = 0, edges_max = 0;
-    for (int i = 0; i < np; ++i) {
-      nodes_max = std::max(nodes_max, node_ptr[i + 1] - node_ptr[i]);
-      edges_max = std::max(edges_max, edge_ptr[i + 1] - edge_ptr[i]);
-    }
-    const char* knob = getenv("PXR_KA_STREAM");
-    const size_t stream_bytes = sizeof(double) * (size_t)nodes_max * (KA_SROW + 4);
-    const size_t stream_at = (state_bytes + 15) & ~(size_t)15;
-    if (!(knob && knob[0] == '0') && a.lds_state_n > 0 && view->n_unary == 0 && cfg->l2_normalize && (arena->C == 128 || arena->C == 64) &&
-        (arena->dtype == PXR_F16 || arena->dtype == PXR_F32) && nodes_max >= 1 && nodes_max <= KA_STREAM_MAX && edges_max <= KA_EDGE_CACHE &&
-        stream_at + stream_bytes <= (size_t)56 * 1024) {
-      a.stream_slots = (int)nodes_max; a.stream_off = (int)(stream_at / sizeof(double));
-      shmem = stream_at + stream_bytes;
-    }
-  }
-#else
-  (void)edge_ptr;
-#endif
-  // the two-phase launch (ka_solve_kernel_sched): an EXPERIMENT, off unless PXR_KA_TWO_PHASE=1 (profiles/r6_ka_schedule.txt: the
-  // dispatch ORDER is worth 1.8 ms of the 5.3 -- 3.4 ms with the heaviest sub-problems first -- but which ones are heavy does
-  // not show after one LM iteration, and the persistent grid costs 0.6 ms in spilled registers and barrier time: 5.55 ms).  Needs
-  // more sub-problems than the launch keeps resident, no label groups that span workgroups, the fp16 / fp32 CNN-feature kernels.
-  // The two-LAUNCH schedule (round 6, the default when there are more sub-problems than resident workgroups): the launch is as
-  // long as its tail -- the ~7 % of the sub-problems that run twenty-probe line searches against an active bound take 2.5-3.3 ms,
-  // the others 0.65-0.9, and dispatch in index order starts some of the long ones last (with the heaviest first the same kernel
-  // needs 3.4 instead of 5.3 ms at configs[1]: profiles/r6_ka_schedule.txt).  Which ones are heavy shows after TWO LM iterations
-  // (a keypoint clamped onto its bound: 131 of 137 caught).  So: launch 1 runs two iterations of every sub-problem and parks the
-  // complete LM state (nothing is evaluated twice), a one-workgroup kernel lists the parked ones -- on a bound first --, launch 2
-  // resumes them in that order.  Same arithmetic per sub-problem: identical bits (tests/test_ka_gpu.py::test_two_phase_launch_*).
-  // 5.36 -> 4.97 ms at configs[1].  PXR_KA_TWO_LAUNCH=0 switches it off, =N parks after N iterations.
-  const char* two_launch_knob = getenv("PXR_KA_TWO_LAUNCH");
-  const int park_iters = two_launch_knob && atoi(two_launch_knob) > 0 ? atoi(two_launch_knob) : 2;
-  int resident_hint = 2 * ctx->num_cus;
-  if (const char* e = getenv("PXR_KA_TWO_PHASE_RESIDENT")) resident_hint = std::max(1, atoi(e));
-  const bool two_launch = !(two_launch_knob && two_launch_knob[0] == '0') && grp_max <= 1 && np > resident_hint;
-  const char* two_phase_knob = getenv("PXR_KA_TWO_PHASE");
-  const bool two_phase_wanted = two_phase_knob && two_phase_knob[0] == '1' && grp_max <= 1;
-#define KA_SOLVE_LAUNCH(KERNEL, SCHED, ST, CC)                                                                    \
-  do {                                                                                                       \
-    void (*kfn)(const KaArgs, const KaInfo*) = a.det_scale != 0.0 ? KERNEL<ST, CC, true> : KERNEL<ST, CC, false>; \
-    unsigned grid = (unsigned)np;                                                                            \
-    void (*sfn)(const KaArgs, const KaInfo*) = a.det_scale != 0.0 ? SCHED<ST, CC, true> : SCHED<ST, CC, false>;   \
-    if (two_phase_wanted && sfn != kfn) {                                                                    \
-      PXR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-      int per_cu = 0;                                                                                        \
-      PXR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(sfn), KA_NT, shmem)); \
-      int resident = per_cu * ctx->num_cus;                                                                  \
-      if (const char* e = getenv("PXR_KA_TWO_PHASE_RESIDENT")) resident = std::min(resident, std::max(1, atoi(e)));   /* tests: a small grid */ \
-      if (getenv("PXR_VERBOSE")) fprintf(stderr, "[pxr_ka_solve] two-phase launch: %d workgroups per CU x %d CUs resident, %d sub-problems, %zu B of dynamic LDS\n", per_cu, ctx->num_cus, np, (size_t)shmem); \
-      if (resident >= 1 && np > resident) {        /* (everything resident at once: no tail to schedule away) */ \
-        kfn = sfn; grid = (unsigned)resident;                                                                \
-        if (getenv("PXR_KA_PHASE1_ONLY")) a.stream_off = -1;                                                 \
-        PXR_HIP(hipMemsetAsync(a.sched, 0, sizeof(int) * 4, st));                                            \
-        PXR_HIP(hipMemsetAsync(a.prob_heavy, 0, np, st));                                                    \
-      }                                                                                                      \
-    }                                                                                                        \
-    PXR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                                          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                    \
-    if (grp_max > 1) {   /* every member of a group must be resident at the same time (ka_group_sum4 spins) */ \
-      int per_cu = 0;                                                                                        \
-      PXR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kfn), KA_NT, shmem)); \
-      const int resident = per_cu * ctx->num_cus;                                                            \
-      if (grp_max > resident * 7 / 8)                                                                        \
-        return set_error(PXR_EUNSUPPORTED, "pxr_ka_solve: a label group of %d chunks exceeds what one launch keeps resident (%d workgroups): use smaller groups", grp_max, resident); \
-      PXR_HIP(hipMemsetAsync(a.grp_cnt, 0, sizeof(unsigned) * KA_GRP_CNT_STRIDE * np, st));                  \
-    }                                                                                                        \
-    PXR_HIP(hipEventRecord(ctx->ev_start, st));                                                              \
-    if (two_launch && kfn != sfn && sfn != (void (*)(const KaArgs, const KaInfo*))nullptr && (void*)SCHED<ST, CC, true> != (void*)KERNEL<ST, CC, true>) { \
-      /* two launches of the plain kernel: every sub-problem runs `park_iters` LM iterations and parks its complete LM state, */ \
-      /* a one-workgroup kernel lists the parked ones (those on a bound first), the second launch resumes them in that order  */ \
-      PXR_HIP(hipMemsetAsync(a.prob_heavy, 0, np, st));                                                      \
-      KaArgs a1 = a; a1.phase = 1; a1.park_iters = park_iters;                                               \
-      hipLaunchKernelGGL(kfn, dim3(grid), dim3(KA_NT), shmem, st, a1, d_info);                               \
-      hipLaunchKernelGGL(ka_order_kernel, dim3(1), dim3(1024), 0, st, a, a.sched_list);                      \
-      KaArgs a2 = a; a2.phase = 2; a2.order = a.sched_list;                                                  \
-      hipLaunchKernelGGL(kfn, dim3(grid), dim3(KA_NT), shmem, st, a2, d_info);                               \
-    } else                                                                                                   \
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(KA_NT), shmem, st, a, d_info);                                  \
-    PXR_HIP(hipEventRecord(ctx->ev_stop, st));                                                               \
-  } while (0)
+  PXR_HIP(hipMemcpyAsync(w.d_hptr, h_ptr.data(), sizeof(int64_t) * (np + 1), hipMemcpyHostToDevice, st));
+  const size_t shmem = a.lds_state_n > 0 ? state_bytes : sizeof(double) * (size_t)lds_elems;
+  // 2. the solve.  Two launches when there are more sub-problems than one launch keeps resident and no label group spans
+  // workgroups (ka_launch_solve)
+  const bool two_launch = knobs.two_launch && grp_max <= 1 && np > (knobs.resident ? knobs.resident : 2 * ctx->num_cus);
+  KaKernels kernels;
+  if (int rc = ka_kernels("pxr_ka_solve", arena, a.det_scale != 0.0, &kernels)) return rc;
   std::vector<pxr_lm_summary> sums(np), pass(np);
   double kernel_ms = 0.0;
-  // One launch solves every sub-problem.  Deterministic mode: a sub-problem whose fixed-point grid does not fit (its overflow
+  // One pass solves every sub-problem.  Deterministic mode: a sub-problem whose fixed-point grid does not fit (its overflow
   // guard; raw un-normalised features) stops with KA_TERM_RESCALE and its new grid in prob_scale -- launch again: finished
-  // sub-problems return at once, the others go on from their current keypoints.  (Never more than one launch with unit-norm
+  // sub-problems return at once, the others go on from their current keypoints.  (Never more than one pass with unit-norm
   // descriptors.)
   for (int launch = 0; launch < 8; ++launch) {
-    if (arena->dtype == PXR_F16 && arena->C == 128) KA_SOLVE_LAUNCH(ka_solve_kernel_occ2, ka_solve_kernel_sched, _Float16, 128);
-    else if (arena->dtype == PXR_F16 && arena->C == 64) KA_SOLVE_LAUNCH(ka_solve_kernel_occ2, ka_solve_kernel_sched, _Float16, 64);
-    else if (arena->dtype == PXR_F32 && arena->C == 128) KA_SOLVE_LAUNCH(ka_solve_kernel_occ2, ka_solve_kernel_sched, float, 128);
-    else if (arena->dtype == PXR_F64 && arena->C == 128) KA_SOLVE_LAUNCH(ka_solve_kernel, ka_solve_kernel, double, 128);
-    else if (arena->dtype == PXR_F32 && arena->C == 64) KA_SOLVE_LAUNCH(ka_solve_kernel_occ2, ka_solve_kernel_sched, float, 64);
-    else if (arena->dtype == PXR_F64 && arena->C == 64) KA_SOLVE_LAUNCH(ka_solve_kernel, ka_solve_kernel, double, 64);
-    else if (arena->dtype == PXR_F16 && arena->C == 1) KA_SOLVE_LAUNCH(ka_solve_kernel, ka_solve_kernel, _Float16, 1);
-    else if (arena->dtype == PXR_F32 && arena->C == 1) KA_SOLVE_LAUNCH(ka_solve_kernel, ka_solve_kernel, float, 1);
-    else if (arena->dtype == PXR_F64 && arena->C == 1) KA_SOLVE_LAUNCH(ka_solve_kernel, ka_solve_kernel, double, 1);
-    else return set_error(PXR_EUNSUPPORTED, "pxr_ka_solve: CHANNELS=%d not supported (128, 64, 1)", arena->C);
-    PXR_HIP(hipGetLastError());
-    PXR_HIP(hipMemcpyAsync(pass.data(), d_sum, sizeof(pxr_lm_summary) * np, hipMemcpyDeviceToHost, st));
+    if (int rc = ka_launch_solve(ctx, kernels, a, w, shmem, grp_max, two_launch, knobs)) return rc;
+    PXR_HIP(hipMemcpyAsync(pass.data(), a.summaries, sizeof(pxr_lm_summary) * np, hipMemcpyDeviceToHost, st));
     PXR_HIP(hipStreamSynchronize(st));
     float kms = 0.f;
     PXR_HIP(hipEventElapsedTime(&kms, ctx->ev_start, ctx->ev_stop));
@@ -2040,7 +1705,6 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
     if (!again) break;
     PXR_REQUIRE(launch < 7, "pxr_ka_solve: the fixed-point grid of the deterministic mode could not be fitted (non-finite features?)");
   }
-#undef KA_SOLVE_LAUNCH
   total->accumulation = a.det_scale != 0.0 ? 1 : 0;
   total->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   total->setup_ms = total->total_ms - kernel_ms;   // everything but the solve kernel itself (workspace, uploads, summaries download)

@@ -155,6 +155,29 @@ def test_solve_every_storage_type_and_channel_count(ctx, dtype, channels):
     assert np.abs(ka.keypoints() - kpo).max() < 1e-6
 
 
+@pytest.mark.parametrize("dtype,channels", [(np.float16, 128), (np.float16, 64), (np.float32, 128), (np.float32, 64)])
+def test_solve_with_floating_point_atomics_every_capped_kernel(dtype, channels):
+    """The register-capped solve kernel (fp16 / fp32 storage x CHANNELS 128 / 64) in its floating-point-atomics instantiation
+    (Context.deterministic = False): the same problem, oracle comparison and tolerances as
+    test_solve_every_storage_type_and_channel_count, which runs the fixed-point instantiations.  Seed 33 as there: the reference
+    decides the iteration counts and floating-point atomics may flip a borderline step, but at this seed all four cases agree."""
+    import pxo
+    import pxo_ka
+    from pixsfm_amd.engine import Context, interp_cfg, make_loss
+    c = Context(0)
+    c.deterministic = False
+    prob, arena, ka = _setup(c, n_tracks=8, track_len=4, seed=33, dtype=dtype, channels=channels, max_kps_per_problem=16)
+    total, per = ka.solve(interp_cfg(), make_loss("cauchy", [0.25]), bound=4.0, per_problem=True)
+    kp = ka.keypoints()
+    arena.close(); c.close()
+    assert total["accumulation"] == 0
+    kpo, sums = pxo_ka.ka_solve(prob, pxo.cfg(), pxo.loss("cauchy", 0.25), 4.0)
+    for g, o in zip(per, sums):
+        assert g["iterations"] == o["iterations"] and g["termination"] == o["termination"]
+        assert abs(g["final_cost"] - o["final_cost"]) < 1e-7 * max(o["final_cost"], 1e-6)
+    assert np.abs(kp - kpo).max() < 1e-6
+
+
 def test_check_bounds_has_no_effect_on_keypoint_adjustment(ctx):
     """check_bounds with a keypoint outside its patch: the KA functors ignore what PatchInterpolator::Evaluate returns and
     always succeed (featuremetric.h:44-63, feature_reference.h:44-60), so evaluation and solve are those without the option
@@ -344,11 +367,11 @@ def test_a_group_with_too_many_chunks_is_refused_through_the_c_abi(ctx):
     arena.close()
 
 
-# ---- the two-phase launch (ka_solve_kernel_sched, round 6) ------------------------------------------------------------------------
-@pytest.mark.parametrize("variant", ["persistent", "two_launches_1", "two_launches_2"])
+# ---- the two-launch schedule: park after N LM iterations, resume those on a bound first (PXR_KA_TWO_LAUNCH) ------------------------
+@pytest.mark.parametrize("variant", ["two_launches_1", "two_launches_2"])
 @pytest.mark.parametrize("sigma,bound", [(1.0, 4.0), (1.5, 1.5)])
 def test_two_phase_launch_gives_the_one_phase_results_bit_for_bit(ctx, monkeypatch, sigma, bound, variant):
-    """More sub-problems than resident workgroups (forced here: a grid of 5): every sub-problem runs ONE LM iteration, parks its LM
+    """More sub-problems than resident workgroups (forced here: 5): every sub-problem runs one / two LM iterations, parks its LM
     state, and is resumed from a list that starts with those sitting on a bound.  Same arithmetic per sub-problem -- the resumed
     linearisation is accumulated on the grid the interrupted one used -- so keypoints, costs and counts equal the one-phase
     launch's bit for bit (deterministic default), and the oracle's to the usual tolerances."""
@@ -362,9 +385,8 @@ def test_two_phase_launch_gives_the_one_phase_results_bit_for_bit(ctx, monkeypat
     arena = PatchArena.from_numpy(ctx, prob["patches"], prob["corners"], prob["scales"])
     out = []
     for knob in ("0", "1"):
-        # (the persistent grid, or two launches of the plain kernel that park after 1 / 2 LM iterations: PXR_KA_TWO_LAUNCH)
-        monkeypatch.setenv("PXR_KA_TWO_PHASE", knob if variant == "persistent" else "0")
-        monkeypatch.setenv("PXR_KA_TWO_LAUNCH", "0" if (variant == "persistent" or knob == "0") else variant[-1])
+        # (one launch, or two launches that park after 1 / 2 LM iterations)
+        monkeypatch.setenv("PXR_KA_TWO_LAUNCH", "0" if knob == "0" else variant[-1])
         monkeypatch.setenv("PXR_KA_TWO_PHASE_RESIDENT", "5")
         ka = KAProblem(ctx, arena, prob)
         total, per = ka.solve(interp_cfg(), make_loss("cauchy", [0.25]), bound=bound, options=lm_options(parameter_tolerance=1e-5), per_problem=True)
@@ -392,8 +414,7 @@ def test_two_phase_launch_with_floating_point_atomics(monkeypatch):
     prob = synthetic_ka.make_ka_problem(n_tracks=60, track_len=5, seed=18, max_kps_per_problem=10, sigma=1.5)
     arena = PatchArena.from_numpy(c, prob["patches"], prob["corners"], prob["scales"])
     out = []
-    for knob in ("0", "1", "launches"):
-        monkeypatch.setenv("PXR_KA_TWO_PHASE", "1" if knob == "1" else "0")
+    for knob in ("0", "launches"):
         monkeypatch.setenv("PXR_KA_TWO_LAUNCH", "2" if knob == "launches" else "0")
         monkeypatch.setenv("PXR_KA_TWO_PHASE_RESIDENT", "7")
         ka = KAProblem(c, arena, prob)

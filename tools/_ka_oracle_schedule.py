@@ -15,7 +15,6 @@ import bench_ka
 from pixsfm_amd.engine import Context, PatchArena, interp_cfg, make_loss
 from pixsfm_amd.ka_engine import KAProblem
 
-os.environ["PXR_KA_TWO_PHASE"] = "0"
 torch.cuda.set_device(0)
 ctx = Context(0, stream=torch.cuda.current_stream().cuda_stream)
 prob, patches = bench_ka.make_problem_gpu("cuda:0", 10000, 10)
