@@ -512,6 +512,52 @@ int pxr_absolute_pose_timed(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_qu
                             int32_t* d_status, int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err,
                             double* h_kernel_ms);
 
+/* ---- descriptor matching (descriptors of image pairs in, mutual nearest neighbours out) --------
+ * What produces the match graph (and a query's 2D-3D pairs): hloc's match_features with the NearestNeighbor matcher, whose output
+ * pixsfm/util/hloc.py:read_matches_hloc reads back.  hloc is not available where this library is built, so parity with it is
+ * unpinned; the specification below is this library's own and reproduces bit for bit.
+ * ratio_threshold <= 0 / distance_threshold <= 0 switch the test off.  hloc's confs: "NN-mutual" (0, 0, 1), "NN-ratio" (0.8, 0, 1),
+ * "NN-superpoint" (0, 0.7, 1). */
+#define PXR_MATCH_MAX_DIM 512
+typedef struct {
+  double ratio_threshold;      /* 0   Lowe's ratio on distances: d1 <= ratio^2 d2 (squared distances)      */
+  double distance_threshold;   /* 0   d1 <= dist^2                                                         */
+  int32_t do_mutual_check;     /* 1   keep i -> j only if j -> i                                           */
+  int32_t reserved;            /* 0                                                                        */
+} pxr_match_options;
+/* Writes the defaults above ("NN-mutual"). */
+void pxr_match_default_options(pxr_match_options* options);
+
+/* A batch: n_images images, image m owning rows [d_image_offsets[m], d_image_offsets[m+1]) of d_desc (n_total x dim float32,
+ * row-major), and n_pairs pairs of image indices d_pairs (n_pairs x 2 int32; a pair may name one image twice).  1 <= dim <=
+ * PXR_MATCH_MAX_DIM.  Descriptors are expected to be finite and L2-normalised; nothing is normalised here.  All arrays are device
+ * pointers.  For a pair (a, b) with na, nb descriptors A, B:
+ *   similarity  sim[i][j] = the float32 value of  s = 0; for k = 0 .. dim-1: s = fmaf(A[i][k], B[j][k], s)  -- one rounding per
+ *               product, ascending k, no wider accumulator, no split over k (what v_mfma_f32_32x32x2_f32 computes when the
+ *               instructions of one output tile are issued in k order on one accumulator).  k is padded with zeros to a multiple
+ *               of 16, which leaves every comparison below unchanged.  A NaN similarity never wins a comparison.
+ *   forward     per row i: best = the j of the largest sim[i][j], ties to the lowest j; s1 that value; s2 the largest value over
+ *               j != best.  In float32 d1 = 2 (1 - s1), d2 = 2 (1 - s2).  Ratio test: d1 <= r2 d2 with r2 = (float)(ratio ratio),
+ *               skipped when ratio_threshold <= 0 and, for the whole pair, when na == 1 or nb == 1.  Distance test: d1 <= t2 with
+ *               t2 = (float)(dist dist), skipped when distance_threshold <= 0.  m0[i] = best if both pass, else -1.
+ *   backward    the same over the columns with the same thresholds: m1[j].
+ *   mutual      (do_mutual_check != 0) m0[i] stays iff m1[m0[i]] == i.
+ * Outputs of pair p at d_pair_offsets[p] of the flat arrays (d_pair_offsets: n_pairs + 1 entries, the prefix sum of na over the
+ * pairs, computed by the caller and checked here): d_matches0 int32 of length na (-1: no match), d_scores0 float32 of length na
+ * ((s1 + 1) / 2 where matches0 >= 0, else 0 -- also where the mutual check removed the match), d_n_matches[p] the count.
+ * An empty image gives an empty result (first image) or all -1 (second image).  The similarity matrix is never stored.
+ * PXR_EINVAL (nothing launched, outputs untouched): image offsets not starting at 0, not monotone or not ending at n_total, a pair
+ * index out of range, d_pair_offsets not that prefix sum, dim outside [1, PXR_MATCH_MAX_DIM].  Synchronises the context's stream
+ * (offsets and pairs are validated on a host copy). */
+int pxr_match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                          const float* d_desc, int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets,
+                          const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[3] = tiles, columns, mutual. */
+int pxr_match_descriptors_timed(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                                const float* d_desc, int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets,
+                                const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches,
+                                double* h_kernel_ms);
+
 /* ---- BA reference extraction -----------------------------------------------------------
  * Replaces ReferenceExtractor::Run (bundle_adjustment/src/reference_extractor.h:125-318) +
  * RobustMeanIRLS (base/src/irls_optim.h:24-71) for N_NODES = 1: per point, descriptors of all

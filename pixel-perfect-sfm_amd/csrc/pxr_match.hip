@@ -1,0 +1,416 @@
+// pxr_match.hip -- batched descriptor matching: mutual nearest neighbours of image pairs (pxr_match_descriptors; the specification
+// is in include/pixsfm_hip.h and DESIGN.md section 20).
+//
+// k_match_tiles    one workgroup of four wavefronts per (pair, strip of 128 rows of the first image).  A wavefront owns 32 rows and
+//                  keeps their descriptors as MFMA A fragments in registers for the whole sweep (lane l: row l & 31, k = 2 kk + (l >> 5)
+//                  in register kk).  The second image goes by in tiles of 32 columns through LDS, double-buffered and shared by the four
+//                  wavefronts, stored in FRAGMENT order (word kk * 64 + l is what lane l feeds to instruction kk), so a fragment read is
+//                  one linear ds_read_b32 per instruction and needs no padding.  One accumulator per tile, the v_mfma_f32_32x32x2_f32 of a
+//                  tile issued in k order: the accumulator is the k-ordered fmaf chain of the specification.  The similarity tile lives in
+//                  the 16 accumulator registers only (lane l: column l & 31, rows (r & 3) + 8 (r >> 2) + 4 (l >> 5)):
+//                    rows     each lane keeps a running (s1, j1, s2) per register; it meets its columns in ascending order, so a strict
+//                             '>' is "lowest index wins".  After the last tile a 32-lane butterfly merges the lanes of a row.
+//                    columns  per tile each lane reduces its 16 registers to (s1, i1, s2) of its column, merges with lane l ^ 32, the four
+//                             wavefronts meet in LDS and the workgroup writes one partial per column and strip.
+//                  Every merge compares keys (value, -index) and takes the second as the maximum of the loser's best and both seconds:
+//                  associative and commutative, so no result depends on an order of arrival.  No floating-point atomics.
+// k_match_columns  one lane per (pair, column): merges the strips' partials, applies the tests, writes m1.
+// k_match_mutual   one workgroup per (pair, strip), one lane per row: the mutual check, matches0 / scores0, one integer add per
+//                  workgroup to n_matches.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
+#include "pxr_internal.h"
+
+namespace pxr {
+namespace {
+
+constexpr int MT_THREADS = 256;   // four wavefronts
+constexpr int MT_ROWS = 128;      // rows of a strip: 32 per wavefront
+constexpr int MT_COLS = 32;       // columns of a tile
+constexpr int MT_KSTEP = 8;       // instructions between two tests of the k bound: k is padded to a multiple of 2 * MT_KSTEP = 16
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct MatchItem { int32_t pair, strip; };
+
+struct MatchPair {       // one pair, as the host laid it out
+  int64_t a_row, b_row;  // first descriptor row of either image
+  int64_t out;           // pair_offsets[p]
+  int64_t col;           // prefix sum of nb: where the pair's m1 starts
+  int64_t part;          // where the pair's partials start (strips x nb entries)
+  int32_t na, nb;
+};
+
+struct MatchArgs {
+  const float* desc;
+  const MatchPair* pairs;
+  const MatchItem* items;
+  const int64_t* col_prefix;   // [n_pairs + 1]
+  float* part_s1; int32_t* part_i1; float* part_s2;
+  int32_t* m1;
+  int32_t* matches0; float* scores0; int32_t* n_matches;
+  int64_t n_cols;
+  int32_t n_pairs, dim, kp;    // kp: k pairs (instructions per tile), a multiple of MT_KSTEP
+  float r2, t2;
+  int32_t use_ratio, use_dist, mutual;
+};
+
+struct Top2 { float s1; int32_t i1; float s2; };
+
+__device__ __forceinline__ void top2_push(Top2& t, float v, int32_t idx) {   // indices arrive in ascending order
+  if (v > t.s1) { t.s2 = t.s1; t.s1 = v; t.i1 = idx; }
+  else if (v > t.s2) t.s2 = v;
+}
+
+// key (value, -index); an empty side is (-inf, -1, -inf) and loses to anything but another empty side
+__device__ __forceinline__ Top2 top2_merge(const Top2& x, const Top2& y) {
+  const bool x_wins = x.s1 > y.s1 || (x.s1 == y.s1 && x.i1 < y.i1);
+  Top2 r;
+  r.s1 = x_wins ? x.s1 : y.s1;
+  r.i1 = x_wins ? x.i1 : y.i1;
+  r.s2 = fmaxf(x_wins ? y.s1 : x.s1, fmaxf(x.s2, y.s2));
+  return r;
+}
+
+__device__ __forceinline__ Top2 top2_shfl_xor(const Top2& t, int mask) {
+  Top2 o;
+  o.s1 = __shfl_xor(t.s1, mask);
+  o.i1 = __shfl_xor(t.i1, mask);
+  o.s2 = __shfl_xor(t.s2, mask);
+  return o;
+}
+
+// the comparisons of the specification: the index that stays, or -1
+__device__ __forceinline__ int32_t match_tests(const Top2& t, bool ratio_on, bool dist_on, float r2, float t2) {
+  if (t.i1 < 0) return -1;
+  const float d1 = 2.0f * (1.0f - t.s1);
+  if (ratio_on) {
+    const float d2 = 2.0f * (1.0f - t.s2);
+    if (!(d1 <= r2 * d2)) return -1;
+  }
+  if (dist_on && !(d1 <= t2)) return -1;
+  return t.i1;
+}
+
+// KP: k pairs a wavefront can hold (registers of A fragments); the LDS tiles are sized by it too
+template <int KP>
+__global__ __launch_bounds__(MT_THREADS) void k_match_tiles(const MatchArgs a) {
+  __shared__ float bs[2][KP * 64];
+  __shared__ float cp_s1[2][4][MT_COLS];
+  __shared__ int32_t cp_i1[2][4][MT_COLS];
+  __shared__ float cp_s2[2][4][MT_COLS];
+
+  const MatchItem it = a.items[blockIdx.x];
+  const MatchPair p = a.pairs[it.pair];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, c = lane & 31;
+  const int dim = a.dim, kp = a.kp;
+  const float NEG = -INFINITY;
+
+  // A fragments: row0 + c, k = 2 kk + h
+  const int row_a = it.strip * MT_ROWS + w * 32 + c;            // the row this lane loads (as an A operand)
+  float af[KP];
+  {
+    const bool row_ok = row_a < p.na;
+    const float* ap = a.desc + (p.a_row + (row_ok ? row_a : 0)) * (int64_t)dim;
+#pragma unroll
+    for (int kk = 0; kk < KP; ++kk) {
+      const int k = 2 * kk + h;
+      af[kk] = (row_ok && k < dim) ? ap[k] : 0.0f;
+    }
+  }
+
+  // the loader's share of a tile: column tid & 31, k = 4 (q * 8 + (tid >> 5)) .. + 3 for q = 0 .. KP / 16 - 1
+  constexpr int NQ = KP / 16;
+  const int lc = tid & 31, lk = tid >> 5;
+  float4 pf[NQ];
+  const bool dim4 = (dim & 3) == 0;
+  auto fetch = [&](int tile) {
+    const int j = tile * MT_COLS + lc;
+    const bool col_ok = j < p.nb;
+    const float* bp = a.desc + (p.b_row + (col_ok ? j : 0)) * (int64_t)dim;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int k0 = 4 * (q * 8 + lk);
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (k0 < 2 * kp && col_ok) {
+        if (dim4 && k0 + 3 < dim) v = *reinterpret_cast<const float4*>(bp + k0);
+        else {
+          if (k0 < dim) v.x = bp[k0];
+          if (k0 + 1 < dim) v.y = bp[k0 + 1];
+          if (k0 + 2 < dim) v.z = bp[k0 + 2];
+          if (k0 + 3 < dim) v.w = bp[k0 + 3];
+        }
+      }
+      pf[q] = v;
+    }
+  };
+  auto stash = [&](int buf) {     // k = k0 + e sits at word (k >> 1) * 64 + (k & 1) * 32 + column
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int k0 = 4 * (q * 8 + lk);
+      if (k0 < 2 * kp) {
+        float* d = &bs[buf][(k0 >> 1) * 64 + lc];
+        d[0] = pf[q].x; d[32] = pf[q].y; d[64] = pf[q].z; d[96] = pf[q].w;
+      }
+    }
+  };
+
+  const int n_tiles = (p.nb + MT_COLS - 1) / MT_COLS;
+  Top2 rt[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { rt[r].s1 = NEG; rt[r].i1 = -1; rt[r].s2 = NEG; }
+
+  if (n_tiles > 0) { fetch(0); stash(0); }
+  __syncthreads();
+
+  const int row_base = it.strip * MT_ROWS + w * 32 + 4 * h;     // + (r & 3) + 8 (r >> 2): the rows of this lane's accumulators
+  for (int t = 0; t < n_tiles; ++t) {
+    const int buf = t & 1;
+    const bool more = t + 1 < n_tiles;
+    if (more) fetch(t + 1);
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    const float* bt = &bs[buf][lane];
+#pragma unroll
+    for (int g = 0; g < KP / MT_KSTEP; ++g) {
+      if (g * MT_KSTEP < kp) {
+#pragma unroll
+        for (int u = 0; u < MT_KSTEP; ++u) {
+          const int kk = g * MT_KSTEP + u;
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], bt[kk * 64], acc, 0, 0, 0);
+        }
+      }
+    }
+
+    const int j = t * MT_COLS + c;
+    const bool col_ok = j < p.nb;
+    Top2 ct; ct.s1 = NEG; ct.i1 = -1; ct.s2 = NEG;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = row_base + (r & 3) + 8 * (r >> 2);
+      float v = acc[r];
+      v = (col_ok && row < p.na && v == v) ? v : NEG;           // outside the pair, or NaN: never wins
+      top2_push(rt[r], v, j);
+      top2_push(ct, v, row);
+    }
+    if (a.mutual) {
+      ct = top2_merge(ct, top2_shfl_xor(ct, 32));
+      if (h == 0) { cp_s1[buf][w][c] = ct.s1; cp_i1[buf][w][c] = ct.i1; cp_s2[buf][w][c] = ct.s2; }
+    }
+    if (more) stash(buf ^ 1);
+    __syncthreads();
+    if (a.mutual && tid < MT_COLS && t * MT_COLS + tid < p.nb) {
+      Top2 m; m.s1 = cp_s1[buf][0][tid]; m.i1 = cp_i1[buf][0][tid]; m.s2 = cp_s2[buf][0][tid];
+#pragma unroll
+      for (int ww = 1; ww < 4; ++ww) {
+        Top2 o; o.s1 = cp_s1[buf][ww][tid]; o.i1 = cp_i1[buf][ww][tid]; o.s2 = cp_s2[buf][ww][tid];
+        m = top2_merge(m, o);
+      }
+      const int64_t at = p.part + (int64_t)it.strip * p.nb + (t * MT_COLS + tid);
+      a.part_s1[at] = m.s1; a.part_i1[at] = m.i1; a.part_s2[at] = m.s2;
+    }
+  }
+
+  // rows: the 32 lanes of a half hold the same 16 rows over different columns
+  const bool ratio_on = a.use_ratio && p.na != 1 && p.nb != 1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    Top2 m = rt[r];
+#pragma unroll
+    for (int mask = 16; mask >= 1; mask >>= 1) m = top2_merge(m, top2_shfl_xor(m, mask));
+    const int row = row_base + (r & 3) + 8 * (r >> 2);
+    if (c == 0 && row < p.na) {
+      a.matches0[p.out + row] = match_tests(m, ratio_on, a.use_dist != 0, a.r2, a.t2);
+      a.scores0[p.out + row] = m.s1;                             // provisional: k_match_mutual turns it into the score
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_match_columns(const MatchArgs a) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= a.n_cols) return;
+  int lo = 0, hi = a.n_pairs;                 // the pair with col_prefix[pair] <= g < col_prefix[pair + 1]
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.col_prefix[mid] <= g) lo = mid; else hi = mid; }
+  const MatchPair p = a.pairs[lo];
+  const int64_t j = g - p.col;
+  const int n_strips = (p.na + MT_ROWS - 1) / MT_ROWS;
+  Top2 m; m.s1 = -INFINITY; m.i1 = -1; m.s2 = -INFINITY;
+  for (int s = 0; s < n_strips; ++s) {
+    const int64_t at = p.part + (int64_t)s * p.nb + j;
+    Top2 o; o.s1 = a.part_s1[at]; o.i1 = a.part_i1[at]; o.s2 = a.part_s2[at];
+    m = top2_merge(m, o);
+  }
+  const bool ratio_on = a.use_ratio && p.na != 1 && p.nb != 1;
+  a.m1[g] = match_tests(m, ratio_on, a.use_dist != 0, a.r2, a.t2);
+}
+
+__global__ __launch_bounds__(MT_ROWS) void k_match_mutual(const MatchArgs a) {
+  const MatchItem it = a.items[blockIdx.x];
+  const MatchPair p = a.pairs[it.pair];
+  const int row = it.strip * MT_ROWS + threadIdx.x;
+  int kept = 0;
+  if (row < p.na) {
+    int32_t m = a.matches0[p.out + row];
+    const float s1 = a.scores0[p.out + row];
+    if (m >= 0 && a.mutual && a.m1[p.col + m] != row) m = -1;
+    a.matches0[p.out + row] = m;
+    a.scores0[p.out + row] = m >= 0 ? (s1 + 1.0f) / 2.0f : 0.0f;
+    kept = m >= 0;
+  }
+  const int total = __syncthreads_count(kept);
+  if (threadIdx.x == 0 && total > 0) atomicAdd(&a.n_matches[it.pair], total);
+}
+
+int match_grow_workspace(pxr_ctx* ctx, size_t bytes) {
+  if (bytes <= ctx->workspace_bytes) return PXR_OK;
+  PXR_HIP(hipStreamSynchronize(ctx->stream));
+  if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
+  PXR_HIP(hipMalloc(&ctx->d_workspace, bytes));
+  ctx->workspace_bytes = bytes;
+  return PXR_OK;
+}
+
+int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim, const float* d_desc,
+                      int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets, const pxr_match_options* o,
+                      int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches, double* h_ms) {
+  const char* fn = "pxr_match_descriptors";
+  PXR_REQUIRE(ctx && o, "%s: NULL argument", fn);
+  PXR_REQUIRE(n_images >= 0 && n_total >= 0 && n_pairs >= 0, "%s: negative size", fn);
+  PXR_REQUIRE(dim >= 1 && dim <= PXR_MATCH_MAX_DIM, "%s: dim = %d is outside [1, %d]", fn, (int)dim, PXR_MATCH_MAX_DIM);
+  PXR_REQUIRE(n_total < ((int64_t)1 << 31), "%s: n_total = %lld: more than 2^31 descriptors", fn, (long long)n_total);
+  PXR_REQUIRE(std::isfinite(o->ratio_threshold) && std::isfinite(o->distance_threshold), "%s: options: a threshold is not finite", fn);
+  PXR_REQUIRE(o->reserved == 0, "%s: options.reserved must be 0", fn);
+  PXR_REQUIRE(n_images == 0 || d_image_offsets, "%s: NULL d_image_offsets", fn);
+  PXR_REQUIRE(n_total == 0 || d_desc, "%s: NULL d_desc", fn);
+  PXR_REQUIRE(n_pairs == 0 || (d_pairs && d_pair_offsets && d_n_matches), "%s: NULL d_pairs / d_pair_offsets / d_n_matches", fn);
+  if (h_ms) h_ms[0] = h_ms[1] = h_ms[2] = 0.0;
+  PXR_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+
+  // validation on a host copy of the offsets and the pairs
+  std::vector<int64_t> off((size_t)n_images + 1, 0), pair_off((size_t)n_pairs + 1, 0);
+  std::vector<int32_t> pairs((size_t)n_pairs * 2);
+  if (n_images > 0) PXR_HIP(hipMemcpyAsync(off.data(), d_image_offsets, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost, st));
+  if (n_pairs > 0) {
+    PXR_HIP(hipMemcpyAsync(pairs.data(), d_pairs, sizeof(int32_t) * pairs.size(), hipMemcpyDeviceToHost, st));
+    PXR_HIP(hipMemcpyAsync(pair_off.data(), d_pair_offsets, sizeof(int64_t) * pair_off.size(), hipMemcpyDeviceToHost, st));
+  }
+  PXR_HIP(hipStreamSynchronize(st));
+  PXR_REQUIRE(off[0] == 0, "%s: d_image_offsets[0] = %lld, not 0", fn, (long long)off[0]);
+  for (int32_t m = 0; m < n_images; ++m)
+    PXR_REQUIRE(off[m + 1] >= off[m], "%s: d_image_offsets is not monotone at image %d", fn, (int)m);
+  PXR_REQUIRE(off[n_images] == n_total, "%s: d_image_offsets ends at %lld, not at n_total = %lld", fn, (long long)off[n_images], (long long)n_total);
+
+  std::vector<MatchPair> hp((size_t)n_pairs);
+  std::vector<MatchItem> items;
+  std::vector<int64_t> col_prefix((size_t)n_pairs + 1, 0);
+  int64_t rows = 0, cols = 0, parts = 0;
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    const int32_t ia = pairs[2 * (size_t)p], ib = pairs[2 * (size_t)p + 1];
+    PXR_REQUIRE(ia >= 0 && ia < n_images && ib >= 0 && ib < n_images, "%s: d_pairs[%d] = (%d, %d) names an image outside [0, n_images = %d)",
+                fn, (int)p, (int)ia, (int)ib, (int)n_images);
+    MatchPair& q = hp[(size_t)p];
+    q.a_row = off[ia]; q.na = (int32_t)(off[ia + 1] - off[ia]);
+    q.b_row = off[ib]; q.nb = (int32_t)(off[ib + 1] - off[ib]);
+    PXR_REQUIRE(pair_off[p] == rows, "%s: d_pair_offsets[%d] = %lld is not the prefix sum of the first images' sizes (%lld)", fn, (int)p,
+                (long long)pair_off[p], (long long)rows);
+    q.out = rows; q.col = cols; q.part = parts;
+    const int32_t n_strips = (q.na + MT_ROWS - 1) / MT_ROWS;
+    for (int32_t s = 0; s < n_strips; ++s) items.push_back(MatchItem{p, s});
+    rows += q.na;
+    if (q.na > 0) { cols += q.nb; parts += (int64_t)n_strips * q.nb; }
+    col_prefix[(size_t)p + 1] = cols;
+  }
+  PXR_REQUIRE(pair_off[n_pairs] == rows, "%s: d_pair_offsets ends at %lld, not at the sum of the first images' sizes (%lld)", fn,
+              (long long)pair_off[n_pairs], (long long)rows);
+  PXR_REQUIRE(rows < ((int64_t)1 << 31) && items.size() < ((size_t)1 << 31), "%s: more than 2^31 output rows", fn);
+  PXR_REQUIRE(rows == 0 || (d_matches0 && d_scores0), "%s: NULL d_matches0 / d_scores0", fn);
+  if (rows == 0) {                   // no pairs, or only empty first images: nothing to write but zero counts, nothing to launch
+    if (n_pairs > 0) PXR_HIP(hipMemsetAsync(d_n_matches, 0, sizeof(int32_t) * (size_t)n_pairs, st));
+    return PXR_OK;
+  }
+  const bool mutual = o->do_mutual_check != 0;
+
+  size_t wsz = 0;
+  auto carve = [&](size_t count, size_t elem) { const size_t at = wsz; wsz += (count * elem + 255) & ~(size_t)255; return at; };
+  const size_t o_pairs = carve(hp.size(), sizeof(MatchPair)), o_items = carve(items.size(), sizeof(MatchItem));
+  const size_t o_colp = carve(col_prefix.size(), 8), o_m1 = carve((size_t)cols, 4);
+  const size_t o_s1 = carve((size_t)parts, 4), o_i1 = carve((size_t)parts, 4), o_s2 = carve((size_t)parts, 4);
+  if (int rc = match_grow_workspace(ctx, wsz)) return rc;
+  char* ws = static_cast<char*>(ctx->d_workspace);
+
+  MatchArgs a;
+  a.desc = d_desc;
+  a.pairs = (const MatchPair*)(ws + o_pairs); a.items = (const MatchItem*)(ws + o_items); a.col_prefix = (const int64_t*)(ws + o_colp);
+  a.part_s1 = (float*)(ws + o_s1); a.part_i1 = (int32_t*)(ws + o_i1); a.part_s2 = (float*)(ws + o_s2);
+  a.m1 = (int32_t*)(ws + o_m1);
+  a.matches0 = d_matches0; a.scores0 = d_scores0; a.n_matches = d_n_matches;
+  a.n_cols = cols; a.n_pairs = n_pairs; a.dim = dim;
+  a.kp = ((dim + 1) / 2 + MT_KSTEP - 1) / MT_KSTEP * MT_KSTEP;
+  a.r2 = (float)(o->ratio_threshold * o->ratio_threshold);
+  a.t2 = (float)(o->distance_threshold * o->distance_threshold);
+  a.use_ratio = o->ratio_threshold > 0.0; a.use_dist = o->distance_threshold > 0.0; a.mutual = mutual;
+
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // tiles | columns | mutual
+  auto mark = [&](int k) { if (h_ms) (void)hipEventRecord(ev[k], st); };
+  auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
+  if (h_ms) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { drop(); return set_error(PXR_EHIP, "%s: hipEventCreate failed", fn); }
+
+  int rc = hip_check(hipMemcpyAsync(ws + o_pairs, hp.data(), sizeof(MatchPair) * hp.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(ws + o_items, items.data(), sizeof(MatchItem) * items.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(ws + o_colp, col_prefix.data(), 8 * col_prefix.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  if (rc == PXR_OK) rc = hip_check(hipMemsetAsync(d_n_matches, 0, sizeof(int32_t) * (size_t)n_pairs, st), "hipMemsetAsync");
+  if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (the host vectors may go out of scope)
+  if (rc != PXR_OK) { drop(); return rc; }
+
+  const dim3 grid((unsigned)items.size());
+  mark(0);
+  if (a.kp <= 64) hipLaunchKernelGGL(k_match_tiles<64>, grid, dim3(MT_THREADS), 0, st, a);
+  else if (a.kp <= 128) hipLaunchKernelGGL(k_match_tiles<128>, grid, dim3(MT_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(k_match_tiles<256>, grid, dim3(MT_THREADS), 0, st, a);
+  mark(1);
+  if (mutual && cols > 0) hipLaunchKernelGGL(k_match_columns, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, a);
+  mark(2);
+  hipLaunchKernelGGL(k_match_mutual, grid, dim3(MT_ROWS), 0, st, a);
+  mark(3);
+  rc = hip_check(hipGetLastError(), "k_match_mutual launch");
+  if (rc == PXR_OK && h_ms) {
+    rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+    for (int k = 0; k < 3 && rc == PXR_OK; ++k) {
+      float ms = 0.f;
+      rc = hip_check(hipEventElapsedTime(&ms, ev[k], ev[k + 1]), "hipEventElapsedTime");
+      h_ms[k] = ms;
+    }
+  }
+  drop();
+  return rc;
+}
+
+}  // namespace
+}  // namespace pxr
+
+extern "C" void pxr_match_default_options(pxr_match_options* o) {
+  if (!o) return;
+  o->ratio_threshold = 0.0; o->distance_threshold = 0.0; o->do_mutual_check = 1; o->reserved = 0;
+}
+
+extern "C" int pxr_match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                                     const float* d_desc, int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets,
+                                     const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches) {
+  return pxr::match_descriptors(ctx, n_images, d_image_offsets, n_total, dim, d_desc, n_pairs, d_pairs, d_pair_offsets, options,
+                                d_matches0, d_scores0, d_n_matches, nullptr);
+}
+
+extern "C" int pxr_match_descriptors_timed(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                                           const float* d_desc, int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets,
+                                           const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches,
+                                           double* h_kernel_ms) {
+  PXR_REQUIRE(h_kernel_ms, "pxr_match_descriptors_timed: NULL h_kernel_ms");
+  return pxr::match_descriptors(ctx, n_images, d_image_offsets, n_total, dim, d_desc, n_pairs, d_pairs, d_pair_offsets, options,
+                                d_matches0, d_scores0, d_n_matches, h_kernel_ms);
+}

@@ -100,6 +100,15 @@ class AbsposeOptions(C.Structure):
 
 ABSPOSE_LDS_CORR = 1024      # PXR_ABSPOSE_LDS_CORR
 
+
+class MatchOptions(C.Structure):
+    """pxr_match_options"""
+    _fields_ = [("ratio_threshold", C.c_double), ("distance_threshold", C.c_double), ("do_mutual_check", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+MATCH_MAX_DIM = 512          # PXR_MATCH_MAX_DIM
+
 # every symbol include/pixsfm_hip.h declares (checked by tests/test_cabi_and_host.py)
 _SIGNATURES = {
     "pxr_version": (C.c_int, []),
@@ -153,6 +162,12 @@ _SIGNATURES = {
     "pxr_absolute_pose_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.POINTER(AbsposeOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "pxr_match_default_options": (None, [C.POINTER(MatchOptions)]),
+    "pxr_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pxr_match_descriptors_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_double)]),
     "pxr_ba_compute_references": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BaView), C.POINTER(InterpCfg),
                                             C.POINTER(Loss), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pxr_costmap_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,

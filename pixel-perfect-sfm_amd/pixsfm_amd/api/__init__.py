@@ -17,3 +17,4 @@ from .localization import (QueryBundleAdjuster, QueryBundleOptimizer, QueryKeypo
 from .extract import (FeatureExtractor, extract_patchdata_from_graph, features_from_graph,  # noqa: F401,E402
                       features_from_image_list, features_from_reconstruction)
 from .triangulation import TrackTriangulator  # noqa: F401,E402
+from .matching import DescriptorMatcher, pairs_2d3d_from_matches  # noqa: F401,E402

@@ -22,8 +22,9 @@ local optimisation on the GPU (pxr_absolute_pose; DESIGN.md section 19 -- NOT CO
 `QueryLocalizer(reconstruction, conf, dense_features=..., references=...).localize(...)` is main.py:261-499 step by step:
 query features, the references of the query (nearest / robust_mean / all_observations), QKA, PnP, unique inliers
 (find_unique_inliers, find_unique_min_by_group, find_unique_min_reproj_inliers, compute_reprojection_errors: main.py:38-86),
-QBA, the final inlier recount.  Retrieval and matching, which produce the 2D-3D pairs, stay outside (SURVEY section 8:
-control plane).
+QBA, the final inlier recount.  The 2D-3D pairs come from descriptor matching against the map's images
+(api.matching: DescriptorMatcher + pairs_2d3d_from_matches); image retrieval, which picks those
+images, stays outside (control plane).
 """
 from collections import OrderedDict
 from copy import deepcopy

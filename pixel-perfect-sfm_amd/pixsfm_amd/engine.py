@@ -922,3 +922,85 @@ class AbsolutePoseProblem:
         else:
             check(ctx.lib.pxr_absolute_pose(*args), "pxr_absolute_pose")
         return d_q, d_t, d_status, d_ninl, d_ntr, d_inl, d_err
+
+
+MATCH_CONFS = {            # hloc's match_features confs for its NearestNeighbor matcher
+    "NN-mutual": dict(ratio_threshold=0.0, distance_threshold=0.0, do_mutual_check=True),
+    "NN-ratio": dict(ratio_threshold=0.8, distance_threshold=0.0, do_mutual_check=True),
+    "NN-superpoint": dict(ratio_threshold=0.0, distance_threshold=0.7, do_mutual_check=True),
+}
+
+
+def match_options(ratio_threshold=0.0, distance_threshold=0.0, do_mutual_check=True):
+    """pxr_match_options: a threshold <= 0 (or None) switches its test off; the defaults are hloc's "NN-mutual"."""
+    return _lib.MatchOptions(float(ratio_threshold or 0.0), float(distance_threshold or 0.0), int(bool(do_mutual_check)), 0)
+
+
+class MatchProblem:
+    """Device-resident descriptors of a set of images and a list of image pairs (pxr_match_descriptors).
+
+    descriptors: a list of (n, D) float32 host arrays or DeviceArrays (one per image; n may be 0), or one (n_total, D) array
+    with image_offsets (n_images + 1), which is used in place when it is a DeviceArray (a DeviceArray inside a list is staged
+    through the host).  pairs: (n_pairs, 2) image indices.  Every image is uploaded once, however many pairs name it.
+    """
+
+    def __init__(self, ctx, descriptors, pairs, image_offsets=None):
+        self.ctx = ctx
+        if image_offsets is not None:
+            desc = descriptors if isinstance(descriptors, DeviceArray) else np.ascontiguousarray(descriptors, dtype=np.float32)
+            if len(desc.shape) != 2:
+                raise ValueError("descriptors must be (n_total, D)")
+            offsets = np.ascontiguousarray(image_offsets, dtype=np.int64).reshape(-1)
+            self.dim = int(desc.shape[1])
+            self.d_desc = desc if isinstance(desc, DeviceArray) else ctx.to_device(desc, np.float32)
+        else:
+            shapes = [tuple(d.shape) for d in descriptors]
+            if any(len(s) != 2 for s in shapes) or len({s[1] for s in shapes}) > 1:
+                raise ValueError("descriptors must be (n, D) arrays of one D")
+            self.dim = int(shapes[0][1]) if shapes else 1
+            offsets = np.concatenate([[0], np.cumsum([s[0] for s in shapes])]).astype(np.int64)
+            self.d_desc = ctx.empty((int(offsets[-1]), self.dim), np.float32)
+            row = self.dim * 4
+            for d, first in zip(descriptors, offsets[:-1]):
+                if d.shape[0] == 0:
+                    continue
+                dst = C.c_void_p(self.d_desc.ptr.value + int(first) * row)
+                h = np.ascontiguousarray(d.download() if isinstance(d, DeviceArray) else d, dtype=np.float32)
+                check(ctx.lib.pxr_memcpy_h2d(ctx.handle, dst, h.ctypes.data, h.nbytes), "pxr_memcpy_h2d")
+        if len(offsets) < 1:
+            raise ValueError("image_offsets must hold n_images + 1 entries")
+        self.image_offsets = offsets
+        self.n_images = len(offsets) - 1
+        self.n_total = int(self.d_desc.shape[0])
+        self.pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        self.n_pairs = len(self.pairs)
+        counts = np.diff(offsets)
+        first = self.pairs[:, 0]
+        in_range = (first >= 0) & (first < self.n_images)          # an index out of range is the library's to report
+        rows = np.zeros(self.n_pairs, dtype=np.int64)
+        rows[in_range] = counts[first[in_range]]
+        self.pair_offsets = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+        self.d_offsets = ctx.to_device(offsets, np.int64)
+        self.d_pairs = ctx.to_device(self.pairs, np.int32)
+        self.d_pair_offsets = ctx.to_device(self.pair_offsets, np.int64)
+        self.kernel_ms = None
+
+    def run(self, timed=False, out=None, **options):
+        """Run the kernels (pxr_match_descriptors) with match_options(**options).  Returns the device arrays (matches0
+        (n_rows,) int32, scores0 (n_rows,) float32, n_matches (n_pairs,) int32); pair p owns rows [pair_offsets[p],
+        pair_offsets[p + 1]).  out: the three device arrays to write into.  timed: also keep the kernels' HIP-event times in
+        self.kernel_ms {"tiles", "columns", "mutual"} (milliseconds)."""
+        ctx = self.ctx
+        opts = match_options(**options)
+        n_rows = int(self.pair_offsets[-1])
+        d_m, d_s, d_n = out if out is not None else (ctx.empty((n_rows,), np.int32), ctx.empty((n_rows,), np.float32),
+                                                      ctx.empty((self.n_pairs,), np.int32))
+        args = (ctx.handle, self.n_images, self.d_offsets.ptr, self.n_total, self.dim, self.d_desc.ptr, self.n_pairs, self.d_pairs.ptr,
+                self.d_pair_offsets.ptr, C.byref(opts), d_m.ptr, d_s.ptr, d_n.ptr)
+        if timed:
+            ms = (C.c_double * 3)()
+            check(ctx.lib.pxr_match_descriptors_timed(*args, ms), "pxr_match_descriptors_timed")
+            self.kernel_ms = dict(zip(("tiles", "columns", "mutual"), (float(x) for x in ms)))
+        else:
+            check(ctx.lib.pxr_match_descriptors(*args), "pxr_match_descriptors")
+        return d_m, d_s, d_n
