@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "pxr_device.h"
+#include "pxr_dispatch.h"
 #include "pxr_interp.h"
 #include "pxr_internal.h"
 
@@ -384,8 +385,9 @@ template <typename ST, int C>
 static int launch_eval_small(pxr_ctx* ctx, const BaEvalArgs& a, bool with_jac) {
   const int64_t blocks = (a.v.n_obs + 255) / 256;
   if (blocks == 0) return PXR_OK;
-  if (with_jac) hipLaunchKernelGGL((ba_eval_small_kernel<ST, C, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((ba_eval_small_kernel<ST, C, false>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+  for_flag(with_jac, [&](auto wj) {
+    hipLaunchKernelGGL((ba_eval_small_kernel<ST, C, decltype(wj)::value>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
+  });
   return pxr::hip_check(hipGetLastError(), "ba_eval_small_kernel launch");
 }
 
@@ -441,26 +443,12 @@ static int launch_eval(pxr_ctx* ctx, const BaEvalArgs& a_in, bool with_jac, bool
   const int64_t blocks = (a.v.n_obs + obs_per_block - 1) / obs_per_block;
   if (blocks == 0) return PXR_OK;
   dim3 grid((unsigned)blocks), block(256);
-  if (with_jac) {
-    if (float_simd) hipLaunchKernelGGL((ba_eval_kernel<ST, C, true, true>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((ba_eval_kernel<ST, C, true, false>), grid, block, 0, ctx->stream, a);
-  } else {
-    if (float_simd) hipLaunchKernelGGL((ba_eval_kernel<ST, C, false, true>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((ba_eval_kernel<ST, C, false, false>), grid, block, 0, ctx->stream, a);
-  }
+  for_flag(with_jac, [&](auto wj) {
+    for_flag(float_simd, [&](auto fs) {
+      hipLaunchKernelGGL((ba_eval_kernel<ST, C, decltype(wj)::value, decltype(fs)::value>), grid, block, 0, ctx->stream, a);
+    });
+  });
   return pxr::hip_check(hipGetLastError(), "ba_eval_kernel launch");
-}
-
-template <typename ST>
-static int launch_eval_c(pxr_ctx* ctx, int C, const BaEvalArgs& a, bool with_jac, bool float_simd) {
-  switch (C) {
-    case 128: return launch_eval<ST, 128>(ctx, a, with_jac, float_simd);
-    case 64: return launch_eval<ST, 64>(ctx, a, with_jac, float_simd);
-    case 3: return launch_eval_small<ST, 3>(ctx, a, with_jac);   // cost maps (costmap_bundle_optimizer.h:9-14)
-    case 1: return launch_eval_small<ST, 1>(ctx, a, with_jac);
-    default:
-      return set_error(PXR_EUNSUPPORTED, "pxr_ba_eval: CHANNELS=%d not supported (128, 64; cost maps: 3, 1)", C);
-  }
 }
 
 }  // namespace pxr
@@ -490,17 +478,20 @@ int pxr::ba_eval_with_cost(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* vi
   PXR_HIP(hipSetDevice(ctx->device));
   pxr::BaEvalArgs a;
   a.v = *view;
-  a.arena = arena->d_data; a.corners = arena->d_corners; a.scales = arena->d_scales;
-  a.H = arena->H; a.W = arena->W; a.up = arena->up; a.l2_normalize = cfg->l2_normalize; a.check_bounds = cfg->check_bounds;
+  pxr::set_arena(a, arena);
+  a.up = arena->up; a.l2_normalize = cfg->l2_normalize; a.check_bounds = cfg->check_bounds;
   a.rec = d_rec; a.out_r = d_r; a.out_gx = d_gx; a.out_gy = d_gy;
   a.cost_out = d_cost_sum;
   if (loss) a.loss = *loss; else { a.loss.type = PXR_LOSS_TRIVIAL; a.loss.a = 1.0; }
   const bool wj = with_jacobian != 0, fs = cfg->use_float_simd != 0;
-  switch (arena->dtype) {
-    case PXR_F16: return pxr::launch_eval_c<_Float16>(ctx, arena->C, a, wj, fs);
-    case PXR_F32: return pxr::launch_eval_c<float>(ctx, arena->C, a, wj, fs);
-    case PXR_F64: return pxr::launch_eval_c<double>(ctx, arena->C, a, wj, fs);
-  }
+  int rc = PXR_OK;
+  const bool known = pxr::for_storage<_Float16, float, double>(arena->dtype, [&](auto st) {
+    using ST = typename decltype(st)::type;
+    if (!pxr::for_channels<128, 64>(arena->C, [&](auto c) { rc = pxr::launch_eval<ST, decltype(c)::value>(ctx, a, wj, fs); }) &&
+        !pxr::for_channels<3, 1>(arena->C, [&](auto c) { rc = pxr::launch_eval_small<ST, decltype(c)::value>(ctx, a, wj); }))   // cost maps (costmap_bundle_optimizer.h:9-14)
+      rc = pxr::set_error(PXR_EUNSUPPORTED, "pxr_ba_eval: CHANNELS=%d not supported (128, 64; cost maps: 3, 1)", arena->C);
+  });
+  if (known) return rc;
   return pxr::set_error(PXR_EINVAL, "pxr_ba_eval: bad arena dtype");
 }
 

@@ -26,6 +26,7 @@
 
 #include "pxr_ba_solve.h"
 #include "pxr_device.h"
+#include "pxr_dispatch.h"
 #include "pxr_gram.h"
 #include "pxr_internal.h"
 
@@ -284,38 +285,41 @@ int gram_eval_prepare(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, G
   return hip_check(hipGetLastError(), "Gram-matrix cache set-up");
 }
 
-// rebuild the matrices of the observations flagged in the cache's `dirty` array (the caller set the flags and the cells)
-int gram_build_flagged(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v, const GramCache& gc) {
+static GramArgs gram_args(const pxr_arena* arena, const pxr_ba_view* v, const GramCache& gc, int l2_normalize, double* rec) {
   GramArgs a;
   a.v = *v;
-  a.arena = arena->d_data; a.corners = arena->d_corners; a.scales = arena->d_scales;
-  a.H = arena->H; a.W = arena->W; a.l2_normalize = 0;
-  a.G = gc.G; a.cell = static_cast<int2*>(gc.cell); a.dirty = gc.list; a.r2 = gc.r2; a.rec = nullptr;
-  const int64_t n = v->n_obs;
-  const unsigned build_grid = (unsigned)std::min<int64_t>((n + 63) / 64, (int64_t)ctx->num_cus * 16);
-#define GRAM_BUILD(ST, CC) hipLaunchKernelGGL((k_gram_build<ST, CC>), dim3(build_grid), dim3(64), 0, ctx->stream, a)
-  if (arena->dtype == PXR_F16) { if (arena->C == 128) GRAM_BUILD(_Float16, 128); else GRAM_BUILD(_Float16, 64); }
-  else { if (arena->C == 128) GRAM_BUILD(float, 128); else GRAM_BUILD(float, 64); }
-#undef GRAM_BUILD
+  set_arena(a, arena);
+  a.l2_normalize = l2_normalize;
+  a.G = gc.G; a.cell = static_cast<int2*>(gc.cell); a.dirty = gc.list; a.r2 = gc.r2; a.rec = rec;
+  return a;
+}
+
+// k_gram_build exists for the arenas gram_eval_supported admits (both callers checked it, or the inner iterations' fp16 / fp32 branch)
+static int launch_gram_build(pxr_ctx* ctx, const pxr_arena* arena, const GramArgs& a) {
+  const unsigned build_grid = (unsigned)std::min<int64_t>((a.v.n_obs + 63) / 64, (int64_t)ctx->num_cus * 16);
+  bool ok = false;
+  for_storage<_Float16, float>(arena->dtype, [&](auto st) {
+    ok = for_channels<128, 64>(arena->C, [&](auto c) {
+      hipLaunchKernelGGL((k_gram_build<typename decltype(st)::type, decltype(c)::value>), dim3(build_grid), dim3(64), 0, ctx->stream, a);
+    });
+  });
+  return ok ? PXR_OK : set_error(PXR_EUNSUPPORTED, "Gram-matrix build: needs 128 / 64 channels in fp16 / fp32 storage");
+}
+
+// rebuild the matrices of the observations flagged in the cache's `dirty` array (the caller set the flags and the cells)
+int gram_build_flagged(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v, const GramCache& gc) {
+  if (int rc = launch_gram_build(ctx, arena, gram_args(arena, v, gc, 0, nullptr))) return rc;
   return hip_check(hipGetLastError(), "Gram-matrix build");
 }
 
 int gram_evaluate(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v, const pxr_interp_cfg* cfg, const GramCache& gc, double* rec) {
-  GramArgs a;
-  a.v = *v;
-  a.arena = arena->d_data; a.corners = arena->d_corners; a.scales = arena->d_scales;
-  a.H = arena->H; a.W = arena->W; a.l2_normalize = cfg->l2_normalize;
-  a.G = gc.G; a.cell = static_cast<int2*>(gc.cell); a.dirty = gc.list; a.r2 = gc.r2; a.rec = rec;
+  const GramArgs a = gram_args(arena, v, gc, cfg->l2_normalize, rec);
   hipStream_t st = ctx->stream;
   const int64_t n = v->n_obs;
   hipLaunchKernelGGL(k_gram_eval, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, st, a);
   // the observations that left their cell: rebuild, then evaluate them (both scan the flags: a wavefront with nothing to do leaves
   // after one 256-byte load)
-  const unsigned build_grid = (unsigned)std::min<int64_t>((n + 63) / 64, (int64_t)ctx->num_cus * 16);
-#define GRAM_BUILD(ST, CC) hipLaunchKernelGGL((k_gram_build<ST, CC>), dim3(build_grid), dim3(64), 0, st, a)
-  if (arena->dtype == PXR_F16) { if (arena->C == 128) GRAM_BUILD(_Float16, 128); else GRAM_BUILD(_Float16, 64); }
-  else { if (arena->C == 128) GRAM_BUILD(float, 128); else GRAM_BUILD(float, 64); }
-#undef GRAM_BUILD
+  if (int rc = launch_gram_build(ctx, arena, a)) return rc;
   hipLaunchKernelGGL(k_gram_eval_dirty, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
   return hip_check(hipGetLastError(), "Gram-matrix evaluation");
 }

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "pxr_device.h"
+#include "pxr_dispatch.h"
 #include "pxr_gram.h"
 #include "pxr_interp.h"
 #include "pxr_internal.h"
@@ -1127,49 +1128,40 @@ int launch_inner_iterations(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
     return set_error(PXR_EUNSUPPORTED, "inner iterations: CHANNELS=%d not supported (128, 64; cost maps: 3, 1)", arena->C);
   InnerArgs a;
   a.v = *view;
-  a.arena = arena->d_data; a.corners = arena->d_corners; a.scales = arena->d_scales;
-  a.H = arena->H; a.W = arena->W; a.up = arena->up; a.l2_normalize = cfg->l2_normalize; a.check_bounds = cfg->check_bounds; a.loss = *loss;
+  set_arena(a, arena);
+  a.up = arena->up; a.l2_normalize = cfg->l2_normalize; a.check_bounds = cfg->check_bounds; a.loss = *loss;
   a.pt_ptr = d_pt_ptr; a.pt_obs = d_pt_obs; a.pt_var = d_pt_var;
   a.xyz_out = const_cast<double*>(view->d_xyz); a.cost_before = d_cost_before; a.cost_pt = d_cost_per_point;
   a.gram_G = gram ? gram->G : nullptr; a.gram_cell = gram ? static_cast<int2*>(gram->cell) : nullptr; a.gram_warm = gram_warm ? 1 : 0;
   const int ppb = arena->C >= 64 ? 1 : 8;   // points per workgroup (InnerShape)
-  const int threads = 64;
   const unsigned blocks = (unsigned)((view->n_points + ppb - 1) / ppb);
   if (blocks == 0) return PXR_OK;
-#define INNER_LAUNCH(KERNEL, ST, CC)                                                                          \
-  do {                                                                                                        \
-    if (cfg->use_float_simd) hipLaunchKernelGGL((KERNEL<ST, CC, true>), dim3(blocks), dim3(threads), 0, ctx->stream, a);  \
-    else hipLaunchKernelGGL((KERNEL<ST, CC, false>), dim3(blocks), dim3(threads), 0, ctx->stream, a);             \
-  } while (0)
-#define INNER_PACKED(ST, CC, NBLK, PPW, LIST)                                                                             \
-  do {                                                                                                                    \
-    if (cfg->use_float_simd) hipLaunchKernelGGL((k_inner_packed<ST, CC, true, 4>), dim3(NBLK), dim3(64), 0, ctx->stream, a, PPW, LIST);  \
-    else hipLaunchKernelGGL((k_inner_packed<ST, CC, false, 4>), dim3(NBLK), dim3(64), 0, ctx->stream, a, PPW, LIST);         \
-  } while (0)
-#define INNER_BY_STORAGE(MACRO, ...)                                                    \
-  do {                                                                                  \
-    if (arena->dtype == PXR_F16 && arena->C == 128) MACRO(_Float16, 128, __VA_ARGS__);  \
-    else if (arena->dtype == PXR_F16) MACRO(_Float16, 64, __VA_ARGS__);                 \
-    else if (arena->C == 128) MACRO(float, 128, __VA_ARGS__);                           \
-    else MACRO(float, 64, __VA_ARGS__);                                                 \
-  } while (0)
-#define INNER_GRAM_PACKED(ST, CC, NBLK) \
-  hipLaunchKernelGGL((k_inner_gram_packed<ST, CC>), dim3(NBLK), dim3(64), 0, ctx->stream, a, static_cast<const char*>(lists->d_waves))
+  // one wavefront per workgroup everywhere.  Which kernel: cost maps (3 / 1 channels) and fp64 feature patches go through
+  // k_inner_points; fp16 / fp32 feature patches through the packed kernels, which exist for those two storages only.
+  auto points = [&](auto st, auto c) {
+    for_flag(cfg->use_float_simd, [&](auto fs) {
+      hipLaunchKernelGGL((k_inner_points<typename decltype(st)::type, decltype(c)::value, decltype(fs)::value>), dim3(blocks), dim3(64), 0,
+                         ctx->stream, a);
+    });
+  };
+  auto packed = [&](unsigned nblk, int ppw, const int* list) {
+    for_storage<_Float16, float>(arena->dtype, [&](auto st) {
+      for_channels<128, 64>(arena->C, [&](auto c) {
+        for_flag(cfg->use_float_simd, [&](auto fs) {
+          hipLaunchKernelGGL((k_inner_packed<typename decltype(st)::type, decltype(c)::value, decltype(fs)::value, 4>), dim3(nblk), dim3(64),
+                             0, ctx->stream, a, ppw, list);
+        });
+      });
+    });
+  };
   if (arena->C <= 4) {
-    if (arena->dtype == PXR_F16 && arena->C == 3) INNER_LAUNCH(k_inner_points, _Float16, 3);
-    else if (arena->dtype == PXR_F16) INNER_LAUNCH(k_inner_points, _Float16, 1);
-    else if (arena->dtype == PXR_F32 && arena->C == 3) INNER_LAUNCH(k_inner_points, float, 3);
-    else if (arena->dtype == PXR_F32) INNER_LAUNCH(k_inner_points, float, 1);
-    else if (arena->C == 3) INNER_LAUNCH(k_inner_points, double, 3);
-    else INNER_LAUNCH(k_inner_points, double, 1);
+    for_storage<_Float16, float, double>(arena->dtype, [&](auto st) { for_channels<3, 1>(arena->C, [&](auto c) { points(st, c); }); });
   } else if (arena->dtype != PXR_F64) {
     if (lists == nullptr) {
       // packed kernel: points per wavefront from the mean track length (16 observation slots per trip)
       const int64_t per16 = view->n_obs > 0 ? (16 * view->n_points) / view->n_obs : 1;
       const int ppw = (int)(per16 < 1 ? 1 : (per16 > IP_MAXPTS ? IP_MAXPTS : per16));
-      const unsigned pblocks = (unsigned)((view->n_points + ppw - 1) / ppw);
-      const int* no_list = nullptr;
-      INNER_BY_STORAGE(INNER_PACKED, pblocks, ppw, no_list);
+      packed((unsigned)((view->n_points + ppw - 1) / ppw), ppw, nullptr);
     } else {
       // Gram-matrix kernel for the points whose observations' Gram matrices fit a wavefront's LDS, packed kernel (one point per
       // wavefront) for the long tracks; short tracks: up to four points (sixteen observation slots) per wavefront in lockstep
@@ -1183,16 +1175,16 @@ int launch_inner_iterations(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v
           if (int rc = gram_build_flagged(ctx, arena, view, *gram)) return rc;
           a.gram_warm = 1;
         }
-        INNER_BY_STORAGE(INNER_GRAM_PACKED, (unsigned)lists->n_waves);
+        for_storage<_Float16, float>(arena->dtype, [&](auto st) {
+          for_channels<128, 64>(arena->C, [&](auto c) {
+            hipLaunchKernelGGL((k_inner_gram_packed<typename decltype(st)::type, decltype(c)::value>), dim3((unsigned)lists->n_waves), dim3(64), 0,
+                               ctx->stream, a, static_cast<const char*>(lists->d_waves));
+          });
+        });
       }
-      if (lists->n_long > 0) INNER_BY_STORAGE(INNER_PACKED, (unsigned)lists->n_long, 1, lists->d_long);
+      if (lists->n_long > 0) packed((unsigned)lists->n_long, 1, lists->d_long);
     }
-  } else if (arena->dtype == PXR_F64 && arena->C == 128) INNER_LAUNCH(k_inner_points, double, 128);
-  else INNER_LAUNCH(k_inner_points, double, 64);
-#undef INNER_LAUNCH
-#undef INNER_PACKED
-#undef INNER_GRAM_PACKED
-#undef INNER_BY_STORAGE
+  } else for_channels<128, 64>(arena->C, [&](auto c) { points(type_tag<double>{}, c); });
   return hip_check(hipGetLastError(), "k_inner_points launch");
 }
 

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pxr_device.h"
+#include "pxr_dispatch.h"
 #include "pxr_interp.h"
 #include "pxr_internal.h"
 
@@ -762,21 +763,6 @@ __global__ __launch_bounds__(256) void costmap_interp_kernel(const CostmapArgs a
   }
 }
 
-template <typename ST, int C>
-static int launch_costmap_interp(pxr_ctx* ctx, int out_dtype, const CostmapArgs& a, int64_t n, int Ho, int Wo, double up,
-                                 bool grad, bool cross, const pxr_interp_cfg* cfg) {
-  const dim3 grid((unsigned)n), block(256);
-#define CMI(OT, FS) hipLaunchKernelGGL((costmap_interp_kernel<ST, OT, C, FS>), grid, block, 0, ctx->stream, a, Ho, Wo, 1.0 / up, \
-                                       grad ? 1 : 0, cross ? 1 : 0, cfg->l2_normalize)
-  if (cfg->use_float_simd) {
-    if (out_dtype == PXR_F16) CMI(_Float16, true); else if (out_dtype == PXR_F32) CMI(float, true); else CMI(double, true);
-  } else {
-    if (out_dtype == PXR_F16) CMI(_Float16, false); else if (out_dtype == PXR_F32) CMI(float, false); else CMI(double, false);
-  }
-#undef CMI
-  return hip_check(hipGetLastError(), "costmap_interp_kernel launch");
-}
-
 template <typename OT>
 static int launch_costmap_f16(pxr_ctx* ctx, const CostmapArgs& a, int64_t n, bool grad) {
   hipDeviceProp_t prop;
@@ -807,33 +793,27 @@ static int launch_costmap(pxr_ctx* ctx, const CostmapArgs& a, int64_t n, bool gr
     if (a.H == a.W && (a.H == 16 || a.H == 8)) return launch_costmap_f16<OT>(ctx, a, n, grad);
   }
   const dim3 grid((unsigned)n), block((unsigned)(a.W * (C / 8)));
-  if (grad) hipLaunchKernelGGL((costmap_kernel<ST, OT, C, true>), grid, block, 0, ctx->stream, a);
-  else hipLaunchKernelGGL((costmap_kernel<ST, OT, C, false>), grid, block, 0, ctx->stream, a);
+  for_flag(grad, [&](auto g) { hipLaunchKernelGGL((costmap_kernel<ST, OT, C, decltype(g)::value>), grid, block, 0, ctx->stream, a); });
   return hip_check(hipGetLastError(), "costmap_kernel launch");
 }
 
 template <typename ST, typename OT, int C>
 static int launch_costmap_small(pxr_ctx* ctx, const CostmapArgs& a, int64_t n, bool grad) {
-  if (grad) hipLaunchKernelGGL((costmap_small_kernel<ST, OT, C, true>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((costmap_small_kernel<ST, OT, C, false>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a);
+  for_flag(grad, [&](auto g) {
+    hipLaunchKernelGGL((costmap_small_kernel<ST, OT, C, decltype(g)::value>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a);
+  });
   return hip_check(hipGetLastError(), "costmap_small_kernel launch");
 }
-template <typename ST, int C>
-static int launch_costmap_small_o(pxr_ctx* ctx, int out_dtype, const CostmapArgs& a, int64_t n, bool grad) {
-  switch (out_dtype) {
-    case PXR_F16: return launch_costmap_small<ST, _Float16, C>(ctx, a, n, grad);
-    case PXR_F32: return launch_costmap_small<ST, float, C>(ctx, a, n, grad);
-    default: return launch_costmap_small<ST, double, C>(ctx, a, n, grad);
-  }
-}
 
-template <typename ST, int C>
-static int launch_costmap_o(pxr_ctx* ctx, int out_dtype, const CostmapArgs& a, int64_t n, bool grad) {
-  switch (out_dtype) {
-    case PXR_F16: return launch_costmap<ST, _Float16, C>(ctx, a, n, grad);
-    case PXR_F32: return launch_costmap<ST, float, C>(ctx, a, n, grad);
-    default: return launch_costmap<ST, double, C>(ctx, a, n, grad);
-  }
+// the arguments both entry points share (CO: the cost maps' channels)
+static CostmapArgs costmap_args(const pxr_arena* features, const pxr_arena* costmaps, int CO, int apply_sqrt, int64_t first_out,
+                                const int64_t* d_patch, const int32_t* d_ref_index, const double* d_refs, const pxr_loss* loss) {
+  CostmapArgs a;
+  a.fin = features->d_data; a.cin = features->d_corners; a.sin = features->d_scales;
+  a.fout = costmaps->d_data; a.cout = costmaps->d_corners; a.sout = costmaps->d_scales;
+  a.H = features->H; a.W = features->W; a.CO = CO; a.apply_sqrt = apply_sqrt;
+  a.first_out = first_out; a.patch = d_patch; a.ref_index = d_ref_index; a.refs = d_refs; a.loss = *loss;
+  return a;
 }
 
 }  // namespace pxr
@@ -860,24 +840,20 @@ extern "C" int pxr_costmap_extract(pxr_ctx* ctx, pxr_arena* features, pxr_arena*
   if (n == 0) return PXR_OK;
   PXR_REQUIRE(d_patch && d_ref_index && d_refs, "pxr_costmap_extract: NULL argument");
   PXR_HIP(hipSetDevice(ctx->device));
-  pxr::CostmapArgs a;
-  a.fin = features->d_data; a.cin = features->d_corners; a.sin = features->d_scales;
-  a.fout = costmaps->d_data; a.cout = costmaps->d_corners; a.sout = costmaps->d_scales;
-  a.H = features->H; a.W = features->W; a.CO = costmaps->C; a.apply_sqrt = apply_sqrt;
-  a.first_out = first_out; a.patch = d_patch; a.ref_index = d_ref_index; a.refs = d_refs; a.loss = *loss;
+  const pxr::CostmapArgs a = pxr::costmap_args(features, costmaps, costmaps->C, apply_sqrt, first_out, d_patch, d_ref_index, d_refs, loss);
   const bool grad = as_gradientfield != 0;
-  const int od = costmaps->dtype;
-  if (few) {
-    if (features->dtype == PXR_F16) return features->C == 3 ? pxr::launch_costmap_small_o<_Float16, 3>(ctx, od, a, n, grad) : pxr::launch_costmap_small_o<_Float16, 1>(ctx, od, a, n, grad);
-    if (features->dtype == PXR_F32) return features->C == 3 ? pxr::launch_costmap_small_o<float, 3>(ctx, od, a, n, grad) : pxr::launch_costmap_small_o<float, 1>(ctx, od, a, n, grad);
-    return features->C == 3 ? pxr::launch_costmap_small_o<double, 3>(ctx, od, a, n, grad) : pxr::launch_costmap_small_o<double, 1>(ctx, od, a, n, grad);
-  }
-  if (features->dtype == PXR_F16 && features->C == 128) return pxr::launch_costmap_o<_Float16, 128>(ctx, od, a, n, grad);
-  if (features->dtype == PXR_F16) return pxr::launch_costmap_o<_Float16, 64>(ctx, od, a, n, grad);
-  if (features->dtype == PXR_F32 && features->C == 128) return pxr::launch_costmap_o<float, 128>(ctx, od, a, n, grad);
-  if (features->dtype == PXR_F32) return pxr::launch_costmap_o<float, 64>(ctx, od, a, n, grad);
-  if (features->C == 128) return pxr::launch_costmap_o<double, 128>(ctx, od, a, n, grad);
-  return pxr::launch_costmap_o<double, 64>(ctx, od, a, n, grad);
+  int rc = PXR_OK;
+  bool ok = false;
+  using pxr::for_channels;
+  pxr::for_storage<_Float16, float, double>(features->dtype, [&](auto st) {
+    using ST = typename decltype(st)::type;
+    pxr::for_storage<_Float16, float, double>(costmaps->dtype, [&](auto ot) {
+      using OT = typename decltype(ot)::type;
+      ok = for_channels<128, 64>(features->C, [&](auto c) { rc = pxr::launch_costmap<ST, OT, decltype(c)::value>(ctx, a, n, grad); }) ||
+           for_channels<3, 1>(features->C, [&](auto c) { rc = pxr::launch_costmap_small<ST, OT, decltype(c)::value>(ctx, a, n, grad); });
+    });
+  });
+  return ok ? rc : pxr::set_error(PXR_EINVAL, "pxr_costmap_extract: bad arena dtype");   // (the channels were checked above)
 }
 
 extern "C" int pxr_costmap_extract_ex(pxr_ctx* ctx, pxr_arena* features, pxr_arena* costmaps, int64_t first_out, int64_t n,
@@ -908,18 +884,21 @@ extern "C" int pxr_costmap_extract_ex(pxr_ctx* ctx, pxr_arena* features, pxr_are
   if (n == 0) return PXR_OK;
   PXR_REQUIRE(d_patch && d_ref_index && d_refs, "pxr_costmap_extract_ex: NULL argument");
   PXR_HIP(hipSetDevice(ctx->device));
-  pxr::CostmapArgs a;
-  a.fin = features->d_data; a.cin = features->d_corners; a.sin = features->d_scales;
-  a.fout = costmaps->d_data; a.cout = costmaps->d_corners; a.sout = costmaps->d_scales;
-  a.H = features->H; a.W = features->W; a.CO = CO; a.apply_sqrt = apply_sqrt;
-  a.first_out = first_out; a.patch = d_patch; a.ref_index = d_ref_index; a.refs = d_refs; a.loss = *loss;
-  const bool grad = as_gradientfield != 0, cross = compute_cross_derivative != 0;
-  const int od = costmaps->dtype;
-  const double up = upsampling_factor;
-  if (features->dtype == PXR_F16 && features->C == 128) return pxr::launch_costmap_interp<_Float16, 128>(ctx, od, a, n, Ho, Wo, up, grad, cross, cfg);
-  if (features->dtype == PXR_F16) return pxr::launch_costmap_interp<_Float16, 64>(ctx, od, a, n, Ho, Wo, up, grad, cross, cfg);
-  if (features->dtype == PXR_F32 && features->C == 128) return pxr::launch_costmap_interp<float, 128>(ctx, od, a, n, Ho, Wo, up, grad, cross, cfg);
-  if (features->dtype == PXR_F32) return pxr::launch_costmap_interp<float, 64>(ctx, od, a, n, Ho, Wo, up, grad, cross, cfg);
-  if (features->C == 128) return pxr::launch_costmap_interp<double, 128>(ctx, od, a, n, Ho, Wo, up, grad, cross, cfg);
-  return pxr::launch_costmap_interp<double, 64>(ctx, od, a, n, Ho, Wo, up, grad, cross, cfg);
+  const pxr::CostmapArgs a = pxr::costmap_args(features, costmaps, CO, apply_sqrt, first_out, d_patch, d_ref_index, d_refs, loss);
+  const int grad = as_gradientfield != 0, cross = compute_cross_derivative != 0;
+  bool ok = false;
+  pxr::for_storage<_Float16, float, double>(features->dtype, [&](auto st) {
+    using ST = typename decltype(st)::type;
+    pxr::for_storage<_Float16, float, double>(costmaps->dtype, [&](auto ot) {
+      using OT = typename decltype(ot)::type;
+      ok = pxr::for_channels<128, 64>(features->C, [&](auto c) {   // (the set checked above)
+        pxr::for_flag(cfg->use_float_simd, [&](auto fs) {
+          hipLaunchKernelGGL((pxr::costmap_interp_kernel<ST, OT, decltype(c)::value, decltype(fs)::value>), dim3((unsigned)n), dim3(256), 0,
+                             ctx->stream, a, Ho, Wo, 1.0 / upsampling_factor, grad, cross, cfg->l2_normalize);
+        });
+      });
+    });
+  });
+  if (!ok) return pxr::set_error(PXR_EINVAL, "pxr_costmap_extract_ex: bad arena dtype");
+  return pxr::hip_check(hipGetLastError(), "costmap_interp_kernel launch");
 }

@@ -12,6 +12,7 @@
 // 16 lanes, lane `sub` holding channels 8 sub .. 8 sub + 7 (extract_kernel's store mapping: one 16-B store per lane at fp16).
 #include <hip/hip_runtime.h>
 
+#include "pxr_dispatch.h"
 #include "pxr_dsift.h"
 #include "pxr_internal.h"
 
@@ -107,12 +108,11 @@ extern "C" int pxr_dsift_dense(pxr_ctx* ctx, const void* d_image, int image_dtyp
   if (rc != PXR_OK) return rc;
   PXR_HIP(hipSetDevice(ctx->device));
   const dim3 grid((unsigned)((w + DS_T - 1) / DS_T), (unsigned)((h + DS_T - 1) / DS_T));
-  if (image_dtype == PXR_U8)
-    hipLaunchKernelGGL(dsift_dense_kernel<unsigned char>, grid, dim3(256), 0, ctx->stream, (const unsigned char*)d_image, h, w,
-                       spatial_bin_size, rootsift, (float)clipval, d_out);
-  else
-    hipLaunchKernelGGL(dsift_dense_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)d_image, h, w,
-                       spatial_bin_size, rootsift, (float)clipval, d_out);
+  for_storage<unsigned char, float>(image_dtype, [&](auto sr) {   // (the set ds_check admits)
+    using SRC = typename decltype(sr)::type;
+    hipLaunchKernelGGL(dsift_dense_kernel<SRC>, grid, dim3(256), 0, ctx->stream, (const SRC*)d_image, h, w, spatial_bin_size, rootsift,
+                       (float)clipval, d_out);
+  });
   return hip_check(hipGetLastError(), "dsift_dense_kernel launch");
 }
 
@@ -135,19 +135,16 @@ extern "C" int pxr_dsift_extract(pxr_ctx* ctx, pxr_arena* a, int64_t first, int6
   PXR_REQUIRE(n < ((int64_t)1 << 31), "pxr_dsift_extract: %lld keypoints in one call (at most 2^31 - 1)", (long long)n);
   PXR_HIP(hipSetDevice(ctx->device));
   const double sx = (double)w / image_w, sy = (double)h / image_h;   // extractor.py:177
-#define DS_LAUNCH(SRC, DST)                                                                                          \
-  hipLaunchKernelGGL((dsift_extract_kernel<SRC, DST>), dim3((unsigned)n), dim3(256), 0, ctx->stream, (const SRC*)d_image, \
-                     h, w, spatial_bin_size, rootsift, (float)clipval, d_keypoints, sx, sy, l2_normalize,               \
-                     (DST*)a->d_data, a->d_corners, a->d_scales, first, a->H)
-#define DS_DST(SRC)                                       \
-  do {                                                    \
-    if (a->dtype == PXR_F16) DS_LAUNCH(SRC, _Float16);    \
-    else if (a->dtype == PXR_F32) DS_LAUNCH(SRC, float);  \
-    else DS_LAUNCH(SRC, double);                          \
-  } while (0)
-  if (image_dtype == PXR_U8) DS_DST(unsigned char);
-  else DS_DST(float);
-#undef DS_DST
-#undef DS_LAUNCH
+  bool ok = false;
+  for_storage<unsigned char, float>(image_dtype, [&](auto sr) {   // (the set ds_check admits)
+    using SRC = typename decltype(sr)::type;
+    ok = for_storage<_Float16, float, double>(a->dtype, [&](auto ds) {
+      using DST = typename decltype(ds)::type;
+      hipLaunchKernelGGL((dsift_extract_kernel<SRC, DST>), dim3((unsigned)n), dim3(256), 0, ctx->stream, (const SRC*)d_image, h, w,
+                         spatial_bin_size, rootsift, (float)clipval, d_keypoints, sx, sy, l2_normalize, (DST*)a->d_data, a->d_corners,
+                         a->d_scales, first, a->H);
+    });
+  });
+  if (!ok) return set_error(PXR_EINVAL, "pxr_dsift_extract: bad arena dtype");
   return hip_check(hipGetLastError(), "dsift_extract_kernel launch");
 }

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pxr_device.h"
+#include "pxr_dispatch.h"
 #include "pxr_internal.h"
 
 namespace pxr {
@@ -196,40 +197,22 @@ extern "C" int pxr_arena_extract(pxr_ctx* ctx, pxr_arena* a, int64_t first, int6
     hipLaunchKernelGGL(ex_tile_scatter, dim3(nb), dim3(256), 0, ctx->stream, n, tile_of, hist, order);
     d_order = order;
   }
-#define EX_LAUNCH(SRC, DST, CC)                                                                              \
-  hipLaunchKernelGGL((extract_kernel<SRC, DST, CC>), dim3((unsigned)n), dim3(256), 0, ctx->stream,          \
-                     (const SRC*)d_fmap, h, w, d_keypoints, sx, sy, l2_normalize, (DST*)a->d_data,          \
-                     a->d_corners, a->d_scales, first, a->H, d_order)
-#define EX_DST(SRC, CC)                                                   \
-  do {                                                                    \
-    if (a->dtype == PXR_F16) EX_LAUNCH(SRC, _Float16, CC);                \
-    else if (a->dtype == PXR_F32) EX_LAUNCH(SRC, float, CC);              \
-    else EX_LAUNCH(SRC, double, CC);                                      \
-  } while (0)
-  if (src_dtype == PXR_F32 && a->C == 128) EX_DST(float, 128);
-  else if (src_dtype == PXR_F32 && a->C == 64) EX_DST(float, 64);
-  else if (src_dtype == PXR_F16 && a->C == 128) EX_DST(_Float16, 128);
-  else if (src_dtype == PXR_F16 && a->C == 64) EX_DST(_Float16, 64);
-  else if ((src_dtype == PXR_F32 || src_dtype == PXR_F16) && (a->C == 3 || a->C == 1)) {
-#define EX_SMALL(SRC, DST, CC)                                                                               \
-  hipLaunchKernelGGL((extract_small_kernel<SRC, DST, CC>), dim3((unsigned)n), dim3(256), 0, ctx->stream,    \
-                     (const SRC*)d_fmap, h, w, d_keypoints, sx, sy, l2_normalize, (DST*)a->d_data,          \
-                     a->d_corners, a->d_scales, first, a->H)
-#define EX_SMALL_DST(SRC, CC)                                             \
-  do {                                                                    \
-    if (a->dtype == PXR_F16) EX_SMALL(SRC, _Float16, CC);                 \
-    else if (a->dtype == PXR_F32) EX_SMALL(SRC, float, CC);               \
-    else EX_SMALL(SRC, double, CC);                                       \
-  } while (0)
-    if (src_dtype == PXR_F32 && a->C == 3) EX_SMALL_DST(float, 3);
-    else if (src_dtype == PXR_F32) EX_SMALL_DST(float, 1);
-    else if (a->C == 3) EX_SMALL_DST(_Float16, 3);
-    else EX_SMALL_DST(_Float16, 1);
-#undef EX_SMALL_DST
-#undef EX_SMALL
-  }
-  else return set_error(PXR_EUNSUPPORTED, "pxr_arena_extract: source dtype %d / CHANNELS %d not supported (f16/f32 x 128/64/3/1)", src_dtype, a->C);
-#undef EX_DST
-#undef EX_LAUNCH
+  bool ok = false;
+  for_storage<float, _Float16>(src_dtype, [&](auto sr) {
+    using SRC = typename decltype(sr)::type;
+    for_storage<_Float16, float, double>(a->dtype, [&](auto ds) {
+      using DST = typename decltype(ds)::type;
+      ok = for_channels<128, 64>(a->C, [&](auto c) {
+        hipLaunchKernelGGL((extract_kernel<SRC, DST, decltype(c)::value>), dim3((unsigned)n), dim3(256), 0, ctx->stream,
+                           (const SRC*)d_fmap, h, w, d_keypoints, sx, sy, l2_normalize, (DST*)a->d_data, a->d_corners, a->d_scales,
+                           first, a->H, d_order);
+      }) || for_channels<3, 1>(a->C, [&](auto c) {
+        hipLaunchKernelGGL((extract_small_kernel<SRC, DST, decltype(c)::value>), dim3((unsigned)n), dim3(256), 0, ctx->stream,
+                           (const SRC*)d_fmap, h, w, d_keypoints, sx, sy, l2_normalize, (DST*)a->d_data, a->d_corners, a->d_scales,
+                           first, a->H);
+      });
+    });
+  });
+  if (!ok) return set_error(PXR_EUNSUPPORTED, "pxr_arena_extract: source dtype %d / CHANNELS %d not supported (f16/f32 x 128/64/3/1)", src_dtype, a->C);
   return hip_check(hipGetLastError(), "extract_kernel launch");
 }

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "pxr_device.h"
+#include "pxr_dispatch.h"
 #include "pxr_interp.h"
 #include "pxr_internal.h"
 
@@ -1429,8 +1430,8 @@ __global__ __launch_bounds__(256) void ka_eval_kernel(const KaArgs a, bool fsimd
 
 static void fill_args(pxr_arena* arena, const pxr_ka_view* view, const pxr_interp_cfg* cfg, const pxr_loss* loss, KaArgs& a) {
   a.v = *view;
-  a.arena = arena->d_data; a.corners = arena->d_corners; a.scales = arena->d_scales;
-  a.H = arena->H; a.W = arena->W; a.l2_normalize = cfg->l2_normalize; a.float_simd = cfg->use_float_simd; a.check_bounds = cfg->check_bounds; a.loss = *loss;
+  set_arena(a, arena);
+  a.l2_normalize = cfg->l2_normalize; a.float_simd = cfg->use_float_simd; a.check_bounds = cfg->check_bounds; a.loss = *loss;
 }
 
 // ---- which kernels serve an arena: (storage type, channel count, accumulation mode) -> entry points --------------------------------

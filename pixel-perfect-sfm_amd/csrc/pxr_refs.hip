@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "pxr_device.h"
+#include "pxr_dispatch.h"
 #include "pxr_interp.h"
 #include "pxr_internal.h"
 
@@ -362,29 +363,21 @@ extern "C" int pxr_interpolate(pxr_ctx* ctx, pxr_arena* arena, const pxr_interp_
   PXR_REQUIRE(ctx && arena && cfg && d_kp && d_patch && d_desc, "pxr_interpolate: NULL argument");
   if (n == 0) return PXR_OK;
   PXR_HIP(hipSetDevice(ctx->device));
-#define INTERP_LAUNCH(ST, CC)                                                                                      \
-  hipLaunchKernelGGL((k_interpolate<ST, CC>), dim3((unsigned)((n + (256 / (CC / 8)) - 1) / (256 / (CC / 8)))), dim3(256), 0, \
-                     ctx->stream, n, (const ST*)arena->d_data, arena->d_corners, arena->d_scales, arena->H, arena->W, \
-                     cfg->l2_normalize, cfg->use_float_simd, d_kp, d_patch, d_desc, d_J)
-  if (arena->dtype == PXR_F16 && arena->C == 128) INTERP_LAUNCH(_Float16, 128);
-  else if (arena->dtype == PXR_F16 && arena->C == 64) INTERP_LAUNCH(_Float16, 64);
-  else if (arena->dtype == PXR_F32 && arena->C == 128) INTERP_LAUNCH(float, 128);
-  else if (arena->dtype == PXR_F32 && arena->C == 64) INTERP_LAUNCH(float, 64);
-  else if (arena->dtype == PXR_F64 && arena->C == 128) INTERP_LAUNCH(double, 128);
-  else if (arena->dtype == PXR_F64 && arena->C == 64) INTERP_LAUNCH(double, 64);
-#define INTERP_SMALL(ST, CC)                                                                                       \
-  hipLaunchKernelGGL((k_interpolate_small<ST, CC>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,   \
-                     (const ST*)arena->d_data, arena->d_corners, arena->d_scales, arena->H, arena->W, cfg->l2_normalize, \
-                     d_kp, d_patch, d_desc, d_J)
-  else if (arena->dtype == PXR_F16 && arena->C == 3) INTERP_SMALL(_Float16, 3);
-  else if (arena->dtype == PXR_F16 && arena->C == 1) INTERP_SMALL(_Float16, 1);
-  else if (arena->dtype == PXR_F32 && arena->C == 3) INTERP_SMALL(float, 3);
-  else if (arena->dtype == PXR_F32 && arena->C == 1) INTERP_SMALL(float, 1);
-  else if (arena->dtype == PXR_F64 && arena->C == 3) INTERP_SMALL(double, 3);
-  else if (arena->dtype == PXR_F64 && arena->C == 1) INTERP_SMALL(double, 1);
-  else return set_error(PXR_EUNSUPPORTED, "pxr_interpolate: CHANNELS=%d not supported (128, 64, 3, 1)", arena->C);
-#undef INTERP_SMALL
-#undef INTERP_LAUNCH
+  bool ok = false;
+  for_storage<_Float16, float, double>(arena->dtype, [&](auto st) {
+    using ST = typename decltype(st)::type;
+    ok = for_channels<128, 64>(arena->C, [&](auto c) {
+      constexpr int C = decltype(c)::value, G = 256 / (C / 8);
+      hipLaunchKernelGGL((k_interpolate<ST, C>), dim3((unsigned)((n + G - 1) / G)), dim3(256), 0, ctx->stream, n,
+                         (const ST*)arena->d_data, arena->d_corners, arena->d_scales, arena->H, arena->W, cfg->l2_normalize,
+                         cfg->use_float_simd, d_kp, d_patch, d_desc, d_J);
+    }) || for_channels<3, 1>(arena->C, [&](auto c) {
+      hipLaunchKernelGGL((k_interpolate_small<ST, decltype(c)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                         n, (const ST*)arena->d_data, arena->d_corners, arena->d_scales, arena->H, arena->W, cfg->l2_normalize,
+                         d_kp, d_patch, d_desc, d_J);
+    });
+  });
+  if (!ok) return set_error(PXR_EUNSUPPORTED, "pxr_interpolate: CHANNELS=%d not supported (128, 64, 3, 1)", arena->C);
   return hip_check(hipGetLastError(), "k_interpolate launch");
 }
 
@@ -396,30 +389,21 @@ extern "C" int pxr_nearest_references(pxr_ctx* ctx, pxr_arena* arena, const pxr_
   PXR_REQUIRE(ctx && arena && cfg && d_kp && d_patch && d_cand_ptr && d_cand_desc && d_best, "pxr_nearest_references: NULL argument");
   if (n == 0) return PXR_OK;
   PXR_HIP(hipSetDevice(ctx->device));
-#define NEAREST_LAUNCH(ST, CC)                                                                                     \
-  hipLaunchKernelGGL((k_nearest<ST, CC>), dim3((unsigned)((n + (256 / (CC / 8)) - 1) / (256 / (CC / 8)))), dim3(256), 0,     \
-                     ctx->stream, n, (const ST*)arena->d_data, arena->d_corners, arena->d_scales, arena->H, arena->W, \
-                     cfg->l2_normalize, cfg->use_float_simd, d_kp, d_patch, d_cand_ptr, d_cand_index, d_cand_desc, d_best, \
-                     d_best_dist, d_out_desc)
-  if (arena->dtype == PXR_F16 && arena->C == 128) NEAREST_LAUNCH(_Float16, 128);
-  else if (arena->dtype == PXR_F16 && arena->C == 64) NEAREST_LAUNCH(_Float16, 64);
-  else if (arena->dtype == PXR_F32 && arena->C == 128) NEAREST_LAUNCH(float, 128);
-  else if (arena->dtype == PXR_F32 && arena->C == 64) NEAREST_LAUNCH(float, 64);
-  else if (arena->dtype == PXR_F64 && arena->C == 128) NEAREST_LAUNCH(double, 128);
-  else if (arena->dtype == PXR_F64 && arena->C == 64) NEAREST_LAUNCH(double, 64);
-#define NEAREST_SMALL(ST, CC)                                                                                      \
-  hipLaunchKernelGGL((k_nearest_small<ST, CC>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,       \
-                     (const ST*)arena->d_data, arena->d_corners, arena->d_scales, arena->H, arena->W, cfg->l2_normalize, \
-                     d_kp, d_patch, d_cand_ptr, d_cand_index, d_cand_desc, d_best, d_best_dist, d_out_desc)
-  else if (arena->dtype == PXR_F16 && arena->C == 3) NEAREST_SMALL(_Float16, 3);
-  else if (arena->dtype == PXR_F16 && arena->C == 1) NEAREST_SMALL(_Float16, 1);
-  else if (arena->dtype == PXR_F32 && arena->C == 3) NEAREST_SMALL(float, 3);
-  else if (arena->dtype == PXR_F32 && arena->C == 1) NEAREST_SMALL(float, 1);
-  else if (arena->dtype == PXR_F64 && arena->C == 3) NEAREST_SMALL(double, 3);
-  else if (arena->dtype == PXR_F64 && arena->C == 1) NEAREST_SMALL(double, 1);
-  else return set_error(PXR_EUNSUPPORTED, "pxr_nearest_references: CHANNELS=%d not supported (128, 64, 3, 1)", arena->C);
-#undef NEAREST_SMALL
-#undef NEAREST_LAUNCH
+  bool ok = false;
+  for_storage<_Float16, float, double>(arena->dtype, [&](auto st) {
+    using ST = typename decltype(st)::type;
+    ok = for_channels<128, 64>(arena->C, [&](auto c) {
+      constexpr int C = decltype(c)::value, G = 256 / (C / 8);
+      hipLaunchKernelGGL((k_nearest<ST, C>), dim3((unsigned)((n + G - 1) / G)), dim3(256), 0, ctx->stream, n,
+                         (const ST*)arena->d_data, arena->d_corners, arena->d_scales, arena->H, arena->W, cfg->l2_normalize,
+                         cfg->use_float_simd, d_kp, d_patch, d_cand_ptr, d_cand_index, d_cand_desc, d_best, d_best_dist, d_out_desc);
+    }) || for_channels<3, 1>(arena->C, [&](auto c) {
+      hipLaunchKernelGGL((k_nearest_small<ST, decltype(c)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
+                         (const ST*)arena->d_data, arena->d_corners, arena->d_scales, arena->H, arena->W, cfg->l2_normalize,
+                         d_kp, d_patch, d_cand_ptr, d_cand_index, d_cand_desc, d_best, d_best_dist, d_out_desc);
+    });
+  });
+  if (!ok) return set_error(PXR_EUNSUPPORTED, "pxr_nearest_references: CHANNELS=%d not supported (128, 64, 3, 1)", arena->C);
   return hip_check(hipGetLastError(), "k_nearest launch");
 }
 
@@ -474,20 +458,12 @@ extern "C" int pxr_ba_compute_references(pxr_ctx* ctx, pxr_arena* arena, const p
     rc = pxr_ba_eval(ctx, arena, &v, cfg, 0, d_rec, d_desc, nullptr, nullptr);
   }
   if (!rc) {
-    const int G = C >= 64 ? 256 / (C / 8) : 256;
-    const unsigned blocks = (unsigned)((n_pts + G - 1) / G);
-    if (C == 3)
-      hipLaunchKernelGGL((k_irls_small<3>), dim3(blocks), dim3(256), 0, st, n_pts, d_ptr, d_lst, d_desc, *loss, iters,
+    for_channels<128, 64, 3, 1>(C, [&](auto c) {   // (the set PXR_REQUIREd above)
+      constexpr int CC = decltype(c)::value, G = 256 / (CC >= 64 ? CC / 8 : 1);   // points per workgroup
+      constexpr auto kernel = [] { if constexpr (CC >= 64) return k_irls<CC>; else return k_irls_small<CC>; }();
+      hipLaunchKernelGGL(kernel, dim3((unsigned)((n_pts + G - 1) / G)), dim3(256), 0, st, n_pts, d_ptr, d_lst, d_desc, *loss, iters,
                          cfg->l2_normalize, d_w, d_refs_out, d_ref_obs_out, d_robust_mean_out);
-    else if (C == 1)
-      hipLaunchKernelGGL((k_irls_small<1>), dim3(blocks), dim3(256), 0, st, n_pts, d_ptr, d_lst, d_desc, *loss, iters,
-                         cfg->l2_normalize, d_w, d_refs_out, d_ref_obs_out, d_robust_mean_out);
-    else if (C == 128)
-      hipLaunchKernelGGL((k_irls<128>), dim3(blocks), dim3(256), 0, st, n_pts, d_ptr, d_lst, d_desc, *loss, iters,
-                         cfg->l2_normalize, d_w, d_refs_out, d_ref_obs_out, d_robust_mean_out);
-    else
-      hipLaunchKernelGGL((k_irls<64>), dim3(blocks), dim3(256), 0, st, n_pts, d_ptr, d_lst, d_desc, *loss, iters,
-                         cfg->l2_normalize, d_w, d_refs_out, d_ref_obs_out, d_robust_mean_out);
+    });
     rc = hip_check(hipGetLastError(), "k_irls launch");
   }
   if (!rc) rc = hip_check(hipStreamSynchronize(st), "sync");
