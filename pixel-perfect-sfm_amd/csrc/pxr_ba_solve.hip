@@ -544,6 +544,63 @@ __global__ void k_jacobi_scale(int64_t n, const double* __restrict__ diag, doubl
   if (i < n) scale[i] = 1.0 / (1.0 + sqrt(diag[i]));
 }
 
+// ---- deterministic direct solver: columns that stay small under Ceres' Jacobi scaling --------------------------------------------
+// The fixed-point grid of a linearisation is ONE absolute step for every slot of U, g_c and S, made for the largest diagonal entry.
+// Ceres' scaling 1 / (1 + sqrt d) leaves a column with d = |J_col|^2 << 1 as small as it was -- the r^6 coefficients of FULL_OPENCV
+// have d ~ 1e-6 .. 1e-10 where a rotation has 1e6 --, so such a column (a) had its d measured by the unscaled pass to a few per cent
+// only, hence a Jacobi scale and a damping that were not Ceres', and (b) kept 30 .. 40 significant bits in U and S where the
+// others keep 60: a reduced system that is ill-conditioned in just those columns (k3 against k6) ended 1e-4 away from the
+// floating-point solve.  The cure is a power of two 2^k per column on top of Ceres' scale: powers of two commute with every
+// rounding of the floating-point path (the system becomes P S P, its Cholesky factor P L, the step keeps its bits), only the grid
+// sees them.  pow_c = 4^k; the damping is Ceres': clamp(diag / 4^k) 4^k (k_clamp_pow).
+//  * k_column_pow2, apply = 0: count the columns whose diagonal is below `below`;  apply = 1: move every column into [1/4, 1)
+//    (scale, pow_c and -- the same linearisation point -- the damping follow).
+//  * At the start (LmSolve::resolve_small_columns): only when the unscaled pass leaves a column with fewer than 2^16 grid steps
+//    (d < 5e-4 on the first grid) the columns are moved and measured again; a scene without such a column -- the usual models,
+//    whose focal lengths have d ~ 3e-3 .. 1 -- takes the path and the bits it always took (cols_pow2 stays false).
+//  * k is NOT fixed for the solve the way Ceres' scale is: a column's norm may be small at the first point only (the FOV scene of
+//    tests/test_camera_models_ext.py has one that grows by 1e5 with the first step), and left at its first k it would set the
+//    grid of every later linearisation and take the bits from all the others.  The columns are moved again before every new
+//    linearisation, from the diagonal of the last one, and after the overflow guard had to repeat one (LmSolve::move_columns).
+__global__ void k_column_pow2(int64_t n, const double* __restrict__ diag, double below, int apply, double* __restrict__ scale,
+                              double* __restrict__ pow_c, double* __restrict__ damp, double* __restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double v = diag[i];
+  if (!(v > 0.0) || !isfinite(v)) return;        // (a column without a derivative stays as it is)
+  if (!apply) { if (v < below) atomicAdd(count, 1.0); return; }      // (a sum of ones: exact in any order)
+  int e;
+  (void)frexp(v, &e);                            // v = m 2^e, m in [1/2, 1)
+  const int dk = min(max((-e) >> 1, -300), 300); // e + 2 dk in {-1, 0}
+  scale[i] = ldexp(scale[i], dk);
+  pow_c[i] = ldexp(pow_c[i], 2 * dk);
+  damp[i] = ldexp(damp[i], 2 * dk);
+}
+
+// Ceres' scale from d = diag / pow_c (the diagonal was measured with the columns moved by pow_c = 4^k), times the 2^k that brings the
+// SCALED column's d / (1 + sqrt d)^2 into [1/4, 1) (k = 0 for d >= 1); pow_c = 4^k afterwards
+__global__ void k_jacobi_scale_pow2(int64_t n, const double* __restrict__ diag, double* __restrict__ scale, double* __restrict__ pow_c) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double d = diag[i] / pow_c[i];
+  const double s = 1.0 / (1.0 + sqrt(d));
+  const double ds = d * s * s;
+  int k = 0;
+  if (ds > 0.0 && isfinite(ds)) {
+    int e;
+    (void)frexp(ds, &e);                         // ds = m 2^e, m in [1/2, 1)
+    k = min(max((-e) >> 1, 0), 300);             // e + 2 k in {-1, 0}
+  }
+  scale[i] = ldexp(s, k);
+  pow_c[i] = ldexp(1.0, 2 * k);
+}
+
+__global__ void k_clamp_pow(int64_t n, const double* __restrict__ in, const double* __restrict__ pow_c, double lo, double hi,
+                            double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = fmin(fmax(in[i] / pow_c[i], lo), hi) * pow_c[i];
+}
+
 __global__ void k_axpy1(int n, const double* __restrict__ x, double* __restrict__ y) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) y[i] += x[i];
@@ -1009,7 +1066,7 @@ struct SolveMode {
 
 // ---- the device buffers of a solve (behind the structure's) ----------------------------------------------------------------------
 struct SolveWorkspace {
-  DevBuf<double> L, V, gp, Vd0, T, W, U, S /* S | rhs */, gcd /* diagU | g_c | trace limbs of the overflow guard */, damp_c, scale_c, scale_p,
+  DevBuf<double> L, V, gp, Vd0, T, W, U, S /* S | rhs */, gcd /* diagU | g_c | trace limbs of the overflow guard */, damp_c, scale_c, pow_c /* resolve_small_columns */, scale_p,
       delta_c, delta_p, rec_a, rec_b, q1, t1, k1, X1, scal /* the scalar block, pxr_ba_solve.h */, xsol, linv;
   // iterative solver: preconditioner blocks and the conjugate-gradient work space
   PrecondBlocks precond;              // (host; alive while its uploads may be in flight)
@@ -1027,6 +1084,7 @@ struct SolveWorkspace {
   DevBuf<double> i64_halves;          // several ranks through the callback: the integers' exact 32-bit halves
   DevBuf<double> det_part;            // the inner iterations' per-point costs (every mode)
   DevBuf<double> chunk_trace;
+  DevBuf<double> col_count;           // k_column_pow2's answer
 
   int allocate(pxr_ctx* ctx, const pxr_ba_view* view, const SolveStructure& sx, const SolveMode& m) {
     hipStream_t st = ctx->stream;
@@ -1040,7 +1098,7 @@ struct SolveWorkspace {
     // direct solver: dense U and [S | rhs]; iterative solver: one DC x DC block of U per image, nothing quadratic in n_c
     RC(U.alloc(m.iterative ? (size_t)n_img * DC * DC : nc1 * nc1)); RC(S.alloc(m.iterative ? 1 : (nc1 + 1) * (nc1 + 1)));
     RC(gcd.alloc(2 * nc1 + 8)); RC(damp_c.alloc(nc1));
-    RC(scale_c.alloc(nc1)); RC(scale_p.alloc((size_t)n_pts * 3)); RC(delta_c.alloc(nc1)); RC(delta_p.alloc((size_t)n_pts * 3));
+    RC(scale_c.alloc(nc1)); RC(pow_c.alloc(nc1)); RC(scale_p.alloc((size_t)n_pts * 3)); RC(delta_c.alloc(nc1)); RC(delta_p.alloc((size_t)n_pts * 3));
     RC(rec_a.alloc((size_t)n_obs * PXR_OBS_REC)); RC(rec_b.alloc((size_t)n_obs * PXR_OBS_REC));
     RC(q1.alloc((size_t)n_img * 4)); RC(t1.alloc((size_t)n_img * 3)); RC(k1.alloc((size_t)n_cam * PXR_KPAD)); RC(X1.alloc((size_t)n_pts * 3));
     RC(scal.alloc(kScalAll));
@@ -1072,6 +1130,7 @@ struct SolveWorkspace {
       RC(i64_halves.alloc((size_t)2 * std::max<int64_t>({packed_doubles, 2 * (int64_t)nc1 + 8, kScalSlots * PXR_LIMBS})));
     RC(det_part.alloc((size_t)n_pts + 8));
     RC(chunk_trace.alloc(sx.chunks.size() + 1));
+    RC(col_count.alloc(1));
     return PXR_OK;
   }
 };
@@ -1157,6 +1216,9 @@ struct LmSolve {
   bool lin_fits(const double* stt, double md_made_for) const;
   int linearize_checked(const double* rec, double md_guess, double cost_now, bool refine = false);
   int refresh_damping();
+  int resolve_small_columns(const double* rec);
+  int move_columns();
+  bool cols_pow2 = false;
   int gradient_below_tolerance(bool* below);
   int reduced_step_direct(double inv_radius);
   int reduced_step_iterative(double inv_radius, bool* ok, double* inexact_correction);
@@ -1296,8 +1358,44 @@ int LmSolve::linearize_checked(const double* rec, double md_guess, double cost_n
   }
   return set_error(PXR_EINVAL, "pxr_ba_solve: the fixed-point grid of the deterministic mode could not be fitted");
 }
+// deterministic direct solver, before the Jacobi scaling: diag(U) of the unscaled pass is in diagU.  If a column's entry is fewer
+// than 2^16 steps of the grid it was measured on, every column is moved into [1/4, 1) by a power of two (scale_c, pow_c = its
+// square) and the diagonal is measured again on the grid of that range -- and once more if a column that the first grid could not
+// see at all shows up in the second.  cols_pow2: it happened (from then on the columns are kept there: move_columns)
+// every column into [1/4, 1) by the diagonal of the newest linearisation (diagU); a linearisation must follow
+int LmSolve::move_columns() {
+  hipLaunchKernelGGL(k_column_pow2, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, (const double*)diagU, 0.0, 1, ws.scale_c.p, ws.pow_c.p, ws.damp_c.p,
+                     ws.col_count.p);
+  LAUNCH_CHECK("k_column_pow2");
+  return PXR_OK;
+}
+int LmSolve::resolve_small_columns(const double* rec) {
+  cols_pow2 = false;
+  for (int pass = 0; pass < 4; ++pass) {
+    double h = 0.0;
+    PXR_HIP(hipMemsetAsync(ws.col_count.p, 0, sizeof(double), st));
+    hipLaunchKernelGGL(k_column_pow2, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, (const double*)diagU, 65536.0 / lin_scale, 0,
+                       ws.scale_c.p, ws.pow_c.p, ws.damp_c.p, ws.col_count.p);
+    PXR_HIP(hipMemcpyAsync(&h, ws.col_count.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    PXR_HIP(hipStreamSynchronize(st));
+    if (knobs.verbose) {
+      std::vector<double> hd((size_t)n_c);
+      PXR_HIP(hipMemcpy(hd.data(), diagU, sizeof(double) * n_c, hipMemcpyDeviceToHost));
+      double mn = 1e300, mx = 0.0;
+      for (double v : hd) if (v > 0.0) { mn = std::min(mn, v); mx = std::max(mx, v); }
+      fprintf(stderr, "[pxr_ba_solve] pass %d: diag(U) in [%.3e, %.3e], grid step %.3e\n", pass, mn, mx, 1.0 / lin_scale);
+    }
+    if (h == 0.0) return PXR_OK;
+    if (knobs.verbose) fprintf(stderr, "[pxr_ba_solve] %d columns of fewer than 2^16 grid steps: diag(U) measured again on their grid\n", (int)h);
+    cols_pow2 = true;
+    RC(move_columns());
+    RC(linearize_checked(rec, 1.0 / 8.0, cost));
+    if (lin_not_finite) return PXR_OK;
+  }
+  return PXR_OK;
+}
 int LmSolve::refresh_damping() {  // LevenbergMarquardtStrategy: diagonal clamped to [min, max]
-  if (n_c > 0) hipLaunchKernelGGL(k_clamp, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, diagU, opt->min_lm_diagonal, opt->max_lm_diagonal, ws.damp_c.p);
+  if (n_c > 0) hipLaunchKernelGGL(k_clamp_pow, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, diagU, ws.pow_c.p, opt->min_lm_diagonal, opt->max_lm_diagonal, ws.damp_c.p);
   hipLaunchKernelGGL(k_point_diag, dim3(nblk(n_pts)), dim3(256), 0, st, n_pts, ws.V.p, ws.Vd0.p);
   hipLaunchKernelGGL(k_clamp, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, ws.Vd0.p, opt->min_lm_diagonal, opt->max_lm_diagonal, ws.Vd0.p);
   LAUNCH_CHECK("damping kernels");
@@ -1546,6 +1644,10 @@ int LmSolve::candidate(double inv_radius, double inexact_correction, Candidate* 
     // the overflow guard: a slot of the linearisation this iteration was computed from did not fit its grid -- repeat the
     // linearisation on a grid from the measured trace and the iteration with it (state untouched: radius, damping, counts)
     RC(linearize_checked(rec_cur, std::max(h_lin_stats[3], 2.0 * lin_md), cost));
+    if (cols_pow2 && !lin_not_finite) {      // a column outgrew its power of two: moved by the diagonal just measured, once more on the fine grid
+      RC(move_columns());
+      RC(linearize_checked(rec_cur, 1.0 / 8.0, cost));
+    }
     c->repeat = true;
     return PXR_OK;
   }
@@ -1617,13 +1719,19 @@ int LmSolve::run() {
   sum->initial_cost = cost;
   if (!std::isfinite(cost)) return finish(PXR_TERM_FAILURE);   // [upstream] "Initial residual and Jacobian evaluation failed" (e.g. check_bounds)
   hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.scale_c.p);
+  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.pow_c.p);
   hipLaunchKernelGGL(k_fill, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, 1.0, ws.scale_p.p);
   // (deterministic mode: the UNSCALED pass only yields diag(U) for the Jacobi scaling and has no a-priori bound: a first guess
   //  of 2^32 for its diagonal -- unit-norm descriptors give 1e3 .. 1e6 -- and the checked retry from the measured trace otherwise)
   RC(linearize_checked(rec_cur, std::ldexp(1.0, 32), cost, !opt->jacobi_scaling));
   if (lin_not_finite) return finish(PXR_TERM_FAILURE, opt->initial_radius);
   if (opt->jacobi_scaling) {   // 1 / (1 + sqrt(diag(J~^T J~))), fixed for the whole solve
-    if (n_c > 0) hipLaunchKernelGGL(k_jacobi_scale, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, diagU, ws.scale_c.p);
+    if (m.det_fixed && n_c > 0) {
+      RC(resolve_small_columns(rec_cur));
+      if (lin_not_finite) return finish(PXR_TERM_FAILURE, opt->initial_radius);
+    }
+    if (n_c > 0 && cols_pow2) hipLaunchKernelGGL(k_jacobi_scale_pow2, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, diagU, ws.scale_c.p, ws.pow_c.p);
+    else if (n_c > 0) hipLaunchKernelGGL(k_jacobi_scale, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, diagU, ws.scale_c.p);
     hipLaunchKernelGGL(k_point_diag, dim3(nblk(n_pts)), dim3(256), 0, st, n_pts, ws.V.p, ws.Vd0.p);
     hipLaunchKernelGGL(k_jacobi_scale, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, ws.Vd0.p, ws.scale_p.p);
     RC(linearize_checked(rec_cur, 1.0 / 8.0, cost));      // scaled columns have norm < 1: diag(U) < 1 = 8 x 1/8
@@ -1699,6 +1807,7 @@ int LmSolve::run() {
       cost = c.cost;
       cur_is_exact = false;
       if (m.det_fixed) { lin_md = std::max(h_lin_stats[0], 1e-300); lin_scale = det_scale_for(lin_md, cost); }   // checked with the next iteration's scalars
+      if (cols_pow2) RC(move_columns());      // (by the diagonal at the point that is left: a factor 4 of drift at most is carried along)
       RC(linearize(rec_cur));
       phase(6);
       ++sum->num_successful;

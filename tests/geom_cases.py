@@ -104,6 +104,57 @@ def make_case(n_cams=6, n_points=40, obs_per_point=4, seed=0, model=2, keypoint_
     return out
 
 
+# the generator's own parameter sets (synthetic.make_ba_problem), by COLMAP model id; the six others come from EXT
+_BASE_PARAMS = {0: [1200.0, 500, 500], 1: [1200.0, 1180.0, 500, 500], 2: [1200.0, 500, 500, 0.02], 3: [1200.0, 500, 500, 0.02, -0.01],
+                4: [1200.0, 1180.0, 500, 500, 0.02, -0.01, 1e-3, -5e-4]}
+_TWO_FOCALS = (1, 4, 5, 6, 7, 10)
+
+
+def model_params(model, pinhole):
+    """The initial parameters of a camera of any of the eleven models: the parameter set the suite already uses for the model
+    (the generator's for 0-4, EXT of tests/test_camera_models_ext.py for 5-10) with the distortion terms scaled by 0.05 -- FOV's
+    omega set to 0.02, as in that file's _problem -- and focal length(s) and principal point of `pinhole` (fx, fy, cx, cy)."""
+    if model in _BASE_PARAMS:
+        k = np.array(_BASE_PARAMS[model], dtype=np.float64)
+    else:
+        from test_camera_models_ext import EXT
+        k = np.array(EXT[model], dtype=np.float64)
+    nf = 4 if model in _TWO_FOCALS else 3
+    k[nf:] = 0.02 if model == 7 else k[nf:] * 0.05
+    k[:nf] = pinhole if nf == 4 else [pinhole[0], pinhole[2], pinhole[3]]
+    return k
+
+
+def make_model_case(models, n_cams=6, n_points=90, obs_per_point=4, seed=0, keypoint_noise=0.7, shared_camera=False, ramp=True,
+                    channels=2, patch_size=PATCH_SIZE):
+    """A case for any of the eleven camera models; `models`: one id, or a list with one id per camera.  The scene is
+    synthetic.make_ba_problem's PINHOLE scene (its perturbed poses and points) with cam_model / cam_params replaced by
+    model_params; the observed keypoints are the projections AT THESE INITIAL PARAMETERS (pxo.world_to_pixel: the generator
+    projects five models only) plus seeded Gaussian noise of `keypoint_noise` px.  ramp as in make_case."""
+    from pixsfm_amd import synthetic
+    assert obs_per_point <= n_cams, "a track of n observations needs a scene of at least n cameras"
+    base = synthetic.make_ba_problem(n_cams=n_cams, n_points=n_points, obs_per_point=obs_per_point, seed=seed, model=1,
+                                     shared_camera=shared_camera, channels=1, patch_size=2, dtype=np.float64, rot_deg=0.1)
+    n_cam = len(base["cam_model"])
+    models = [int(models)] * n_cam if np.isscalar(models) else [int(m) for m in models]
+    assert len(models) == n_cam, "one model per camera"
+    cam_params = np.zeros((n_cam, base["cam_params"].shape[1]))
+    for c, m in enumerate(models):
+        k = model_params(m, base["cam_params"][c, :4])
+        cam_params[c, :len(k)] = k
+    out = {k: v for k, v in base.items() if k not in ("patches", "corners", "scales", "refs", "obs_patch", "centers")}
+    out["cam_model"] = np.array(models, dtype=np.int32)
+    out["cam_params"] = cam_params
+    rng = np.random.default_rng(1000 + seed)
+    obs_xy = reprojection(out)
+    obs_xy = obs_xy + rng.normal(0.0, keypoint_noise, obs_xy.shape)
+    if ramp:
+        return as_ramp_problem(out, obs_xy, patch_size, channels)
+    out["obs_xy"] = obs_xy
+    assert_inside(out, what="initial parameters")
+    return out
+
+
 def geometric_dict(prob):
     """What engine.GeometricBAProblem takes."""
     return {k: prob[k] for k in ("obs_image", "obs_point", "obs_xy", "image_camera", "qvec", "tvec", "cam_model", "cam_params", "xyz")}

@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NUM_PARAMS = [3, 4, 4, 5, 8, 8, 12, 5, 4, 5, 12]        # COLMAP camera models by id
-SIMPLE_PINHOLE, OPENCV = 0, 4
+SIMPLE_PINHOLE, PINHOLE, OPENCV, FULL_OPENCV = 0, 1, 4, 6
 GS = 18                                                  # PCG_GS: rows of the largest preconditioner block
 
 
@@ -173,7 +173,30 @@ def _case_e():
     return _case([0, 1], [SIMPLE_PINHOLE, SIMPLE_PINHOLE], [1, 0], [0, 0], [0b110, 0b110], np.zeros(1025, int), obs_image, obs_point)
 
 
-CASES = {"a": _case_a, "b": _case_b, "c": _case_c, "d": _case_d, "e": _case_e}
+def _case_f():
+    """the widest layout: two images with a FULL_OPENCV camera each, nothing constant -- two joint blocks that fill all GS rows"""
+    return _case([0, 1], [FULL_OPENCV, FULL_OPENCV], [0, 0], [0, 0], [0, 0], [0, 0, 0], [0, 1, 0, 1, 0, 1], [0, 0, 1, 1, 2, 2])
+
+
+def _case_g():
+    """case (f) with ONE FULL_OPENCV camera shared by both images: two pose blocks and a block of the 12 intrinsics"""
+    return dict(_case_f(), image_camera=np.asarray([0, 0], np.int64), cam_model=np.asarray([FULL_OPENCV], np.int64),
+                cam_mask=np.asarray([0], np.int64))
+
+
+def _case_h():
+    """the mixture of tests/test_ba_wide_blocks_gpu.py's scene k: 8 images with a camera each, FULL_OPENCV (all refined) and PINHOLE
+    (principal point constant); images 0 and 2 pose-constant, t_x of image 1 and t_x, t_z of image 3 constant, every seventh point
+    constant; tracks of 4"""
+    models = [FULL_OPENCV] + [FULL_OPENCV, PINHOLE] * 3 + [FULL_OPENCV]
+    n_pts = 15
+    obs_point = np.repeat(np.arange(n_pts), 4)
+    obs_image = np.concatenate([(p + 3 * np.arange(4)) % 8 for p in range(n_pts)])
+    return _case(list(range(8)), models, [1, 0, 1, 0, 0, 0, 0, 0], [0, 1, 0, 0b101, 0, 0, 0, 0],
+                 [0b1100 if m == PINHOLE else 0 for m in models], [int(p % 7 == 0) for p in range(n_pts)], obs_image, obs_point)
+
+
+CASES = {"a": _case_a, "b": _case_b, "c": _case_c, "d": _case_d, "e": _case_e, "f": _case_f, "g": _case_g, "h": _case_h}
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -205,6 +228,34 @@ def test_smallest_case_by_hand(program):
     assert got["ent_ptr"] == list(range(12)) + [13, 15, 17] + list(range(18, 25))
     assert got["ent"] == [[1, a] for a in range(5)] + [[2, a] for a in range(6)] + [[0, 0], [1, 5], [0, 1], [1, 6], [0, 2], [1, 7]] + \
         [[2, a] for a in range(6, 13)]
+
+
+def test_widest_layout_by_hand(program):
+    """FULL_OPENCV with everything refined: DC = 18 = GS.  A camera per image: two joint blocks of 18 rows, no padding column; one
+    camera for both images: blocks of 6, 6 and 12 rows, every intrinsics column with an entry from each image."""
+    got = _run(program, _case_f())
+    assert (got["n_c"], got["DC"], got["LS"]) == (36, 18, 47)
+    assert got["pose_off"] == [0, 6] and got["intr_off"] == [12, 24] and got["intr_dim"] == [12, 12]
+    assert got["group_size"] == [GS, GS] and len(got["group_cols"]) == 2 * GS
+    assert got["group_cols"] == list(range(0, 6)) + list(range(12, 24)) + list(range(6, 12)) + list(range(24, 36))
+    assert got["ent_ptr"] == list(range(37))
+    got = _run(program, _case_g())
+    assert (got["n_c"], got["DC"], got["LS"]) == (24, 18, 47)
+    assert got["group_size"] == [6, 6, 12]
+    assert got["group_cols"][2 * GS:2 * GS + 12] == list(range(12, 24)) and len(got["group_cols"]) == 3 * GS
+    assert got["ent_ptr"] == list(range(13)) + list(range(14, 37, 2))
+    assert got["ent"][12:] == [[i, 6 + a] for a in range(12) for i in (0, 1)]
+
+
+def test_mixed_widths_by_hand(program):
+    """Case (h): blocks of 12 / 17 / 2 / 16 / 8 / 18 / 8 / 18 columns per image under DC = 18."""
+    c = _case_h()
+    got = _run(program, c)
+    assert got["pose_dim"] == [0, 5, 0, 4, 6, 6, 6, 6] and got["intr_dim"] == [12, 12, 2, 12, 2, 12, 2, 12]
+    assert (got["n_c"], got["DC"], got["LS"]) == (33 + 66, 18, 47)
+    assert got["group_size"] == [12, 17, 2, 16, 8, 18, 8, 18]              # every camera has one user: joint blocks throughout
+    assert got["pt_var"] == [int(p % 7 != 0) for p in range(15)] and got["n_pvar"] == 12
+    assert np.bincount(c["obs_image"], minlength=8).min() > 0
 
 
 def test_chunk_boundaries(program):
