@@ -512,6 +512,91 @@ int pxr_absolute_pose_timed(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_qu
                             int32_t* d_status, int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err,
                             double* h_kernel_ms);
 
+/* ---- two-view geometry (the matches of image pairs in, one relative pose and one inlier mask per pair out) ----
+ * Geometric verification of matches, which the reference hands to COLMAP: pycolmap.verify_matches
+ * (examples/refine_sift_aachen.py:51) and the same step inside hloc's reconstruction and triangulation -- for calibrated cameras.
+ * A batch of image pairs in CSR form over their matches (matches of one pair are contiguous), laid out like pxr_absolute_pose.
+ * All arrays are device pointers.
+ *
+ * max_error, confidence, max_num_trials, min_inlier_ratio and min_num_inliers are COLMAP 3.8's two-view geometry options as
+ * remembered; COLMAP is not available where this library is built, so parity with it is UNPINNED.  min_num_trials, round_size,
+ * seed, refine_max_iterations and lo_rounds are this estimator's own. */
+#define PXR_TWOVIEW_LDS_MATCHES 1024 /* matches of a pair the estimator stages on chip; a longer pair reads the rest from memory */
+typedef struct {
+  double max_error;             /* 4.0      pixels: inlier threshold on the Sampson distance                              */
+  double min_inlier_ratio;      /* 0.25     success needs n_inliers >= max(min_num_inliers, ceil(min_inlier_ratio n))      */
+  double confidence;            /* 0.999    of the stop rule                                                              */
+  uint64_t seed;                /* 0        of the sample hash                                                            */
+  int32_t min_num_inliers;      /* 15                                                                                     */
+  int32_t min_num_trials;       /* 64       lower clamp of the stop rule                                                  */
+  int32_t max_num_trials;       /* 10000    upper clamp of the stop rule, rounded up to a multiple of round_size          */
+  int32_t round_size;           /* 64       samples per round: the stop rule is evaluated at round boundaries only        */
+  int32_t refine_max_iterations;/* 100      Levenberg-Marquardt iterations per refinement                                 */
+  int32_t lo_rounds;            /* 4        at most this many refine / re-classify repetitions                            */
+} pxr_two_view_options;
+/* Writes the defaults above. */
+void pxr_two_view_default_options(pxr_two_view_options* options);
+
+/* Essential-matrix estimation and verification for a batch of image pairs.  This is NOT COLMAP's LO-RANSAC: the estimator has no
+ * random state and reproduces bit for bit; a pair alone and the same pair inside any batch give the same bits (DESIGN.md section
+ * 21).  Pair p owns matches [d_pair_offsets[p], d_pair_offsets[p+1]): pixel d_xy1[i] (COLMAP convention) of camera
+ * d_pair_camera[2p] and pixel d_xy2[i] of camera d_pair_camera[2p+1] show one point.  The pose (q, t) is that of camera 2
+ * relative to camera 1: X2 = R(q) X1 + t, |t| = 1, E = [t]x R.  Per pair:
+ *   1. both pixels go through ImageToWorld (pxr_image_to_world); a match that cannot be undistorted on either side or holds a
+ *      non-finite coordinate is unusable for the whole call; n = the usable ones, in order; n < 5: status 1.
+ *   2. sample h = 0, 1, ... is five distinct indices: draw d = mix(mix(seed + G (h + 1)) + G (d + 1)) mod n, d = 0, 1, ..., with
+ *      mix = the output function of splitmix64 and G = 0x9E3779B97F4A7C15 (64-bit wrap-around), a repeated index drawn again;
+ *      the five are used in ascending order.  Neither p nor the batch enters.
+ *   3. the five-point solver (Nister 2004): null space of the 5 x 9 epipolar system (rows x2 (x) x1) by Gauss-Jordan with full
+ *      pivoting (the largest entry, the first of equals in row-major order; vector k = (-C[:, k], e_k) of [I | C] in the permuted
+ *      columns), orthonormalised by modified Gram-Schmidt in the order k = 0 .. 3 and mixed by the 4 x 4 Hadamard matrix / 2
+ *      (signs ++++ +-+- ++-- +--+) into X, Y, Z, W, so that no single entry of E decides the size of the constant term;
+ *      E = x X + y Y + z Z + W; the ten cubic constraints (the nine of
+ *      (E E^t - tr(E E^t) / 2) E row by row, then det E) as a 10 x 20 matrix in the monomial order x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2
+ *      xyz xy xz^2 xz x yz^2 yz y z^3 z^2 z 1, Gauss-Jordan with partial pivoting on its first ten columns; B(z) from rows (4) - z (5), (6) - z (7),
+ *      (8) - z (9); det B(z) of degree 10 scaled by its largest coefficient; Cauchy's bound 1 + max |c_k / c_10|; a Sturm chain
+ *      with every remainder scaled to a largest coefficient of 1 (a leading coefficient <= 1e-12 after that is dropped); the k-th
+ *      real root by 64 bisection steps on the sign-change count from (-bound, bound), then 4 Newton steps, each kept only inside
+ *      the last interval; roots ascending, at most ten; (x, y, 1) = the cross product of the two rows of B(z) with the largest third
+ *      component.  No hypothesis (and no NaN) from a sample with a pivot <= 1e-12 of its system's largest entry, a leading
+ *      coefficient <= 1e-9 of the largest, or any value that is not finite.
+ *   4. each E is scored over all n in the normalised image plane by the squared Sampson error err = (x2^t E x1)^2 / ((E x1)_0^2 +
+ *      (E x1)_1^2 + (E^t x2)_0^2 + (E^t x2)_1^2); inlier iff err <= thr^2, thr = (max_error / f1 + max_error / f2) / 2 with f the
+ *      mean focal length; the largest key (inlier count, -sum min(err, thr^2), -h, -root) wins, the sum taken in index order.
+ *   5. after each round of round_size samples: stop once samples done >= clamp(log(1 - confidence) / log(1 - w^5),
+ *      min_num_trials, max_num_trials), w = best count / n.  No hypothesis at all: status 2.
+ *   6. the winner's E becomes (R, +-t) in closed form (Horn 1990, no SVD): t t^t = tr(E E^t) / 2 I - E E^t, t from the row of
+ *      the largest diagonal entry; with E scaled to tr(E E^t) = 2, Ra = Cof(E) - [t]x E and Rb = Cof(E) + [t]x E (Cof: row i = row
+ *      i+1 x row i+2).  Of (Ra, t) (Ra, -t) (Rb, t) (Rb, -t) the one with the most of the winner's inliers in front of both cameras
+ *      stays (ties: the first).  Local optimisation: Levenberg-Marquardt on the inliers' signed Sampson residuals over five
+ *      parameters (rotation on the quaternion manifold as in pxr_absolute_pose; t + a b1 + b b2 re-normalised, b1 = t x e_m /
+ *      |t x e_m| for the axis m of the smallest |t_m|, b2 = t x b1; step norm <= 1e-12 or refine_max_iterations), then all n
+ *      classified under E = [t]x R; repeated until the set stands still or lo_rounds; a refined pose with fewer inliers than
+ *      the one before it is dropped.
+ *   7. n_inliers < max(min_num_inliers, ceil(min_inlier_ratio n)): status 3.
+ * With d_prior_qvec [n_pairs][4] / d_prior_tvec [n_pairs][3] non-NULL (both or neither; any length of t) steps 2-6 are skipped:
+ * d_n_trials is 0, the matches are classified under the given pose (q and t normalised for E), and d_qvec / d_tvec come back
+ * as they were given, bit for bit: not unit unless the prior was, and w may be negative; a prior that is not finite or has a zero
+ * quaternion or translation gives status 2.
+ * Outputs: d_status[p] 0 = pose written to d_qvec[p] (unit, w >= 0) / d_tvec[p] (unit; with a prior: as given) and E = [t]x R (row-major, Frobenius
+ * norm sqrt 2) to d_E[p], all three left untouched otherwise; d_n_inliers[p] (0 unless status is 0); d_n_trials[p] samples drawn;
+ * per match d_inlier (0 unless status is 0) and d_err (sqrt(err) max_error / thr, i.e. the Sampson distance in pixels, of the
+ * usable matches of a status-0 pair; NaN elsewhere).
+ * PXR_EINVAL (nothing launched): offsets not starting at 0, not monotone or not ending at n_matches, a camera index out of
+ * range, an option out of range, one prior array without the other.
+ * Synchronises the context's stream (offsets and cameras are validated and the pairs ordered by size on the host). */
+int pxr_two_view_geometry(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
+                          const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,
+                          const double* d_cam_params, const double* d_prior_qvec, const double* d_prior_tvec,
+                          const pxr_two_view_options* options, double* d_qvec, double* d_tvec, double* d_E, int32_t* d_status,
+                          int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[4] = records, compaction, hypotheses, refinement. */
+int pxr_two_view_geometry_timed(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
+                                const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,
+                                const double* d_cam_params, const double* d_prior_qvec, const double* d_prior_tvec,
+                                const pxr_two_view_options* options, double* d_qvec, double* d_tvec, double* d_E, int32_t* d_status,
+                                int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err, double* h_kernel_ms);
+
 /* ---- descriptor matching (descriptors of image pairs in, mutual nearest neighbours out) --------
  * What produces the match graph (and a query's 2D-3D pairs): hloc's match_features with the NearestNeighbor matcher, whose output
  * pixsfm/util/hloc.py:read_matches_hloc reads back.  hloc is not available where this library is built, so parity with it is

@@ -101,6 +101,16 @@ class AbsposeOptions(C.Structure):
 ABSPOSE_LDS_CORR = 1024      # PXR_ABSPOSE_LDS_CORR
 
 
+class TwoViewOptions(C.Structure):
+    """pxr_two_view_options"""
+    _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double), ("seed", C.c_uint64),
+                ("min_num_inliers", C.c_int32), ("min_num_trials", C.c_int32), ("max_num_trials", C.c_int32),
+                ("round_size", C.c_int32), ("refine_max_iterations", C.c_int32), ("lo_rounds", C.c_int32)]
+
+
+TWOVIEW_LDS_MATCHES = 1024   # PXR_TWOVIEW_LDS_MATCHES
+
+
 class MatchOptions(C.Structure):
     """pxr_match_options"""
     _fields_ = [("ratio_threshold", C.c_double), ("distance_threshold", C.c_double), ("do_mutual_check", C.c_int32),
@@ -162,6 +172,14 @@ _SIGNATURES = {
     "pxr_absolute_pose_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.POINTER(AbsposeOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "pxr_two_view_default_options": (None, [C.POINTER(TwoViewOptions)]),
+    "pxr_two_view_geometry": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TwoViewOptions), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pxr_two_view_geometry_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TwoViewOptions),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_match_default_options": (None, [C.POINTER(MatchOptions)]),
     "pxr_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p, C.c_void_p]),

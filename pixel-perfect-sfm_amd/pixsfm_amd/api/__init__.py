@@ -1,6 +1,6 @@
 """pixsfm-compatible Python surface of the accelerated KA/BA path (same class / method names as
 pixsfm.keypoint_adjustment, pixsfm.bundle_adjustment, pixsfm._pixsfm._base/_features)."""
-from . import base, extract, features, localization, reconstruction, triangulation  # noqa: F401
+from . import base, extract, features, localization, reconstruction, triangulation, two_view  # noqa: F401
 from .bundle_adjustment import (BundleAdjuster, BundleAdjustmentSetup, CostMapBundleAdjuster,  # noqa: F401
                                 CostMapBundleOptimizer, CostMapExtractor, FeatureReferenceBundleAdjuster,
                                 FeatureReferenceBundleOptimizer, FeatureView, GeometricBundleAdjuster,
@@ -18,3 +18,4 @@ from .extract import (FeatureExtractor, extract_patchdata_from_graph, features_f
                       features_from_image_list, features_from_reconstruction)
 from .triangulation import TrackTriangulator  # noqa: F401,E402
 from .matching import DescriptorMatcher, pairs_2d3d_from_matches  # noqa: F401,E402
+from .two_view import TwoViewVerifier, essential_matrix_estimation  # noqa: F401,E402
