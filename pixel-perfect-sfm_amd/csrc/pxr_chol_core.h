@@ -168,14 +168,22 @@ __device__ __forceinline__ int factor_panel(FactorLds& lds, int p, int lane, int
   return bad;
 }
 
-// wavefront 1, one panel behind: panel p of L out of the LDS copy
+// wavefront 1, one panel behind: panel p of L out of the LDS copy.  The DIAGONAL entry is not P's: column j of L below the
+// diagonal, Dinv, inv(L) and both substitutions are all products with the reciprocal inv_j that factor_panel formed, so the
+// diagonal that belongs to them is 1 / inv_j.  What falls out of scaling the pivot row itself, (d11 - l10^2) inv1 for the second
+// pivot of a pair, carries the cancellation in d11 - l10^2 by another route than inv1 = rsqrt(d00 d11 - d10^2) (d00 inv0) and
+// differs from 1 / inv1 relatively by ~u / (1 - rho^2), rho the pair's conditional correlation: with it |A - L L^T| missed
+// (n + 8) u |L||L^T| by up to 2e7 on nearly dependent column pairs (tests/chol_cases.py, correlated_pairs).  One division per
+// lane (row 8 p + k owns diagonal k), here and not in factor_panel: off wavefront 0's chain.
 __device__ __forceinline__ void store_diag_panel(const FactorLds& lds, int p, int lane, const RowSink& sink) {
   if (!sink.l_diag || lane < PW * p || lane >= sink.nb) return;           // one exec-mask branch; rows above the panel's diagonal block hold zeros
   double* out = sink.l_diag + lane + (PW * p) * NB;
+  const int kd = lane - PW * p;                                           // < PW: this lane's row has its diagonal entry in this panel
+  const double diag = 1.0 / lds.Dinv[p & 1][kd & (PW - 1)];
 #pragma unroll
   for (int k = 0; k < PW; ++k)
-    if (PW * p + k < sink.nb) out[k * NB] = lds.P[p & 1][k][lane];   // wave-uniform test; entries above the diagonal inside the
-                                                                                  // 8 x 8 block are stored as the zeros P holds (upper part: never read)
+    if (PW * p + k < sink.nb) out[k * NB] = (k == kd) ? diag : lds.P[p & 1][k][lane];   // wave-uniform test; entries above the diagonal
+                                                                  // inside the 8 x 8 block are stored as the zeros P holds (upper part: never read)
 }
 
 // a row wavefront (16 extra rows): the panel-p part of its triangular solve, then its rank-8 updates
