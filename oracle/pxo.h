@@ -238,6 +238,55 @@ int pxo_ba_solve(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
                  const uint8_t* tvec_const_mask, const uint16_t* cam_const_mask,
                  const uint8_t* point_const, const pxo_lm_options* opt, pxo_lm_summary* sum);
 
+/* The same LM loop with the ITERATIVE reduced step the project specifies for scenes above 1000 images (include/pixsfm_hip.h:
+ * pxr_lm_options; the header comment of csrc/pxr_ba_pcg.hip), on the dense scaled system: the 3 x 3 point blocks eliminated
+ * (damped by diag / radius), preconditioned conjugate gradients on S x = b from x = 0 with Q = -(x.b + x.r) / 2 from the
+ * recurrence residual, the points back-substituted exactly for that x, the model cost change from the full step
+ * (-d.g - d.H.d / 2: never from the solver's residual).  The stops, in the order they are tested in iteration i:
+ * rho = r.z zero or not finite (iteration not counted); p.Sp <= 0 (not counted, the last x kept); i (Q_i - Q_{i-1}) / Q_i < eta;
+ * |r| <= r_tolerance |b| (r_tolerance > 0 only); i = max_linear_solver_iterations.  No counted iteration = invalid step.
+ * Preconditioner: per pose block of an image / intrinsics block of a camera (joint where the camera has a single image)
+ * A[g, g] - sum_i W_i[g] T_p W_i[g]^T -- the block diagonal of S without the cross terms of two observations of one point. */
+typedef struct {
+  int32_t max_linear_solver_iterations;  /* 200 (bundle_adjustment_options.h:55)   */
+  double eta;                            /* 0.1 [upstream Solver::Options::eta]    */
+  double r_tolerance;                    /* <= 0: off                              */
+} pxo_linear_options;
+
+enum { PXO_CG_STOP_MAX_ITERATIONS = 0, PXO_CG_STOP_Q = 1, PXO_CG_STOP_R_TOLERANCE = 2, PXO_CG_STOP_RHO = 3, PXO_CG_STOP_INDEFINITE = 4,
+       PXO_CG_STOP_PRECONDITIONER = 5 /* a block (or a point block) is not positive definite */, PXO_CG_STOP_ZERO_RHS = 6 };
+
+typedef struct {
+  int32_t cg_iterations;       /* counted conjugate-gradient iterations of this LM iteration            */
+  int32_t cg_stop;             /* PXO_CG_STOP_*                                                         */
+  int32_t step_is_valid, step_is_successful;
+  double relative_decrease;    /* cost change / model cost change (0 for an invalid step)               */
+  double radius;               /* the radius AFTER this iteration                                       */
+  /* |zeta - eta| / eta, zeta = i (Q_i - Q_{i-1}) / Q_i: at the last counted iteration, at the one before it, and the smallest
+   * over the iterations of this solve; -1 where there is none (eta = 0, fewer iterations)             */
+  double margin_last, margin_prev, margin_min;
+} pxo_lm_trace_entry;
+
+typedef struct {
+  int32_t capacity;            /* entries the caller allocated                                          */
+  int32_t count;               /* LM iterations that ended in a decision (may exceed capacity)          */
+  pxo_lm_trace_entry* entries;
+} pxo_lm_trace;
+
+int pxo_ba_solve_iterative(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
+                           const pxo_interp_cfg* cfg, const pxo_loss* loss, const uint8_t* pose_const,
+                           const uint8_t* tvec_const_mask, const uint16_t* cam_const_mask,
+                           const uint8_t* point_const, const pxo_lm_options* opt, const pxo_linear_options* lin,
+                           pxo_lm_summary* sum, pxo_lm_trace* trace /* or NULL */);
+
+/* The reduced system of the first LM iteration (radius = opt->initial_radius) at the batch's parameters; see pxo_solve.c. */
+int pxo_ba_reduced_system(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
+                          const pxo_interp_cfg* cfg, const pxo_loss* loss, const uint8_t* pose_const,
+                          const uint8_t* tvec_const_mask, const uint16_t* cam_const_mask,
+                          const uint8_t* point_const, const pxo_lm_options* opt, const pxo_linear_options* lin,
+                          double* S_out, double* rhs_out, double* M_out, double* x_out, int32_t* col_group_out,
+                          int32_t* cg_iterations);
+
 
 /* ONE LM iteration with Schur elimination, staged and timed the way the reference's CPU path spends it
  * (pxo_lm_bench.c; OpenMP over observations / points): bench.py's cpu_baseline_lm and an independent check of a

@@ -338,6 +338,88 @@ def ba_solve(problem, config, ls, pose_const, tvec_const_mask, cam_const_mask, p
     return s.as_dict(), prob["qvec"], prob["tvec"], prob["cam_params"], prob["xyz"]
 
 
+class LinearOptions(C.Structure):
+    _fields_ = [("max_linear_solver_iterations", C.c_int32), ("eta", C.c_double), ("r_tolerance", C.c_double)]
+
+
+CG_STOPS = ("max_iterations", "q", "r_tolerance", "rho", "indefinite", "preconditioner", "zero_rhs")
+
+
+class LMTraceEntry(C.Structure):
+    _fields_ = [("cg_iterations", C.c_int32), ("cg_stop", C.c_int32), ("step_is_valid", C.c_int32),
+                ("step_is_successful", C.c_int32), ("relative_decrease", C.c_double), ("radius", C.c_double),
+                ("margin_last", C.c_double), ("margin_prev", C.c_double), ("margin_min", C.c_double)]
+
+
+class LMTrace(C.Structure):
+    _fields_ = [("capacity", C.c_int32), ("count", C.c_int32), ("entries", C.POINTER(LMTraceEntry))]
+
+
+def linear_options(max_linear_solver_iterations=200, eta=0.1, r_tolerance=-1.0):
+    return LinearOptions(int(max_linear_solver_iterations), float(eta), float(r_tolerance))
+
+
+def _gauge_arrays(pose_const, tvec_const_mask, cam_const_mask, point_const):
+    return (np.ascontiguousarray(pose_const, dtype=np.uint8), np.ascontiguousarray(tvec_const_mask, dtype=np.uint8),
+            np.ascontiguousarray(cam_const_mask, dtype=np.uint16), np.ascontiguousarray(point_const, dtype=np.uint8))
+
+
+def ba_solve_iterative(problem, config, ls, pose_const, tvec_const_mask, cam_const_mask, point_const, opts=None, lin=None):
+    """pxo_ba_solve_iterative: the oracle's LM loop with the iterative reduced step.  Returns (summary dict, trace, refined copies
+    of qvec, tvec, cam_params, xyz); trace: one dict per LM iteration (cg_iterations, cg_stop as a name of CG_STOPS,
+    step_is_valid, step_is_successful, relative_decrease, radius, margin_last, margin_prev, margin_min); the summary gains
+    linear_iterations, their sum."""
+    prob = dict(problem)
+    for k in ("qvec", "tvec", "cam_params", "xyz"):
+        prob[k] = np.array(problem[k], dtype=np.float64, order="C", copy=True)
+    b, keep = ba_batch(prob)
+    for k in ("qvec", "tvec", "cam_params", "xyz"):
+        assert keep[k] is prob[k] or keep[k].ctypes.data == prob[k].ctypes.data
+    opts = opts or lm_options()
+    lin = lin or linear_options()
+    s = LMSummary()
+    cap = max(1, int(opts.max_iterations))
+    entries = (LMTraceEntry * cap)()
+    tr = LMTrace(cap, 0, C.cast(entries, C.POINTER(LMTraceEntry)))
+    pc, tm, cm, ptc = _gauge_arrays(pose_const, tvec_const_mask, cam_const_mask, point_const)
+    fn = lib().pxo_ba_solve_iterative
+    fn.restype = C.c_int
+    rc = fn(C.byref(b), len(prob["image_camera"]), len(prob["cam_model"]), C.c_int64(len(prob["xyz"])), C.byref(config),
+            C.byref(ls), _p(pc), _p(tm), _p(cm), _p(ptc), C.byref(opts), C.byref(lin), C.byref(s), C.byref(tr))
+    assert rc == 0 and tr.count <= cap
+    trace = []
+    for e in entries[:tr.count]:
+        d = {k: getattr(e, k) for k, _ in LMTraceEntry._fields_}
+        d["cg_stop"] = CG_STOPS[d["cg_stop"]]
+        trace.append(d)
+    out = s.as_dict()
+    out["linear_iterations"] = sum(e["cg_iterations"] for e in trace)
+    return out, trace, prob["qvec"], prob["tvec"], prob["cam_params"], prob["xyz"]
+
+
+def ba_reduced_system(problem, config, ls, pose_const, tvec_const_mask, cam_const_mask, point_const, opts=None, lin=None):
+    """pxo_ba_reduced_system: dict with S (n_c x n_c), rhs, M (the specified preconditioner blocks, damped, not inverted, zero
+    outside them), x (the conjugate-gradient iterate `lin` stops at), col_group, cg_iterations -- of the first LM iteration
+    (radius = opts.initial_radius) at the problem's parameters."""
+    b, keep = ba_batch(problem)
+    opts = opts or lm_options()
+    lin = lin or linear_options()
+    n_img, n_cam = len(problem["image_camera"]), len(problem["cam_model"])
+    cap = 6 * n_img + KPAD * n_cam
+    S, M = np.zeros(cap * cap), np.zeros(cap * cap)
+    rhs, x = np.zeros(cap), np.zeros(cap)
+    grp = np.zeros(cap, np.int32)
+    its = C.c_int32(0)
+    pc, tm, cm, ptc = _gauge_arrays(pose_const, tvec_const_mask, cam_const_mask, point_const)
+    fn = lib().pxo_ba_reduced_system
+    fn.restype = C.c_int
+    n_c = fn(C.byref(b), n_img, n_cam, C.c_int64(len(problem["xyz"])), C.byref(config), C.byref(ls), _p(pc), _p(tm), _p(cm),
+             _p(ptc), C.byref(opts), C.byref(lin), _p(S), _p(rhs), _p(M), _p(x), _p(grp), C.byref(its))
+    assert n_c >= 0
+    return dict(n_c=n_c, S=S[:n_c * n_c].reshape(n_c, n_c).copy(), rhs=rhs[:n_c].copy(), M=M[:n_c * n_c].reshape(n_c, n_c).copy(),
+                x=x[:n_c].copy(), col_group=grp[:n_c].copy(), cg_iterations=its.value)
+
+
 def ba_lm_iteration_schur(problem, config, ls, pose_const, tvec_const_mask, cam_const_mask, point_const, radius=1e4,
                           n_threads=0, want_step=True):
     """One Schur-complement LM iteration on the host cores (pxo_lm_bench.c).  Returns a dict with the stage times

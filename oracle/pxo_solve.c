@@ -17,6 +17,8 @@
  * parameter tolerance |dx| <= tol (|x| + tol); function tolerance |dcost| <= tol * cost.
  * Unlike the reference's SPARSE_SCHUR / SPARSE_NORMAL_CHOLESKY the oracle factorises the full
  * damped normal matrix densely -- mathematically the same step, independent code path.
+ * pxo_ba_solve_iterative runs the same loop with the iterative reduced step the project specifies for ITERATIVE_SCHUR
+ * (preconditioned conjugate gradients on the dense Schur complement, Q-based stop): see "the iterative reduced step" below.
  * PARITY UNPINNED: Ceres is not available, so trajectories cannot be compared with the real
  * reference; the GPU solver is compared with THIS restatement.  Inner iterations
  * (bundle_adjustment/main.py:43) and the bounds line search are restated in simplified
@@ -94,7 +96,11 @@ typedef struct {
   const uint8_t* point_const;
   int n_images, n_cams; int64_t n_points;
   ba_layout L;
+  /* optional extra output of ba_evaluate (the iterative step's preconditioner): per observation the UNSCALED block
+   * W_i = Jc_i^T JX_i of its camera-side columns (pose then intrinsics, PXO_WROWS x 3) and their global indices */
+  double* obs_W; int* obs_idx; int* obs_ncs;
 } ba_ctx;
+#define PXO_WROWS 18
 
 static void ba_build_layout(ba_ctx* c) {
   ba_layout* L = &c->L;
@@ -200,6 +206,7 @@ static double ba_evaluate(ba_ctx* c, const double* qvec, const double* tvec, con
         idx[dl] = c->L.intr_off[cam] + kc; ++kc; ++dl;
       }
     }
+    const int ncs = dl; /* camera-side columns of this observation */
     if (c->L.pt_off[pt] >= 0) {
       for (int a = 0; a < 3; ++a) {
         for (int k = 0; k < C; ++k) Jl[k * 24 + dl] = JX[k * 3 + a];
@@ -210,6 +217,17 @@ static double ba_evaluate(ba_ctx* c, const double* qvec, const double* tvec, con
     double* Jc = (double*)malloc(sizeof(double) * C * (dl > 0 ? dl : 1));
     for (int k = 0; k < C; ++k) for (int a = 0; a < dl; ++a) Jc[k * dl + a] = Jl[k * 24 + a];
     pxo_corrector(s, rho, C, dl, r, Jc);
+    if (c->obs_W) {
+      c->obs_ncs[i] = dl > ncs ? ncs : 0; /* a constant point has no block */
+      for (int a = 0; a < c->obs_ncs[i]; ++a) {
+        c->obs_idx[i * PXO_WROWS + a] = idx[a];
+        for (int m = 0; m < 3; ++m) {
+          double w = 0;
+          for (int k = 0; k < C; ++k) w += Jc[k * dl + a] * Jc[k * dl + ncs + m];
+          c->obs_W[((size_t)i * PXO_WROWS + a) * 3 + m] = w;
+        }
+      }
+    }
     for (int a = 0; a < dl; ++a) {
       double ga = 0;
       for (int k = 0; k < C; ++k) ga += Jc[k * dl + a] * r[k];
@@ -399,10 +417,270 @@ static void ba_inner_iterations(ba_ctx* c, const double* q1, const double* t1, c
   free(cnt); free(lst); free(cur);
 }
 
-int pxo_ba_solve(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
-                 const pxo_interp_cfg* cfg, const pxo_loss* loss, const uint8_t* pose_const,
-                 const uint8_t* tvec_const_mask, const uint16_t* cam_const_mask,
-                 const uint8_t* point_const, const pxo_lm_options* opt, pxo_lm_summary* sum) {
+
+/* ---- the iterative reduced step --------------------------------------------------------------------------------------
+ * What the project's ITERATIVE_SCHUR branch is SPECIFIED to compute (include/pixsfm_hip.h: pxr_lm_options; the header comment of
+ * csrc/pxr_ba_pcg.hip), written on the oracle's dense scaled H, g with plain loops.  [upstream Ceres 2.1
+ * conjugate_gradients_solver.cc: the Q-based termination.]
+ *   A = H + diag / radius;  T_p = A_pp^-1;  S = A_cc - sum_p A_cp T_p A_pc;  b = -(g_c - sum_p A_cp T_p g_p)
+ *   preconditioned conjugate gradients on S x = b from x = 0;  delta_c = x;  delta_p = T_p (-g_p - A_pc delta_c)  (exact for that x)
+ * Preconditioner: the block diagonal of S over the pose columns of every image and the intrinsics columns of every camera (one
+ * joint block where the camera has a single image), keeping of the point terms only those of single observations:
+ *   M_g = A[g, g] - sum_i W_i[g] T_p(i) W_i[g]^T
+ * -- the cross terms W_i T_p W_j^T (i != j two observations of one point in the same block: a shared-intrinsics block) are dropped.
+ * This joint block and the dropped term are the project's specification, not Ceres' SCHUR_JACOBI. */
+typedef struct {
+  int n_c, n_groups;
+  int* col_group;   /* per camera column */
+  int* group_size; int* group_cols; /* [n_groups][PXO_WROWS] */
+} pcg_groups;
+
+static void pcg_build_groups(const ba_ctx* c, pcg_groups* G) {
+  const ba_layout* L = &c->L;
+  int n_c = 0;
+  for (int i = 0; i < c->n_images; ++i) n_c += L->pose_dim[i];
+  for (int j = 0; j < c->n_cams; ++j) n_c += L->intr_dim[j];
+  G->n_c = n_c; G->n_groups = 0;
+  G->col_group = (int*)malloc(sizeof(int) * (n_c > 0 ? n_c : 1));
+  G->group_size = (int*)calloc(c->n_images + c->n_cams + 1, sizeof(int));
+  G->group_cols = (int*)calloc((size_t)(c->n_images + c->n_cams + 1) * PXO_WROWS, sizeof(int));
+  int* users = (int*)calloc(c->n_cams, sizeof(int));
+  for (int i = 0; i < c->n_images; ++i) ++users[c->b->image_camera[i]];
+#define ADD_COLS(first, count) do { for (int a_ = 0; a_ < (count); ++a_) { G->col_group[(first) + a_] = g; G->group_cols[g * PXO_WROWS + G->group_size[g]++] = (first) + a_; } } while (0)
+  for (int i = 0; i < c->n_images; ++i) {
+    const int cam = c->b->image_camera[i];
+    const int joint = users[cam] == 1 && L->intr_dim[cam] > 0;
+    if (L->pose_dim[i] == 0 && !joint) continue;
+    const int g = G->n_groups++;
+    ADD_COLS(L->pose_off[i], L->pose_dim[i]);
+    if (joint) ADD_COLS(L->intr_off[cam], L->intr_dim[cam]);
+  }
+  for (int j = 0; j < c->n_cams; ++j)
+    if (users[j] != 1 && L->intr_dim[j] > 0) { const int g = G->n_groups++; ADD_COLS(L->intr_off[j], L->intr_dim[j]); }
+#undef ADD_COLS
+  free(users);
+}
+static void pcg_free_groups(pcg_groups* G) { free(G->col_group); free(G->group_size); free(G->group_cols); }
+
+/* Cholesky factor (lower, in place) of a symmetric positive definite m x m matrix; 0 on success */
+static int spd_factor(int m, double* A) {
+  for (int j = 0; j < m; ++j) {
+    double d = A[j * m + j];
+    for (int k = 0; k < j; ++k) d -= A[j * m + k] * A[j * m + k];
+    if (!(d > 0.0) || !isfinite(d)) return -1;
+    d = sqrt(d);
+    A[j * m + j] = d;
+    for (int i = j + 1; i < m; ++i) {
+      double v = A[i * m + j];
+      for (int k = 0; k < j; ++k) v -= A[i * m + k] * A[j * m + k];
+      A[i * m + j] = v / d;
+    }
+  }
+  return 0;
+}
+/* b <- (L L^T)^-1 b */
+static void spd_solve(int m, const double* L, double* b) {
+  for (int i = 0; i < m; ++i) {
+    double v = b[i];
+    for (int k = 0; k < i; ++k) v -= L[i * m + k] * b[k];
+    b[i] = v / L[i * m + i];
+  }
+  for (int i = m - 1; i >= 0; --i) {
+    double v = b[i];
+    for (int k = i + 1; k < m; ++k) v -= L[k * m + i] * b[k];
+    b[i] = v / L[i * m + i];
+  }
+}
+/* inverse of a symmetric positive definite m x m matrix (m <= PXO_WROWS) from Cholesky solves of the unit vectors; 0 on success */
+static int spd_inverse(int m, const double* M, double* Minv) {
+  double Lw[PXO_WROWS * PXO_WROWS], e[PXO_WROWS];
+  memcpy(Lw, M, sizeof(double) * m * m);
+  if (spd_factor(m, Lw) != 0) return -1;
+  for (int j = 0; j < m; ++j) {
+    for (int a = 0; a < m; ++a) e[a] = a == j ? 1.0 : 0.0;
+    spd_solve(m, Lw, e);
+    for (int a = 0; a < m; ++a) { if (!isfinite(e[a])) return -1; Minv[a * m + j] = e[a]; }
+  }
+  return 0;
+}
+
+/* everything the iterative step forms before the conjugate gradients, kept for the tests that look at it */
+typedef struct {
+  int n_c;
+  double* S; double* rhs;   /* n_c x n_c, n_c */
+  double* T;                /* [n_points][9], zero for constant points */
+  double* Mblk;             /* [n_groups][PXO_WROWS^2]: the specified block, damped, NOT inverted (row stride = group size) */
+  double* Mfac;             /* its Cholesky factor (lower) */
+  int precond_ok;
+} pcg_system;
+
+static void pcg_system_alloc(const ba_ctx* c, const pcg_groups* G, pcg_system* ps) {
+  const int n_c = G->n_c;
+  ps->n_c = n_c;
+  ps->S = (double*)malloc(sizeof(double) * (size_t)(n_c > 0 ? n_c : 1) * (n_c > 0 ? n_c : 1));
+  ps->rhs = (double*)malloc(sizeof(double) * (n_c > 0 ? n_c : 1));
+  ps->T = (double*)malloc(sizeof(double) * 9 * (c->n_points > 0 ? c->n_points : 1));
+  ps->Mblk = (double*)malloc(sizeof(double) * (size_t)(G->n_groups > 0 ? G->n_groups : 1) * PXO_WROWS * PXO_WROWS);
+  ps->Mfac = (double*)malloc(sizeof(double) * (size_t)(G->n_groups > 0 ? G->n_groups : 1) * PXO_WROWS * PXO_WROWS);
+}
+static void pcg_system_free(pcg_system* ps) { free(ps->S); free(ps->rhs); free(ps->T); free(ps->Mblk); free(ps->Mfac); }
+
+/* A: the damped scaled normal matrix (n x n), g: the scaled gradient.  Returns 0, or -1 if a point block is not positive definite. */
+static int pcg_form_system(const ba_ctx* c, const pcg_groups* G, int n, const double* A, const double* g, const double* scale,
+                           pcg_system* ps) {
+  const int n_c = G->n_c;
+  for (int a = 0; a < n_c; ++a) {
+    ps->rhs[a] = -g[a];
+    for (int bb = 0; bb < n_c; ++bb) ps->S[(size_t)a * n_c + bb] = A[(size_t)a * n + bb];
+  }
+  memset(ps->T, 0, sizeof(double) * 9 * c->n_points);
+  for (int64_t p = 0; p < c->n_points; ++p) {
+    const int po = c->L.pt_off[p];
+    if (po < 0) continue;
+    double V[9], *T = ps->T + 9 * p;
+    for (int a = 0; a < 3; ++a) for (int bb = 0; bb < 3; ++bb) V[a * 3 + bb] = A[(size_t)(po + a) * n + po + bb];
+    if (spd_inverse(3, V, T) != 0) return -1;
+    double Tg[3];
+    for (int a = 0; a < 3; ++a) Tg[a] = T[a * 3] * g[po] + T[a * 3 + 1] * g[po + 1] + T[a * 3 + 2] * g[po + 2];
+    for (int a = 0; a < n_c; ++a) {
+      const double* Ya = A + (size_t)a * n + po;        /* row a of A_cp */
+      if (Ya[0] == 0.0 && Ya[1] == 0.0 && Ya[2] == 0.0) continue;
+      double YT[3];
+      for (int m = 0; m < 3; ++m) YT[m] = Ya[0] * T[m] + Ya[1] * T[3 + m] + Ya[2] * T[6 + m];
+      ps->rhs[a] += Ya[0] * Tg[0] + Ya[1] * Tg[1] + Ya[2] * Tg[2];
+      for (int bb = 0; bb < n_c; ++bb) {
+        const double* Yb = A + (size_t)bb * n + po;
+        ps->S[(size_t)a * n_c + bb] -= YT[0] * Yb[0] + YT[1] * Yb[1] + YT[2] * Yb[2];
+      }
+    }
+  }
+  /* the preconditioner blocks */
+  ps->precond_ok = 1;
+  for (int gi = 0; gi < G->n_groups; ++gi) {
+    const int m = G->group_size[gi];
+    const int* cols = G->group_cols + gi * PXO_WROWS;
+    double* M = ps->Mblk + (size_t)gi * PXO_WROWS * PXO_WROWS;
+    for (int a = 0; a < m; ++a) for (int bb = 0; bb < m; ++bb) M[a * m + bb] = A[(size_t)cols[a] * n + cols[bb]];
+  }
+  for (int64_t i = 0; i < c->b->n_obs; ++i) {
+    const int ncs = c->obs_ncs[i];
+    if (ncs == 0) continue;
+    const int64_t p = c->b->obs_point[i];
+    const int po = c->L.pt_off[p];
+    const double* T = ps->T + 9 * p;
+    const int* idx = c->obs_idx + i * PXO_WROWS;
+    double Ws[PXO_WROWS][3], WT[PXO_WROWS][3];
+    for (int a = 0; a < ncs; ++a) {
+      for (int m = 0; m < 3; ++m) Ws[a][m] = c->obs_W[((size_t)i * PXO_WROWS + a) * 3 + m] * scale[idx[a]] * scale[po + m];
+      for (int m = 0; m < 3; ++m) WT[a][m] = Ws[a][0] * T[m] + Ws[a][1] * T[3 + m] + Ws[a][2] * T[6 + m];
+    }
+    for (int a = 0; a < ncs; ++a)
+      for (int bb = 0; bb < ncs; ++bb) {
+        const int ga = G->col_group[idx[a]];
+        if (ga != G->col_group[idx[bb]]) continue;
+        const int m = G->group_size[ga];
+        const int* cols = G->group_cols + ga * PXO_WROWS;
+        int ra = -1, rb = -1;
+        for (int k = 0; k < m; ++k) { if (cols[k] == idx[a]) ra = k; if (cols[k] == idx[bb]) rb = k; }
+        ps->Mblk[(size_t)ga * PXO_WROWS * PXO_WROWS + ra * m + rb] -= WT[a][0] * Ws[bb][0] + WT[a][1] * Ws[bb][1] + WT[a][2] * Ws[bb][2];
+      }
+  }
+  for (int gi = 0; gi < G->n_groups; ++gi) {
+    const int m = G->group_size[gi];
+    double* L = ps->Mfac + (size_t)gi * PXO_WROWS * PXO_WROWS;
+    memcpy(L, ps->Mblk + (size_t)gi * PXO_WROWS * PXO_WROWS, sizeof(double) * m * m);
+    if (spd_factor(m, L) != 0) ps->precond_ok = 0;
+  }
+  return 0;
+}
+
+/* preconditioned conjugate gradients on S x = rhs; returns the number of counted iterations, fills the trace fields of `te` */
+static int pcg_run(const pcg_groups* G, const pcg_system* ps, const pxo_linear_options* lin, double* x, pxo_lm_trace_entry* te) {
+  const int n = ps->n_c;
+  const int max_it = lin->max_linear_solver_iterations > 0 ? lin->max_linear_solver_iterations : 200;
+  double* r = (double*)malloc(sizeof(double) * 4 * (n > 0 ? n : 1));
+  double *z = r + n, *pv = z + n, *q = pv + n;
+  double bb = 0;
+  for (int a = 0; a < n; ++a) { x[a] = 0.0; r[a] = ps->rhs[a]; bb += ps->rhs[a] * ps->rhs[a]; }
+  const double norm_b = sqrt(bb);
+  int iters = 0, stop = PXO_CG_STOP_MAX_ITERATIONS;
+  double Q0 = 0.0, rho_prev = 0.0, m_last = -1.0, m_prev = -1.0, m_min = -1.0;
+  if (!ps->precond_ok) stop = PXO_CG_STOP_PRECONDITIONER;
+  else if (!isfinite(norm_b)) stop = PXO_CG_STOP_RHO;
+  else if (norm_b == 0.0) stop = PXO_CG_STOP_ZERO_RHS;
+  else
+    for (int it = 1; it <= max_it; ++it) {
+      double rho = 0;
+      for (int gi = 0; gi < G->n_groups; ++gi) {            /* z = M^-1 r, block by block */
+        const int m = G->group_size[gi];
+        const int* cols = G->group_cols + gi * PXO_WROWS;
+        double v[PXO_WROWS];
+        for (int k = 0; k < m; ++k) v[k] = r[cols[k]];
+        spd_solve(m, ps->Mfac + (size_t)gi * PXO_WROWS * PXO_WROWS, v);
+        for (int k = 0; k < m; ++k) { z[cols[k]] = v[k]; rho += r[cols[k]] * v[k]; }
+      }
+      if (rho == 0.0 || !isfinite(rho)) { stop = PXO_CG_STOP_RHO; break; }           /* the iteration is not counted */
+      const double beta = it == 1 ? 0.0 : rho / rho_prev;
+      for (int a = 0; a < n; ++a) pv[a] = it == 1 ? z[a] : z[a] + beta * pv[a];
+      double pq = 0;
+      for (int a = 0; a < n; ++a) {
+        double v = 0;
+        for (int k = 0; k < n; ++k) v += ps->S[(size_t)a * n + k] * pv[k];
+        q[a] = v; pq += pv[a] * v;
+      }
+      if (!(pq > 0.0) || !isfinite(pq)) { stop = PXO_CG_STOP_INDEFINITE; break; }    /* the last x is kept */
+      const double alpha = rho / pq;
+      double xb = 0, xr = 0, rr = 0;
+      for (int a = 0; a < n; ++a) {
+        x[a] += alpha * pv[a]; r[a] -= alpha * q[a];
+        xb += x[a] * ps->rhs[a]; xr += x[a] * r[a]; rr += r[a] * r[a];
+      }
+      iters = it; rho_prev = rho;
+      const double Q1 = -0.5 * (xb + xr);
+      const double zeta = it * (Q1 - Q0) / Q1;
+      m_prev = m_last;
+      m_last = lin->eta > 0.0 ? fabs(zeta - lin->eta) / lin->eta : -1.0;
+      if (m_last >= 0.0 && (m_min < 0.0 || m_last < m_min)) m_min = m_last;
+      if (zeta < lin->eta) { stop = PXO_CG_STOP_Q; break; }
+      Q0 = Q1;
+      if (lin->r_tolerance > 0.0 && sqrt(rr) <= lin->r_tolerance * norm_b) { stop = PXO_CG_STOP_R_TOLERANCE; break; }
+    }
+  if (te) { te->cg_iterations = iters; te->cg_stop = stop; te->margin_last = m_last; te->margin_prev = m_prev; te->margin_min = m_min; }
+  free(r);
+  return iters;
+}
+
+/* the iterative linear step of an LM iteration: step (scaled space, n) or 0 = invalid */
+static int linear_step_iterative(const ba_ctx* c, const pcg_groups* G, pcg_system* ps, int n, const double* A, const double* g,
+                                 const double* scale, const pxo_linear_options* lin, double* step, pxo_lm_trace_entry* te) {
+  const int n_c = G->n_c;
+  pxo_lm_trace_entry local;
+  if (!te) te = &local;
+  te->cg_iterations = 0; te->cg_stop = PXO_CG_STOP_PRECONDITIONER; te->margin_last = te->margin_prev = te->margin_min = -1.0;
+  if (pcg_form_system(c, G, n, A, g, scale, ps) != 0) return 0;
+  const int iters = pcg_run(G, ps, lin, step, te);
+  if (n_c > 0 && iters == 0 && te->cg_stop != PXO_CG_STOP_ZERO_RHS) return 0;   /* a solve that counted no iteration is an invalid step */
+  for (int64_t p = 0; p < c->n_points; ++p) {              /* back-substitution, exact for this x */
+    const int po = c->L.pt_off[p];
+    if (po < 0) continue;
+    const double* T = ps->T + 9 * p;
+    double v[3];
+    for (int m = 0; m < 3; ++m) {
+      double acc = -g[po + m];
+      for (int a = 0; a < n_c; ++a) acc -= A[(size_t)(po + m) * n + a] * step[a];
+      v[m] = acc;
+    }
+    for (int m = 0; m < 3; ++m) step[po + m] = T[m * 3] * v[0] + T[m * 3 + 1] * v[1] + T[m * 3 + 2] * v[2];
+  }
+  return 1;
+}
+
+/* the LM loop of both entry points; lin == NULL: the dense Cholesky step, else the iterative reduced step */
+static int ba_lm_run(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
+                     const pxo_interp_cfg* cfg, const pxo_loss* loss, const uint8_t* pose_const,
+                     const uint8_t* tvec_const_mask, const uint16_t* cam_const_mask,
+                     const uint8_t* point_const, const pxo_lm_options* opt, const pxo_linear_options* lin,
+                     pxo_lm_summary* sum, pxo_lm_trace* trace) {
   ba_ctx c;
   memset(&c, 0, sizeof(c));
   c.b = b; c.cfg = cfg; c.loss = loss; c.pose_const = pose_const; c.tvec_const_mask = tvec_const_mask;
@@ -410,6 +688,15 @@ int pxo_ba_solve(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
   c.n_images = n_images; c.n_cams = n_cams; c.n_points = n_points;
   ba_build_layout(&c);
   const int n = c.L.n;
+  pcg_groups G; pcg_system ps;
+  if (lin) {
+    c.obs_W = (double*)malloc(sizeof(double) * PXO_WROWS * 3 * (size_t)(b->n_obs > 0 ? b->n_obs : 1));
+    c.obs_idx = (int*)malloc(sizeof(int) * PXO_WROWS * (size_t)(b->n_obs > 0 ? b->n_obs : 1));
+    c.obs_ncs = (int*)calloc(b->n_obs > 0 ? b->n_obs : 1, sizeof(int));
+    pcg_build_groups(&c, &G);
+    pcg_system_alloc(&c, &G, &ps);
+  }
+  if (trace) trace->count = 0;
   double* q = (double*)b->qvec; double* t = (double*)b->tvec;
   double* k = (double*)b->cam_params; double* X = (double*)b->xyz;
   /* AddImageToProblem normalises the quaternions (bundle_optimizer.h:255) */
@@ -458,10 +745,22 @@ int pxo_ba_solve(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
       }
     memcpy(A, H, sizeof(double) * (size_t)n * n);
     for (int j = 0; j < n; ++j) { A[(size_t)j * n + j] += diag[j] / radius; step[j] = -g[j]; }
-    int ok = chol_solve(n, A, step) == 0;
+    pxo_lm_trace_entry te;
+    memset(&te, 0, sizeof(te));
+    te.margin_last = te.margin_prev = te.margin_min = -1.0;
+    int ok = lin ? linear_step_iterative(&c, &G, &ps, n, A, g, scale, lin, step, &te) : chol_solve(n, A, step) == 0;
+#define TRACE(valid, successful, rel_)                                                           \
+  do {                                                                                           \
+    if (trace && trace->count < trace->capacity) {                                               \
+      te.step_is_valid = (valid); te.step_is_successful = (successful);                          \
+      te.relative_decrease = (rel_); te.radius = radius;                                         \
+      trace->entries[trace->count] = te;                                                         \
+    }                                                                                            \
+    if (trace) ++trace->count;                                                                   \
+  } while (0)
     double model_cost_change = 0;
     if (ok) {
-      /* -(J d).(r + J d/2) = -d.g - 0.5 d.H.d */
+      /* -(J d).(r + J d/2) = -d.g - 0.5 d.H.d with the FULL step (exact or not: no use of the linear solver's residual) */
       double dg = 0, dHd = 0;
       for (int a = 0; a < n; ++a) {
         dg += step[a] * g[a];
@@ -476,6 +775,7 @@ int pxo_ba_solve(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
     if (!ok) { /* HandleInvalidStep */
       if (++invalid >= opt->max_consecutive_invalid_steps) { sum->termination = PXO_TERM_FAILURE; break; }
       radius *= 0.5; reuse_diag = 1;   /* StepIsInvalid */
+      TRACE(0, 0, 0.0);
       continue;
     }
     invalid = 0;
@@ -513,16 +813,99 @@ int pxo_ba_solve(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
       radius = radius / f;
       if (radius > opt->max_radius) radius = opt->max_radius;
       decrease_factor = 2.0; reuse_diag = 0;
+      TRACE(1, 1, rel);
       if (gmax <= opt->gradient_tolerance) { sum->termination = PXO_TERM_CONVERGENCE; break; }
     } else { /* StepRejected */
       radius = radius / decrease_factor; decrease_factor *= 2.0; reuse_diag = 1;
+      TRACE(1, 0, rel);
     }
   }
+#undef TRACE
   sum->final_cost = cost; sum->final_radius = radius;
   free(H); free(A); free(g); free(scale); free(step); free(delta); free(diag);
   free(q1); free(t1); free(k1); free(X1);
   free(c.L.pose_off); free(c.L.pose_dim); free(c.L.intr_off); free(c.L.intr_dim); free(c.L.pt_off);
+  if (lin) { free(c.obs_W); free(c.obs_idx); free(c.obs_ncs); pcg_free_groups(&G); pcg_system_free(&ps); }
   return 0;
+}
+
+int pxo_ba_solve(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
+                 const pxo_interp_cfg* cfg, const pxo_loss* loss, const uint8_t* pose_const,
+                 const uint8_t* tvec_const_mask, const uint16_t* cam_const_mask,
+                 const uint8_t* point_const, const pxo_lm_options* opt, pxo_lm_summary* sum) {
+  return ba_lm_run(b, n_images, n_cams, n_points, cfg, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, opt, NULL, sum, NULL);
+}
+
+int pxo_ba_solve_iterative(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
+                           const pxo_interp_cfg* cfg, const pxo_loss* loss, const uint8_t* pose_const,
+                           const uint8_t* tvec_const_mask, const uint16_t* cam_const_mask,
+                           const uint8_t* point_const, const pxo_lm_options* opt, const pxo_linear_options* lin,
+                           pxo_lm_summary* sum, pxo_lm_trace* trace) {
+  if (!lin) return -1;
+  return ba_lm_run(b, n_images, n_cams, n_points, cfg, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, opt, lin, sum, trace);
+}
+
+/* The reduced system of the FIRST LM iteration at the batch's parameters (nothing is updated), for the tests of the step itself:
+ * S and M_spec are n_c x n_c row-major (M_spec: the specified preconditioner blocks, damped, not inverted, zero outside them),
+ * rhs and x have n_c entries (x: the conjugate-gradient iterate the options stop at), col_group the block of every column.
+ * The caller sizes the outputs for 6 n_images + 12 n_cams columns.  Returns n_c, or -1. */
+int pxo_ba_reduced_system(pxo_ba_batch* b, int n_images, int n_cams, int64_t n_points,
+                          const pxo_interp_cfg* cfg, const pxo_loss* loss, const uint8_t* pose_const,
+                          const uint8_t* tvec_const_mask, const uint16_t* cam_const_mask,
+                          const uint8_t* point_const, const pxo_lm_options* opt, const pxo_linear_options* lin,
+                          double* S_out, double* rhs_out, double* M_out, double* x_out, int32_t* col_group_out,
+                          int32_t* cg_iterations) {
+  ba_ctx c;
+  memset(&c, 0, sizeof(c));
+  c.b = b; c.cfg = cfg; c.loss = loss; c.pose_const = pose_const; c.tvec_const_mask = tvec_const_mask;
+  c.cam_const_mask = cam_const_mask; c.point_const = point_const;
+  c.n_images = n_images; c.n_cams = n_cams; c.n_points = n_points;
+  ba_build_layout(&c);
+  const int n = c.L.n;
+  pcg_groups G; pcg_system ps;
+  const size_t no = (size_t)(b->n_obs > 0 ? b->n_obs : 1);
+  c.obs_W = (double*)malloc(sizeof(double) * PXO_WROWS * 3 * no);
+  c.obs_idx = (int*)malloc(sizeof(int) * PXO_WROWS * no);
+  c.obs_ncs = (int*)calloc(no, sizeof(int));
+  pcg_build_groups(&c, &G);
+  pcg_system_alloc(&c, &G, &ps);
+  double* H = (double*)malloc(sizeof(double) * (size_t)n * n);
+  double* g = (double*)malloc(sizeof(double) * n);
+  double* scale = (double*)malloc(sizeof(double) * n);
+  double* step = (double*)malloc(sizeof(double) * n);
+  /* (the quaternions are taken as they are: the callers hand in unit quaternions) */
+  ba_evaluate(&c, (const double*)b->qvec, (const double*)b->tvec, (const double*)b->cam_params, (const double*)b->xyz, H, g);
+  for (int j = 0; j < n; ++j) scale[j] = opt->jacobi_scaling ? 1.0 / (1.0 + sqrt(H[(size_t)j * n + j])) : 1.0;
+  for (int a = 0; a < n; ++a) {
+    g[a] *= scale[a];
+    for (int bb = 0; bb < n; ++bb) H[(size_t)a * n + bb] *= scale[a] * scale[bb];
+  }
+  for (int j = 0; j < n; ++j) {
+    const double d = H[(size_t)j * n + j];
+    H[(size_t)j * n + j] += (d < opt->min_lm_diagonal ? opt->min_lm_diagonal : (d > opt->max_lm_diagonal ? opt->max_lm_diagonal : d)) / opt->initial_radius;
+  }
+  const int n_c = G.n_c;
+  int rc = n_c;
+  if (pcg_form_system(&c, &G, n, H, g, scale, &ps) != 0) rc = -1;
+  else {
+    pxo_lm_trace_entry te;
+    *cg_iterations = pcg_run(&G, &ps, lin, step, &te);
+    memcpy(S_out, ps.S, sizeof(double) * (size_t)n_c * n_c);
+    memcpy(rhs_out, ps.rhs, sizeof(double) * n_c);
+    memcpy(x_out, step, sizeof(double) * n_c);
+    memset(M_out, 0, sizeof(double) * (size_t)n_c * n_c);
+    for (int a = 0; a < n_c; ++a) col_group_out[a] = G.col_group[a];
+    for (int gi = 0; gi < G.n_groups; ++gi) {
+      const int m = G.group_size[gi];
+      const int* cols = G.group_cols + gi * PXO_WROWS;
+      for (int a = 0; a < m; ++a)
+        for (int bb = 0; bb < m; ++bb) M_out[(size_t)cols[a] * n_c + cols[bb]] = ps.Mblk[(size_t)gi * PXO_WROWS * PXO_WROWS + a * m + bb];
+    }
+  }
+  free(H); free(g); free(scale); free(step);
+  free(c.obs_W); free(c.obs_idx); free(c.obs_ncs); pcg_free_groups(&G); pcg_system_free(&ps);
+  free(c.L.pose_off); free(c.L.pose_dim); free(c.L.intr_off); free(c.L.intr_dim); free(c.L.pt_off);
+  return rc;
 }
 
 /* ======================================================================================

@@ -155,6 +155,23 @@ def make_model_case(models, n_cams=6, n_points=90, obs_per_point=4, seed=0, keyp
     return out
 
 
+def make_decoupled_case(models, nv, points_per_image=30, seed=0, keypoint_noise=0.7, ramp=False, channels=2, patch_size=PATCH_SIZE):
+    """A scene whose reduced camera system is BLOCK DIAGONAL once images 0, 1, 2 are constant: 3 + nv images with one camera each
+    (`models`: one id, or one per camera), nv * points_per_image points, point p observed in images 0, 1, 2 and in image
+    3 + p % nv only -- no point is seen by two of the images 3 ... (make_model_case with every point in every image, filtered)."""
+    n_cams = 3 + nv
+    full = make_model_case(models, n_cams=n_cams, n_points=nv * points_per_image, obs_per_point=n_cams, seed=seed,
+                           keypoint_noise=keypoint_noise, ramp=False)
+    img, pt = np.asarray(full["obs_image"]), np.asarray(full["obs_point"])
+    keep = (img < 3) | (img == 3 + pt % nv)
+    out = dict(full)
+    for key in ("obs_image", "obs_point", "obs_xy"):
+        out[key] = np.ascontiguousarray(np.asarray(full[key])[keep])
+    assert len(out["obs_image"]) == 4 * nv * points_per_image
+    assert_inside(out, what="initial parameters")
+    return as_ramp_problem(out, out["obs_xy"], patch_size, channels) if ramp else out
+
+
 def geometric_dict(prob):
     """What engine.GeometricBAProblem takes."""
     return {k: prob[k] for k in ("obs_image", "obs_point", "obs_xy", "image_camera", "qvec", "tvec", "cam_model", "cam_params", "xyz")}

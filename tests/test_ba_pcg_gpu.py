@@ -2,7 +2,11 @@
 SCHUR_JACOBI, bundle_adjustment/src/bundle_optimizer.h:180-191).  Ceres itself cannot be run here, so the checks are
 (a) against the direct solver (exact Schur complement + dense Cholesky, itself tested against the oracle) on problems
 where both fit -- with the conjugate gradients driven to a tight residual the two must take the same LM steps -- and
-(b) the behaviour of the reference's default inexact configuration (eta = 0.1, at most 200 linear iterations)."""
+(b) the behaviour of the reference's default inexact configuration (eta = 0.1, at most 200 linear iterations).
+Tight conjugate gradients reach the same x with any positive definite preconditioner, never stop on the Q test and have no
+residual left, so (c) the preconditioner -- one iteration is exact where S is block diagonal -- and (d) the inexact steps -- counts,
+decisions, relative decrease and radius per iteration against the oracle's iterative step (oracle/pxo_solve.c, pinned in
+tests/test_oracle_pcg.py) -- are checked in tests/test_ba_pcg_precond_gpu.py."""
 import numpy as np
 import pytest
 
