@@ -7,7 +7,8 @@
 // the query's own correspondences alone, bit for bit, alone or inside any batch.
 //
 //   k_abs_bearings   one lane per correspondence: its query (binary search of the offsets), undistort -> record (u, v, X, Y, Z), usable
-//   k_abs_compact    one lane per query: the usable records of a query moved to the front of its slice (in order), positions kept
+//   k_compact_records<5>  (pxr_robust.h) one lane per query: the usable records of a query moved to the front of its slice (in
+//                    order), positions kept
 //   k_abs_hypotheses the estimator's samples: one workgroup of 256 lanes per query, the first ABS_LDS_CORR records staged in LDS;
 //                    a round of samples per wavefront, a sample per lane, every lane scoring its own poses against all records
 //   k_abs_refine     the winner's local optimisation and the final classification, the same mapping of queries to workgroups
@@ -22,8 +23,10 @@
 #include <cmath>
 #include <vector>
 
+#include "pxr_batch.h"
 #include "pxr_device.h"
 #include "pxr_internal.h"
+#include "pxr_robust.h"
 #include "pxr_undistort.h"
 
 namespace pxr {
@@ -35,38 +38,9 @@ constexpr int ABS_LDS_CORR = PXR_ABSPOSE_LDS_CORR;     // records of a query sta
 constexpr int ABS_ACC = 28;                            // the refinement's sums: H (21, upper triangle by rows), g (6), cost
 constexpr int ABS_CHUNK = 7;                           // of which this many cross the workgroup at a time (ABS_THREADS x ABS_CHUNK doubles of LDS)
 constexpr int ABS_NEWTON = 3;                          // Newton steps on every quartic root
-constexpr int ABS_MAX_DRAWS = 256;                     // draws of one sample before the smallest unused indices complete it
 constexpr double ABS_STEP_TOL = 1e-12;                 // the refinement stops at a step of this norm
 constexpr double ABS_COST_SLACK = 1e-12;               // a step is kept unless the cost grows by more than this fraction: below it the
                                                        // comparison is rounding noise, and refusing would stall short of the minimum
-
-__device__ __forceinline__ double abs_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ double abs_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
-
-// ---- samples: splitmix64's output function [Steele, Lea, Flood, "Fast splittable pseudorandom number generators", 2014] ---------
-__device__ __forceinline__ uint64_t abs_mix(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-// sample h of a query with n >= 4 usable correspondences: three distinct indices, ascending.  draw d = mix(mix(seed + G (h + 1)) +
-// G (d + 1)) mod n; a repeated index is drawn again
-__device__ __forceinline__ void abs_sample(uint64_t seed, int64_t h, int n, int& i0, int& i1, int& i2) {
-  const uint64_t G = 0x9E3779B97F4A7C15ull;
-  const uint64_t a = abs_mix(seed + G * (uint64_t)(h + 1));
-  int draw = 0;
-  auto next = [&]() { ++draw; return (int)(abs_mix(a + G * (uint64_t)draw) % (uint64_t)n); };
-  const int c0 = next();
-  int c1 = next();
-  while (c1 == c0 && draw < ABS_MAX_DRAWS) c1 = next();
-  if (c1 == c0) c1 = c0 == 0 ? 1 : 0;                   // (never in practice: the smallest unused index)
-  int c2 = next();
-  while ((c2 == c0 || c2 == c1) && draw < ABS_MAX_DRAWS) c2 = next();
-  if (c2 == c0 || c2 == c1) c2 = (c0 != 0 && c1 != 0) ? 0 : (c0 != 1 && c1 != 1) ? 1 : 2;
-  const int lo = min(c0, min(c1, c2)), hi = max(c0, max(c1, c2));
-  i0 = lo; i1 = c0 + c1 + c2 - lo - hi; i2 = hi;
-}
 
 // ---- P3P -------------------------------------------------------------------------------------------------------------------------
 struct P3P {
@@ -79,11 +53,6 @@ __device__ __forceinline__ void abs_bearing(const double* r, double f[3]) {
   const double inv = 1.0 / sqrt(r[0] * r[0] + r[1] * r[1] + 1.0);
   f[0] = r[0] * inv; f[1] = r[1] * inv; f[2] = inv;
 }
-__device__ __forceinline__ void abs_cross(const double* a, const double* b, double c[3]) {
-  c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ double abs_dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
 __device__ __forceinline__ double abs_polish(double v, double B, double C, double D, double E) {
 #pragma unroll
   for (int it = 0; it < ABS_NEWTON; ++it) {
@@ -99,16 +68,16 @@ __device__ __forceinline__ bool p3p_setup(const double* r1, const double* r2, co
   double e1[3], e2[3], e3[3], cr[3];
 #pragma unroll
   for (int m = 0; m < 3; ++m) { s.P1[m] = r1[2 + m]; e1[m] = r2[2 + m] - r1[2 + m]; e2[m] = r3[2 + m] - r1[2 + m]; e3[m] = r3[2 + m] - r2[2 + m]; }
-  const double c2 = abs_dot(e1, e1), b2 = abs_dot(e2, e2), a2 = abs_dot(e3, e3);
-  abs_cross(e1, e2, cr);
-  const double cr2 = abs_dot(cr, cr);
-  s.v0 = s.v1 = s.v2 = s.v3 = abs_nan();
+  const double c2 = dot3(e1, e1), b2 = dot3(e2, e2), a2 = dot3(e3, e3);
+  cross3(e1, e2, cr);
+  const double cr2 = dot3(cr, cr);
+  s.v0 = s.v1 = s.v2 = s.v3 = quiet_nan();
   if (!(cr2 > 1e-12 * c2 * b2) || !isfinite(cr2)) return false;
   const double ic = 1.0 / sqrt(c2), icr = 1.0 / sqrt(cr2);
 #pragma unroll
   for (int m = 0; m < 3; ++m) { s.w1[m] = e1[m] * ic; s.w3[m] = cr[m] * icr; }
-  abs_cross(s.w3, s.w1, s.w2);
-  const double ca = abs_dot(s.f2, s.f3), cb = abs_dot(s.f1, s.f3), cg = abs_dot(s.f1, s.f2);
+  cross3(s.w3, s.w1, s.w2);
+  const double ca = dot3(s.f2, s.f3), cb = dot3(s.f1, s.f3), cg = dot3(s.f1, s.f2);
   const double k1 = (a2 - c2) / b2, k2 = c2 / b2;
   const double N0 = k1 + 1.0, N1 = -2.0 * k1 * cb, N2 = k1 - 1.0, D0 = 2.0 * cg, D1 = -2.0 * ca;
   const double M0 = 1.0 - k2, M1 = 2.0 * k2 * cb, M2 = -k2;
@@ -167,12 +136,12 @@ __device__ __forceinline__ bool p3p_pose(const P3P& s, double v, double R[9], do
   double Q1[3], g1[3], g2[3], cr[3], c1[3], c2[3], c3[3];
 #pragma unroll
   for (int m = 0; m < 3; ++m) { Q1[m] = s1 * s.f1[m]; g1[m] = s2 * s.f2[m] - Q1[m]; g2[m] = s3 * s.f3[m] - Q1[m]; }
-  abs_cross(g1, g2, cr);
-  const double n1 = sqrt(abs_dot(g1, g1)), n3 = sqrt(abs_dot(cr, cr));
+  cross3(g1, g2, cr);
+  const double n1 = sqrt(dot3(g1, g1)), n3 = sqrt(dot3(cr, cr));
   if (!(n1 > 0.0) || !(n3 > 0.0)) return false;
 #pragma unroll
   for (int m = 0; m < 3; ++m) { c1[m] = g1[m] / n1; c3[m] = cr[m] / n3; }
-  abs_cross(c3, c1, c2);
+  cross3(c3, c1, c2);
   bool ok = true;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -185,27 +154,6 @@ __device__ __forceinline__ bool p3p_pose(const P3P& s, double v, double R[9], do
 }
 
 __device__ __forceinline__ double p3p_root(const P3P& s, int root) { return root == 0 ? s.v0 : root == 1 ? s.v1 : root == 2 ? s.v2 : s.v3; }
-
-// unit quaternion (w first) of a rotation matrix, by the largest of the four pivots
-__device__ __forceinline__ void abs_rotation_to_quat(const double* R, double q[4]) {
-  const double tr = R[0] + R[4] + R[8];
-  if (tr > 0.0) {
-    const double s = 2.0 * sqrt(tr + 1.0);
-    q[0] = 0.25 * s; q[1] = (R[7] - R[5]) / s; q[2] = (R[2] - R[6]) / s; q[3] = (R[3] - R[1]) / s;
-  } else if (R[0] > R[4] && R[0] > R[8]) {
-    const double s = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
-    q[0] = (R[7] - R[5]) / s; q[1] = 0.25 * s; q[2] = (R[1] + R[3]) / s; q[3] = (R[2] + R[6]) / s;
-  } else if (R[4] > R[8]) {
-    const double s = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
-    q[0] = (R[2] - R[6]) / s; q[1] = (R[1] + R[3]) / s; q[2] = 0.25 * s; q[3] = (R[5] + R[7]) / s;
-  } else {
-    const double s = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
-    q[0] = (R[3] - R[1]) / s; q[1] = (R[2] + R[6]) / s; q[2] = (R[5] + R[7]) / s; q[3] = 0.25 * s;
-  }
-  const double inv = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) q[j] *= inv;
-}
 
 // ---- kernel A: records -----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(ABS_THREADS) void k_abs_bearings(int64_t n_corr, int32_t n_queries, const int64_t* __restrict__ offsets,
@@ -232,28 +180,7 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_bearings(int64_t n_corr, in
   r[0] = u; r[1] = v; r[2] = X; r[3] = Y; r[4] = Z;
   valid[i] = ok ? 1 : 0;
   inlier[i] = 0;                                       // what a correspondence keeps unless its query gets a pose
-  err[i] = abs_nan();
-}
-
-// The usable records of every query moved to the front of the query's slice, order kept; pos[o0 + j] = where the j-th came from.
-__global__ __launch_bounds__(ABS_THREADS) void k_abs_compact(int32_t n_queries, const int64_t* __restrict__ offsets, double* __restrict__ rec,
-                                                             const uint8_t* __restrict__ valid, int32_t* __restrict__ pos,
-                                                             int32_t* __restrict__ n_valid) {
-  const int64_t q = (int64_t)blockIdx.x * ABS_THREADS + threadIdx.x;
-  if (q >= n_queries) return;
-  const int64_t o0 = offsets[q];
-  const int64_t n = offsets[q + 1] - o0;
-  int32_t nv = 0;
-  for (int64_t j = 0; j < n; ++j) {
-    if (!valid[o0 + j]) continue;
-    if (nv != j) {
-#pragma unroll
-      for (int m = 0; m < ABS_REC; ++m) rec[(size_t)(o0 + nv) * ABS_REC + m] = rec[(size_t)(o0 + j) * ABS_REC + m];
-    }
-    pos[o0 + nv] = (int32_t)j;
-    ++nv;
-  }
-  n_valid[q] = nv;
+  err[i] = quiet_nan();
 }
 
 // ---- kernel B: the estimator -------------------------------------------------------------------------------------------------------
@@ -270,51 +197,11 @@ struct AbsArgs {
   double* qvec; double* tvec; int32_t* status; int32_t* n_inliers; int32_t* n_trials; uint8_t* inlier; double* err;
 };
 
-struct AbsKey {                // larger count, then smaller sum, then smaller sample, then smaller root
-  int cnt; double sum; int h; int root;
-  __device__ __forceinline__ bool beats(const AbsKey& o) const {
-    return cnt > o.cnt || (cnt == o.cnt && (sum < o.sum || (sum == o.sum && (h < o.h || (h == o.h && root < o.root)))));
-  }
-};
-
 struct AbsQuery {              // what every lane of the workgroup knows about its query
   const double* sh; const double* g; int n; int64_t o0;
   int model; double k[PXR_KPAD];
   __device__ __forceinline__ const double* rec(int j) const { return j < ABS_LDS_CORR ? sh + j * ABS_REC : g + (size_t)j * ABS_REC; }
 };
-
-// trials the stop rule asks for at `cnt` inliers among n
-__device__ __forceinline__ double abs_trials_needed(const pxr_abspose_options& o, int max_trials, int cnt, int n) {
-  double need = (double)max_trials;
-  if (cnt > 0) {
-    const double w = (double)cnt / (double)n;
-    const double x = log(1.0 - o.confidence) / log(1.0 - w * w * w);      // w = 1: -inf below, x = +0
-    if (x < need) need = x;
-  }
-  if (need < (double)o.min_num_trials) need = (double)o.min_num_trials;
-  if (need > (double)max_trials) need = (double)max_trials;
-  return need;
-}
-
-// sums over the workgroup in a fixed order: lane t's addends to sh_part[t], column c summed over t = 0 .. 255 by lane c
-template <int N>
-__device__ __forceinline__ void abs_block_sum(double (&v)[N], double* sh_part, double* sh_tot) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int c0 = 0; c0 < N; c0 += ABS_CHUNK) {
-#pragma unroll
-    for (int c = 0; c < ABS_CHUNK; ++c) if (c0 + c < N) sh_part[tid * ABS_CHUNK + c] = v[c0 + c];
-    __syncthreads();
-    if (tid < ABS_CHUNK && c0 + tid < N) {
-      double s = 0.0;
-      for (int t = 0; t < ABS_THREADS; ++t) s += sh_part[t * ABS_CHUNK + tid];
-      sh_tot[c0 + tid] = s;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int c = 0; c < N; ++c) v[c] = sh_tot[c];
-}
 
 // pixel error of compacted record j under (q, t): NaN behind the camera or where the model fails
 __device__ __forceinline__ double abs_pixel_err(const AbsArgs& a, const AbsQuery& Q, int j, const double* q, const double* t) {
@@ -322,8 +209,8 @@ __device__ __forceinline__ double abs_pixel_err(const AbsArgs& a, const AbsQuery
   const double X[3] = {r[2], r[3], r[4]};
   double p[3], x, y;
   rotate_translate(q, t, X, p);
-  if (!(p[2] > 0.0)) return abs_nan();
-  if (!world_to_image(Q.model, Q.k, p[0] / p[2], p[1] / p[2], x, y)) return abs_nan();
+  if (!(p[2] > 0.0)) return quiet_nan();
+  if (!world_to_image(Q.model, Q.k, p[0] / p[2], p[1] / p[2], x, y)) return quiet_nan();
   const int64_t i = Q.o0 + a.pos[Q.o0 + j];
   const double ex = x - a.xy[2 * i], ey = y - a.xy[2 * i + 1];
   return sqrt(ex * ex + ey * ey);
@@ -347,7 +234,7 @@ __device__ __forceinline__ void abs_normal_equations(const AbsArgs& a, const Abs
     double x, y, Juv[2][2];
     const double iz = 1.0 / p[2];
     if (!(p[2] > 0.0) || !camera_model_jac<false, true>(Q.model, Q.k, p[0] * iz, p[1] * iz, x, y, Juv, nullptr)) {
-      acc[27] = abs_inf();
+      acc[27] = pos_inf();
       continue;
     }
     const int64_t i = Q.o0 + a.pos[Q.o0 + j];
@@ -372,73 +259,12 @@ __device__ __forceinline__ void abs_normal_equations(const AbsArgs& a, const Abs
     }
     acc[27] += rho[0];
   }
-  abs_block_sum(acc, sh_part, sh_tot);
-}
-
-// (H + lambda diag(H)) d = -g by Cholesky; false: not positive definite
-__device__ __forceinline__ bool abs_solve6(const double (&acc)[ABS_ACC], double lambda, double d[6]) {
-  double L[6][6];
-  {
-    int c = 0;
-#pragma unroll
-    for (int m = 0; m < 6; ++m)
-#pragma unroll
-      for (int l = m; l < 6; ++l) { L[l][m] = acc[c]; ++c; }
-  }
-#pragma unroll
-  for (int m = 0; m < 6; ++m) L[m][m] += lambda * L[m][m];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double s = L[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-    ok = ok && s > 0.0;
-    const double piv = sqrt(s);
-    L[j][j] = piv;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double v = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-      L[i][j] = v / piv;
-    }
-  }
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double v = -acc[21 + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-    y[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double v = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) v -= L[k][i] * d[k];
-    d[i] = v / L[i][i];
-    ok = ok && isfinite(d[i]);
-  }
-  return ok;
+  block_sum<ABS_THREADS, ABS_CHUNK>(acc, sh_part, sh_tot);
 }
 
 // x (+) d as the bundle adjustment moves a pose: QuaternionManifold::Plus [upstream Ceres manifold.cc] on q, t + d; q re-normalised
 __device__ __forceinline__ void abs_pose_plus(const double* q0, const double* t0, const double* d, double q1[4], double t1[3]) {
-  const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) q1[j] = q0[j];
-  if (nd != 0.0) {
-    const double sn = sin(nd) / nd;
-    const double qd[4] = {cos(nd), sn * d[0], sn * d[1], sn * d[2]};
-    q1[0] = qd[0] * q0[0] - qd[1] * q0[1] - qd[2] * q0[2] - qd[3] * q0[3];
-    q1[1] = qd[0] * q0[1] + qd[1] * q0[0] + qd[2] * q0[3] - qd[3] * q0[2];
-    q1[2] = qd[0] * q0[2] - qd[1] * q0[3] + qd[2] * q0[0] + qd[3] * q0[1];
-    q1[3] = qd[0] * q0[3] + qd[1] * q0[2] - qd[2] * q0[1] + qd[3] * q0[0];
-  }
-  const double inv = 1.0 / sqrt(q1[0] * q1[0] + q1[1] * q1[1] + q1[2] * q1[2] + q1[3] * q1[3]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) q1[j] *= inv;
+  quat_plus(q0, d, q1);
 #pragma unroll
   for (int j = 0; j < 3; ++j) t1[j] = t0[j] + d[3 + j];
 }
@@ -454,7 +280,7 @@ __device__ __forceinline__ void abs_refine(const AbsArgs& a, const AbsQuery& Q, 
   double lambda = 1e-4;
   for (int it = 0; it < a.o.refine_max_iterations; ++it) {
     double d[6], q1[4], t1[3];
-    if (!abs_solve6(acc, lambda, d)) {
+    if (!solve_damped<6>(acc, lambda, d)) {
       lambda *= 10.0;
       if (lambda > 1e12) break;
       continue;
@@ -494,15 +320,7 @@ __device__ __forceinline__ bool abs_open_query(const AbsArgs& a, int qi, double*
   Q.model = a.cam_model[cam];
 #pragma unroll
   for (int j = 0; j < PXR_KPAD; ++j) Q.k[j] = a.cam_params[(size_t)cam * PXR_KPAD + j];
-  double focal;
-  switch (Q.model) {
-    case PXR_SIMPLE_PINHOLE: case PXR_SIMPLE_RADIAL: case PXR_RADIAL: case PXR_SIMPLE_RADIAL_FISHEYE: case PXR_RADIAL_FISHEYE:
-      focal = Q.k[0];
-      break;
-    default:
-      focal = 0.5 * (Q.k[0] + Q.k[1]);
-  }
-  const double thr = a.o.max_error / focal;
+  const double thr = a.o.max_error / mean_focal(Q.model, Q.k);
   thr2 = thr * thr;
   __syncthreads();
   return true;
@@ -525,18 +343,22 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_hypotheses(const AbsArgs a)
   const int n = Q.n;
 
   // 1. hypotheses: round r (round_size samples) on wavefront r mod 4, its samples strided over the lanes
-  AbsKey best = {-1, 0.0, 0x7fffffff, 4};
+  HypKey best = {-1, 0.0, 0x7fffffff, 4};
   int done = 0;
+  const auto need = [&](int cnt) {                       // the stop rule: three inliers in a sample
+    const double w = (double)cnt / (double)n;
+    return trials_needed(a.o.confidence, a.o.min_num_trials, a.max_trials, cnt, w * w * w);
+  };
   for (int pass = 0;; ++pass) {
     const int round = pass * ABS_WAVES + wave;
-    AbsKey mine = {-1, 0.0, 0x7fffffff, 4};
+    HypKey mine = {-1, 0.0, 0x7fffffff, 4};
     if ((int64_t)round * a.o.round_size < a.max_trials) {
       for (int s = lane; s < a.o.round_size; s += 64) {
         const int h = round * a.o.round_size + s;
-        int i0, i1, i2;
-        abs_sample(a.o.seed, h, n, i0, i1, i2);
+        int i[3];
+        sample_distinct<3>(a.o.seed, h, n, i);
         P3P p3;
-        if (!p3p_setup(Q.rec(i0), Q.rec(i1), Q.rec(i2), p3)) continue;
+        if (!p3p_setup(Q.rec(i[0]), Q.rec(i[1]), Q.rec(i[2]), p3)) continue;
         for (int root = 0; root < 4; ++root) {
           double R[9], t[3];
           if (!p3p_pose(p3, p3p_root(p3, root), R, t)) continue;
@@ -555,31 +377,13 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_hypotheses(const AbsArgs a)
             }
             sum += e;
           }
-          const AbsKey key = {cnt, sum, h, root};
+          const HypKey key = {cnt, sum, h, root};
           if (key.beats(mine)) mine = key;
         }
       }
     }
-    // the round's best key: compared, never accumulated, across the lanes
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      AbsKey other;
-      other.cnt = __shfl_xor(mine.cnt, off, 64); other.sum = __shfl_xor(mine.sum, off, 64);
-      other.h = __shfl_xor(mine.h, off, 64); other.root = __shfl_xor(mine.root, off, 64);
-      if (other.beats(mine)) mine = other;
-    }
-    if (lane == 0) { sh_ksum[wave] = mine.sum; sh_kint[wave][0] = mine.cnt; sh_kint[wave][1] = mine.h; sh_kint[wave][2] = mine.root; }
-    __syncthreads();
-    bool stop = false;
-    for (int w = 0; w < ABS_WAVES && !stop; ++w) {      // the rounds in order; the stop rule at every round boundary
-      if ((int64_t)(pass * ABS_WAVES + w) * a.o.round_size >= a.max_trials) { stop = true; break; }
-      const AbsKey key = {sh_kint[w][0], sh_ksum[w], sh_kint[w][1], sh_kint[w][2]};
-      if (key.beats(best)) best = key;
-      done = (pass * ABS_WAVES + w + 1) * a.o.round_size;
-      stop = (double)done >= abs_trials_needed(a.o, a.max_trials, best.cnt, n);
-    }
-    __syncthreads();
-    if (stop) break;
+    wave_best(mine);
+    if (merge_rounds<ABS_WAVES>(sh_ksum, sh_kint, mine, pass, a.o.round_size, a.max_trials, best, done, need)) break;
   }
   if (tid == 0) {
     a.n_trials[qi] = done;
@@ -597,7 +401,7 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_refine(const AbsArgs a) {
   __shared__ double sh_cur[ABS_ACC];
   const int tid = threadIdx.x;
   const int qi = a.order[blockIdx.x];
-  AbsKey best;
+  HypKey best;
   best.cnt = a.winner[3 * (size_t)qi]; best.h = a.winner[3 * (size_t)qi + 1]; best.root = a.winner[3 * (size_t)qi + 2]; best.sum = 0.0;
   AbsQuery Q;
   double thr2;
@@ -607,13 +411,13 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_refine(const AbsArgs a) {
   // 2. the winner's pose (its own arithmetic again, on every lane) and its inliers in the normalised image plane
   double q[4], t[3];
   {
-    int i0, i1, i2;
-    abs_sample(a.o.seed, best.h, n, i0, i1, i2);
+    int i[3];
+    sample_distinct<3>(a.o.seed, best.h, n, i);
     P3P p3;
     double R[9];
-    p3p_setup(Q.rec(i0), Q.rec(i1), Q.rec(i2), p3);
+    p3p_setup(Q.rec(i[0]), Q.rec(i[1]), Q.rec(i[2]), p3);
     p3p_pose(p3, p3p_root(p3, best.root), R, t);
-    abs_rotation_to_quat(R, q);
+    rotation_to_quat(R, q);
     for (int j = tid; j < n; j += ABS_THREADS) {
       const double* r = Q.rec(j);
       const double pz = R[6] * r[2] + R[7] * r[3] + R[8] * r[4] + t[2];
@@ -646,7 +450,7 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_refine(const AbsArgs a) {
       cc[0] += in ? 1.0 : 0.0;
       cc[1] += (in != (cur[Q.o0 + j] != 0)) ? 1.0 : 0.0;
     }
-    abs_block_sum(cc, sh_part, sh_tot);
+    block_sum<ABS_THREADS, ABS_CHUNK>(cc, sh_part, sh_tot);
     if (cc[0] < (double)cur_cnt) break;                 // fewer inliers: the pose before it stays
 #pragma unroll
     for (int j = 0; j < 4; ++j) q[j] = q1[j];
@@ -660,7 +464,7 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_refine(const AbsArgs a) {
   // 4. the final set: pixel error <= max_error under the pose that stays
   double fin[1] = {0.0};
   for (int j = tid; j < n; j += ABS_THREADS) fin[0] += abs_pixel_err(a, Q, j, q, t) <= a.o.max_error ? 1.0 : 0.0;
-  abs_block_sum(fin, sh_part, sh_tot);
+  block_sum<ABS_THREADS, ABS_CHUNK>(fin, sh_part, sh_tot);
   const int n_in = (int)fin[0];
   const int need = max(a.o.min_num_inliers, (int)ceil(a.o.min_inlier_ratio * (double)n));
   if (n_in < need) {
@@ -679,15 +483,6 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_refine(const AbsArgs a) {
     for (int j = 0; j < 3; ++j) a.tvec[3 * (size_t)qi + j] = t[j];
     a.status[qi] = 0; a.n_inliers[qi] = n_in;
   }
-}
-
-static int abs_grow_workspace(pxr_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->workspace_bytes) return PXR_OK;
-  PXR_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
-  PXR_HIP(hipMalloc(&ctx->d_workspace, bytes));
-  ctx->workspace_bytes = bytes;
-  return PXR_OK;
 }
 
 static int absolute_pose(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_query_offsets, int64_t n_corr, const double* d_xy,
@@ -716,32 +511,19 @@ static int absolute_pose(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_query
 
   // offsets and cameras are validated on a host copy, which also gives the processing order: queries by descending
   // correspondence count (a stable counting sort), so that the longest start first
-  std::vector<int64_t> off((size_t)T + 1);
-  std::vector<int32_t> qcam((size_t)T);
-  PXR_HIP(hipMemcpyAsync(off.data(), d_query_offsets, sizeof(int64_t) * ((size_t)T + 1), hipMemcpyDeviceToHost, st));
+  std::vector<int64_t> off;
+  std::vector<int32_t> order, qcam((size_t)T);
   PXR_HIP(hipMemcpyAsync(qcam.data(), d_query_camera, sizeof(int32_t) * (size_t)T, hipMemcpyDeviceToHost, st));
-  PXR_HIP(hipStreamSynchronize(st));
-  PXR_REQUIRE(off[0] == 0, "%s: query_offsets[0] = %lld, not 0", fn, (long long)off[0]);
-  int64_t longest = 0;
-  for (int64_t t = 0; t < T; ++t) {
-    PXR_REQUIRE(off[t + 1] >= off[t], "%s: query_offsets is not monotone at query %lld", fn, (long long)t);
+  const auto camera_in_range = [&](int64_t t) {
     PXR_REQUIRE(qcam[t] >= 0 && qcam[t] < n_cameras, "%s: query %lld names a camera outside [0, n_cameras = %d)", fn, (long long)t, (int)n_cameras);
-    longest = std::max(longest, off[t + 1] - off[t]);
-  }
-  PXR_REQUIRE(off[T] == N, "%s: query_offsets ends at %lld, not at n_corr = %lld", fn, (long long)off[T], (long long)N);
-  std::vector<int32_t> order((size_t)T);
-  {
-    std::vector<int64_t> first((size_t)longest + 2, 0);
-    for (int64_t t = 0; t < T; ++t) ++first[(size_t)(longest - (off[t + 1] - off[t])) + 1];
-    for (size_t k = 1; k < first.size(); ++k) first[k] += first[k - 1];
-    for (int64_t t = 0; t < T; ++t) order[(size_t)first[(size_t)(longest - (off[t + 1] - off[t]))]++] = (int32_t)t;
-  }
+    return (int)PXR_OK;
+  };
+  if (int rc = batch_order(ctx, {fn, "query_offsets", "query", "n_corr"}, false, d_query_offsets, T, N, off, order, camera_in_range)) return rc;
 
-  size_t wsz = 0;
-  auto carve = [&](size_t count, size_t elem) { const size_t p = wsz; wsz += (count * elem + 255) & ~(size_t)255; return p; };
-  const size_t o_rec = carve((size_t)N * ABS_REC, 8), o_valid = carve((size_t)N, 1), o_pos = carve((size_t)N, 4);
-  const size_t o_ma = carve((size_t)N, 1), o_mb = carve((size_t)N, 1), o_nv = carve((size_t)T, 4), o_order = carve((size_t)T, 4), o_win = carve((size_t)T * 3, 4);
-  if (int rc = abs_grow_workspace(ctx, wsz)) return rc;
+  Carver cv;
+  const size_t o_rec = cv.take((size_t)N * ABS_REC, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
+  const size_t o_ma = cv.take((size_t)N, 1), o_mb = cv.take((size_t)N, 1), o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4), o_win = cv.take((size_t)T * 3, 4);
+  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
   char* ws = static_cast<char*>(ctx->d_workspace);
   double* rec = (double*)(ws + o_rec);
   uint8_t* valid = (uint8_t*)(ws + o_valid);
@@ -749,22 +531,20 @@ static int absolute_pose(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_query
   int32_t* n_valid = (int32_t*)(ws + o_nv);
   int32_t* d_order = (int32_t*)(ws + o_order);
 
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // bearings | compact | hypotheses | refine
-  auto mark = [&](int k) { if (h_ms) (void)hipEventRecord(ev[k], st); };
-  auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
-  if (h_ms) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { drop(); return set_error(PXR_EHIP, "%s: hipEventCreate failed", fn); }
+  StageTimer<5> timer(st, h_ms);                         // bearings | compact | hypotheses | refine
+  if (int rc = timer.create(fn)) return rc;
 
   auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
   int rc = hip_check(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (`order` may go out of scope)
-  if (rc != PXR_OK) { drop(); return rc; }
-  mark(0);
+  if (rc != PXR_OK) return rc;
+  timer.mark(0);
   if (N > 0)
     hipLaunchKernelGGL(k_abs_bearings, blocks(N, ABS_THREADS), dim3(ABS_THREADS), 0, st, N, n_queries, d_query_offsets, d_query_camera,
                        d_cam_model, d_cam_params, d_xy, d_xyz, rec, valid, d_inlier, d_err);
-  mark(1);
-  hipLaunchKernelGGL(k_abs_compact, blocks(T, ABS_THREADS), dim3(ABS_THREADS), 0, st, n_queries, d_query_offsets, rec, valid, pos, n_valid);
-  mark(2);
+  timer.mark(1);
+  hipLaunchKernelGGL(k_compact_records<ABS_REC>, blocks(T, ABS_THREADS), dim3(ABS_THREADS), 0, st, T, d_query_offsets, rec, valid, pos, n_valid);
+  timer.mark(2);
   AbsArgs a;
   a.offsets = d_query_offsets; a.query_camera = d_query_camera; a.cam_model = d_cam_model; a.cam_params = d_cam_params; a.xy = d_xy;
   a.order = d_order; a.rec = rec; a.pos = pos; a.n_valid = n_valid; a.mask_a = (uint8_t*)(ws + o_ma); a.mask_b = (uint8_t*)(ws + o_mb);
@@ -773,20 +553,12 @@ static int absolute_pose(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_query
   a.qvec = d_qvec; a.tvec = d_tvec; a.status = d_status; a.n_inliers = d_n_inliers; a.n_trials = d_n_trials; a.inlier = d_inlier; a.err = d_err;
   a.winner = (int32_t*)(ws + o_win);
   hipLaunchKernelGGL(k_abs_hypotheses, dim3((unsigned)T), dim3(ABS_THREADS), 0, st, a);
-  mark(3);
+  timer.mark(3);
   hipLaunchKernelGGL(k_abs_refine, dim3((unsigned)T), dim3(ABS_THREADS), 0, st, a);
-  mark(4);
+  timer.mark(4);
   rc = hip_check(hipGetLastError(), "k_abs_refine launch");
-  if (rc == PXR_OK && h_ms) {
-    rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-    for (int k = 0; k < 4 && rc == PXR_OK; ++k) {
-      float ms = 0.f;
-      rc = hip_check(hipEventElapsedTime(&ms, ev[k], ev[k + 1]), "hipEventElapsedTime");
-      h_ms[k] = ms;
-    }
-  }
-  drop();
-  return rc;
+  const int from[4] = {0, 1, 2, 3};
+  return rc == PXR_OK ? timer.read(from, 4) : rc;
 }
 
 }  // namespace pxr

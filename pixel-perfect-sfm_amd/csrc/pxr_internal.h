@@ -112,3 +112,16 @@ int gram_build_flagged(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v, con
   do {                                                       \
     if (!(cond)) return pxr::set_error(PXR_EINVAL, __VA_ARGS__); \
   } while (0)
+
+namespace pxr {
+// at least `bytes` of ctx->d_workspace (grow-only; growing waits for the stream, frees the old block and loses its contents).
+// Inline, so that a driver's translation unit is complete without pxr_runtime.cpp: the lane-emulation tests compile one alone.
+inline int grow_workspace(pxr_ctx* ctx, size_t bytes) {
+  if (bytes <= ctx->workspace_bytes) return PXR_OK;
+  PXR_HIP(hipStreamSynchronize(ctx->stream));
+  if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
+  PXR_HIP(hipMalloc(&ctx->d_workspace, bytes));
+  ctx->workspace_bytes = bytes;
+  return PXR_OK;
+}
+}  // namespace pxr

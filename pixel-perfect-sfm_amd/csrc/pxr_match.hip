@@ -22,6 +22,7 @@
 #include <cmath>
 #include <vector>
 
+#include "pxr_batch.h"
 #include "pxr_internal.h"
 
 namespace pxr {
@@ -266,15 +267,6 @@ __global__ __launch_bounds__(MT_ROWS) void k_match_mutual(const MatchArgs a) {
   if (threadIdx.x == 0 && total > 0) atomicAdd(&a.n_matches[it.pair], total);
 }
 
-int match_grow_workspace(pxr_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->workspace_bytes) return PXR_OK;
-  PXR_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
-  PXR_HIP(hipMalloc(&ctx->d_workspace, bytes));
-  ctx->workspace_bytes = bytes;
-  return PXR_OK;
-}
-
 int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim, const float* d_desc,
                       int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets, const pxr_match_options* o,
                       int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches, double* h_ms) {
@@ -336,12 +328,11 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
   }
   const bool mutual = o->do_mutual_check != 0;
 
-  size_t wsz = 0;
-  auto carve = [&](size_t count, size_t elem) { const size_t at = wsz; wsz += (count * elem + 255) & ~(size_t)255; return at; };
-  const size_t o_pairs = carve(hp.size(), sizeof(MatchPair)), o_items = carve(items.size(), sizeof(MatchItem));
-  const size_t o_colp = carve(col_prefix.size(), 8), o_m1 = carve((size_t)cols, 4);
-  const size_t o_s1 = carve((size_t)parts, 4), o_i1 = carve((size_t)parts, 4), o_s2 = carve((size_t)parts, 4);
-  if (int rc = match_grow_workspace(ctx, wsz)) return rc;
+  Carver cv;
+  const size_t o_pairs = cv.take(hp.size(), sizeof(MatchPair)), o_items = cv.take(items.size(), sizeof(MatchItem));
+  const size_t o_colp = cv.take(col_prefix.size(), 8), o_m1 = cv.take((size_t)cols, 4);
+  const size_t o_s1 = cv.take((size_t)parts, 4), o_i1 = cv.take((size_t)parts, 4), o_s2 = cv.take((size_t)parts, 4);
+  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
   char* ws = static_cast<char*>(ctx->d_workspace);
 
   MatchArgs a;
@@ -356,39 +347,29 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
   a.t2 = (float)(o->distance_threshold * o->distance_threshold);
   a.use_ratio = o->ratio_threshold > 0.0; a.use_dist = o->distance_threshold > 0.0; a.mutual = mutual;
 
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // tiles | columns | mutual
-  auto mark = [&](int k) { if (h_ms) (void)hipEventRecord(ev[k], st); };
-  auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
-  if (h_ms) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { drop(); return set_error(PXR_EHIP, "%s: hipEventCreate failed", fn); }
+  StageTimer<4> timer(st, h_ms);                         // tiles | columns | mutual
+  if (int rc = timer.create(fn)) return rc;
 
   int rc = hip_check(hipMemcpyAsync(ws + o_pairs, hp.data(), sizeof(MatchPair) * hp.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(ws + o_items, items.data(), sizeof(MatchItem) * items.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(ws + o_colp, col_prefix.data(), 8 * col_prefix.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipMemsetAsync(d_n_matches, 0, sizeof(int32_t) * (size_t)n_pairs, st), "hipMemsetAsync");
   if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (the host vectors may go out of scope)
-  if (rc != PXR_OK) { drop(); return rc; }
+  if (rc != PXR_OK) return rc;
 
   const dim3 grid((unsigned)items.size());
-  mark(0);
+  timer.mark(0);
   if (a.kp <= 64) hipLaunchKernelGGL(k_match_tiles<64>, grid, dim3(MT_THREADS), 0, st, a);
   else if (a.kp <= 128) hipLaunchKernelGGL(k_match_tiles<128>, grid, dim3(MT_THREADS), 0, st, a);
   else hipLaunchKernelGGL(k_match_tiles<256>, grid, dim3(MT_THREADS), 0, st, a);
-  mark(1);
+  timer.mark(1);
   if (mutual && cols > 0) hipLaunchKernelGGL(k_match_columns, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, a);
-  mark(2);
+  timer.mark(2);
   hipLaunchKernelGGL(k_match_mutual, grid, dim3(MT_ROWS), 0, st, a);
-  mark(3);
+  timer.mark(3);
   rc = hip_check(hipGetLastError(), "k_match_mutual launch");
-  if (rc == PXR_OK && h_ms) {
-    rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-    for (int k = 0; k < 3 && rc == PXR_OK; ++k) {
-      float ms = 0.f;
-      rc = hip_check(hipEventElapsedTime(&ms, ev[k], ev[k + 1]), "hipEventElapsedTime");
-      h_ms[k] = ms;
-    }
-  }
-  drop();
-  return rc;
+  const int from[3] = {0, 1, 2};
+  return rc == PXR_OK ? timer.read(from, 3) : rc;
 }
 
 }  // namespace

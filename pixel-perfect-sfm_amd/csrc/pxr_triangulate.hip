@@ -8,7 +8,8 @@
 //
 //   k_tri_check     obs_image / image_camera in range (nothing is trusted into the other kernels)
 //   k_tri_rays      one lane per observation: undistort, rotate into the world frame -> unit bearing d, camera centre c, valid
-//   k_tri_compact   one lane per track: the valid rays of a track moved to the front of its slice (in order), their positions kept
+//   k_compact_records<6>  (pxr_robust.h) one lane per track: the valid rays of a track moved to the front of its slice (in order),
+//                   their positions kept
 //   k_tri_tracks    the estimator: a track per group of 16 lanes (one DPP row), four tracks per wavefront; hypotheses strided
 //                   over the lanes, each lane scoring its own against all rays of the track
 //
@@ -20,8 +21,10 @@
 #include <cmath>
 #include <vector>
 
+#include "pxr_batch.h"
 #include "pxr_device.h"
 #include "pxr_internal.h"
+#include "pxr_robust.h"
 #include "pxr_undistort.h"
 
 namespace pxr {
@@ -31,8 +34,6 @@ constexpr int TRI_GROUP = 16;        // lanes per track
 constexpr int TRI_TPW = 64 / TRI_GROUP;
 constexpr int TRI_RAY = 6;           // doubles per ray: d (3), c (3)
 constexpr int TRI_LDS_RAYS = 32;     // a track of up to this many valid rays is staged in LDS; longer ones read global memory (L2)
-
-__device__ __forceinline__ double tri_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // ---- validation --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TRI_THREADS) void k_tri_check(int64_t n_obs, const int32_t* __restrict__ obs_image, int32_t n_images,
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(TRI_THREADS) void k_image_to_world(int64_t n, const
   const int64_t i = (int64_t)blockIdx.x * TRI_THREADS + threadIdx.x;
   if (i >= n) return;
   const int32_t cam = cam_index ? cam_index[i] : 0;
-  double u = tri_nan(), v = tri_nan();
+  double u = quiet_nan(), v = quiet_nan();
   bool good = false;
   if (cam >= 0 && cam < n_cameras) {
     double k[PXR_KPAD];
@@ -93,29 +94,7 @@ __global__ __launch_bounds__(TRI_THREADS) void k_tri_rays(const pxr_tri_view v, 
   }
   valid[i] = ok ? 1 : 0;
   obs_inlier[i] = 0;            // what an observation keeps unless its track gets a point
-  obs_err[i] = tri_nan();
-}
-
-// The valid rays of every track moved to the front of the track's slice, order kept (position j <- the j-th valid one; a move
-// only ever goes towards the front, so the slice is compacted in place); pos[o0 + j] = where the j-th valid ray came from.
-__global__ __launch_bounds__(TRI_THREADS) void k_tri_compact(int64_t n_tracks, const int64_t* __restrict__ offsets, double* __restrict__ rays,
-                                                             const uint8_t* __restrict__ valid, int32_t* __restrict__ pos,
-                                                             int32_t* __restrict__ n_valid) {
-  const int64_t t = (int64_t)blockIdx.x * TRI_THREADS + threadIdx.x;
-  if (t >= n_tracks) return;
-  const int64_t o0 = offsets[t];
-  const int64_t n = offsets[t + 1] - o0;
-  int32_t nv = 0;
-  for (int64_t j = 0; j < n; ++j) {
-    if (!valid[o0 + j]) continue;
-    if (nv != j) {
-#pragma unroll
-      for (int m = 0; m < TRI_RAY; ++m) rays[(size_t)(o0 + nv) * TRI_RAY + m] = rays[(size_t)(o0 + j) * TRI_RAY + m];
-    }
-    pos[o0 + nv] = (int32_t)j;
-    ++nv;
-  }
-  n_valid[t] = nv;
+  obs_err[i] = quiet_nan();
 }
 
 // ---- kernel B: the estimator -----------------------------------------------------------------------------------------------------
@@ -196,7 +175,7 @@ __device__ __forceinline__ double tri_reproj(const TriArgs& a, int64_t o0, int j
 #pragma unroll
   for (int m = 0; m < PXR_KPAD; ++m) k[m] = a.v.d_cam_params[(size_t)cam * PXR_KPAD + m];
   double x, y;
-  if (!world_to_pixel(a.v.d_cam_model[cam], k, a.v.d_qvec + 4 * (size_t)img, a.v.d_tvec + 3 * (size_t)img, X, x, y)) return tri_nan();
+  if (!world_to_pixel(a.v.d_cam_model[cam], k, a.v.d_qvec + 4 * (size_t)img, a.v.d_tvec + 3 * (size_t)img, X, x, y)) return quiet_nan();
   const double ex = x - a.v.d_obs_xy[2 * i], ey = y - a.v.d_obs_xy[2 * i + 1];
   return sqrt(ex * ex + ey * ey);
 }
@@ -350,15 +329,6 @@ __global__ __launch_bounds__(64) void k_tri_tracks(const TriArgs a) {
   }
 }
 
-static int grow_workspace(pxr_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->workspace_bytes) return PXR_OK;
-  PXR_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
-  PXR_HIP(hipMalloc(&ctx->d_workspace, bytes));
-  ctx->workspace_bytes = bytes;
-  return PXR_OK;
-}
-
 static int triangulate(pxr_ctx* ctx, const pxr_tri_view* v, const pxr_tri_options* o, double* d_xyz, int32_t* d_status,
                        int32_t* d_n_inliers, uint8_t* d_obs_inlier, double* d_obs_err, double* h_ms) {
   const char* fn = "pxr_triangulate_tracks";
@@ -378,29 +348,15 @@ static int triangulate(pxr_ctx* ctx, const pxr_tri_view* v, const pxr_tri_option
 
   // the offsets are validated on a host copy, which also gives the processing order: tracks by descending length (a stable
   // counting sort), so that the groups of a wavefront run tracks of like length and the longest start first
-  std::vector<int64_t> off((size_t)T + 1);
-  PXR_HIP(hipMemcpyAsync(off.data(), v->d_track_offsets, sizeof(int64_t) * ((size_t)T + 1), hipMemcpyDeviceToHost, st));
-  PXR_HIP(hipStreamSynchronize(st));
-  PXR_REQUIRE(off[0] >= 0, "%s: track_offsets[0] = %lld is negative", fn, (long long)off[0]);
-  int64_t longest = 0;
-  for (int64_t t = 0; t < T; ++t) {
-    PXR_REQUIRE(off[t + 1] >= off[t], "%s: track_offsets is not monotone at track %lld", fn, (long long)t);
-    longest = std::max(longest, off[t + 1] - off[t]);
-  }
-  PXR_REQUIRE(off[T] == N, "%s: track_offsets ends at %lld, not at n_obs = %lld", fn, (long long)off[T], (long long)N);
-  std::vector<int32_t> order((size_t)T);
-  {
-    std::vector<int64_t> first((size_t)longest + 2, 0);                    // first[len]: where the tracks of that length begin
-    for (int64_t t = 0; t < T; ++t) ++first[(size_t)(longest - (off[t + 1] - off[t])) + 1];
-    for (size_t k = 1; k < first.size(); ++k) first[k] += first[k - 1];
-    for (int64_t t = 0; t < T; ++t) order[(size_t)first[(size_t)(longest - (off[t + 1] - off[t]))]++] = (int32_t)t;
-  }
+  std::vector<int64_t> off;
+  std::vector<int32_t> order;
+  if (int rc = batch_order(ctx, {fn, "track_offsets", "track", "n_obs"}, true, v->d_track_offsets, T, N, off, order, [](int64_t) { return (int)PXR_OK; }))
+    return rc;
 
-  size_t wsz = 0;
-  auto carve = [&](size_t count, size_t elem) { const size_t p = wsz; wsz += (count * elem + 255) & ~(size_t)255; return p; };
-  const size_t o_flag = carve(4, 4), o_rays = carve((size_t)N * TRI_RAY, 8), o_valid = carve((size_t)N, 1), o_pos = carve((size_t)N, 4);
-  const size_t o_nv = carve((size_t)T, 4), o_order = carve((size_t)T, 4);
-  if (int rc = grow_workspace(ctx, wsz)) return rc;
+  Carver cv;
+  const size_t o_flag = cv.take(4, 4), o_rays = cv.take((size_t)N * TRI_RAY, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
+  const size_t o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4);
+  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
   char* ws = static_cast<char*>(ctx->d_workspace);
   int* flag = (int*)(ws + o_flag);
   double* rays = (double*)(ws + o_rays);
@@ -409,37 +365,34 @@ static int triangulate(pxr_ctx* ctx, const pxr_tri_view* v, const pxr_tri_option
   int32_t* n_valid = (int32_t*)(ws + o_nv);
   int32_t* d_order = (int32_t*)(ws + o_order);
 
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // check | rays | compact | tracks
-  auto mark = [&](int k) { if (h_ms) (void)hipEventRecord(ev[k], st); };
-  auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
-  if (h_ms) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { drop(); return set_error(PXR_EHIP, "%s: hipEventCreate failed", fn); }
+  StageTimer<6> timer(st, h_ms);                         // check | (the flag's read-back) | rays | compact | tracks
+  if (int rc = timer.create(fn)) return rc;
 
   auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
   int h_flag = 0;
   int rc = hip_check(hipMemsetAsync(flag, 0, 16, st), "hipMemsetAsync");
   if (rc == PXR_OK) {
-    mark(0);
+    timer.mark(0);
     const int64_t n_check = std::max<int64_t>(N, v->n_images);
     if (n_check > 0)
       hipLaunchKernelGGL(k_tri_check, blocks(n_check, TRI_THREADS), dim3(TRI_THREADS), 0, st, N, v->d_obs_image, v->n_images,
                          v->d_image_camera, v->n_cameras, flag);
-    mark(1);
+    timer.mark(1);
     rc = hip_check(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
   }
   if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (also: `order` may go out of scope)
-  if (rc != PXR_OK) { drop(); return rc; }
+  if (rc != PXR_OK) return rc;
   if (h_flag) {
-    drop();
     if (h_flag & 1) return set_error(PXR_EINVAL, "%s: an observation names an image outside [0, n_images = %d)", fn, (int)v->n_images);
     return set_error(PXR_EINVAL, "%s: an image names a camera outside [0, n_cameras = %d)", fn, (int)v->n_cameras);
   }
 
-  mark(2);
+  timer.mark(2);
   if (N > 0) hipLaunchKernelGGL(k_tri_rays, blocks(N, TRI_THREADS), dim3(TRI_THREADS), 0, st, *v, rays, valid, d_obs_inlier, d_obs_err);
-  mark(3);
-  hipLaunchKernelGGL(k_tri_compact, blocks(T, TRI_THREADS), dim3(TRI_THREADS), 0, st, T, v->d_track_offsets, rays, valid, pos, n_valid);
-  mark(4);
+  timer.mark(3);
+  hipLaunchKernelGGL(k_compact_records<TRI_RAY>, blocks(T, TRI_THREADS), dim3(TRI_THREADS), 0, st, T, v->d_track_offsets, rays, valid, pos, n_valid);
+  timer.mark(4);
   TriArgs a;
   a.v = *v; a.order = d_order; a.rays = rays; a.pos = pos; a.n_valid = n_valid;
   const double rad = 3.14159265358979323846 / 180.0;
@@ -447,19 +400,10 @@ static int triangulate(pxr_ctx* ctx, const pxr_tri_view* v, const pxr_tri_option
   a.max_reproj = o->max_reproj_error; a.min_len = o->min_track_len; a.max_hyp = o->max_hypotheses;
   a.xyz = d_xyz; a.status = d_status; a.n_inliers = d_n_inliers; a.obs_inlier = d_obs_inlier; a.obs_err = d_obs_err;
   hipLaunchKernelGGL(k_tri_tracks, blocks(T, TRI_TPW), dim3(64), 0, st, a);
-  mark(5);
+  timer.mark(5);
   rc = hip_check(hipGetLastError(), "k_tri_tracks launch");
-  if (rc == PXR_OK && h_ms) {
-    rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-    const int from[4] = {0, 2, 3, 4};
-    for (int k = 0; k < 4 && rc == PXR_OK; ++k) {
-      float ms = 0.f;
-      rc = hip_check(hipEventElapsedTime(&ms, ev[from[k]], ev[from[k] + 1]), "hipEventElapsedTime");
-      h_ms[k] = ms;
-    }
-  }
-  drop();
-  return rc;
+  const int from[4] = {0, 2, 3, 4};
+  return rc == PXR_OK ? timer.read(from, 4) : rc;
 }
 
 }  // namespace pxr

@@ -9,7 +9,8 @@
 // keys, so the result is a function of the pair's own matches alone, bit for bit, alone or inside any batch.
 //
 //   k_tv_bearings    one lane per match: its pair (binary search of the offsets), undistort both sides -> record (u1, v1, u2, v2)
-//   k_tv_compact     one lane per pair: the usable records of a pair moved to the front of its slice (in order), positions kept
+//   k_compact_records<4>  (pxr_robust.h) one lane per pair: the usable records of a pair moved to the front of its slice (in
+//                    order), positions kept
 //   k_tv_hypotheses  the estimator's samples: one workgroup of 256 lanes per pair, the first TV_LDS records staged in LDS; a round
 //                    of samples per wavefront, a sample per lane, every lane scoring its own essential matrices against all records
 //   k_tv_refine      the winner's decomposition, local optimisation and final classification; with a pose prior, only the last
@@ -30,8 +31,10 @@
 #include <cmath>
 #include <vector>
 
+#include "pxr_batch.h"
 #include "pxr_device.h"
 #include "pxr_internal.h"
+#include "pxr_robust.h"
 #include "pxr_undistort.h"
 
 namespace pxr {
@@ -42,7 +45,6 @@ constexpr int TV_REC = 4;                              // doubles per record: u1
 constexpr int TV_LDS = PXR_TWOVIEW_LDS_MATCHES;        // records of a pair staged in LDS (32 B each); the rest is read from global memory (L2)
 constexpr int TV_ACC = 21;                             // the refinement's sums: H (15, upper triangle by rows), g (5), cost
 constexpr int TV_CHUNK = 7;                            // of which this many cross the workgroup at a time (TV_THREADS x TV_CHUNK doubles of LDS)
-constexpr int TV_MAX_DRAWS = 256;                      // draws of one sample before the smallest unused indices complete it
 constexpr int TV_DEG = 10;                             // degree of the polynomial in z
 constexpr int TV_BISECT = 64;                          // bisection steps per root
 constexpr int TV_NEWTON = 4;                           // Newton steps per root, each kept only inside the bisection's last interval
@@ -51,48 +53,6 @@ constexpr double TV_LEAD_TOL = 1e-9;                   // the leading coefficien
 constexpr double TV_TRIM_TOL = 1e-12;                  // so does the leading coefficient of a rescaled Sturm remainder
 constexpr double TV_STEP_TOL = 1e-12;                  // the refinement stops at a step of this norm
 constexpr double TV_COST_SLACK = 1e-12;                // a step is kept unless the cost grows by more than this fraction
-
-__device__ __forceinline__ double tv_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ double tv_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
-
-// ---- samples: the hash of section 19 (splitmix64's output function), five indices ----------------------------------------------
-__device__ __forceinline__ uint64_t tv_mix(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-// sample h of a pair with n >= 5 usable matches: five distinct indices, ascending.  draw d = mix(mix(seed + G (h + 1)) + G (d + 1))
-// mod n; a repeated index is drawn again
-__device__ __forceinline__ void tv_sample(uint64_t seed, int64_t h, int n, int idx[5]) {
-  const uint64_t G = 0x9E3779B97F4A7C15ull;
-  const uint64_t a = tv_mix(seed + G * (uint64_t)(h + 1));
-  int draw = 0;
-  for (int m = 0; m < 5; ++m) {
-    int c = 0;
-    bool fresh = false;
-    while (!fresh && draw < TV_MAX_DRAWS) {
-      ++draw;
-      c = (int)(tv_mix(a + G * (uint64_t)draw) % (uint64_t)n);
-      fresh = true;
-      for (int l = 0; l < m; ++l) fresh = fresh && idx[l] != c;
-    }
-    if (!fresh) {                                       // (never in practice: the smallest unused index)
-      for (c = 0;; ++c) {
-        bool used = false;
-        for (int l = 0; l < m; ++l) used = used || idx[l] == c;
-        if (!used) break;
-      }
-    }
-    idx[m] = c;
-  }
-  for (int m = 1; m < 5; ++m) {                         // insertion sort
-    const int c = idx[m];
-    int l = m;
-    while (l > 0 && idx[l - 1] > c) { idx[l] = idx[l - 1]; --l; }
-    idx[l] = c;
-  }
-}
 
 // ---- the five-point solver ---------------------------------------------------------------------------------------------------------
 // Gauss-Jordan with partial pivoting on the first `rows` columns of M (rows x cols, row-major): M -> [I | C].  false: a pivot
@@ -437,28 +397,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_bearings(int64_t n_matches, i
   r[0] = uv[0]; r[1] = uv[1]; r[2] = uv[2]; r[3] = uv[3];
   valid[i] = ok ? 1 : 0;
   inlier[i] = 0;                                       // what a match keeps unless its pair gets a pose
-  err[i] = tv_nan();
-}
-
-// The usable records of every pair moved to the front of the pair's slice, order kept; pos[o0 + j] = where the j-th came from.
-__global__ __launch_bounds__(TV_THREADS) void k_tv_compact(int32_t n_pairs, const int64_t* __restrict__ offsets, double* __restrict__ rec,
-                                                           const uint8_t* __restrict__ valid, int32_t* __restrict__ pos,
-                                                           int32_t* __restrict__ n_valid) {
-  const int64_t p = (int64_t)blockIdx.x * TV_THREADS + threadIdx.x;
-  if (p >= n_pairs) return;
-  const int64_t o0 = offsets[p];
-  const int64_t n = offsets[p + 1] - o0;
-  int32_t nv = 0;
-  for (int64_t j = 0; j < n; ++j) {
-    if (!valid[o0 + j]) continue;
-    if (nv != j) {
-#pragma unroll
-      for (int m = 0; m < TV_REC; ++m) rec[(size_t)(o0 + nv) * TV_REC + m] = rec[(size_t)(o0 + j) * TV_REC + m];
-    }
-    pos[o0 + nv] = (int32_t)j;
-    ++nv;
-  }
-  n_valid[p] = nv;
+  err[i] = quiet_nan();
 }
 
 // ---- kernel B: the estimator -------------------------------------------------------------------------------------------------------
@@ -477,60 +416,11 @@ struct TvArgs {
   double* qvec; double* tvec; double* E; int32_t* status; int32_t* n_inliers; int32_t* n_trials; uint8_t* inlier; double* err;
 };
 
-struct TvKey {                 // larger count, then smaller sum, then smaller sample, then smaller root
-  int cnt; double sum; int h; int root;
-  __device__ __forceinline__ bool beats(const TvKey& o) const {
-    return cnt > o.cnt || (cnt == o.cnt && (sum < o.sum || (sum == o.sum && (h < o.h || (h == o.h && root < o.root)))));
-  }
-};
-
 struct TvPair {                // what every lane of the workgroup knows about its pair
   const double* sh; const double* g; int n; int64_t o0;
   double thr, thr2;
   __device__ __forceinline__ const double* rec(int j) const { return j < TV_LDS ? sh + j * TV_REC : g + (size_t)j * TV_REC; }
 };
-
-__device__ __forceinline__ double tv_mean_focal(int model, const double* k) {
-  switch (model) {
-    case PXR_SIMPLE_PINHOLE: case PXR_SIMPLE_RADIAL: case PXR_RADIAL: case PXR_SIMPLE_RADIAL_FISHEYE: case PXR_RADIAL_FISHEYE:
-      return k[0];
-    default:
-      return 0.5 * (k[0] + k[1]);
-  }
-}
-
-// trials the stop rule asks for at `cnt` inliers among n
-__device__ __forceinline__ double tv_trials_needed(const pxr_two_view_options& o, int max_trials, int cnt, int n) {
-  double need = (double)max_trials;
-  if (cnt > 0) {
-    const double w = (double)cnt / (double)n;
-    const double x = log(1.0 - o.confidence) / log(1.0 - (w * w) * (w * w) * w);      // w = 1: -inf below, x = +0
-    if (x < need) need = x;
-  }
-  if (need < (double)o.min_num_trials) need = (double)o.min_num_trials;
-  if (need > (double)max_trials) need = (double)max_trials;
-  return need;
-}
-
-// sums over the workgroup in a fixed order: lane t's addends to sh_part[t], column c summed over t = 0 .. 255 by lane c
-template <int N>
-__device__ __forceinline__ void tv_block_sum(double (&v)[N], double* sh_part, double* sh_tot) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int c0 = 0; c0 < N; c0 += TV_CHUNK) {
-#pragma unroll
-    for (int c = 0; c < TV_CHUNK; ++c) if (c0 + c < N) sh_part[tid * TV_CHUNK + c] = v[c0 + c];
-    __syncthreads();
-    if (tid < TV_CHUNK && c0 + tid < N) {
-      double s = 0.0;
-      for (int t = 0; t < TV_THREADS; ++t) s += sh_part[t * TV_CHUNK + tid];
-      sh_tot[c0 + tid] = s;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int c = 0; c < N; ++c) v[c] = sh_tot[c];
-}
 
 // what every lane of a workgroup needs of its pair; false: fewer than five usable matches
 __device__ __forceinline__ bool tv_open_pair(const TvArgs& a, int pi, double* sh_rec, TvPair& P) {
@@ -541,8 +431,8 @@ __device__ __forceinline__ bool tv_open_pair(const TvArgs& a, int pi, double* sh
   P.sh = sh_rec;
   for (int x = threadIdx.x; x < min(P.n, TV_LDS) * TV_REC; x += TV_THREADS) sh_rec[x] = P.g[x];
   const int cam1 = a.pair_camera[2 * (size_t)pi], cam2 = a.pair_camera[2 * (size_t)pi + 1];
-  const double f1 = tv_mean_focal(a.cam_model[cam1], a.cam_params + (size_t)cam1 * PXR_KPAD);
-  const double f2 = tv_mean_focal(a.cam_model[cam2], a.cam_params + (size_t)cam2 * PXR_KPAD);
+  const double f1 = mean_focal(a.cam_model[cam1], a.cam_params + (size_t)cam1 * PXR_KPAD);
+  const double f2 = mean_focal(a.cam_model[cam2], a.cam_params + (size_t)cam2 * PXR_KPAD);
   P.thr = 0.5 * (a.o.max_error / f1 + a.o.max_error / f2);
   P.thr2 = P.thr * P.thr;
   __syncthreads();
@@ -566,16 +456,20 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_hypotheses(const TvArgs a) {
   const double thr2 = P.thr2;
 
   // 1. hypotheses: round r (round_size samples) on wavefront r mod 4, its samples strided over the lanes
-  TvKey best = {-1, 0.0, 0x7fffffff, TV_DEG};
+  HypKey best = {-1, 0.0, 0x7fffffff, TV_DEG};
   int done = 0;
+  const auto need = [&](int cnt) {                       // the stop rule: five inliers in a sample
+    const double w = (double)cnt / (double)n;
+    return trials_needed(a.o.confidence, a.o.min_num_trials, a.max_trials, cnt, (w * w) * (w * w) * w);
+  };
   for (int pass = 0;; ++pass) {
     const int round = pass * TV_WAVES + wave;
-    TvKey mine = {-1, 0.0, 0x7fffffff, TV_DEG};
+    HypKey mine = {-1, 0.0, 0x7fffffff, TV_DEG};
     if ((int64_t)round * a.o.round_size < a.max_trials) {
       for (int s = lane; s < a.o.round_size; s += 64) {
         const int h = round * a.o.round_size + s;
         int idx[5];
-        tv_sample(a.o.seed, h, n, idx);
+        sample_distinct<5>(a.o.seed, h, n, idx);
         const double* five[5] = {P.rec(idx[0]), P.rec(idx[1]), P.rec(idx[2]), P.rec(idx[3]), P.rec(idx[4])};
         TvSolver sv;
         if (!tv_solver_setup(five, sv)) continue;
@@ -590,15 +484,16 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_hypotheses(const TvArgs a) {
             if (e2 <= thr2) { ++cnt; e = e2; }
             sum += e;
           }
-          const TvKey key = {cnt, sum, h, root};
+          const HypKey key = {cnt, sum, h, root};
           if (key.beats(mine)) mine = key;
         }
       }
     }
-    // the round's best key: compared, never accumulated, across the lanes
+    // wave_best and merge_rounds (pxr_robust.h) written out: called as functions, the same statements leave this kernel -- at
+    // 256 VGPRs with spills -- two spill registers fewer (186 AGPRs for 188), and its resource table is kept as it was
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-      TvKey other;
+      HypKey other;
       other.cnt = __shfl_xor(mine.cnt, off, 64); other.sum = __shfl_xor(mine.sum, off, 64);
       other.h = __shfl_xor(mine.h, off, 64); other.root = __shfl_xor(mine.root, off, 64);
       if (other.beats(mine)) mine = other;
@@ -608,10 +503,10 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_hypotheses(const TvArgs a) {
     bool stop = false;
     for (int w = 0; w < TV_WAVES && !stop; ++w) {       // the rounds in order; the stop rule at every round boundary
       if ((int64_t)(pass * TV_WAVES + w) * a.o.round_size >= a.max_trials) { stop = true; break; }
-      const TvKey key = {sh_kint[w][0], sh_ksum[w], sh_kint[w][1], sh_kint[w][2]};
+      const HypKey key = {sh_kint[w][0], sh_ksum[w], sh_kint[w][1], sh_kint[w][2]};
       if (key.beats(best)) best = key;
       done = (pass * TV_WAVES + w + 1) * a.o.round_size;
-      stop = (double)done >= tv_trials_needed(a.o, a.max_trials, best.cnt, n);
+      stop = (double)done >= need(best.cnt);
     }
     __syncthreads();
     if (stop) break;
@@ -623,7 +518,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_hypotheses(const TvArgs a) {
       a.status[pi] = 2; a.n_inliers[pi] = 0;
     } else {                                             // the winner's essential matrix: its own arithmetic again, on one lane
       int idx[5];
-      tv_sample(a.o.seed, best.h, n, idx);
+      sample_distinct<5>(a.o.seed, best.h, n, idx);
       const double* five[5] = {P.rec(idx[0]), P.rec(idx[1]), P.rec(idx[2]), P.rec(idx[3]), P.rec(idx[4])};
       TvSolver sv;
       double E[9];
@@ -635,11 +530,6 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_hypotheses(const TvArgs a) {
 }
 
 // ---- kernel C: decomposition, local optimisation, classification -------------------------------------------------------------------
-__device__ __forceinline__ void tv_cross(const double* a, const double* b, double c[3]) {
-  c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ double tv_dot(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
 // E = [t]x R, row-major: column j of E = t x (column j of R)
 __device__ __forceinline__ void tv_essential_of_pose(const double* R, const double* t, double E[9]) {
 #pragma unroll
@@ -650,36 +540,15 @@ __device__ __forceinline__ void tv_essential_of_pose(const double* R, const doub
   }
 }
 
-// unit quaternion (w first) of a (nearly orthogonal) rotation matrix, by the largest of the four pivots
-__device__ __forceinline__ void tv_rotation_to_quat(const double* R, double q[4]) {
-  const double tr = R[0] + R[4] + R[8];
-  if (tr > 0.0) {
-    const double s = 2.0 * sqrt(tr + 1.0);
-    q[0] = 0.25 * s; q[1] = (R[7] - R[5]) / s; q[2] = (R[2] - R[6]) / s; q[3] = (R[3] - R[1]) / s;
-  } else if (R[0] > R[4] && R[0] > R[8]) {
-    const double s = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
-    q[0] = (R[7] - R[5]) / s; q[1] = 0.25 * s; q[2] = (R[1] + R[3]) / s; q[3] = (R[2] + R[6]) / s;
-  } else if (R[4] > R[8]) {
-    const double s = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
-    q[0] = (R[2] - R[6]) / s; q[1] = (R[1] + R[3]) / s; q[2] = 0.25 * s; q[3] = (R[5] + R[7]) / s;
-  } else {
-    const double s = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
-    q[0] = (R[3] - R[1]) / s; q[1] = (R[2] + R[6]) / s; q[2] = (R[5] + R[7]) / s; q[3] = 0.25 * s;
-  }
-  const double inv = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) q[j] *= inv;
-}
-
 // Horn 1990: t t^t = tr(E E^t) / 2 I - E E^t (t from the row of the largest diagonal entry, unit length); |t|^2 R = Cof(E) -+ [t]x E
 // with Cof(E) the matrix of cofactors (row i = row i+1 x row i+2 of E).  Ra goes with -, Rb (the twisted pair) with +.
 // false: E = 0 or a value that is not finite.
 __device__ __forceinline__ bool tv_horn(const double* E, double t[3], double Ra[9], double Rb[9]) {
-  const double d0 = tv_dot(E, E), d1 = tv_dot(E + 3, E + 3), d2 = tv_dot(E + 6, E + 6);
+  const double d0 = dot3(E, E), d1 = dot3(E + 3, E + 3), d2 = dot3(E + 6, E + 6);
   const double half_tr = 0.5 * ((d0 + d1) + d2);
-  const double T[3][3] = {{half_tr - d0, -tv_dot(E, E + 3), -tv_dot(E, E + 6)},
-                          {-tv_dot(E + 3, E), half_tr - d1, -tv_dot(E + 3, E + 6)},
-                          {-tv_dot(E + 6, E), -tv_dot(E + 6, E + 3), half_tr - d2}};
+  const double T[3][3] = {{half_tr - d0, -dot3(E, E + 3), -dot3(E, E + 6)},
+                          {-dot3(E + 3, E), half_tr - d1, -dot3(E + 3, E + 6)},
+                          {-dot3(E + 6, E), -dot3(E + 6, E + 3), half_tr - d2}};
   int m = 0;
   if (T[1][1] > T[m][m]) m = 1;
   if (T[2][2] > T[m][m]) m = 2;
@@ -693,7 +562,7 @@ __device__ __forceinline__ bool tv_horn(const double* E, double t[3], double Ra[
   double En[9], C[9], tE[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j) En[j] = E[j] * sc;
-  tv_cross(En + 3, En + 6, C); tv_cross(En + 6, En, C + 3); tv_cross(En, En + 3, C + 6);
+  cross3(En + 3, En + 6, C); cross3(En + 6, En, C + 3); cross3(En, En + 3, C + 6);
   tv_essential_of_pose(En, t, tE);                       // [t]x En, column by column
   bool ok = true;
 #pragma unroll
@@ -706,10 +575,10 @@ __device__ __forceinline__ bool tv_in_front(const double* R, const double* t, co
   const double x2[3] = {r[2], r[3], 1.0};
   const double a[3] = {(R[0] * r[0] + R[1] * r[1]) + R[2], (R[3] * r[0] + R[4] * r[1]) + R[5], (R[6] * r[0] + R[7] * r[1]) + R[8]};
   double c[3], d[3];
-  tv_cross(x2, a, c); tv_cross(x2, t, d);
-  const double s1 = -tv_dot(c, d), cc = tv_dot(c, c);
+  cross3(x2, a, c); cross3(x2, t, d);
+  const double s1 = -dot3(c, d), cc = dot3(c, c);
   const double p[3] = {s1 * a[0] + cc * t[0], s1 * a[1] + cc * t[1], s1 * a[2] + cc * t[2]};
-  return s1 > 0.0 && tv_dot(p, x2) > 0.0;
+  return s1 > 0.0 && dot3(p, x2) > 0.0;
 }
 
 // the tangent basis of the unit sphere at t: m = the axis of the smallest |t_m| (the first of equals), b1 = t x e_m / |t x e_m|,
@@ -719,11 +588,11 @@ __device__ __forceinline__ void tv_tangent_basis(const double* t, double b1[3], 
   if (fabs(t[1]) < fabs(t[m])) m = 1;
   if (fabs(t[2]) < fabs(t[m])) m = 2;
   const double e[3] = {m == 0 ? 1.0 : 0.0, m == 1 ? 1.0 : 0.0, m == 2 ? 1.0 : 0.0};
-  tv_cross(t, e, b1);
-  const double inv = 1.0 / sqrt(tv_dot(b1, b1));
+  cross3(t, e, b1);
+  const double inv = 1.0 / sqrt(dot3(b1, b1));
 #pragma unroll
   for (int j = 0; j < 3; ++j) b1[j] *= inv;
-  tv_cross(t, b1, b2);
+  cross3(t, b1, b2);
 }
 
 // H = sum J^t J, g = sum J^t r, cost = sum r^2 over the records of `mask`; r = x2^t E x1 / sqrt(D) the signed Sampson residual of
@@ -753,7 +622,7 @@ __device__ __forceinline__ void tv_normal_equations(const TvPair& P, const uint8
     const double c0 = (E[0] * u2 + E[3] * v2) + E[6], c1 = (E[1] * u2 + E[4] * v2) + E[7];
     const double N = (u2 * a0 + v2 * a1) + a2;
     const double D = ((a0 * a0 + a1 * a1) + c0 * c0) + c1 * c1;
-    if (!(D > 0.0) || !isfinite(D)) { acc[20] = tv_inf(); continue; }
+    if (!(D > 0.0) || !isfinite(D)) { acc[20] = pos_inf(); continue; }
     const double sD = sqrt(D), res = N / sD;
     double J[5];
 #pragma unroll
@@ -774,79 +643,18 @@ __device__ __forceinline__ void tv_normal_equations(const TvPair& P, const uint8
     }
     acc[20] += res * res;
   }
-  tv_block_sum(acc, sh_part, sh_tot);
-}
-
-// (H + lambda diag(H)) d = -g by Cholesky; false: not positive definite
-__device__ __forceinline__ bool tv_solve5(const double (&acc)[TV_ACC], double lambda, double d[5]) {
-  double L[5][5];
-  {
-    int c = 0;
-#pragma unroll
-    for (int m = 0; m < 5; ++m)
-#pragma unroll
-      for (int l = m; l < 5; ++l) { L[l][m] = acc[c]; ++c; }
-  }
-#pragma unroll
-  for (int m = 0; m < 5; ++m) L[m][m] += lambda * L[m][m];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    double s = L[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-    ok = ok && s > 0.0;
-    const double piv = sqrt(s);
-    L[j][j] = piv;
-#pragma unroll
-    for (int i = j + 1; i < 5; ++i) {
-      double v = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-      L[i][j] = v / piv;
-    }
-  }
-  double y[5];
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    double v = -acc[15 + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-    y[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = 4; i >= 0; --i) {
-    double v = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 5; ++k) v -= L[k][i] * d[k];
-    d[i] = v / L[i][i];
-    ok = ok && isfinite(d[i]);
-  }
-  return ok;
+  block_sum<TV_THREADS, TV_CHUNK>(acc, sh_part, sh_tot);
 }
 
 // x (+) d: QuaternionManifold::Plus [upstream Ceres manifold.cc] on q as section 19 moves it (q re-normalised); t along its
 // tangent basis and back onto the sphere
 __device__ __forceinline__ void tv_pose_plus(const double* q0, const double* t0, const double* d, double q1[4], double t1[3]) {
-  const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) q1[j] = q0[j];
-  if (nd != 0.0) {
-    const double sn = sin(nd) / nd;
-    const double qd[4] = {cos(nd), sn * d[0], sn * d[1], sn * d[2]};
-    q1[0] = qd[0] * q0[0] - qd[1] * q0[1] - qd[2] * q0[2] - qd[3] * q0[3];
-    q1[1] = qd[0] * q0[1] + qd[1] * q0[0] + qd[2] * q0[3] - qd[3] * q0[2];
-    q1[2] = qd[0] * q0[2] - qd[1] * q0[3] + qd[2] * q0[0] + qd[3] * q0[1];
-    q1[3] = qd[0] * q0[3] + qd[1] * q0[2] - qd[2] * q0[1] + qd[3] * q0[0];
-  }
-  const double inv = 1.0 / sqrt(q1[0] * q1[0] + q1[1] * q1[1] + q1[2] * q1[2] + q1[3] * q1[3]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) q1[j] *= inv;
+  quat_plus(q0, d, q1);
   double b1[3], b2[3];
   tv_tangent_basis(t0, b1, b2);
 #pragma unroll
   for (int j = 0; j < 3; ++j) t1[j] = (t0[j] + d[3] * b1[j]) + d[4] * b2[j];
-  const double it = 1.0 / sqrt(tv_dot(t1, t1));
+  const double it = 1.0 / sqrt(dot3(t1, t1));
 #pragma unroll
   for (int j = 0; j < 3; ++j) t1[j] *= it;
 }
@@ -861,7 +669,7 @@ __device__ __forceinline__ void tv_refine(const TvArgs& a, const TvPair& P, cons
   double lambda = 1e-4;
   for (int it = 0; it < a.o.refine_max_iterations; ++it) {
     double d[5], q1[4], t1[3];
-    if (!tv_solve5(acc, lambda, d)) {
+    if (!solve_damped<5>(acc, lambda, d)) {
       lambda *= 10.0;
       if (lambda > 1e12) break;
       continue;
@@ -938,7 +746,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
       }
       front[4] += in ? 1.0 : 0.0;
     }
-    tv_block_sum(front, sh_part, sh_tot);
+    block_sum<TV_THREADS, TV_CHUNK>(front, sh_part, sh_tot);
     if (!have) {
       if (tid == 0) { a.status[pi] = 3; a.n_inliers[pi] = 0; }
       return;
@@ -946,7 +754,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
     int pick = 0;
 #pragma unroll
     for (int m = 1; m < 4; ++m) if (front[m] > front[pick]) pick = m;
-    tv_rotation_to_quat(pick < 2 ? Ra : Rb, q);
+    rotation_to_quat(pick < 2 ? Ra : Rb, q);
     if (pick & 1) { t[0] = tm[0]; t[1] = tm[1]; t[2] = tm[2]; }
 
     // 3. local optimisation: refine on the inliers, classify again, until the set stands still
@@ -969,7 +777,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
         cc[0] += in ? 1.0 : 0.0;
         cc[1] += (in != (cur[P.o0 + j] != 0)) ? 1.0 : 0.0;
       }
-      tv_block_sum(cc, sh_part, sh_tot);
+      block_sum<TV_THREADS, TV_CHUNK>(cc, sh_part, sh_tot);
       if (cc[0] < (double)cur_cnt) break;                 // fewer inliers: the pose before it stays
 #pragma unroll
       for (int j = 0; j < 4; ++j) q[j] = q1[j];
@@ -986,7 +794,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
   tv_essential_of_pose(R, t, E);
   double fin[1] = {0.0};
   for (int j = tid; j < n; j += TV_THREADS) fin[0] += tv_sampson(E, P.rec(j)) <= thr2 ? 1.0 : 0.0;
-  tv_block_sum(fin, sh_part, sh_tot);
+  block_sum<TV_THREADS, TV_CHUNK>(fin, sh_part, sh_tot);
   const int n_in = (int)fin[0];
   const int need = max(a.o.min_num_inliers, (int)ceil(a.o.min_inlier_ratio * (double)n));
   if (n_in < need) {
@@ -1012,15 +820,6 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
     for (int j = 0; j < 9; ++j) a.E[9 * (size_t)pi + j] = E[j];
     a.status[pi] = 0; a.n_inliers[pi] = n_in;
   }
-}
-
-static int tv_grow_workspace(pxr_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->workspace_bytes) return PXR_OK;
-  PXR_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
-  PXR_HIP(hipMalloc(&ctx->d_workspace, bytes));
-  ctx->workspace_bytes = bytes;
-  return PXR_OK;
 }
 
 static int two_view_geometry(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
@@ -1051,35 +850,22 @@ static int two_view_geometry(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pai
 
   // offsets and cameras are validated on a host copy, which also gives the processing order: pairs by descending match count
   // (a stable counting sort), so that the longest start first
-  std::vector<int64_t> off((size_t)T + 1);
-  std::vector<int32_t> pcam((size_t)T * 2);
-  PXR_HIP(hipMemcpyAsync(off.data(), d_pair_offsets, sizeof(int64_t) * ((size_t)T + 1), hipMemcpyDeviceToHost, st));
+  std::vector<int64_t> off;
+  std::vector<int32_t> order, pcam((size_t)T * 2);
   PXR_HIP(hipMemcpyAsync(pcam.data(), d_pair_camera, sizeof(int32_t) * (size_t)T * 2, hipMemcpyDeviceToHost, st));
-  PXR_HIP(hipStreamSynchronize(st));
-  PXR_REQUIRE(off[0] == 0, "%s: pair_offsets[0] = %lld, not 0", fn, (long long)off[0]);
-  int64_t longest = 0;
-  for (int64_t t = 0; t < T; ++t) {
-    PXR_REQUIRE(off[t + 1] >= off[t], "%s: pair_offsets is not monotone at pair %lld", fn, (long long)t);
+  const auto cameras_in_range = [&](int64_t t) {
     for (int side = 0; side < 2; ++side)
       PXR_REQUIRE(pcam[2 * t + side] >= 0 && pcam[2 * t + side] < n_cameras, "%s: pair %lld names a camera outside [0, n_cameras = %d)", fn,
                   (long long)t, (int)n_cameras);
-    longest = std::max(longest, off[t + 1] - off[t]);
-  }
-  PXR_REQUIRE(off[T] == N, "%s: pair_offsets ends at %lld, not at n_matches = %lld", fn, (long long)off[T], (long long)N);
-  std::vector<int32_t> order((size_t)T);
-  {
-    std::vector<int64_t> first((size_t)longest + 2, 0);
-    for (int64_t t = 0; t < T; ++t) ++first[(size_t)(longest - (off[t + 1] - off[t])) + 1];
-    for (size_t k = 1; k < first.size(); ++k) first[k] += first[k - 1];
-    for (int64_t t = 0; t < T; ++t) order[(size_t)first[(size_t)(longest - (off[t + 1] - off[t]))]++] = (int32_t)t;
-  }
+    return (int)PXR_OK;
+  };
+  if (int rc = batch_order(ctx, {fn, "pair_offsets", "pair", "n_matches"}, false, d_pair_offsets, T, N, off, order, cameras_in_range)) return rc;
 
-  size_t wsz = 0;
-  auto carve = [&](size_t count, size_t elem) { const size_t p = wsz; wsz += (count * elem + 255) & ~(size_t)255; return p; };
-  const size_t o_rec = carve((size_t)N * TV_REC, 8), o_valid = carve((size_t)N, 1), o_pos = carve((size_t)N, 4);
-  const size_t o_ma = carve((size_t)N, 1), o_mb = carve((size_t)N, 1), o_nv = carve((size_t)T, 4), o_order = carve((size_t)T, 4);
-  const size_t o_win = carve((size_t)T * 3, 4), o_winE = carve((size_t)T * 9, 8);
-  if (int rc = tv_grow_workspace(ctx, wsz)) return rc;
+  Carver cv;
+  const size_t o_rec = cv.take((size_t)N * TV_REC, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
+  const size_t o_ma = cv.take((size_t)N, 1), o_mb = cv.take((size_t)N, 1), o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4);
+  const size_t o_win = cv.take((size_t)T * 3, 4), o_winE = cv.take((size_t)T * 9, 8);
+  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
   char* ws = static_cast<char*>(ctx->d_workspace);
   double* rec = (double*)(ws + o_rec);
   uint8_t* valid = (uint8_t*)(ws + o_valid);
@@ -1087,22 +873,20 @@ static int two_view_geometry(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pai
   int32_t* n_valid = (int32_t*)(ws + o_nv);
   int32_t* d_order = (int32_t*)(ws + o_order);
 
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // bearings | compact | hypotheses | refine
-  auto mark = [&](int k) { if (h_ms) (void)hipEventRecord(ev[k], st); };
-  auto drop = [&]() { for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } };
-  if (h_ms) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { drop(); return set_error(PXR_EHIP, "%s: hipEventCreate failed", fn); }
+  StageTimer<5> timer(st, h_ms);                         // bearings | compact | hypotheses | refine
+  if (int rc = timer.create(fn)) return rc;
 
   auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
   int rc = hip_check(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (`order` may go out of scope)
-  if (rc != PXR_OK) { drop(); return rc; }
-  mark(0);
+  if (rc != PXR_OK) return rc;
+  timer.mark(0);
   if (N > 0)
     hipLaunchKernelGGL(k_tv_bearings, blocks(N, TV_THREADS), dim3(TV_THREADS), 0, st, N, n_pairs, d_pair_offsets, d_pair_camera,
                        d_cam_model, d_cam_params, d_xy1, d_xy2, rec, valid, d_inlier, d_err);
-  mark(1);
-  hipLaunchKernelGGL(k_tv_compact, blocks(T, TV_THREADS), dim3(TV_THREADS), 0, st, n_pairs, d_pair_offsets, rec, valid, pos, n_valid);
-  mark(2);
+  timer.mark(1);
+  hipLaunchKernelGGL(k_compact_records<TV_REC>, blocks(T, TV_THREADS), dim3(TV_THREADS), 0, st, T, d_pair_offsets, rec, valid, pos, n_valid);
+  timer.mark(2);
   TvArgs a;
   a.offsets = d_pair_offsets; a.pair_camera = d_pair_camera; a.cam_model = d_cam_model; a.cam_params = d_cam_params;
   a.prior_qvec = d_prior_qvec; a.prior_tvec = d_prior_tvec;
@@ -1113,20 +897,12 @@ static int two_view_geometry(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pai
   a.inlier = d_inlier; a.err = d_err;
   a.winner = (int32_t*)(ws + o_win); a.winner_E = (double*)(ws + o_winE);
   if (!d_prior_qvec) hipLaunchKernelGGL(k_tv_hypotheses, dim3((unsigned)T), dim3(TV_THREADS), 0, st, a);
-  mark(3);
+  timer.mark(3);
   hipLaunchKernelGGL(k_tv_refine, dim3((unsigned)T), dim3(TV_THREADS), 0, st, a);
-  mark(4);
+  timer.mark(4);
   rc = hip_check(hipGetLastError(), "k_tv_refine launch");
-  if (rc == PXR_OK && h_ms) {
-    rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-    for (int k = 0; k < 4 && rc == PXR_OK; ++k) {
-      float ms = 0.f;
-      rc = hip_check(hipEventElapsedTime(&ms, ev[k], ev[k + 1]), "hipEventElapsedTime");
-      h_ms[k] = ms;
-    }
-  }
-  drop();
-  return rc;
+  const int from[4] = {0, 1, 2, 3};
+  return rc == PXR_OK ? timer.read(from, 4) : rc;
 }
 
 }  // namespace pxr

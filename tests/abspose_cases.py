@@ -35,26 +35,22 @@ def mix(z):
     return z ^ (z >> 31)
 
 
-def sample(seed, h, n, max_draws=256):
-    """Sample h of a query with n >= 4 usable correspondences: three distinct indices, ascending."""
+def sample(seed, h, n, k=3, max_draws=256):
+    """Sample h of an item with n > k usable records: k distinct indices, ascending (pxr_robust.h's sample_distinct<k>; three for
+    a query's P3P, five for a pair's essential matrix).  The draw counter is shared by the k indices.  (The kernel's written-out k = 3 form takes
+    one more draw for the third index where the second used up all max_draws: never in practice.)"""
     a = mix(seed + G * (h + 1))
-    draw = [0]
-
-    def nxt():
-        draw[0] += 1
-        return mix(a + G * draw[0]) % n
-    c0 = nxt()
-    c1 = nxt()
-    while c1 == c0 and draw[0] < max_draws:
-        c1 = nxt()
-    if c1 == c0:                  # (never in practice: the smallest unused index)
-        c1 = 1 if c0 == 0 else 0
-    c2 = nxt()
-    while c2 in (c0, c1) and draw[0] < max_draws:
-        c2 = nxt()
-    if c2 in (c0, c1):
-        c2 = min(c for c in (0, 1, 2) if c not in (c0, c1))
-    return tuple(sorted((c0, c1, c2)))
+    draw, idx = 0, []
+    for _ in range(k):
+        c, fresh = 0, False
+        while not fresh and draw < max_draws:
+            draw += 1
+            c = mix(a + G * draw) % n
+            fresh = c not in idx
+        if not fresh:                 # (never in practice: the smallest unused index)
+            c = min(x for x in range(k) if x not in idx)
+        idx.append(c)
+    return tuple(sorted(idx))
 
 
 # ---- camera models, vectorised (checked against the oracle in tests/test_abspose_cpu.py) ---------------------------------------
@@ -296,12 +292,15 @@ def refine(model, k, q, t, xy, X, o):
 
 
 # ---- the estimator -----------------------------------------------------------------------------------------------------------------
-def trials_needed(o, max_trials, cnt, n):
+def trials_needed(o, max_trials, cnt, n, k=3):
+    """Trials the stop rule asks for at cnt inliers among n, for samples of k (3 or 5; each kernel's own association of w^k)."""
+    assert k in (3, 5)
     need = float(max_trials)
     if cnt > 0:
         w = cnt / n
+        p_all_inliers = w * w * w if k == 3 else (w * w) * (w * w) * w
         with np.errstate(all="ignore"):
-            x = np.log(1.0 - o["confidence"]) / np.log(1.0 - w * w * w)
+            x = np.log(1.0 - o["confidence"]) / np.log(1.0 - p_all_inliers)
         if x < need:
             need = x
     return min(max(need, float(o["min_num_trials"])), float(max_trials))
@@ -476,6 +475,24 @@ def collinear_query(n=12, seed=3):
     return xy, X
 
 
+def eleven_models_queries():
+    """(batch, gt_qvec, gt_tvec): one noise-free query of 40 correspondences per camera model."""
+    models = sorted(tc.MODEL_PARAMS)
+    rng = np.random.default_rng(31)
+    xy, xyz, gq, gt = [], [], [], []
+    for m in models:
+        q, t = random_pose(rng)
+        p = np.concatenate([rng.uniform(-0.3, 0.3, (40, 2)), np.ones((40, 1))], 1) * rng.uniform(2, 20, (40, 1))
+        X = (p - t) @ synthetic.qvec_to_rotmat(q)
+        k = np.array(tc.MODEL_PARAMS[m], dtype=np.float64)
+        xy.append(np.array([pxo.world_to_pixel(m, k, q, t, x, jac=False)[0] for x in X]))
+        xyz.append(X); gq.append(q); gt.append(t)
+    batch = dict(query_offsets=np.arange(len(models) + 1, dtype=np.int64) * 40, xy=np.concatenate(xy), xyz=np.concatenate(xyz),
+                 query_camera=np.arange(len(models), dtype=np.int32), cam_model=np.array(models, np.int32),
+                 cam_params=tc.pad_params([tc.MODEL_PARAMS[m] for m in models]))
+    return batch, gq, gt
+
+
 # ---- the batch the lane emulation and the GPU are both held to ------------------------------------------------------------------
 BOUNDARY_COUNTS = (0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, LDS_CORR - 1, LDS_CORR, LDS_CORR + 1, 2 * LDS_CORR + 7)
 POSE_TOL = 1e-7        # rotation angle (rad) and |dt| / |t| between two implementations: both stop at a step <= 1e-12 on the same
@@ -483,14 +500,19 @@ POSE_TOL = 1e-7        # rotation angle (rad) and |dt| / |t| between two impleme
 ERR_TOL = 1e-6         # pixels, of the per-correspondence errors
 
 
+def boundary_inputs():
+    """The batch of boundary_batch() without its reference (tools/geometry_fingerprint.py)."""
+    counts = np.repeat(BOUNDARY_COUNTS, 5)
+    np.random.default_rng(11).shuffle(counts)
+    assert len(counts) == 75 and len(counts) % 4 != 0
+    return make_queries(counts, (1, 2, 8), seed=12, p_outlier=0.3)
+
+
 @functools.lru_cache(maxsize=None)
 def boundary_batch():
     """(batch, reference): correspondence counts around the wavefront, the workgroup and the LDS capacity S, five queries each,
     shuffled -- 75 queries, not a multiple of 4 -- with 30 % outliers, a pinhole, a radial and a fisheye camera."""
-    counts = np.repeat(BOUNDARY_COUNTS, 5)
-    np.random.default_rng(11).shuffle(counts)
-    batch = make_queries(counts, (1, 2, 8), seed=12, p_outlier=0.3)
-    assert len(counts) == 75 and len(counts) % 4 != 0
+    batch = boundary_inputs()
     return batch, reference(batch)
 
 

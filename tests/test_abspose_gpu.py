@@ -115,21 +115,8 @@ def test_invalid_arguments_are_refused(ctx):
 
 def test_all_eleven_camera_models(ctx):
     """Every model's undistortion and refinement Jacobian: noise-free queries end at a zero-residual pose."""
-    import pxo
-    from pixsfm_amd import synthetic
-    models = sorted(tc.MODEL_PARAMS)
-    rng = np.random.default_rng(31)
-    xy, xyz, gq, gt = [], [], [], []
-    for m in models:
-        q, t = ac.random_pose(rng)
-        p = np.concatenate([rng.uniform(-0.3, 0.3, (40, 2)), np.ones((40, 1))], 1) * rng.uniform(2, 20, (40, 1))
-        X = (p - t) @ synthetic.qvec_to_rotmat(q)
-        k = np.array(tc.MODEL_PARAMS[m], dtype=np.float64)
-        xy.append(np.array([pxo.world_to_pixel(m, k, q, t, x, jac=False)[0] for x in X]))
-        xyz.append(X); gq.append(q); gt.append(t)
-    batch = dict(query_offsets=np.arange(len(models) + 1, dtype=np.int64) * 40, xy=np.concatenate(xy), xyz=np.concatenate(xyz),
-                 query_camera=np.arange(len(models), dtype=np.int32), cam_model=np.array(models, np.int32),
-                 cam_params=tc.pad_params([tc.MODEL_PARAMS[m] for m in models]))
+    batch, gq, gt = ac.eleven_models_queries()
+    models = batch["cam_model"]
     got = _run(ctx, batch)
     assert (got["status"] == 0).all() and (got["n_inliers"] == 40).all()
     print("largest error over the eleven models, noise-free: %.3e px" % got["err"].max())

@@ -130,24 +130,8 @@ def test_invalid_arguments_are_refused(ctx):
 
 def test_all_eleven_camera_models(ctx):
     """Every model's undistortion: noise-free pairs of 40 matches end at a zero-residual pose (the lanes test's bounds)."""
-    import pxo
-    from pixsfm_amd import synthetic
-    models = sorted(tc.MODEL_PARAMS)
-    rng = np.random.default_rng(31)
-    xy1, xy2, gq, gt = [], [], [], []
-    ident = np.array([1.0, 0, 0, 0])
-    for i, m in enumerate(models):
-        m2 = models[(i + 1) % len(models)]
-        q, t = tv.random_relative_pose(rng)
-        X1 = np.concatenate([rng.uniform(-0.3, 0.3, (40, 2)), np.ones((40, 1))], 1) * rng.uniform(2, 20, (40, 1))
-        k1, k2 = (np.array(tc.MODEL_PARAMS[x], dtype=np.float64) for x in (m, m2))
-        xy1.append(np.array([pxo.world_to_pixel(m, k1, ident, np.zeros(3), x, jac=False)[0] for x in X1]))
-        xy2.append(np.array([pxo.world_to_pixel(m2, k2, q, t, x, jac=False)[0] for x in X1]))
-        gq.append(q); gt.append(t / np.linalg.norm(t))
-    L = len(models)
-    batch = dict(pair_offsets=np.arange(L + 1, dtype=np.int64) * 40, xy1=np.concatenate(xy1), xy2=np.concatenate(xy2),
-                 pair_camera=np.stack([np.arange(L), (np.arange(L) + 1) % L], 1).astype(np.int32), cam_model=np.array(models, np.int32),
-                 cam_params=tc.pad_params([tc.MODEL_PARAMS[m] for m in models]))
+    batch, gq, gt = tv.eleven_models_pairs()
+    L = len(batch["cam_model"])
     got = _run(ctx, batch)
     assert (got["status"] == 0).all() and (got["n_inliers"] == 40).all()
     d = np.array([tv.pose_distance(gq[i], gt[i], got["qvec"][i], got["tvec"][i]) for i in range(L)])

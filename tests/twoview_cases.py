@@ -29,24 +29,9 @@ IMAGE = ac.IMAGE
 PIVOT_TOL, LEAD_TOL, TRIM_TOL = 1e-12, 1e-9, 1e-12
 BISECT, NEWTON = 64, 4
 
-mix, G, M64 = ac.mix, ac.G, ac.M64
-
-
-# ---- samples ---------------------------------------------------------------------------------------------------------------------
-def sample(seed, h, n, max_draws=256):
-    """Sample h of a pair with n >= 5 usable matches: five distinct indices, ascending."""
-    a = mix(seed + G * (h + 1))
-    draw, idx = 0, []
-    for _ in range(5):
-        c, fresh = 0, False
-        while not fresh and draw < max_draws:
-            draw += 1
-            c = mix(a + G * draw) % n
-            fresh = c not in idx
-        if not fresh:                 # (never in practice: the smallest unused index)
-            c = min(x for x in range(5) if x not in idx)
-        idx.append(c)
-    return tuple(sorted(idx))
+# ---- samples and the stop rule: ac's, for samples of five --------------------------------------------------------------------------
+sample = functools.partial(ac.sample, k=5)
+trials_needed = functools.partial(ac.trials_needed, k=5)
 
 
 # ---- polynomials in (x, y, z, 1) = variables 0 .. 3 -------------------------------------------------------------------------------
@@ -443,17 +428,6 @@ def refine(q, t, rec, o):
 
 
 # ---- the estimator -----------------------------------------------------------------------------------------------------------------
-def trials_needed(o, max_trials, cnt, n):
-    need = float(max_trials)
-    if cnt > 0:
-        w = cnt / n
-        with np.errstate(all="ignore"):
-            x = np.log(1.0 - o["confidence"]) / np.log(1.0 - (w * w) * (w * w) * w)
-        if x < need:
-            need = x
-    return min(max(need, float(o["min_num_trials"])), float(max_trials))
-
-
 def _params(model, params):
     return np.asarray(params, dtype=np.float64)[:pxo.lib().pxo_camera_num_params(int(model))]
 
@@ -678,6 +652,27 @@ def noise_free_samples(B, seed):
     return rec, Rs, ts
 
 
+def eleven_models_pairs():
+    """(batch, gt_qvec, gt_tvec): one noise-free pair of 40 matches per camera model, its second camera the next model."""
+    models = sorted(tc.MODEL_PARAMS)
+    rng = np.random.default_rng(31)
+    xy1, xy2, gq, gt = [], [], [], []
+    ident = np.array([1.0, 0, 0, 0])
+    for i, m in enumerate(models):
+        m2 = models[(i + 1) % len(models)]
+        q, t = random_relative_pose(rng)
+        X1 = np.concatenate([rng.uniform(-0.3, 0.3, (40, 2)), np.ones((40, 1))], 1) * rng.uniform(2, 20, (40, 1))
+        k1, k2 = (np.array(tc.MODEL_PARAMS[x], dtype=np.float64) for x in (m, m2))
+        xy1.append(np.array([pxo.world_to_pixel(m, k1, ident, np.zeros(3), x, jac=False)[0] for x in X1]))
+        xy2.append(np.array([pxo.world_to_pixel(m2, k2, q, t, x, jac=False)[0] for x in X1]))
+        gq.append(q); gt.append(t / np.linalg.norm(t))
+    L = len(models)
+    batch = dict(pair_offsets=np.arange(L + 1, dtype=np.int64) * 40, xy1=np.concatenate(xy1), xy2=np.concatenate(xy2),
+                 pair_camera=np.stack([np.arange(L), (np.arange(L) + 1) % L], 1).astype(np.int32), cam_model=np.array(models, np.int32),
+                 cam_params=tc.pad_params([tc.MODEL_PARAMS[m] for m in models]))
+    return batch, gq, gt
+
+
 # ---- the batch the lane emulation and the GPU are both held to ------------------------------------------------------------------
 BOUNDARY_COUNTS = (0, 1, 4, 5, 6, 14, 15, 16, 63, 64, 65, 255, 256, 257, LDS_MATCHES - 1, LDS_MATCHES, LDS_MATCHES + 1, 2 * LDS_MATCHES + 7)
 POSE_CAP, ERR_CAP = 1e-7, 1e-6      # section 19's bounds: no bound of this estimator may exceed them
@@ -691,15 +686,20 @@ ERR_TOL = min(1000 * 3.5e-13, ERR_CAP)         # pixels, of the per-match Sampso
 BOUNDARY_SEED = 12     # one for which the reference ends at the generated inlier set on every pair (asserted by the tests)
 
 
+def boundary_inputs():
+    """The batch of boundary_batch() without its reference (tools/geometry_fingerprint.py)."""
+    counts = np.repeat(BOUNDARY_COUNTS, 3)
+    np.random.default_rng(11).shuffle(counts)
+    assert len(counts) == 54 and len(counts) % 4 != 0
+    return make_pairs(counts, (1, 2, 8), seed=BOUNDARY_SEED, p_outlier=0.3)
+
+
 @functools.lru_cache(maxsize=None)
 def boundary_batch():
     """(batch, reference): match counts around the minimal sample, min_num_inliers, the wavefront, the workgroup and the LDS
     capacity S, three pairs each, shuffled -- 54 pairs, not a multiple of 4 -- with 30 % outliers, a pinhole, a radial and a
     fisheye camera."""
-    counts = np.repeat(BOUNDARY_COUNTS, 3)
-    np.random.default_rng(11).shuffle(counts)
-    batch = make_pairs(counts, (1, 2, 8), seed=BOUNDARY_SEED, p_outlier=0.3)
-    assert len(counts) == 54 and len(counts) % 4 != 0
+    batch = boundary_inputs()
     return batch, reference(batch)
 
 
