@@ -597,6 +597,79 @@ int pxr_two_view_geometry_timed(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_
                                 const pxr_two_view_options* options, double* d_qvec, double* d_tvec, double* d_E, int32_t* d_status,
                                 int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err, double* h_kernel_ms);
 
+/* ---- homography estimation (the matches of image pairs in, one homography, one rotation-only model and one inlier mask per
+ * pair out) ----
+ * The planar / panoramic half of geometric verification: pycolmap.verify_matches classifies a pair from the ratio of homography
+ * inliers to essential-matrix inliers, because an essential matrix fits a pure-rotation or a planar pair with a translation
+ * direction that means nothing.  For calibrated cameras only (fundamental-matrix estimation is not provided).  The batch is laid
+ * out like pxr_two_view_geometry's, and the options are its options with its defaults (COLMAP 3.8's values as remembered, parity
+ * UNPINNED; min_num_trials, round_size, seed, refine_max_iterations and lo_rounds are this estimator's own). */
+typedef struct {
+  double max_error;             /* 4.0      pixels: inlier threshold on the forward transfer error in image 2             */
+  double min_inlier_ratio;      /* 0.25     success needs n_inliers >= max(min_num_inliers, ceil(min_inlier_ratio n))      */
+  double confidence;            /* 0.999    of the stop rule                                                              */
+  uint64_t seed;                /* 0        of the sample hash                                                            */
+  int32_t min_num_inliers;      /* 15                                                                                     */
+  int32_t min_num_trials;       /* 64       lower clamp of the stop rule                                                  */
+  int32_t max_num_trials;       /* 10000    upper clamp of the stop rule, rounded up to a multiple of round_size          */
+  int32_t round_size;           /* 64       samples per round: the stop rule is evaluated at round boundaries only        */
+  int32_t refine_max_iterations;/* 100      Levenberg-Marquardt iterations per refinement                                 */
+  int32_t lo_rounds;            /* 4        at most this many refine / re-classify repetitions                            */
+} pxr_homography_options;
+/* Writes the defaults above. */
+void pxr_homography_default_options(pxr_homography_options* options);
+
+/* Homography estimation for a batch of image pairs, deterministic like pxr_two_view_geometry: no random state, a pair alone and the
+ * same pair inside any batch give the same bits.  Pair p owns matches [d_pair_offsets[p],
+ * d_pair_offsets[p+1]).  H maps the normalised plane of camera 1 to that of camera 2: x2 ~ H (x1, y1, 1).  Per pair:
+ *   1. usable matches and records exactly as in step 1 of pxr_two_view_geometry: both pixels go through ImageToWorld, the record
+ *      is (x1, y1, x2, y2) in the normalised plane; n = the usable ones, in order; n < 4: status 1.
+ *   2. sample h = 0, 1, ... is four distinct indices from the hash of pxr_two_view_geometry's step 2, used in ascending order.
+ *   3. the four-point solver: the 8 x 9 DLT system, per match the rows (0, 0, 0, -x1, -y1, -1, y2 x1, y2 y1, y2) and
+ *      (x1, y1, 1, 0, 0, 0, -x2 x1, -x2 y1, -x2); its null vector by Gauss-Jordan with full pivoting (the largest entry, the first
+ *      of equals in row-major order; the vector (-C[:, 0], e_0) of [I | C] in the permuted columns), scaled to Frobenius norm 1
+ *      (the squares summed in index order).  No hypothesis from a pivot <= 1e-12 of the system's largest entry or a value that
+ *      is not finite.  Sign: w_i = H[2] . (x1_i, y1_i, 1) over the four sample matches; all positive keeps H, all negative
+ *      negates it, mixed signs or a zero give no hypothesis.
+ *   4. each H is scored over all n by the squared forward transfer error in image 2, err = |pi(H x1) - x2|^2 with
+ *      pi(X, Y, W) = (X / W, Y / W), and +inf where W <= 0; inlier iff err <= thr^2, thr = max_error / f2 with f2 the mean focal
+ *      length of camera 2; the largest key (inlier count, -sum min(err, thr^2), -h) wins, the sum taken in index order.
+ *   5. after each round of round_size samples: stop once samples done >= clamp(log(1 - confidence) / log(1 - (w w) (w w)),
+ *      min_num_trials, max_num_trials), w = min(max(best count, need) / n, 1), need = max(min_num_inliers,
+ *      ceil(min_inlier_ratio n)).  The floor `need` is deliberate: a pair that admits no homography -- the usual case in a general
+ *      scene -- stops once a model that could pass step 8 would have been found at the configured confidence (1765 samples at
+ *      ratio 0.25, rounded up to the round: 1792) and does not run to max_num_trials.  No hypothesis at all: status 2.
+ *   6. local optimisation: Levenberg-Marquardt on the inliers' two residuals pi(H x1) - x2 per match over eight parameters: the
+ *      entry of largest magnitude of the unit-norm H is held fixed (the first of equals), the other eight move additively;
+ *      lambda from 1e-4, x 0.1 (not below 1e-12) on a kept step, x 10 on a refused or unsolvable one, until lambda > 1e12, a step
+ *      of norm <= 1e-12 or refine_max_iterations; a step is kept unless the cost grows by more than 1e-12 of itself; H is scaled
+ *      back to Frobenius norm 1 after the refinement, then all n are classified again; repeated until the set stands still or
+ *      lo_rounds; a refined H with fewer inliers than the one before it is dropped.
+ *   7. the rotation-only model (the panoramic test), on the final H of a pair that passes step 8: H with its sign chosen so that det H >= 0; R0 from
+ *      its rows by modified Gram-Schmidt (row 0, row 1, then their cross product; a row of norm <= 1e-12 ends the step with
+ *      n_rot_inliers = 0 and d_rot_qvec untouched); its quaternion refined by the Levenberg-Marquardt of step 6 over the three
+ *      parameters of the quaternion manifold (as in pxr_absolute_pose) on the H inliers' transfer residuals under H = R; all n
+ *      classified under R with the same thr: that count is n_rot_inliers.
+ *   8. n_inliers < need: status 3.
+ * Outputs: d_status[p] 0 = H (row-major, normalised plane, Frobenius norm 1, third component positive on every inlier) written to
+ * d_H[p] and the rotation to d_rot_qvec[p] (unit, w >= 0), both left untouched otherwise; d_n_inliers[p] and d_n_rot_inliers[p]
+ * (0 unless status is 0); d_n_trials[p] samples drawn; per match d_inlier (0 unless status is 0) and d_err (sqrt(err) max_error /
+ * thr, i.e. the transfer error in pixels, of the usable matches of a status-0 pair; NaN elsewhere and where W <= 0).
+ * PXR_EINVAL (nothing launched): offsets not starting at 0, not monotone or not ending at n_matches, a camera index out of
+ * range, an option out of range.
+ * Synchronises the context's stream (offsets and cameras are validated and the pairs ordered by size on the host). */
+int pxr_homography(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
+                   const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,
+                   const double* d_cam_params, const pxr_homography_options* options, double* d_H, double* d_rot_qvec,
+                   int32_t* d_status, int32_t* d_n_inliers, int32_t* d_n_rot_inliers, int32_t* d_n_trials, uint8_t* d_inlier,
+                   double* d_err);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[4] = records, compaction, hypotheses, refinement. */
+int pxr_homography_timed(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
+                         const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,
+                         const double* d_cam_params, const pxr_homography_options* options, double* d_H, double* d_rot_qvec,
+                         int32_t* d_status, int32_t* d_n_inliers, int32_t* d_n_rot_inliers, int32_t* d_n_trials, uint8_t* d_inlier,
+                         double* d_err, double* h_kernel_ms);
+
 /* ---- descriptor matching (descriptors of image pairs in, mutual nearest neighbours out) --------
  * What produces the match graph (and a query's 2D-3D pairs): hloc's match_features with the NearestNeighbor matcher, whose output
  * pixsfm/util/hloc.py:read_matches_hloc reads back.  hloc is not available where this library is built, so parity with it is

@@ -111,6 +111,11 @@ class TwoViewOptions(C.Structure):
 TWOVIEW_LDS_MATCHES = 1024   # PXR_TWOVIEW_LDS_MATCHES
 
 
+class HomographyOptions(C.Structure):
+    """pxr_homography_options"""
+    _fields_ = list(TwoViewOptions._fields_)
+
+
 class MatchOptions(C.Structure):
     """pxr_match_options"""
     _fields_ = [("ratio_threshold", C.c_double), ("distance_threshold", C.c_double), ("do_mutual_check", C.c_int32),
@@ -180,6 +185,13 @@ _SIGNATURES = {
                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TwoViewOptions),
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.POINTER(C.c_double)]),
+    "pxr_homography_default_options": (None, [C.POINTER(HomographyOptions)]),
+    "pxr_homography": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.POINTER(HomographyOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pxr_homography_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.POINTER(HomographyOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_match_default_options": (None, [C.POINTER(MatchOptions)]),
     "pxr_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,7 @@
 """pixsfm-compatible Python surface of the accelerated KA/BA path (same class / method names as
 pixsfm.keypoint_adjustment, pixsfm.bundle_adjustment, pixsfm._pixsfm._base/_features)."""
 from . import base, extract, features, localization, reconstruction, triangulation, two_view  # noqa: F401
+from . import homography  # noqa: F401,E402
 from .bundle_adjustment import (BundleAdjuster, BundleAdjustmentSetup, CostMapBundleAdjuster,  # noqa: F401
                                 CostMapBundleOptimizer, CostMapExtractor, FeatureReferenceBundleAdjuster,
                                 FeatureReferenceBundleOptimizer, FeatureView, GeometricBundleAdjuster,
@@ -19,3 +20,4 @@ from .extract import (FeatureExtractor, extract_patchdata_from_graph, features_f
 from .triangulation import TrackTriangulator  # noqa: F401,E402
 from .matching import DescriptorMatcher, pairs_2d3d_from_matches  # noqa: F401,E402
 from .two_view import TwoViewVerifier, essential_matrix_estimation  # noqa: F401,E402
+from .homography import TwoViewClassifier, homography_matrix_estimation, two_view_config  # noqa: F401,E402

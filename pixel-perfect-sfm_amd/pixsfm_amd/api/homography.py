@@ -1,0 +1,161 @@
+"""Homography estimation and two-view configurations for the accelerated path.
+
+An essential matrix fits a pair taken by a rotating camera, or a pair that shows one plane, with a translation direction that
+means nothing, and nothing `TwoViewVerifier` returns says so.  pycolmap.verify_matches, which that class stands in for,
+classifies such pairs from the ratio of homography inliers to essential-matrix inliers; COLMAP is not installable where this
+library runs, so the stage is native here, for calibrated cameras: a batched, deterministic four-point estimator with local
+optimisation and a rotation-only model on the GPU (pxr_homography; DESIGN.md section 22 -- NOT COLMAP's LO-RANSAC, and the
+classes are decided by this library's own rules: parity with COLMAP is not pinned).  Fundamental-matrix estimation is not
+provided.
+
+`TwoViewClassifier.create(conf).classify_pairs(keypoints, cameras, pairs, matches, scores)` has the shape of
+`TwoViewVerifier.verify_pairs`; `homography_matrix_estimation` has pycolmap's shape.
+"""
+import inspect
+
+import numpy as np
+
+from ..engine import HomographyProblem, TwoViewProblem, homography_options
+from . import two_view as _tv
+from .keypoint_adjustment import default_context
+
+_DEFAULTS = {name: p.default for name, p in inspect.signature(homography_options).parameters.items()}
+_OPTION_KEYS = tuple(_DEFAULTS)
+_NAMES = ("H", "rot_qvec", "status", "n_inliers", "n_rot_inliers", "n_trials", "inlier", "err")
+CONFIGS = ("CALIBRATED", "PLANAR", "PANORAMIC", "DEGENERATE")
+
+
+def homography_engine_options(options=None):
+    """The keyword arguments of engine.homography_options for an option dict (a nested "ransac" dict, as pycolmap groups them,
+    is flattened).  Unknown keys raise ValueError."""
+    opts = dict(options or {})
+    ransac = opts.pop("ransac", None) or {}
+    out = {}
+    for k, v in list(dict(ransac).items()) + list(opts.items()):
+        if k not in _OPTION_KEYS:
+            raise ValueError("unknown homography option %r (known: %s)" % (k, ", ".join(_OPTION_KEYS)))
+        out[k] = v
+    homography_options(**out)                 # fail early on a value ctypes cannot take
+    return out
+
+
+def two_view_config(e_success, n_e, h_success, n_h, n_r, max_H_inlier_ratio=0.8):
+    """The class of a pair from what the two estimators report, the rules applied in this order:
+    DEGENERATE  neither model succeeded
+    CALIBRATED  E succeeded and n_H / n_E <= max_H_inlier_ratio
+    PANORAMIC   n_H / n_E above it, or only H succeeded -- and n_R / n_H > max_H_inlier_ratio
+    PLANAR      the same, without the second condition."""
+    if not e_success and not h_success:
+        return "DEGENERATE"
+    if e_success and (not h_success or n_h <= max_H_inlier_ratio * n_e):
+        return "CALIBRATED"
+    return "PANORAMIC" if n_r > max_H_inlier_ratio * n_h else "PLANAR"
+
+
+def _identity_camera():
+    from .reconstruction import Camera
+    return Camera(0, 0, 1, 1, [1.0, 0.0, 0.0])
+
+
+def _calibration_matrix(camera):
+    k = camera.params
+    if camera.model_id == 0:
+        return np.array([[k[0], 0.0, k[1]], [0.0, k[0], k[2]], [0.0, 0.0, 1.0]])
+    return np.array([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]])
+
+
+def homography_matrix_estimation(points1, points2, options=None, camera1=None, camera2=None, ctx=None):
+    """pycolmap.homography_matrix_estimation's shape: {"success", "H" (3, 3), "num_inliers", "inliers"}, or {"success": False}.
+    points: (n, 2).  Without cameras the points are used as they are (the stand-in is an identity SIMPLE_PINHOLE camera), so
+    max_error is in the points' units and x2 ~ H x1 in those units.  With two cameras the points are pixels (COLMAP convention),
+    H maps the normalised plane of camera 1 to that of camera 2 (unit Frobenius norm), and for two pinhole-family cameras
+    (SIMPLE_PINHOLE, PINHOLE) "H_pixels" = K2 H K1^-1 is returned too."""
+    opts = homography_engine_options(options)
+    xy1, xy2 = np.asarray(points1, dtype=np.float64).reshape(-1, 2), np.asarray(points2, dtype=np.float64).reshape(-1, 2)
+    if len(xy1) != len(xy2):
+        raise ValueError("points1 and points2 must have the same length")
+    if (camera1 is None) != (camera2 is None):
+        raise ValueError("camera1 and camera2 go together")
+    cams = [_identity_camera()] * 2 if camera1 is None else [camera1, camera2]
+    index, model, params = _tv._camera_table(cams)
+    batch = dict(pair_offsets=np.array([0, len(xy1)], np.int64), xy1=xy1, xy2=xy2, pair_camera=index.reshape(1, 2), cam_model=model,
+                 cam_params=params)
+    ctx = ctx or default_context()
+    res = {k: a.download() for k, a in zip(_NAMES, HomographyProblem(ctx, batch).estimate(**opts))}
+    if res["status"][0] != 0:
+        return {"success": False}
+    H = res["H"][0].reshape(3, 3).copy()
+    out = {"success": True, "H": H, "num_inliers": int(res["n_inliers"][0]), "inliers": [bool(x) for x in res["inlier"]]}
+    if camera1 is not None and camera1.model_id in (0, 1) and camera2.model_id in (0, 1):
+        out["H_pixels"] = _calibration_matrix(camera2) @ H @ np.linalg.inv(_calibration_matrix(camera1))
+    return out
+
+
+class TwoViewClassifier:
+    """Geometric verification with a verdict on the configuration: the essential-matrix estimator of TwoViewVerifier and the
+    homography estimator on the same batch, and per pair one of CONFIGS."""
+    default_conf = {"two_view": dict(_tv._DEFAULTS), "homography": dict(_DEFAULTS), "max_H_inlier_ratio": 0.8,
+                    "keep": ("CALIBRATED", "PLANAR", "PANORAMIC")}
+
+    def __init__(self, conf=None, ctx=None):
+        conf = dict(conf or {})
+        for k in conf:
+            if k not in self.default_conf:
+                raise ValueError("unknown classifier option %r (known: %s)" % (k, ", ".join(self.default_conf)))
+        keep = tuple(conf.get("keep", self.default_conf["keep"]))
+        for c in keep:
+            if c not in CONFIGS:
+                raise ValueError("unknown configuration %r in keep (known: %s)" % (c, ", ".join(CONFIGS)))
+        self.conf = {"two_view": {**_tv._DEFAULTS, **_tv.two_view_engine_options(conf.get("two_view"))},
+                     "homography": {**_DEFAULTS, **homography_engine_options(conf.get("homography"))},
+                     "max_H_inlier_ratio": float(conf.get("max_H_inlier_ratio", self.default_conf["max_H_inlier_ratio"])), "keep": keep}
+        self.ctx = ctx
+
+    @classmethod
+    def create(cls, conf=None, ctx=None):
+        """conf: a dict over default_conf; unknown keys, at either level, raise ValueError."""
+        return cls(conf, ctx)
+
+    def classify_pairs(self, keypoints, cameras, pairs, matches, scores=None):
+        """The arguments of TwoViewVerifier.verify_pairs (without poses).  All pairs go through both estimators in one launch each.
+        Returns (matches, scores, geometries): per pair the dict TwoViewVerifier returns for the essential matrix ("success" is
+        the essential matrix's) plus "config", "H" ((3, 3), normalised plane, or None), "num_inliers_H" and "num_inliers_R";
+        the matches and scores are the inliers of the model with more inliers (the essential matrix on a tie), and none for a
+        pair whose class is not in conf["keep"]."""
+        pairs, matches = list(pairs), list(matches)
+        if len(pairs) != len(matches) or (scores is not None and len(scores) != len(pairs)):
+            raise ValueError("pairs, matches and scores must have the same length")
+        if not pairs:
+            return [], (None if scores is None else []), []
+        xy1, xy2, cams = [], [], []
+        for (a, b), m in zip(pairs, matches):
+            for n in (a, b):
+                if n not in keypoints or n not in cameras:
+                    raise KeyError("no keypoints or camera for image %r" % (n,))
+            m = np.asarray(m).reshape(-1, 2).astype(np.int64)
+            xy1.append(np.asarray(keypoints[a], dtype=np.float64)[m[:, 0], :2])
+            xy2.append(np.asarray(keypoints[b], dtype=np.float64)[m[:, 1], :2])
+            cams += [cameras[a], cameras[b]]
+        index, model, params = _tv._camera_table(cams)
+        off = np.concatenate([[0], np.cumsum([len(a) for a in xy1])]).astype(np.int64)
+        batch = dict(pair_offsets=off, xy1=np.concatenate(xy1).reshape(-1, 2), xy2=np.concatenate(xy2).reshape(-1, 2),
+                     pair_camera=index.reshape(-1, 2), cam_model=model, cam_params=params)
+        ctx = self.ctx or default_context()
+        prob = TwoViewProblem(ctx, batch)
+        res_e = {k: a.download() for k, a in zip(_tv._NAMES, prob.estimate(**self.conf["two_view"]))}
+        res_h = {k: a.download() for k, a in zip(_NAMES, HomographyProblem(ctx, prob).estimate(**self.conf["homography"]))}
+        out_m, out_s, geoms = [], [], []
+        for p, m in enumerate(matches):
+            e_ok, h_ok = bool(res_e["status"][p] == 0), bool(res_h["status"][p] == 0)
+            n_e, n_h, n_r = int(res_e["n_inliers"][p]), int(res_h["n_inliers"][p]), int(res_h["n_rot_inliers"][p])
+            g = _tv._geometry(res_e, p, off[p], off[p + 1])
+            g.update(config=two_view_config(e_ok, n_e, h_ok, n_h, n_r, self.conf["max_H_inlier_ratio"]),
+                     H=res_h["H"][p].reshape(3, 3).copy() if h_ok else None, num_inliers_H=n_h, num_inliers_R=n_r)
+            keep = (res_h if n_h > n_e else res_e)["inlier"][off[p]:off[p + 1]].astype(bool)
+            if g["config"] not in self.conf["keep"]:
+                keep = np.zeros(len(keep), bool)
+            out_m.append(np.asarray(m).reshape(-1, 2)[keep])
+            if scores is not None:
+                out_s.append(np.asarray(scores[p]).reshape(-1)[keep])
+            geoms.append(g)
+        return out_m, (out_s if scores is not None else None), geoms

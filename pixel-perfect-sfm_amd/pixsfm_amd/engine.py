@@ -998,6 +998,74 @@ class TwoViewProblem:
         return d_q, d_t, d_E, d_status, d_ninl, d_ntr, d_inl, d_err
 
 
+def homography_options(max_error=4.0, min_inlier_ratio=0.25, min_num_inliers=15, confidence=0.999, min_num_trials=64,
+                       max_num_trials=10000, round_size=64, seed=0, refine_max_iterations=100, lo_rounds=4):
+    """pxr_homography_options: the fields and defaults of two_view_options, as the homography estimator's own struct."""
+    return _lib.HomographyOptions(float(max_error), float(min_inlier_ratio), float(confidence), int(seed), int(min_num_inliers),
+                                  int(min_num_trials), int(max_num_trials), int(round_size), int(refine_max_iterations), int(lo_rounds))
+
+
+class HomographyProblem:
+    """Device-resident flat arrays of a batch of image pairs (pxr_homography): the batch dict of TwoViewProblem without a pose
+    prior -- pair_offsets (n_pairs + 1), xy1 / xy2 (n_matches x 2, image pixels, COLMAP convention), pair_camera (n_pairs x 2),
+    cam_model, cam_params (n_cams x <= KPAD).  A TwoViewProblem in place of the dict shares its device arrays: both estimators
+    on one upload.
+    """
+
+    def __init__(self, ctx, batch):
+        self.ctx = ctx
+        self.kernel_ms = None
+        if isinstance(batch, TwoViewProblem):
+            self.n_pairs, self.n_matches, self.n_cameras, self.d = batch.n_pairs, batch.n_matches, batch.n_cameras, batch.d
+            return
+        g = batch
+        offsets = np.ascontiguousarray(g["pair_offsets"], dtype=np.int64).reshape(-1)
+        if len(offsets) < 1:
+            raise ValueError("pair_offsets must hold n_pairs + 1 entries")
+        self.n_pairs = len(offsets) - 1
+        xy1 = np.ascontiguousarray(g["xy1"], dtype=np.float64).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(g["xy2"], dtype=np.float64).reshape(-1, 2)
+        if len(xy1) != len(xy2):
+            raise ValueError("xy1 and xy2 must hold one row per match")
+        self.n_matches = len(xy1)
+        self.n_cameras = len(g["cam_model"])
+        pair_camera = np.ascontiguousarray(g["pair_camera"], dtype=np.int32).reshape(-1, 2)
+        if len(pair_camera) != self.n_pairs:
+            raise ValueError("pair_camera must hold two cameras per pair")
+        self.d = {
+            "pair_offsets": ctx.to_device(offsets, np.int64),
+            "xy1": ctx.to_device(xy1, np.float64),
+            "xy2": ctx.to_device(xy2, np.float64),
+            "pair_camera": ctx.to_device(pair_camera, np.int32),
+            "cam_model": ctx.to_device(g["cam_model"], np.int32),
+            "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
+        }
+        self.kernel_ms = None
+
+    def estimate(self, H=None, rot_qvec=None, timed=False, **options):
+        """Run the kernels (pxr_homography) with homography_options(**options).  Returns the device arrays (H (n_pairs, 9),
+        rot_qvec (n_pairs, 4), status, n_inliers, n_rot_inliers, n_trials (n_pairs,) int32, inlier (n_matches,) uint8, err
+        (n_matches,) float64).  H / rot_qvec: host arrays the outputs start from -- rows of pairs without a homography keep them
+        (default: NaN).  timed: also keep the kernels' HIP-event times in self.kernel_ms {"records", "compact", "hypotheses",
+        "refine"} (milliseconds)."""
+        ctx, d, T, N = self.ctx, self.d, self.n_pairs, self.n_matches
+        opts = homography_options(**options)
+        start = lambda a, w: np.full((T, w), np.nan) if a is None else np.asarray(a, dtype=np.float64).reshape(T, w)
+        d_H, d_q = (ctx.to_device(start(a, w), np.float64) for a, w in ((H, 9), (rot_qvec, 4)))
+        d_status, d_ninl, d_nrot, d_ntr = (ctx.empty((T,), np.int32) for _ in range(4))
+        d_inl, d_err = ctx.empty((N,), np.uint8), ctx.empty((N,), np.float64)
+        args = (ctx.handle, T, d["pair_offsets"].ptr, N, d["xy1"].ptr, d["xy2"].ptr, d["pair_camera"].ptr, self.n_cameras,
+                d["cam_model"].ptr, d["cam_params"].ptr, C.byref(opts), d_H.ptr, d_q.ptr, d_status.ptr, d_ninl.ptr, d_nrot.ptr,
+                d_ntr.ptr, d_inl.ptr, d_err.ptr)
+        if timed:
+            ms = (C.c_double * 4)()
+            check(ctx.lib.pxr_homography_timed(*args, ms), "pxr_homography_timed")
+            self.kernel_ms = dict(zip(("records", "compact", "hypotheses", "refine"), (float(x) for x in ms)))
+        else:
+            check(ctx.lib.pxr_homography(*args), "pxr_homography")
+        return d_H, d_q, d_status, d_ninl, d_nrot, d_ntr, d_inl, d_err
+
+
 MATCH_CONFS = {            # hloc's match_features confs for its NearestNeighbor matcher
     "NN-mutual": dict(ratio_threshold=0.0, distance_threshold=0.0, do_mutual_check=True),
     "NN-ratio": dict(ratio_threshold=0.8, distance_threshold=0.0, do_mutual_check=True),

@@ -1,7 +1,7 @@
 """One SHA-256 per case over every output of the batched geometry stages -- absolute pose, two-view geometry (estimating, and
-with a pose prior), triangulation, descriptor matching -- timings excluded.
+with a pose prior), triangulation, descriptor matching, homography estimation -- timings excluded.
 
-A refactor of pxr_abspose.hip, pxr_twoview.hip, pxr_triangulate.hip, pxr_match.hip or of the headers they share (pxr_robust.h,
+A refactor of pxr_abspose.hip, pxr_twoview.hip, pxr_triangulate.hip, pxr_match.hip, pxr_homography.hip or of the headers they share (pxr_robust.h,
 pxr_batch.h) must leave every line of this output unchanged: run it before and after on the same machine and compare.  Only the
 public engine API is used, and the seeded generators the tests use (tests/*_cases.py, the repository's own oracle for the
 camera models).
@@ -35,6 +35,11 @@ def abspose(ctx, batch):
 def twoview(ctx, batch):
     from pixsfm_amd.engine import TwoViewProblem
     return digest(TwoViewProblem(ctx, batch).estimate())
+
+
+def homography(ctx, batch):
+    from pixsfm_amd.engine import HomographyProblem
+    return digest(HomographyProblem(ctx, batch).estimate())
 
 
 def triangulation(ctx, scene):
@@ -73,6 +78,10 @@ def cases(ctx):
     yield "twoview_eleven_models", lambda: twoview(ctx, p11)
     scene = tc.make_scene(np.random.default_rng(2).integers(2, 12, 4 * len(models)), n_cams=2 * len(models), models=tuple(models), seed=4, arc=9)
     yield "triangulation_eleven_models", lambda: triangulation(ctx, scene)
+    import homography_cases as hc
+    planes = hc.boundary_inputs()
+    yield "homography_boundaries", lambda: homography(ctx, planes)
+    yield "homography_eleven_models", lambda: homography(ctx, hc.eleven_models_pairs()[0])
 
 
 if __name__ == "__main__":
