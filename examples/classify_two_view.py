@@ -5,6 +5,12 @@ pairs and reports success with a relative pose for each -- for the rotating came
 nothing, since the pair has no baseline.  TwoViewClassifier runs the homography estimator on the same matches and says which
 pair is which: CALIBRATED, PANORAMIC, PLANAR.
 
+Then the translating pair once more, and a camera that moves forward while it turns, handed over with the focal length stated
+x 0.7 (a photograph without EXIF and a guessed focal length): the essential matrix still "verifies" both, the second with a third
+of its inliers gone and nothing that says why; with "fundamental" set the classifier runs the seven-point estimator next to it,
+which finds the matches that are there, and the forward pair is called UNCALIBRATED.  The sideways pair is one of the geometries
+that barely constrain the focal length: E keeps nearly everything there, and only a camera declared untrusted makes it UNCALIBRATED.
+
     python examples/classify_two_view.py            # needs an MI355X and the built libpixsfm_hip.so
 """
 import os
@@ -21,6 +27,7 @@ from pixsfm_amd.api.reconstruction import Camera                                
 
 PARAMS = [1200.0, 500.0, 500.0, 0.02]                                              # SIMPLE_RADIAL
 EXPECTED = {"translating": "CALIBRATED", "rotating": "PANORAMIC", "wall": "PLANAR"}
+WRONG_FOCAL = 0.7
 
 
 def project(X, R, t):
@@ -73,6 +80,30 @@ def main():
           % (g["success"], g["num_inliers"], *g["tvec"]))
     got = {a[:-6]: g["config"] for (a, _), g in zip(pairs, geoms)}
     assert got == EXPECTED, got
+
+    # two pairs with a focal length that is off: the translating pair of above, and a camera that moves forward while it turns
+    rng = np.random.default_rng(1)
+    n = 300
+    rays = np.concatenate([rng.uniform(-0.3, 0.3, (n, 2)), np.ones((n, 1))], 1)
+    cloud = rays * rng.uniform(3.0, 12.0, (n, 1))
+    keypoints["forward_1.jpg"] = project(cloud, np.eye(3), np.zeros(3)) + rng.normal(0, 0.5, (n, 2))
+    xy2 = project(cloud, rotation([0.3, 1.0, 0.2], 0.25), np.array([0.4, 0.2, 1.2])) + rng.normal(0, 0.5, (n, 2))
+    wrong = rng.permutation(n)[:n // 4]
+    xy2[wrong] = rng.uniform(0, 1000, (len(wrong), 2))
+    keypoints["forward_2.jpg"] = xy2
+    two, two_matches = [pairs[0], ("forward_1.jpg", "forward_2.jpg")], [matches[0]] * 2
+    guessed = Camera(2, "SIMPLE_RADIAL", 1000, 1000, [WRONG_FOCAL * PARAMS[0]] + PARAMS[1:])
+    with_f = TwoViewClassifier.create({"fundamental": {}})
+    print("with the fundamental matrix next to it; focal length stated x %.1f where it says wrong:" % WRONG_FOCAL)
+    for label, cam, prior in (("true", camera, True), ("wrong, trusted", guessed, True), ("wrong, no prior", guessed, False)):
+        m, _, gs = with_f.classify_pairs(keypoints, {x: cam for x in keypoints}, two, two_matches, prior_focal_length={x: prior for x in keypoints})
+        for (x, _), g, kept_m in zip(two, gs, m):
+            print("  %-12s %-16s %-13s n_E %3d  n_F %3d  matches kept %d" % (x[:-6], label, g["config"], g.get("num_inliers", 0), g["num_inliers_F"], len(kept_m)))
+            got[x[:-6] + ", " + label] = g["config"]
+    # sideways motion barely constrains the focal length: E keeps nearly all of F's inliers and the pair stays CALIBRATED unless
+    # the camera is declared untrusted; forward motion does, and E loses a third of them
+    assert got["translating, true"] == got["forward, true"] == "CALIBRATED" and got["forward, wrong, trusted"] == "UNCALIBRATED", got
+    assert got["translating, wrong, no prior"] == got["forward, wrong, no prior"] == "UNCALIBRATED", got
     return got
 
 

@@ -601,7 +601,7 @@ int pxr_two_view_geometry_timed(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_
  * pair out) ----
  * The planar / panoramic half of geometric verification: pycolmap.verify_matches classifies a pair from the ratio of homography
  * inliers to essential-matrix inliers, because an essential matrix fits a pure-rotation or a planar pair with a translation
- * direction that means nothing.  For calibrated cameras only (fundamental-matrix estimation is not provided).  The batch is laid
+ * direction that means nothing.  For calibrated cameras (fundamental-matrix estimation: pxr_fundamental below).  The batch is laid
  * out like pxr_two_view_geometry's, and the options are its options with its defaults (COLMAP 3.8's values as remembered, parity
  * UNPINNED; min_num_trials, round_size, seed, refine_max_iterations and lo_rounds are this estimator's own). */
 typedef struct {
@@ -669,6 +669,81 @@ int pxr_homography_timed(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_of
                          const double* d_cam_params, const pxr_homography_options* options, double* d_H, double* d_rot_qvec,
                          int32_t* d_status, int32_t* d_n_inliers, int32_t* d_n_rot_inliers, int32_t* d_n_trials, uint8_t* d_inlier,
                          double* d_err, double* h_kernel_ms);
+
+/* ---- fundamental-matrix estimation (the matches of image pairs in, one fundamental matrix and one inlier mask per pair out) ----
+ * The uncalibrated half of geometric verification: pycolmap.verify_matches estimates F and H only for a camera without a prior
+ * focal length, and next to E otherwise (a pair whose E explains noticeably fewer matches than its F is UNCALIBRATED).  The batch
+ * is laid out like pxr_two_view_geometry's, and the options are its options with its defaults (COLMAP 3.8's values as remembered,
+ * parity UNPINNED; min_num_trials, round_size, seed, refine_max_iterations and lo_rounds are this estimator's own). */
+typedef struct {
+  double max_error;             /* 4.0      pixels: inlier threshold on the Sampson distance                              */
+  double min_inlier_ratio;      /* 0.25     success needs n_inliers >= max(min_num_inliers, ceil(min_inlier_ratio n))      */
+  double confidence;            /* 0.999    of the stop rule                                                              */
+  uint64_t seed;                /* 0        of the sample hash                                                            */
+  int32_t min_num_inliers;      /* 15                                                                                     */
+  int32_t min_num_trials;       /* 64       lower clamp of the stop rule                                                  */
+  int32_t max_num_trials;       /* 10000    upper clamp of the stop rule, rounded up to a multiple of round_size          */
+  int32_t round_size;           /* 64       samples per round: the stop rule is evaluated at round boundaries only        */
+  int32_t refine_max_iterations;/* 100      Levenberg-Marquardt iterations per refinement                                 */
+  int32_t lo_rounds;            /* 4        at most this many refine / re-classify repetitions                            */
+} pxr_fundamental_options;
+/* Writes the defaults above. */
+void pxr_fundamental_default_options(pxr_fundamental_options* options);
+
+/* Fundamental-matrix estimation for a batch of image pairs, deterministic like pxr_two_view_geometry: no random state, a pair alone
+ * and the same pair inside any batch give the same bits.  This is NOT COLMAP's LO-RANSAC, and parity with
+ * COLMAP is UNPINNED.  Pair p owns matches [d_pair_offsets[p], d_pair_offsets[p+1]).  Per pair:
+ *   1. usable matches and records exactly as in step 1 of pxr_two_view_geometry: both pixels go through ImageToWorld, the record
+ *      is (x1, y1, x2, y2) in the normalised planes of the cameras given; F relates those planes: x2^t F x1 = 0.  For an
+ *      uncalibrated pair the "cameras" are conditioning transforms -- a SIMPLE_PINHOLE with a guessed or data-derived focal length
+ *      and centre -- which is what keeps the 7 x 9 system well scaled: there is no Hartley step inside.  n = the usable ones, in
+ *      order; n < 7: status 1.
+ *   2. sample h = 0, 1, ... is seven distinct indices from the hash of pxr_two_view_geometry's step 2, used in ascending order.
+ *   3. the seven-point solver: the 7 x 9 system with rows x2 (x) x1 = (x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1); its two
+ *      null vectors by Gauss-Jordan with full pivoting (the largest entry, the first of equals in row-major order; vector k =
+ *      (-C[:, k], e_k) of [I | C] in the permuted columns), orthonormalised by modified Gram-Schmidt in the order k = 0, 1 into N0,
+ *      N1 and mixed into A = (N0 + N1) r and B = (N0 - N1) r, r = 0.70710678118654752440 (1 / sqrt 2 as a double): with F = x A + B,
+ *      neither null vector being the answer on its own sends a root to infinity (that takes N0 + N1).  The cubic det(x A + B) =
+ *      c3 x^3 + c2 x^2 + c1 x + c0 by expansion along row 0: for a = 0, 1, 2 with b = a + 1, c = a + 2 (mod 3) the minor of rows
+ *      1, 2 is q2 x^2 + q1 x + q0, q2 = A1b A2c - A1c A2b, q1 = (A1b B2c + B1b A2c) - (A1c B2b + B1c A2b), q0 = B1b B2c - B1c B2b,
+ *      and, from zero, c3 += A0a q2, c2 += (A0a q1 + B0a q2), c1 += (A0a q0 + B0a q1), c0 += B0a q0.  The coefficients are scaled
+ *      by the largest; the real roots by the routine of pxr_two_view_geometry's step 3 at degree 3 (Cauchy's bound 1 + max
+ *      |c_k / c_3|, the Sturm chain with rescaled remainders, 64 bisection steps on the sign-change count, 4 guarded Newton
+ *      steps), ascending, at most three.  F = x A[m] + B[m] entry by entry, scaled to Frobenius norm 1 (the squares summed in
+ *      index order).  No hypothesis from a pivot <= 1e-12 of the system's largest entry, a leading coefficient <= 1e-9 of the
+ *      largest, or a value that is not finite.  The roots are walked one at a time, each scored over all n before the next.
+ *   4. each F is scored over all n by the squared Sampson error and the thr of pxr_two_view_geometry's step 4; the largest key
+ *      (inlier count, -sum min(err, thr^2), -h, -root) wins, the sum taken in index order.
+ *   5. after each round of round_size samples: stop once samples done >= clamp(log(1 - confidence) / log(1 - (w2 w2) (w2 w)),
+ *      min_num_trials, max_num_trials), w = best count / n, w2 = w w.  There is no floor like pxr_homography's: at ratio 0.25 it
+ *      would ask for log(0.001) / log(1 - 0.25^7) = 113173 samples, above max_num_trials.  No hypothesis at all: status 2.
+ *   6. local optimisation: Levenberg-Marquardt on the inliers' signed Sampson residuals x2^t F x1 / sqrt(D) (D: the denominator of
+ *      step 4) over an F that is rank 2 by construction, without an SVD: of the column pairs (0, 1), (0, 2), (1, 2) of F the one
+ *      (i, k) whose cross product has the largest squared norm (the first of equals; none above zero: F stays as it is); the third
+ *      column is alpha c_i + beta c_k with (alpha, beta) from the 2 x 2 normal equations by Cramer's rule, alpha = (r1 g22 - r2
+ *      g12) / det, beta = (g11 r2 - g12 r1) / det, g = the Gram matrix of (c_i, c_k), r = their products with the third column (det
+ *      not positive: F stays); the state is (c_i, c_k, alpha, beta), of whose first six entries the one of largest magnitude is
+ *      held fixed (the first of equals) while the other five and alpha, beta move additively: seven parameters.  lambda schedule,
+ *      step acceptance and termination are those of pxr_homography's step 6.  F is rebuilt from the state and scaled back to
+ *      Frobenius norm 1, then all n are classified again; repeated until the set stands still or lo_rounds; a refined F with fewer
+ *      inliers than the one before it is dropped.
+ *   7. n_inliers < max(min_num_inliers, ceil(min_inlier_ratio n)): status 3.
+ * Outputs: d_status[p] 0 = F (row-major, normalised planes, Frobenius norm 1, the entry of largest magnitude positive, the first of
+ * equals) written to d_F[p], left untouched otherwise; d_n_inliers[p] (0 unless status is 0); d_n_trials[p] samples drawn; per
+ * match d_inlier (0 unless status is 0) and d_err (sqrt(err) max_error / thr, i.e. the Sampson distance in pixels, of the usable
+ * matches of a status-0 pair; NaN elsewhere).
+ * PXR_EINVAL (nothing launched): offsets not starting at 0, not monotone or not ending at n_matches, a camera index out of
+ * range, an option out of range.
+ * Synchronises the context's stream (offsets and cameras are validated and the pairs ordered by size on the host). */
+int pxr_fundamental(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
+                    const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,
+                    const double* d_cam_params, const pxr_fundamental_options* options, double* d_F, int32_t* d_status,
+                    int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[4] = records, compaction, hypotheses, refinement. */
+int pxr_fundamental_timed(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
+                          const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,
+                          const double* d_cam_params, const pxr_fundamental_options* options, double* d_F, int32_t* d_status,
+                          int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err, double* h_kernel_ms);
 
 /* ---- descriptor matching (descriptors of image pairs in, mutual nearest neighbours out) --------
  * What produces the match graph (and a query's 2D-3D pairs): hloc's match_features with the NearestNeighbor matcher, whose output

@@ -116,6 +116,11 @@ class HomographyOptions(C.Structure):
     _fields_ = list(TwoViewOptions._fields_)
 
 
+class FundamentalOptions(C.Structure):
+    """pxr_fundamental_options"""
+    _fields_ = list(TwoViewOptions._fields_)
+
+
 class MatchOptions(C.Structure):
     """pxr_match_options"""
     _fields_ = [("ratio_threshold", C.c_double), ("distance_threshold", C.c_double), ("do_mutual_check", C.c_int32),
@@ -192,6 +197,13 @@ _SIGNATURES = {
     "pxr_homography_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.POINTER(HomographyOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "pxr_fundamental_default_options": (None, [C.POINTER(FundamentalOptions)]),
+    "pxr_fundamental": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.POINTER(FundamentalOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pxr_fundamental_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.POINTER(FundamentalOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_match_default_options": (None, [C.POINTER(MatchOptions)]),
     "pxr_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -2,6 +2,7 @@
 pixsfm.keypoint_adjustment, pixsfm.bundle_adjustment, pixsfm._pixsfm._base/_features)."""
 from . import base, extract, features, localization, reconstruction, triangulation, two_view  # noqa: F401
 from . import homography  # noqa: F401,E402
+from . import fundamental  # noqa: F401,E402
 from .bundle_adjustment import (BundleAdjuster, BundleAdjustmentSetup, CostMapBundleAdjuster,  # noqa: F401
                                 CostMapBundleOptimizer, CostMapExtractor, FeatureReferenceBundleAdjuster,
                                 FeatureReferenceBundleOptimizer, FeatureView, GeometricBundleAdjuster,
@@ -21,3 +22,4 @@ from .triangulation import TrackTriangulator  # noqa: F401,E402
 from .matching import DescriptorMatcher, pairs_2d3d_from_matches  # noqa: F401,E402
 from .two_view import TwoViewVerifier, essential_matrix_estimation  # noqa: F401,E402
 from .homography import TwoViewClassifier, homography_matrix_estimation, two_view_config  # noqa: F401,E402
+from .fundamental import fundamental_matrix_estimation, two_view_config_uncalibrated  # noqa: F401,E402

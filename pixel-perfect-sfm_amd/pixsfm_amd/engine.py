@@ -1066,6 +1066,41 @@ class HomographyProblem:
         return d_H, d_q, d_status, d_ninl, d_nrot, d_ntr, d_inl, d_err
 
 
+def fundamental_options(max_error=4.0, min_inlier_ratio=0.25, min_num_inliers=15, confidence=0.999, min_num_trials=64,
+                        max_num_trials=10000, round_size=64, seed=0, refine_max_iterations=100, lo_rounds=4):
+    """pxr_fundamental_options: the fields and defaults of two_view_options, as the fundamental-matrix estimator's own struct."""
+    return _lib.FundamentalOptions(float(max_error), float(min_inlier_ratio), float(confidence), int(seed), int(min_num_inliers),
+                                   int(min_num_trials), int(max_num_trials), int(round_size), int(refine_max_iterations), int(lo_rounds))
+
+
+class FundamentalProblem(HomographyProblem):
+    """Device-resident flat arrays of a batch of image pairs (pxr_fundamental): the batch dict of HomographyProblem.  The cameras
+    are the ones the records are normalised with -- for an uncalibrated pair, conditioning transforms.  A TwoViewProblem in place
+    of the dict shares its device arrays: all three estimators on one upload.
+    """
+
+    def estimate(self, F=None, timed=False, **options):
+        """Run the kernels (pxr_fundamental) with fundamental_options(**options).  Returns the device arrays (F (n_pairs, 9),
+        status, n_inliers, n_trials (n_pairs,) int32, inlier (n_matches,) uint8, err (n_matches,) float64).  F: a host array the
+        output starts from -- rows of pairs without a fundamental matrix keep it (default: NaN).  timed: also keep the kernels'
+        HIP-event times in self.kernel_ms {"records", "compact", "hypotheses", "refine"} (milliseconds)."""
+        ctx, d, T, N = self.ctx, self.d, self.n_pairs, self.n_matches
+        opts = fundamental_options(**options)
+        d_F = ctx.to_device(np.full((T, 9), np.nan) if F is None else np.asarray(F, dtype=np.float64).reshape(T, 9), np.float64)
+        d_status, d_ninl, d_ntr = (ctx.empty((T,), np.int32) for _ in range(3))
+        d_inl, d_err = ctx.empty((N,), np.uint8), ctx.empty((N,), np.float64)
+        args = (ctx.handle, T, d["pair_offsets"].ptr, N, d["xy1"].ptr, d["xy2"].ptr, d["pair_camera"].ptr, self.n_cameras,
+                d["cam_model"].ptr, d["cam_params"].ptr, C.byref(opts), d_F.ptr, d_status.ptr, d_ninl.ptr, d_ntr.ptr, d_inl.ptr,
+                d_err.ptr)
+        if timed:
+            ms = (C.c_double * 4)()
+            check(ctx.lib.pxr_fundamental_timed(*args, ms), "pxr_fundamental_timed")
+            self.kernel_ms = dict(zip(("records", "compact", "hypotheses", "refine"), (float(x) for x in ms)))
+        else:
+            check(ctx.lib.pxr_fundamental(*args), "pxr_fundamental")
+        return d_F, d_status, d_ninl, d_ntr, d_inl, d_err
+
+
 MATCH_CONFS = {            # hloc's match_features confs for its NearestNeighbor matcher
     "NN-mutual": dict(ratio_threshold=0.0, distance_threshold=0.0, do_mutual_check=True),
     "NN-ratio": dict(ratio_threshold=0.8, distance_threshold=0.0, do_mutual_check=True),
