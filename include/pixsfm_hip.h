@@ -522,8 +522,10 @@ int pxr_absolute_pose_timed(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_qu
  * remembered; COLMAP is not available where this library is built, so parity with it is UNPINNED.  min_num_trials, round_size,
  * seed, refine_max_iterations and lo_rounds are this estimator's own. */
 #define PXR_TWOVIEW_LDS_MATCHES 1024 /* matches of a pair the estimator stages on chip; a longer pair reads the rest from memory */
+/* The options of the three estimators over image pairs (essential matrix here, homography and fundamental matrix below): one
+ * struct under three names.  What max_error measures is the estimator's: see its *_default_options. */
 typedef struct {
-  double max_error;             /* 4.0      pixels: inlier threshold on the Sampson distance                              */
+  double max_error;             /* 4.0      pixels: inlier threshold on the estimator's error                             */
   double min_inlier_ratio;      /* 0.25     success needs n_inliers >= max(min_num_inliers, ceil(min_inlier_ratio n))      */
   double confidence;            /* 0.999    of the stop rule                                                              */
   uint64_t seed;                /* 0        of the sample hash                                                            */
@@ -533,8 +535,9 @@ typedef struct {
   int32_t round_size;           /* 64       samples per round: the stop rule is evaluated at round boundaries only        */
   int32_t refine_max_iterations;/* 100      Levenberg-Marquardt iterations per refinement                                 */
   int32_t lo_rounds;            /* 4        at most this many refine / re-classify repetitions                            */
-} pxr_two_view_options;
-/* Writes the defaults above. */
+} pxr_pair_options;
+typedef pxr_pair_options pxr_two_view_options;
+/* Writes the defaults above; max_error is a threshold on the Sampson distance. */
 void pxr_two_view_default_options(pxr_two_view_options* options);
 
 /* Essential-matrix estimation and verification for a batch of image pairs.  This is NOT COLMAP's LO-RANSAC: the estimator has no
@@ -604,19 +607,8 @@ int pxr_two_view_geometry_timed(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_
  * direction that means nothing.  For calibrated cameras (fundamental-matrix estimation: pxr_fundamental below).  The batch is laid
  * out like pxr_two_view_geometry's, and the options are its options with its defaults (COLMAP 3.8's values as remembered, parity
  * UNPINNED; min_num_trials, round_size, seed, refine_max_iterations and lo_rounds are this estimator's own). */
-typedef struct {
-  double max_error;             /* 4.0      pixels: inlier threshold on the forward transfer error in image 2             */
-  double min_inlier_ratio;      /* 0.25     success needs n_inliers >= max(min_num_inliers, ceil(min_inlier_ratio n))      */
-  double confidence;            /* 0.999    of the stop rule                                                              */
-  uint64_t seed;                /* 0        of the sample hash                                                            */
-  int32_t min_num_inliers;      /* 15                                                                                     */
-  int32_t min_num_trials;       /* 64       lower clamp of the stop rule                                                  */
-  int32_t max_num_trials;       /* 10000    upper clamp of the stop rule, rounded up to a multiple of round_size          */
-  int32_t round_size;           /* 64       samples per round: the stop rule is evaluated at round boundaries only        */
-  int32_t refine_max_iterations;/* 100      Levenberg-Marquardt iterations per refinement                                 */
-  int32_t lo_rounds;            /* 4        at most this many refine / re-classify repetitions                            */
-} pxr_homography_options;
-/* Writes the defaults above. */
+typedef pxr_pair_options pxr_homography_options;
+/* Writes the defaults of pxr_pair_options; max_error is a threshold on the forward transfer error in image 2. */
 void pxr_homography_default_options(pxr_homography_options* options);
 
 /* Homography estimation for a batch of image pairs, deterministic like pxr_two_view_geometry: no random state, a pair alone and the
@@ -675,19 +667,8 @@ int pxr_homography_timed(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_of
  * focal length, and next to E otherwise (a pair whose E explains noticeably fewer matches than its F is UNCALIBRATED).  The batch
  * is laid out like pxr_two_view_geometry's, and the options are its options with its defaults (COLMAP 3.8's values as remembered,
  * parity UNPINNED; min_num_trials, round_size, seed, refine_max_iterations and lo_rounds are this estimator's own). */
-typedef struct {
-  double max_error;             /* 4.0      pixels: inlier threshold on the Sampson distance                              */
-  double min_inlier_ratio;      /* 0.25     success needs n_inliers >= max(min_num_inliers, ceil(min_inlier_ratio n))      */
-  double confidence;            /* 0.999    of the stop rule                                                              */
-  uint64_t seed;                /* 0        of the sample hash                                                            */
-  int32_t min_num_inliers;      /* 15                                                                                     */
-  int32_t min_num_trials;       /* 64       lower clamp of the stop rule                                                  */
-  int32_t max_num_trials;       /* 10000    upper clamp of the stop rule, rounded up to a multiple of round_size          */
-  int32_t round_size;           /* 64       samples per round: the stop rule is evaluated at round boundaries only        */
-  int32_t refine_max_iterations;/* 100      Levenberg-Marquardt iterations per refinement                                 */
-  int32_t lo_rounds;            /* 4        at most this many refine / re-classify repetitions                            */
-} pxr_fundamental_options;
-/* Writes the defaults above. */
+typedef pxr_pair_options pxr_fundamental_options;
+/* Writes the defaults of pxr_pair_options; max_error is a threshold on the Sampson distance. */
 void pxr_fundamental_default_options(pxr_fundamental_options* options);
 
 /* Fundamental-matrix estimation for a batch of image pairs, deterministic like pxr_two_view_geometry: no random state, a pair alone

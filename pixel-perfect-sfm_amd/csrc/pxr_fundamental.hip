@@ -4,15 +4,11 @@
 // The uncalibrated half of COLMAP's two-view geometry estimation (pycolmap.verify_matches estimates F next to E, or F alone for a
 // camera without a prior focal length): undistort both pixels of every match with the cameras given -- for an uncalibrated pair
 // these are conditioning transforms -- estimate a fundamental matrix of the two normalised planes robustly from minimal samples
-// (seven points), refine it on its inliers over a parametrisation that is rank 2 by construction.  Built from the shared core of
-// pxr_robust.h and pxr_batch.h like the essential-matrix and homography estimators (pxr_twoview.hip, pxr_homography.hip; DESIGN.md
-// sections 21 and 22): no random state -- sample h of a pair is a counter-based hash of (seed, h) -- and every choice is a
-// comparison of keys, so the result is a function of the pair's own matches alone, bit for bit, alone or inside any batch
+// (seven points), refine it on its inliers over a parametrisation that is rank 2 by construction.  Records, the opening of a
+// pair, the local optimisation and the host side of a call are those of pxr_pairs.h; what is here is the fundamental matrix's own
 // (DESIGN.md section 23).
 //
-//   k_fm_records     one lane per match: its pair (binary search of the offsets), undistort both sides -> record (x1, y1, x2, y2)
-//   k_compact_records<4>  (pxr_robust.h) one lane per pair: the usable records of a pair moved to the front of its slice
-//   k_fm_hypotheses  one workgroup of 256 lanes per pair, the first FM_LDS records staged in LDS; a round of samples per
+//   k_fm_hypotheses  one workgroup of 256 lanes per pair, the first PAIR_LDS records staged in LDS; a round of samples per
 //                    wavefront, a sample per lane, every lane scoring its own fundamental matrices (one per real root of the
 //                    cubic, one at a time) against all records
 //   k_fm_refine      the winner's local optimisation and the final classification
@@ -22,32 +18,21 @@
 // DESIGN.md section 23).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
-#include <vector>
 
-#include "pxr_batch.h"
 #include "pxr_device.h"
-#include "pxr_internal.h"
-#include "pxr_robust.h"
-#include "pxr_undistort.h"
+#include "pxr_pairs.h"
 
 namespace pxr {
 
-constexpr int FM_THREADS = 256;
-constexpr int FM_WAVES = FM_THREADS / 64;
-constexpr int FM_REC = 4;                              // doubles per record: x1, y1, x2, y2 (normalised image points)
-constexpr int FM_LDS = PXR_TWOVIEW_LDS_MATCHES;        // records of a pair staged in LDS (32 B each); the rest is read from global memory (L2)
 constexpr int FM_ACC = 36;                             // the refinement's sums: J^t J (28, upper triangle by rows), g (7), cost
-constexpr int FM_CHUNK = 9;                            // of which this many cross the workgroup at a time (FM_THREADS x FM_CHUNK doubles of LDS)
+constexpr int FM_CHUNK = 9;                            // of which this many cross the workgroup at a time (PAIR_THREADS x FM_CHUNK doubles of LDS)
 constexpr int FM_DEG = 3;                              // degree of det(x A + B)
 constexpr int FM_BISECT = 64;                          // bisection steps per root
 constexpr int FM_NEWTON = 4;                           // Newton steps per root, each kept only inside the bisection's last interval
 constexpr double FM_PIVOT_TOL = 1e-12;                 // a pivot counts as zero below this fraction of the system's largest entry
 constexpr double FM_LEAD_TOL = 1e-9;                   // the leading coefficient counts as zero below this fraction of the largest one
 constexpr double FM_TRIM_TOL = 1e-12;                  // so does the leading coefficient of a rescaled Sturm remainder
-constexpr double FM_STEP_TOL = 1e-12;                  // a refinement stops at a step of this norm
-constexpr double FM_COST_SLACK = 1e-12;                // a step is kept unless the cost grows by more than this fraction
 constexpr double FM_RSQRT2 = 0.70710678118654752440;   // 1 / sqrt 2, rounded to double
 
 // ---- the seven-point solver --------------------------------------------------------------------------------------------------------
@@ -229,44 +214,11 @@ __device__ __forceinline__ double fm_sampson(const double* F, const double* r) {
   return (N * N) / D;
 }
 
-// ---- kernel A: records -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FM_THREADS) void k_fm_records(int64_t n_matches, int32_t n_pairs, const int64_t* __restrict__ offsets,
-                                                           const int32_t* __restrict__ pair_camera, const int32_t* __restrict__ cam_model,
-                                                           const double* __restrict__ cam_params, const double* __restrict__ xy1,
-                                                           const double* __restrict__ xy2, double* __restrict__ rec,
-                                                           uint8_t* __restrict__ valid, uint8_t* __restrict__ inlier, double* __restrict__ err) {
-  const int64_t i = (int64_t)blockIdx.x * FM_THREADS + threadIdx.x;
-  if (i >= n_matches) return;
-  int lo = 0, hi = n_pairs;                            // the pair p with offsets[p] <= i < offsets[p + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) / 2;
-    if (offsets[mid] <= i) lo = mid; else hi = mid;
-  }
-  double uv[4];
-  bool ok = true;
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int cam = pair_camera[2 * (size_t)lo + side];
-    double k[PXR_KPAD];
-#pragma unroll
-    for (int j = 0; j < PXR_KPAD; ++j) k[j] = cam_params[(size_t)cam * PXR_KPAD + j];
-    const double* xy = side == 0 ? xy1 : xy2;
-    const double x = xy[2 * i], y = xy[2 * i + 1];
-    ok = isfinite(x) && isfinite(y) && ok;
-    ok = image_to_world(cam_model[cam], k, x, y, uv[2 * side], uv[2 * side + 1]) && ok;
-  }
-  double* r = rec + (size_t)i * FM_REC;
-  r[0] = uv[0]; r[1] = uv[1]; r[2] = uv[2]; r[3] = uv[3];
-  valid[i] = ok ? 1 : 0;
-  inlier[i] = 0;                                       // what a match keeps unless its pair gets a fundamental matrix
-  err[i] = quiet_nan();
-}
-
 // ---- kernel B: the estimator -------------------------------------------------------------------------------------------------------
 struct FmArgs {
   const int64_t* offsets; const int32_t* pair_camera; const int32_t* cam_model; const double* cam_params;
   const int32_t* order;        // [n_pairs] pairs by descending match count
-  const double* rec;           // [n_matches][FM_REC], compacted per pair
+  const double* rec;           // [n_matches][PAIR_REC], compacted per pair
   const int32_t* pos;          // [n_matches]
   const int32_t* n_valid;      // [n_pairs]
   int32_t* winner;             // [n_pairs][3] the best key: count (-1: none), sample, root
@@ -277,39 +229,16 @@ struct FmArgs {
   double* F; int32_t* status; int32_t* n_inliers; int32_t* n_trials; uint8_t* inlier; double* err;
 };
 
-struct FmPair {                // what every lane of the workgroup knows about its pair
-  const double* sh; const double* g; int n; int64_t o0;
-  double thr, thr2;
-  __device__ __forceinline__ const double* rec(int j) const { return j < FM_LDS ? sh + j * FM_REC : g + (size_t)j * FM_REC; }
-};
-
-// what every lane of a workgroup needs of its pair; false: fewer than seven usable matches
-__device__ __forceinline__ bool fm_open_pair(const FmArgs& a, int pi, double* sh_rec, FmPair& P) {
-  P.o0 = a.offsets[pi];
-  P.n = a.n_valid[pi];
-  if (P.n < 7) return false;
-  P.g = a.rec + (size_t)P.o0 * FM_REC;
-  P.sh = sh_rec;
-  for (int x = threadIdx.x; x < min(P.n, FM_LDS) * FM_REC; x += FM_THREADS) sh_rec[x] = P.g[x];
-  const int cam1 = a.pair_camera[2 * (size_t)pi], cam2 = a.pair_camera[2 * (size_t)pi + 1];
-  const double f1 = mean_focal(a.cam_model[cam1], a.cam_params + (size_t)cam1 * PXR_KPAD);
-  const double f2 = mean_focal(a.cam_model[cam2], a.cam_params + (size_t)cam2 * PXR_KPAD);
-  P.thr = 0.5 * (a.o.max_error / f1 + a.o.max_error / f2);
-  P.thr2 = P.thr * P.thr;
-  __syncthreads();
-  return true;
-}
-
 // Every branch that encloses a barrier or a cross-lane operation is uniform over the workgroup; the hypothesis loop, where the
 // lanes meet different root counts, has none.
-__global__ __launch_bounds__(FM_THREADS, 2) void k_fm_hypotheses(const FmArgs a) {
-  __shared__ double sh_rec[FM_LDS * FM_REC];
-  __shared__ double sh_ksum[FM_WAVES];
-  __shared__ int sh_kint[FM_WAVES][3];
+__global__ __launch_bounds__(PAIR_THREADS, 2) void k_fm_hypotheses(const FmArgs a) {
+  __shared__ double sh_rec[PAIR_LDS * PAIR_REC];
+  __shared__ double sh_ksum[PAIR_WAVES];
+  __shared__ int sh_kint[PAIR_WAVES][3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int pi = a.order[blockIdx.x];
-  FmPair P;
-  if (!fm_open_pair(a, pi, sh_rec, P)) {
+  PairRecords P;
+  if (!open_pair<PairThreshold::BothCameras>(a, pi, 7, sh_rec, P)) {
     if (tid == 0) { a.status[pi] = 1; a.n_inliers[pi] = 0; a.n_trials[pi] = 0; }
     return;
   }
@@ -325,7 +254,7 @@ __global__ __launch_bounds__(FM_THREADS, 2) void k_fm_hypotheses(const FmArgs a)
     return trials_needed(a.o.confidence, a.o.min_num_trials, a.max_trials, cnt, (w2 * w2) * (w2 * w));
   };
   for (int pass = 0;; ++pass) {
-    const int round = pass * FM_WAVES + wave;
+    const int round = pass * PAIR_WAVES + wave;
     HypKey mine = {-1, 0.0, 0x7fffffff, FM_DEG};
     if ((int64_t)round * a.o.round_size < a.max_trials) {
       for (int s = lane; s < a.o.round_size; s += 64) {
@@ -352,7 +281,7 @@ __global__ __launch_bounds__(FM_THREADS, 2) void k_fm_hypotheses(const FmArgs a)
       }
     }
     wave_best(mine);
-    if (merge_rounds<FM_WAVES>(sh_ksum, sh_kint, mine, pass, a.o.round_size, a.max_trials, best, done, need)) break;
+    if (merge_rounds<PAIR_WAVES>(sh_ksum, sh_kint, mine, pass, a.o.round_size, a.max_trials, best, done, need)) break;
   }
   if (tid == 0) {
     a.n_trials[pi] = done;
@@ -415,7 +344,7 @@ __device__ __forceinline__ void fm_build(const FmColumns& col, const double* x, 
 // sums of J^t J, J^t r and r^2 over the records of `mask`; r = x2^t F x1 / sqrt(D) the signed Sampson residual of F = fm_build(x),
 // J = dr / d(the seven entries of x other than `fixed`, in index order).  A record whose denominator is not positive makes the
 // cost +inf.
-__device__ __forceinline__ void fm_normal_equations(const FmPair& P, const uint8_t* mask, const FmColumns& col, const double* x, int fixed,
+__device__ __forceinline__ void fm_normal_equations(const PairRecords& P, const uint8_t* mask, const FmColumns& col, const double* x, int fixed,
                                                     double (&acc)[FM_ACC], double* sh_part, double* sh_tot) {
 #pragma unroll
   for (int c = 0; c < FM_ACC; ++c) acc[c] = 0.0;
@@ -432,7 +361,7 @@ __device__ __forceinline__ void fm_normal_equations(const FmPair& P, const uint8
     dF[6][3 * r + col.cl] = x[r];
     dF[7][3 * r + col.cl] = x[3 + r];
   }
-  for (int j = threadIdx.x; j < P.n; j += FM_THREADS) {
+  for (int j = threadIdx.x; j < P.n; j += PAIR_THREADS) {
     if (!mask[P.o0 + j]) continue;
     const double* r = P.rec(j);
     const double u1 = r[0], v1 = r[1], u2 = r[2], v2 = r[3];
@@ -463,56 +392,17 @@ __device__ __forceinline__ void fm_normal_equations(const FmPair& P, const uint8
     }
     acc[35] += res * res;
   }
-  block_sum<FM_THREADS, FM_CHUNK>(acc, sh_part, sh_tot);
+  block_sum<PAIR_THREADS, FM_CHUNK>(acc, sh_part, sh_tot);
 }
 
-// Levenberg-Marquardt on the records of `mask`, x refined in place: the lambda schedule and the keep / refuse rule of sections 19,
-// 21 and 22.  Every lane holds the same sums, so every lane takes the same decisions and ends with the same state.
-__device__ __forceinline__ void fm_lm(int max_iterations, const FmPair& P, const uint8_t* mask, const FmColumns& col, int fixed,
-                                      double (&x)[8], double* sh_part, double* sh_tot) {
-  double acc[FM_ACC];
-  fm_normal_equations(P, mask, col, x, fixed, acc, sh_part, sh_tot);
-  if (!isfinite(acc[FM_ACC - 1])) return;
-  double lambda = 1e-4;
-  for (int it = 0; it < max_iterations; ++it) {
-    double d[7], x1[8];
-    if (!solve_damped<7>(acc, lambda, d)) {
-      lambda *= 10.0;
-      if (lambda > 1e12) break;
-      continue;
-    }
-    double cur[FM_ACC];                                   // the sums at x, kept while the trial's are formed
-#pragma unroll
-    for (int c = 0; c < FM_ACC; ++c) cur[c] = acc[c];
-    const double cost = acc[FM_ACC - 1];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) x1[m] = m == fixed ? x[m] : x[m] + d[m < fixed ? m : m - 1];
-    fm_normal_equations(P, mask, col, x1, fixed, acc, sh_part, sh_tot);
-    if (acc[FM_ACC - 1] <= cost + FM_COST_SLACK * cost) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = x1[j];
-      lambda = fmax(lambda * 0.1, 1e-12);
-    } else {
-#pragma unroll
-      for (int c = 0; c < FM_ACC; ++c) acc[c] = cur[c];
-      lambda *= 10.0;
-      if (lambda > 1e12) break;
-    }
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) s += d[j] * d[j];
-    if (sqrt(s) <= FM_STEP_TOL) break;
-  }
-}
-
-__global__ __launch_bounds__(FM_THREADS) void k_fm_refine(const FmArgs a) {
-  __shared__ double sh_rec[FM_LDS * FM_REC];
-  __shared__ double sh_part[FM_THREADS * FM_CHUNK];
+__global__ __launch_bounds__(PAIR_THREADS) void k_fm_refine(const FmArgs a) {
+  __shared__ double sh_rec[PAIR_LDS * PAIR_REC];
+  __shared__ double sh_part[PAIR_THREADS * FM_CHUNK];
   __shared__ double sh_tot[FM_ACC];
   const int tid = threadIdx.x;
   const int pi = a.order[blockIdx.x];
-  FmPair P;
-  if (!fm_open_pair(a, pi, sh_rec, P)) return;           // status 1: written by k_fm_hypotheses
+  PairRecords P;
+  if (!open_pair<PairThreshold::BothCameras>(a, pi, 7, sh_rec, P)) return;   // status 1: written by k_fm_hypotheses
   if (a.winner[3 * (size_t)pi] < 0) return;              // status 2: written by k_fm_hypotheses
   const int n = P.n;
   const double thr2 = P.thr2;
@@ -520,49 +410,28 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_refine(const FmArgs a) {
 #pragma unroll
   for (int m = 0; m < 9; ++m) F[m] = a.winner_F[9 * (size_t)pi + m];
 
-  // 1. the winner's inliers
+  // 1-2. the winner's inliers, then the local optimisation: refine on the inliers, classify again, until the set stands still
   uint8_t* cur = a.mask_a;
   uint8_t* nxt = a.mask_b;
-  double first[1] = {0.0};
-  for (int j = tid; j < n; j += FM_THREADS) {
-    const bool in = fm_sampson(F, P.rec(j)) <= thr2;
-    cur[P.o0 + j] = in ? 1 : 0;                          // (a lane reads back only what it wrote: j = tid mod 256)
-    first[0] += in ? 1.0 : 0.0;
-  }
-  block_sum<FM_THREADS, FM_CHUNK>(first, sh_part, sh_tot);
-  int cur_cnt = (int)first[0];
-
-  // 2. local optimisation: refine on the inliers, classify again, until the set stands still
-  for (int lo = 0; lo < a.o.lo_rounds; ++lo) {
-    FmColumns col;
-    double x[8], F1[9];
-    if (!fm_parametrise(F, col, x)) break;                // (uniform: every lane holds the same F)
-    int fixed = 0;                                       // of the six column entries, the one of largest magnitude, the first of equals
+  const int cur_cnt = local_optimisation<FM_CHUNK>(
+      P, a.o.lo_rounds, F, cur, nxt, [](const double* M, const double* r) { return fm_sampson(M, r); },
+      [&](const double* F0, const uint8_t* mask, double (&F1)[9]) {
+        FmColumns col;
+        double x[8];
+        if (!fm_parametrise(F0, col, x)) return false;
+        int fixed = 0;                                   // of the six column entries, the one of largest magnitude, the first of equals
 #pragma unroll
-    for (int m = 1; m < 6; ++m) if (fabs(x[m]) > fabs(x[fixed])) fixed = m;
-    fm_lm(a.o.refine_max_iterations, P, cur, col, fixed, x, sh_part, sh_tot);
-    fm_build(col, x, F1);
-    double s = 0.0;
+        for (int m = 1; m < 6; ++m) if (fabs(x[m]) > fabs(x[fixed])) fixed = m;
+        lm_refine<7, 8>(a.o.refine_max_iterations, x,
+                        [&](const double* y, double (&acc)[FM_ACC]) { fm_normal_equations(P, mask, col, y, fixed, acc, sh_part, sh_tot); },
+                        [&](const double* y, const double* d, double* y1) {
 #pragma unroll
-    for (int m = 0; m < 9; ++m) s += F1[m] * F1[m];
-    const double nrm = sqrt(s);
-#pragma unroll
-    for (int m = 0; m < 9; ++m) F1[m] = F1[m] / nrm;
-    double cc[2] = {0.0, 0.0};                            // inliers of the refined matrix; how many memberships changed
-    for (int j = tid; j < n; j += FM_THREADS) {
-      const bool in = fm_sampson(F1, P.rec(j)) <= thr2;
-      nxt[P.o0 + j] = in ? 1 : 0;
-      cc[0] += in ? 1.0 : 0.0;
-      cc[1] += (in != (cur[P.o0 + j] != 0)) ? 1.0 : 0.0;
-    }
-    block_sum<FM_THREADS, FM_CHUNK>(cc, sh_part, sh_tot);
-    if (!(cc[0] >= (double)cur_cnt)) break;               // fewer inliers: the matrix before it stays
-#pragma unroll
-    for (int m = 0; m < 9; ++m) F[m] = F1[m];
-    uint8_t* sw = cur; cur = nxt; nxt = sw;
-    cur_cnt = (int)cc[0];
-    if (cc[1] == 0.0) break;
-  }
+                          for (int m = 0; m < 8; ++m) y1[m] = m == fixed ? y[m] : y[m] + d[m < fixed ? m : m - 1];
+                        });
+        fm_build(col, x, F1);
+        return true;
+      },
+      sh_part, sh_tot);
 
   // 3. the final set (`cur`: the classification under the F that stays) and the success rule
   const int need = max(a.o.min_num_inliers, (int)ceil(a.o.min_inlier_ratio * (double)n));
@@ -571,7 +440,7 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_refine(const FmArgs a) {
     return;
   }
   const double to_px = a.o.max_error / P.thr;
-  for (int j = tid; j < n; j += FM_THREADS) {
+  for (int j = tid; j < n; j += PAIR_THREADS) {
     const double e2 = fm_sampson(F, P.rec(j));
     const int64_t i = P.o0 + a.pos[P.o0 + j];
     a.err[i] = sqrt(e2) * to_px;
@@ -590,88 +459,24 @@ static int fundamental(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offs
                        const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,
                        const double* d_cam_params, const pxr_fundamental_options* o, double* d_F, int32_t* d_status,
                        int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err, double* h_ms) {
-  const char* fn = "pxr_fundamental";
-  PXR_REQUIRE(ctx && o, "%s: NULL argument", fn);
-  PXR_REQUIRE(n_pairs >= 0 && n_matches >= 0 && n_cameras >= 0, "%s: negative size", fn);
-  PXR_REQUIRE(n_matches < ((int64_t)1 << 31), "%s: more than 2^31 matches", fn);
-  PXR_REQUIRE(n_pairs == 0 || (d_pair_offsets && d_pair_camera && d_F && d_status && d_n_inliers && d_n_trials && d_cam_model &&
-                               d_cam_params), "%s: NULL pair / camera array", fn);
-  PXR_REQUIRE(n_matches == 0 || (d_xy1 && d_xy2 && d_inlier && d_err), "%s: NULL match array", fn);
-  PXR_REQUIRE(o->max_error > 0.0 && o->confidence > 0.0 && o->confidence < 1.0 && o->min_inlier_ratio >= 0.0 && o->min_inlier_ratio <= 1.0 &&
-                  o->min_num_inliers >= 0 && o->min_num_trials >= 0 && o->max_num_trials >= 1 && o->max_num_trials <= (1 << 20) &&
-                  o->round_size >= 1 && o->round_size <= (1 << 20) && o->refine_max_iterations >= 0 && o->lo_rounds >= 0,
-              "%s: option out of range", fn);
-  if (h_ms) h_ms[0] = h_ms[1] = h_ms[2] = h_ms[3] = 0.0;
-  if (n_pairs == 0) {
-    PXR_REQUIRE(n_matches == 0, "%s: pair_offsets ends at 0, not at n_matches = %lld", fn, (long long)n_matches);
-    return PXR_OK;
-  }
-  PXR_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int64_t T = n_pairs, N = n_matches;
-
-  // offsets and cameras are validated on a host copy, which also gives the processing order: pairs by descending match count
-  std::vector<int64_t> off;
-  std::vector<int32_t> order, pcam((size_t)T * 2);
-  PXR_HIP(hipMemcpyAsync(pcam.data(), d_pair_camera, sizeof(int32_t) * (size_t)T * 2, hipMemcpyDeviceToHost, st));
-  const auto cameras_in_range = [&](int64_t t) {
-    for (int side = 0; side < 2; ++side)
-      PXR_REQUIRE(pcam[2 * t + side] >= 0 && pcam[2 * t + side] < n_cameras, "%s: pair %lld names a camera outside [0, n_cameras = %d)", fn,
-                  (long long)t, (int)n_cameras);
-    return (int)PXR_OK;
-  };
-  if (int rc = batch_order(ctx, {fn, "pair_offsets", "pair", "n_matches"}, false, d_pair_offsets, T, N, off, order, cameras_in_range)) return rc;
-
-  Carver cv;
-  const size_t o_rec = cv.take((size_t)N * FM_REC, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
-  const size_t o_ma = cv.take((size_t)N, 1), o_mb = cv.take((size_t)N, 1), o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4);
-  const size_t o_win = cv.take((size_t)T * 3, 4), o_winF = cv.take((size_t)T * 9, 8);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  double* rec = (double*)(ws + o_rec);
-  uint8_t* valid = (uint8_t*)(ws + o_valid);
-  int32_t* pos = (int32_t*)(ws + o_pos);
-  int32_t* n_valid = (int32_t*)(ws + o_nv);
-  int32_t* d_order = (int32_t*)(ws + o_order);
-
-  StageTimer<5> timer(st, h_ms);                         // records | compact | hypotheses | refine
-  if (int rc = timer.create(fn)) return rc;
-
-  auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
-  int rc = hip_check(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-  if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (`order` may go out of scope)
-  if (rc != PXR_OK) return rc;
-  timer.mark(0);
-  if (N > 0)
-    hipLaunchKernelGGL(k_fm_records, blocks(N, FM_THREADS), dim3(FM_THREADS), 0, st, N, n_pairs, d_pair_offsets, d_pair_camera,
-                       d_cam_model, d_cam_params, d_xy1, d_xy2, rec, valid, d_inlier, d_err);
-  timer.mark(1);
-  hipLaunchKernelGGL(k_compact_records<FM_REC>, blocks(T, FM_THREADS), dim3(FM_THREADS), 0, st, T, d_pair_offsets, rec, valid, pos, n_valid);
-  timer.mark(2);
+  const PairCall c = {"pxr_fundamental", ctx, n_pairs, d_pair_offsets, n_matches, d_xy1, d_xy2, d_pair_camera, n_cameras, d_cam_model,
+                      d_cam_params, o, d_status, d_n_inliers, d_n_trials, d_inlier, d_err, h_ms};
+  PairBatch b;
+  if (int rc = open_pair_batch(c, d_F != nullptr, nullptr, 3, b)) return rc;
+  if (n_pairs == 0) return PXR_OK;
   FmArgs a;
-  a.offsets = d_pair_offsets; a.pair_camera = d_pair_camera; a.cam_model = d_cam_model; a.cam_params = d_cam_params;
-  a.order = d_order; a.rec = rec; a.pos = pos; a.n_valid = n_valid; a.mask_a = (uint8_t*)(ws + o_ma); a.mask_b = (uint8_t*)(ws + o_mb);
-  a.o = *o;
-  a.max_trials = (int32_t)(((int64_t)o->max_num_trials + o->round_size - 1) / o->round_size * o->round_size);
-  a.F = d_F; a.status = d_status; a.n_inliers = d_n_inliers; a.n_trials = d_n_trials; a.inlier = d_inlier; a.err = d_err;
-  a.winner = (int32_t*)(ws + o_win); a.winner_F = (double*)(ws + o_winF);
-  hipLaunchKernelGGL(k_fm_hypotheses, dim3((unsigned)T), dim3(FM_THREADS), 0, st, a);
-  timer.mark(3);
-  hipLaunchKernelGGL(k_fm_refine, dim3((unsigned)T), dim3(FM_THREADS), 0, st, a);
-  timer.mark(4);
-  rc = hip_check(hipGetLastError(), "k_fm_refine launch");
-  const int from[4] = {0, 1, 2, 3};
-  return rc == PXR_OK ? timer.read(from, 4) : rc;
+  fill_pair_args(a, c, b);
+  a.winner_F = b.winner_model;
+  a.F = d_F;
+  hipLaunchKernelGGL(k_fm_hypotheses, dim3((unsigned)n_pairs), dim3(PAIR_THREADS), 0, ctx->stream, a);
+  b.timer->mark(3);
+  hipLaunchKernelGGL(k_fm_refine, dim3((unsigned)n_pairs), dim3(PAIR_THREADS), 0, ctx->stream, a);
+  return close_pair_batch(b, "k_fm_refine launch");
 }
 
 }  // namespace pxr
 
-extern "C" void pxr_fundamental_default_options(pxr_fundamental_options* o) {
-  if (!o) return;
-  o->max_error = 4.0; o->min_inlier_ratio = 0.25; o->confidence = 0.999;
-  o->seed = 0; o->min_num_inliers = 15; o->min_num_trials = 64; o->max_num_trials = 10000; o->round_size = 64;
-  o->refine_max_iterations = 100; o->lo_rounds = 4;
-}
+extern "C" void pxr_fundamental_default_options(pxr_fundamental_options* o) { pxr::pair_default_options(o); }
 
 extern "C" int pxr_fundamental(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
                                const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,

@@ -4,14 +4,10 @@
 // The planar / panoramic half of COLMAP's two-view geometry estimation (pycolmap.verify_matches classifies a pair from the ratio
 // of homography inliers to essential-matrix inliers), for calibrated cameras: undistort both pixels of every match, estimate a
 // homography of the normalised plane robustly from minimal samples (four points), refine it on its inliers, then fit the
-// rotation-only model H = R to those inliers and count who agrees with it.  Built from the shared core of pxr_robust.h and
-// pxr_batch.h like the essential-matrix estimator (pxr_twoview.hip): no random state -- sample h of a pair
-// is a counter-based hash of (seed, h) -- and every choice is a comparison of keys, so the result is a function of the pair's own
-// matches alone, bit for bit, alone or inside any batch.
+// rotation-only model H = R to those inliers and count who agrees with it.  Records, the opening of a pair, the local
+// optimisation and the host side of a call are those of pxr_pairs.h; what is here is the homography's own.
 //
-//   k_hg_records     one lane per match: its pair (binary search of the offsets), undistort both sides -> record (x1, y1, x2, y2)
-//   k_compact_records<4>  (pxr_robust.h) one lane per pair: the usable records of a pair moved to the front of its slice
-//   k_hg_hypotheses  one workgroup of 256 lanes per pair, the first HG_LDS records staged in LDS; a round of samples per
+//   k_hg_hypotheses  one workgroup of 256 lanes per pair, the first PAIR_LDS records staged in LDS; a round of samples per
 //                    wavefront, a sample per lane, every lane scoring its own homography against all records
 //   k_hg_refine      the winner's local optimisation, the final classification and the rotation-only model
 //
@@ -19,29 +15,18 @@
 // (figures: DESIGN.md section 22); the homography itself is in registers for the scoring walk.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
-#include <vector>
 
-#include "pxr_batch.h"
 #include "pxr_device.h"
-#include "pxr_internal.h"
-#include "pxr_robust.h"
-#include "pxr_undistort.h"
+#include "pxr_pairs.h"
 
 namespace pxr {
 
-constexpr int HG_THREADS = 256;
-constexpr int HG_WAVES = HG_THREADS / 64;
-constexpr int HG_REC = 4;                              // doubles per record: x1, y1, x2, y2 (normalised image points)
-constexpr int HG_LDS = PXR_TWOVIEW_LDS_MATCHES;        // records of a pair staged in LDS (32 B each); the rest is read from global memory (L2)
 constexpr int HG_ACC = 45;                             // the refinement's sums: J^t J (36, upper triangle by rows), g (8), cost
 constexpr int HG_ROT_ACC = 10;                         // those of the rotation-only model: 6, 3, cost
-constexpr int HG_CHUNK = 9;                            // of which this many cross the workgroup at a time (HG_THREADS x HG_CHUNK doubles of LDS)
+constexpr int HG_CHUNK = 9;                            // of which this many cross the workgroup at a time (PAIR_THREADS x HG_CHUNK doubles of LDS)
 constexpr double HG_PIVOT_TOL = 1e-12;                 // a pivot counts as zero below this fraction of the system's largest entry
 constexpr double HG_ROW_TOL = 1e-12;                   // a Gram-Schmidt row counts as zero at this norm
-constexpr double HG_STEP_TOL = 1e-12;                  // a refinement stops at a step of this norm
-constexpr double HG_COST_SLACK = 1e-12;                // a step is kept unless the cost grows by more than this fraction
 
 // ---- the four-point solver ---------------------------------------------------------------------------------------------------------
 // rec: the records (x1, y1, x2, y2) of a sample.  H (row-major, Frobenius norm 1) with H[2] . (x1, y1, 1) > 0 on all four.
@@ -116,44 +101,11 @@ __device__ __forceinline__ double hg_transfer(const double* H, const double* r) 
   return dx * dx + dy * dy;
 }
 
-// ---- kernel A: records -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(HG_THREADS) void k_hg_records(int64_t n_matches, int32_t n_pairs, const int64_t* __restrict__ offsets,
-                                                           const int32_t* __restrict__ pair_camera, const int32_t* __restrict__ cam_model,
-                                                           const double* __restrict__ cam_params, const double* __restrict__ xy1,
-                                                           const double* __restrict__ xy2, double* __restrict__ rec,
-                                                           uint8_t* __restrict__ valid, uint8_t* __restrict__ inlier, double* __restrict__ err) {
-  const int64_t i = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
-  if (i >= n_matches) return;
-  int lo = 0, hi = n_pairs;                            // the pair p with offsets[p] <= i < offsets[p + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) / 2;
-    if (offsets[mid] <= i) lo = mid; else hi = mid;
-  }
-  double uv[4];
-  bool ok = true;
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int cam = pair_camera[2 * (size_t)lo + side];
-    double k[PXR_KPAD];
-#pragma unroll
-    for (int j = 0; j < PXR_KPAD; ++j) k[j] = cam_params[(size_t)cam * PXR_KPAD + j];
-    const double* xy = side == 0 ? xy1 : xy2;
-    const double x = xy[2 * i], y = xy[2 * i + 1];
-    ok = isfinite(x) && isfinite(y) && ok;
-    ok = image_to_world(cam_model[cam], k, x, y, uv[2 * side], uv[2 * side + 1]) && ok;
-  }
-  double* r = rec + (size_t)i * HG_REC;
-  r[0] = uv[0]; r[1] = uv[1]; r[2] = uv[2]; r[3] = uv[3];
-  valid[i] = ok ? 1 : 0;
-  inlier[i] = 0;                                       // what a match keeps unless its pair gets a homography
-  err[i] = quiet_nan();
-}
-
 // ---- kernel B: the estimator -------------------------------------------------------------------------------------------------------
 struct HgArgs {
   const int64_t* offsets; const int32_t* pair_camera; const int32_t* cam_model; const double* cam_params;
   const int32_t* order;        // [n_pairs] pairs by descending match count
-  const double* rec;           // [n_matches][HG_REC], compacted per pair
+  const double* rec;           // [n_matches][PAIR_REC], compacted per pair
   const int32_t* pos;          // [n_matches]
   const int32_t* n_valid;      // [n_pairs]
   int32_t* winner;             // [n_pairs][2] the best key: count (-1: none), sample
@@ -164,38 +116,19 @@ struct HgArgs {
   double* H; double* rot_qvec; int32_t* status; int32_t* n_inliers; int32_t* n_rot_inliers; int32_t* n_trials; uint8_t* inlier; double* err;
 };
 
-struct HgPair {                // what every lane of the workgroup knows about its pair
-  const double* sh; const double* g; int n; int64_t o0;
-  double thr, thr2;
-  int need;                    // inliers the success rule asks for
-  __device__ __forceinline__ const double* rec(int j) const { return j < HG_LDS ? sh + j * HG_REC : g + (size_t)j * HG_REC; }
-};
-
-// what every lane of a workgroup needs of its pair; false: fewer than four usable matches
-__device__ __forceinline__ bool hg_open_pair(const HgArgs& a, int pi, double* sh_rec, HgPair& P) {
-  P.o0 = a.offsets[pi];
-  P.n = a.n_valid[pi];
-  if (P.n < 4) return false;
-  P.g = a.rec + (size_t)P.o0 * HG_REC;
-  P.sh = sh_rec;
-  for (int x = threadIdx.x; x < min(P.n, HG_LDS) * HG_REC; x += HG_THREADS) sh_rec[x] = P.g[x];
-  const int cam2 = a.pair_camera[2 * (size_t)pi + 1];
-  P.thr = a.o.max_error / mean_focal(a.cam_model[cam2], a.cam_params + (size_t)cam2 * PXR_KPAD);
-  P.thr2 = P.thr * P.thr;
-  P.need = max(a.o.min_num_inliers, (int)ceil(a.o.min_inlier_ratio * (double)P.n));
-  __syncthreads();
-  return true;
-}
+// inliers the success rule asks for of a pair with n usable matches
+__device__ __forceinline__ int hg_need(const HgArgs& a, int n) { return max(a.o.min_num_inliers, (int)ceil(a.o.min_inlier_ratio * (double)n)); }
 
 // Every branch that encloses a barrier or a cross-lane operation is uniform over the workgroup.
-__global__ __launch_bounds__(HG_THREADS) void k_hg_hypotheses(const HgArgs a) {
-  __shared__ double sh_rec[HG_LDS * HG_REC];
-  __shared__ double sh_ksum[HG_WAVES];
-  __shared__ int sh_kint[HG_WAVES][3];
+__global__ __launch_bounds__(PAIR_THREADS) void k_hg_hypotheses(const HgArgs a) {
+  __shared__ double sh_rec[PAIR_LDS * PAIR_REC];
+  __shared__ double sh_ksum[PAIR_WAVES];
+  __shared__ int sh_kint[PAIR_WAVES][3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int pi = a.order[blockIdx.x];
-  HgPair P;
-  if (!hg_open_pair(a, pi, sh_rec, P)) {
+  PairRecords P;
+  int floor_cnt;
+  if (!open_pair<PairThreshold::Camera2>(a, pi, 4, sh_rec, P, [&] { floor_cnt = hg_need(a, P.n); })) {
     if (tid == 0) { a.status[pi] = 1; a.n_inliers[pi] = 0; a.n_rot_inliers[pi] = 0; a.n_trials[pi] = 0; }
     return;
   }
@@ -205,7 +138,6 @@ __global__ __launch_bounds__(HG_THREADS) void k_hg_hypotheses(const HgArgs a) {
   // hypotheses: round r (round_size samples) on wavefront r mod 4, its samples strided over the lanes
   HypKey best = {-1, 0.0, 0x7fffffff, 0};
   int done = 0;
-  const int floor_cnt = P.need;
   const auto need = [&](int cnt) {                       // the stop rule: four inliers in a sample, at no fewer inliers than success asks for
     const int eff = max(cnt, floor_cnt);
     double w = (double)eff / (double)n;
@@ -213,7 +145,7 @@ __global__ __launch_bounds__(HG_THREADS) void k_hg_hypotheses(const HgArgs a) {
     return trials_needed(a.o.confidence, a.o.min_num_trials, a.max_trials, eff, (w * w) * (w * w));
   };
   for (int pass = 0;; ++pass) {
-    const int round = pass * HG_WAVES + wave;
+    const int round = pass * PAIR_WAVES + wave;
     HypKey mine = {-1, 0.0, 0x7fffffff, 0};
     if ((int64_t)round * a.o.round_size < a.max_trials) {
       for (int s = lane; s < a.o.round_size; s += 64) {
@@ -236,7 +168,7 @@ __global__ __launch_bounds__(HG_THREADS) void k_hg_hypotheses(const HgArgs a) {
       }
     }
     wave_best(mine);
-    if (merge_rounds<HG_WAVES>(sh_ksum, sh_kint, mine, pass, a.o.round_size, a.max_trials, best, done, need)) break;
+    if (merge_rounds<PAIR_WAVES>(sh_ksum, sh_kint, mine, pass, a.o.round_size, a.max_trials, best, done, need)) break;
   }
   if (tid == 0) {
     a.n_trials[pi] = done;
@@ -257,11 +189,11 @@ __global__ __launch_bounds__(HG_THREADS) void k_hg_hypotheses(const HgArgs a) {
 // ---- kernel C: local optimisation, classification, the rotation-only model ----------------------------------------------------------
 // sums of J^t J, J^t r and r^2 over the records of `mask`; r = pi(H x1) - x2 (two residuals per record), J = dr / d(the eight
 // entries of H other than `fixed`, in index order).  A record whose third component is not positive makes the cost +inf.
-__device__ __forceinline__ void hg_normal_equations(const HgPair& P, const uint8_t* mask, const double* H, int fixed,
+__device__ __forceinline__ void hg_normal_equations(const PairRecords& P, const uint8_t* mask, const double* H, int fixed,
                                                     double (&acc)[HG_ACC], double* sh_part, double* sh_tot) {
 #pragma unroll
   for (int c = 0; c < HG_ACC; ++c) acc[c] = 0.0;
-  for (int j = threadIdx.x; j < P.n; j += HG_THREADS) {
+  for (int j = threadIdx.x; j < P.n; j += PAIR_THREADS) {
     if (!mask[P.o0 + j]) continue;
     const double* r = P.rec(j);
     const double x1 = r[0], y1 = r[1];
@@ -284,17 +216,17 @@ __device__ __forceinline__ void hg_normal_equations(const HgPair& P, const uint8
     }
     acc[44] += r0 * r0 + r1 * r1;
   }
-  block_sum<HG_THREADS, HG_CHUNK>(acc, sh_part, sh_tot);
+  block_sum<PAIR_THREADS, HG_CHUNK>(acc, sh_part, sh_tot);
 }
 
 // the same for H = R(q) over the rotation tangent (3): R(d) = R(2 d) R, so dp / dd_c = 2 e_c x p with p = R x1
-__device__ __forceinline__ void hg_rot_normal_equations(const HgPair& P, const uint8_t* mask, const double* q,
+__device__ __forceinline__ void hg_rot_normal_equations(const PairRecords& P, const uint8_t* mask, const double* q,
                                                         double (&acc)[HG_ROT_ACC], double* sh_part, double* sh_tot) {
 #pragma unroll
   for (int c = 0; c < HG_ROT_ACC; ++c) acc[c] = 0.0;
   double R[9];
   quat_to_rotation(q, R);
-  for (int j = threadIdx.x; j < P.n; j += HG_THREADS) {
+  for (int j = threadIdx.x; j < P.n; j += PAIR_THREADS) {
     if (!mask[P.o0 + j]) continue;
     const double* r = P.rec(j);
     const double x1 = r[0], y1 = r[1];
@@ -315,118 +247,52 @@ __device__ __forceinline__ void hg_rot_normal_equations(const HgPair& P, const u
     }
     acc[9] += r0 * r0 + r1 * r1;
   }
-  block_sum<HG_THREADS, HG_CHUNK>(acc, sh_part, sh_tot);
+  block_sum<PAIR_THREADS, HG_CHUNK>(acc, sh_part, sh_tot);
 }
 
-// Levenberg-Marquardt over D parameters on a state of NS doubles, refined in place: sums(x, acc) forms the normal equations at
-// x, plus(x, d, x1) moves it.  The lambda schedule and the keep / refuse rule of sections 19 and 21.  Every lane holds the same
-// sums, so every lane takes the same decisions and ends with the same state.
-template <int D, int NS, class Sums, class Plus>
-__device__ __forceinline__ void hg_lm(int max_iterations, double (&x)[NS], Sums sums, Plus plus) {
-  constexpr int NA = D * (D + 1) / 2 + D + 1;
-  double acc[NA];
-  sums(x, acc);
-  if (!isfinite(acc[NA - 1])) return;
-  double lambda = 1e-4;
-  for (int it = 0; it < max_iterations; ++it) {
-    double d[D], x1[NS];
-    if (!solve_damped<D>(acc, lambda, d)) {
-      lambda *= 10.0;
-      if (lambda > 1e12) break;
-      continue;
-    }
-    double cur[NA];                                       // the sums at x, kept while the trial's are formed
-#pragma unroll
-    for (int c = 0; c < NA; ++c) cur[c] = acc[c];
-    const double cost = acc[NA - 1];
-    plus(x, d, x1);
-    sums(x1, acc);
-    if (acc[NA - 1] <= cost + HG_COST_SLACK * cost) {
-#pragma unroll
-      for (int j = 0; j < NS; ++j) x[j] = x1[j];
-      lambda = fmax(lambda * 0.1, 1e-12);
-    } else {
-#pragma unroll
-      for (int c = 0; c < NA; ++c) acc[c] = cur[c];
-      lambda *= 10.0;
-      if (lambda > 1e12) break;
-    }
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < D; ++j) s += d[j] * d[j];
-    if (sqrt(s) <= HG_STEP_TOL) break;
-  }
-}
-
-__global__ __launch_bounds__(HG_THREADS) void k_hg_refine(const HgArgs a) {
-  __shared__ double sh_rec[HG_LDS * HG_REC];
-  __shared__ double sh_part[HG_THREADS * HG_CHUNK];
+__global__ __launch_bounds__(PAIR_THREADS) void k_hg_refine(const HgArgs a) {
+  __shared__ double sh_rec[PAIR_LDS * PAIR_REC];
+  __shared__ double sh_part[PAIR_THREADS * HG_CHUNK];
   __shared__ double sh_tot[HG_ACC];
   const int tid = threadIdx.x;
   const int pi = a.order[blockIdx.x];
-  HgPair P;
-  if (!hg_open_pair(a, pi, sh_rec, P)) return;           // status 1: written by k_hg_hypotheses
-  if (a.winner[2 * (size_t)pi] < 0) return;              // status 2: written by k_hg_hypotheses
+  PairRecords P;
+  int need;
+  // status 1 and status 2 are written by k_hg_hypotheses
+  if (!open_pair<PairThreshold::Camera2>(a, pi, 4, sh_rec, P, [&] { need = hg_need(a, P.n); })) return;
+  if (a.winner[2 * (size_t)pi] < 0) return;
   const int n = P.n;
   const double thr2 = P.thr2;
   double H[9];
 #pragma unroll
   for (int m = 0; m < 9; ++m) H[m] = a.winner_H[9 * (size_t)pi + m];
 
-  // 1. the winner's inliers
+  // 1-2. the winner's inliers, then the local optimisation: refine on the inliers, classify again, until the set stands still
   uint8_t* cur = a.mask_a;
   uint8_t* nxt = a.mask_b;
-  double first[1] = {0.0};
-  for (int j = tid; j < n; j += HG_THREADS) {
-    const bool in = hg_transfer(H, P.rec(j)) <= thr2;
-    cur[P.o0 + j] = in ? 1 : 0;                          // (a lane reads back only what it wrote: j = tid mod 256)
-    first[0] += in ? 1.0 : 0.0;
-  }
-  block_sum<HG_THREADS, HG_CHUNK>(first, sh_part, sh_tot);
-  int cur_cnt = (int)first[0];
-
-  // 2. local optimisation: refine on the inliers, classify again, until the set stands still
-  for (int lo = 0; lo < a.o.lo_rounds; ++lo) {
-    double H1[9];
-    int fixed = 0;                                       // the entry of largest magnitude, the first of equals
+  const int cur_cnt = local_optimisation<HG_CHUNK>(
+      P, a.o.lo_rounds, H, cur, nxt, [](const double* M, const double* r) { return hg_transfer(M, r); },
+      [&](const double* H0, const uint8_t* mask, double (&H1)[9]) {
+        int fixed = 0;                                   // the entry of largest magnitude, the first of equals
 #pragma unroll
-    for (int m = 0; m < 9; ++m) { H1[m] = H[m]; if (fabs(H[m]) > fabs(H[fixed])) fixed = m; }
-    const uint8_t* mask = cur;
-    hg_lm<8, 9>(a.o.refine_max_iterations, H1,
-                [&](const double* x, double (&acc)[HG_ACC]) { hg_normal_equations(P, mask, x, fixed, acc, sh_part, sh_tot); },
-                [&](const double* x, const double* d, double* x1) {
+        for (int m = 0; m < 9; ++m) { H1[m] = H0[m]; if (fabs(H0[m]) > fabs(H0[fixed])) fixed = m; }
+        lm_refine<8, 9>(a.o.refine_max_iterations, H1,
+                        [&](const double* x, double (&acc)[HG_ACC]) { hg_normal_equations(P, mask, x, fixed, acc, sh_part, sh_tot); },
+                        [&](const double* x, const double* d, double* x1) {
 #pragma unroll
-                  for (int m = 0; m < 9; ++m) x1[m] = m == fixed ? x[m] : x[m] + d[m < fixed ? m : m - 1];
-                });
-    double s = 0.0;
-#pragma unroll
-    for (int m = 0; m < 9; ++m) s += H1[m] * H1[m];
-    const double nrm = sqrt(s);
-#pragma unroll
-    for (int m = 0; m < 9; ++m) H1[m] = H1[m] / nrm;
-    double cc[2] = {0.0, 0.0};                            // inliers of the refined homography; how many memberships changed
-    for (int j = tid; j < n; j += HG_THREADS) {
-      const bool in = hg_transfer(H1, P.rec(j)) <= thr2;
-      nxt[P.o0 + j] = in ? 1 : 0;
-      cc[0] += in ? 1.0 : 0.0;
-      cc[1] += (in != (cur[P.o0 + j] != 0)) ? 1.0 : 0.0;
-    }
-    block_sum<HG_THREADS, HG_CHUNK>(cc, sh_part, sh_tot);
-    if (!(cc[0] >= (double)cur_cnt)) break;               // fewer inliers: the homography before it stays
-#pragma unroll
-    for (int m = 0; m < 9; ++m) H[m] = H1[m];
-    uint8_t* sw = cur; cur = nxt; nxt = sw;
-    cur_cnt = (int)cc[0];
-    if (cc[1] == 0.0) break;
-  }
+                          for (int m = 0; m < 9; ++m) x1[m] = m == fixed ? x[m] : x[m] + d[m < fixed ? m : m - 1];
+                        });
+        return true;
+      },
+      sh_part, sh_tot);
 
   // 3. the final set (`cur`: the classification under the H that stays) and the success rule
-  if (cur_cnt < P.need) {
+  if (cur_cnt < need) {
     if (tid == 0) { a.status[pi] = 3; a.n_inliers[pi] = 0; a.n_rot_inliers[pi] = 0; }
     return;
   }
   const double to_px = a.o.max_error / P.thr;
-  for (int j = tid; j < n; j += HG_THREADS) {
+  for (int j = tid; j < n; j += PAIR_THREADS) {
     const double e2 = hg_transfer(H, P.rec(j));
     const int64_t i = P.o0 + a.pos[P.o0 + j];
     a.err[i] = isfinite(e2) ? sqrt(e2) * to_px : quiet_nan();
@@ -460,14 +326,14 @@ __global__ __launch_bounds__(HG_THREADS) void k_hg_refine(const HgArgs a) {
   if (have) {                                            // (uniform: every lane holds the same H)
     rotation_to_quat(R0, q);
     const uint8_t* mask = cur;
-    hg_lm<3, 4>(a.o.refine_max_iterations, q,
+    lm_refine<3, 4>(a.o.refine_max_iterations, q,
                 [&](const double* x, double (&acc)[HG_ROT_ACC]) { hg_rot_normal_equations(P, mask, x, acc, sh_part, sh_tot); },
                 [&](const double* x, const double* d, double* x1) { quat_plus(x, d, x1); });
     double R[9];
     quat_to_rotation(q, R);
     double rc[1] = {0.0};
-    for (int j = tid; j < n; j += HG_THREADS) rc[0] += hg_transfer(R, P.rec(j)) <= thr2 ? 1.0 : 0.0;
-    block_sum<HG_THREADS, HG_CHUNK>(rc, sh_part, sh_tot);
+    for (int j = tid; j < n; j += PAIR_THREADS) rc[0] += hg_transfer(R, P.rec(j)) <= thr2 ? 1.0 : 0.0;
+    block_sum<PAIR_THREADS, HG_CHUNK>(rc, sh_part, sh_tot);
     n_rot = (int)rc[0];
   }
   if (tid == 0) {
@@ -484,89 +350,24 @@ static int homography(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offse
                       const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,
                       const double* d_cam_params, const pxr_homography_options* o, double* d_H, double* d_rot_qvec, int32_t* d_status,
                       int32_t* d_n_inliers, int32_t* d_n_rot_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err, double* h_ms) {
-  const char* fn = "pxr_homography";
-  PXR_REQUIRE(ctx && o, "%s: NULL argument", fn);
-  PXR_REQUIRE(n_pairs >= 0 && n_matches >= 0 && n_cameras >= 0, "%s: negative size", fn);
-  PXR_REQUIRE(n_matches < ((int64_t)1 << 31), "%s: more than 2^31 matches", fn);
-  PXR_REQUIRE(n_pairs == 0 || (d_pair_offsets && d_pair_camera && d_H && d_rot_qvec && d_status && d_n_inliers && d_n_rot_inliers &&
-                               d_n_trials && d_cam_model && d_cam_params), "%s: NULL pair / camera array", fn);
-  PXR_REQUIRE(n_matches == 0 || (d_xy1 && d_xy2 && d_inlier && d_err), "%s: NULL match array", fn);
-  PXR_REQUIRE(o->max_error > 0.0 && o->confidence > 0.0 && o->confidence < 1.0 && o->min_inlier_ratio >= 0.0 && o->min_inlier_ratio <= 1.0 &&
-                  o->min_num_inliers >= 0 && o->min_num_trials >= 0 && o->max_num_trials >= 1 && o->max_num_trials <= (1 << 20) &&
-                  o->round_size >= 1 && o->round_size <= (1 << 20) && o->refine_max_iterations >= 0 && o->lo_rounds >= 0,
-              "%s: option out of range", fn);
-  if (h_ms) h_ms[0] = h_ms[1] = h_ms[2] = h_ms[3] = 0.0;
-  if (n_pairs == 0) {
-    PXR_REQUIRE(n_matches == 0, "%s: pair_offsets ends at 0, not at n_matches = %lld", fn, (long long)n_matches);
-    return PXR_OK;
-  }
-  PXR_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int64_t T = n_pairs, N = n_matches;
-
-  // offsets and cameras are validated on a host copy, which also gives the processing order: pairs by descending match count
-  std::vector<int64_t> off;
-  std::vector<int32_t> order, pcam((size_t)T * 2);
-  PXR_HIP(hipMemcpyAsync(pcam.data(), d_pair_camera, sizeof(int32_t) * (size_t)T * 2, hipMemcpyDeviceToHost, st));
-  const auto cameras_in_range = [&](int64_t t) {
-    for (int side = 0; side < 2; ++side)
-      PXR_REQUIRE(pcam[2 * t + side] >= 0 && pcam[2 * t + side] < n_cameras, "%s: pair %lld names a camera outside [0, n_cameras = %d)", fn,
-                  (long long)t, (int)n_cameras);
-    return (int)PXR_OK;
-  };
-  if (int rc = batch_order(ctx, {fn, "pair_offsets", "pair", "n_matches"}, false, d_pair_offsets, T, N, off, order, cameras_in_range)) return rc;
-
-  Carver cv;
-  const size_t o_rec = cv.take((size_t)N * HG_REC, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
-  const size_t o_ma = cv.take((size_t)N, 1), o_mb = cv.take((size_t)N, 1), o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4);
-  const size_t o_win = cv.take((size_t)T * 2, 4), o_winH = cv.take((size_t)T * 9, 8);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  double* rec = (double*)(ws + o_rec);
-  uint8_t* valid = (uint8_t*)(ws + o_valid);
-  int32_t* pos = (int32_t*)(ws + o_pos);
-  int32_t* n_valid = (int32_t*)(ws + o_nv);
-  int32_t* d_order = (int32_t*)(ws + o_order);
-
-  StageTimer<5> timer(st, h_ms);                         // records | compact | hypotheses | refine
-  if (int rc = timer.create(fn)) return rc;
-
-  auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
-  int rc = hip_check(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-  if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (`order` may go out of scope)
-  if (rc != PXR_OK) return rc;
-  timer.mark(0);
-  if (N > 0)
-    hipLaunchKernelGGL(k_hg_records, blocks(N, HG_THREADS), dim3(HG_THREADS), 0, st, N, n_pairs, d_pair_offsets, d_pair_camera,
-                       d_cam_model, d_cam_params, d_xy1, d_xy2, rec, valid, d_inlier, d_err);
-  timer.mark(1);
-  hipLaunchKernelGGL(k_compact_records<HG_REC>, blocks(T, HG_THREADS), dim3(HG_THREADS), 0, st, T, d_pair_offsets, rec, valid, pos, n_valid);
-  timer.mark(2);
+  const PairCall c = {"pxr_homography", ctx, n_pairs, d_pair_offsets, n_matches, d_xy1, d_xy2, d_pair_camera, n_cameras, d_cam_model,
+                      d_cam_params, o, d_status, d_n_inliers, d_n_trials, d_inlier, d_err, h_ms};
+  PairBatch b;
+  if (int rc = open_pair_batch(c, d_H && d_rot_qvec && d_n_rot_inliers, nullptr, 2, b)) return rc;
+  if (n_pairs == 0) return PXR_OK;
   HgArgs a;
-  a.offsets = d_pair_offsets; a.pair_camera = d_pair_camera; a.cam_model = d_cam_model; a.cam_params = d_cam_params;
-  a.order = d_order; a.rec = rec; a.pos = pos; a.n_valid = n_valid; a.mask_a = (uint8_t*)(ws + o_ma); a.mask_b = (uint8_t*)(ws + o_mb);
-  a.o = *o;
-  a.max_trials = (int32_t)(((int64_t)o->max_num_trials + o->round_size - 1) / o->round_size * o->round_size);
-  a.H = d_H; a.rot_qvec = d_rot_qvec; a.status = d_status; a.n_inliers = d_n_inliers; a.n_rot_inliers = d_n_rot_inliers;
-  a.n_trials = d_n_trials; a.inlier = d_inlier; a.err = d_err;
-  a.winner = (int32_t*)(ws + o_win); a.winner_H = (double*)(ws + o_winH);
-  hipLaunchKernelGGL(k_hg_hypotheses, dim3((unsigned)T), dim3(HG_THREADS), 0, st, a);
-  timer.mark(3);
-  hipLaunchKernelGGL(k_hg_refine, dim3((unsigned)T), dim3(HG_THREADS), 0, st, a);
-  timer.mark(4);
-  rc = hip_check(hipGetLastError(), "k_hg_refine launch");
-  const int from[4] = {0, 1, 2, 3};
-  return rc == PXR_OK ? timer.read(from, 4) : rc;
+  fill_pair_args(a, c, b);
+  a.winner_H = b.winner_model;
+  a.H = d_H; a.rot_qvec = d_rot_qvec; a.n_rot_inliers = d_n_rot_inliers;
+  hipLaunchKernelGGL(k_hg_hypotheses, dim3((unsigned)n_pairs), dim3(PAIR_THREADS), 0, ctx->stream, a);
+  b.timer->mark(3);
+  hipLaunchKernelGGL(k_hg_refine, dim3((unsigned)n_pairs), dim3(PAIR_THREADS), 0, ctx->stream, a);
+  return close_pair_batch(b, "k_hg_refine launch");
 }
 
 }  // namespace pxr
 
-extern "C" void pxr_homography_default_options(pxr_homography_options* o) {
-  if (!o) return;
-  o->max_error = 4.0; o->min_inlier_ratio = 0.25; o->confidence = 0.999;
-  o->seed = 0; o->min_num_inliers = 15; o->min_num_trials = 64; o->max_num_trials = 10000; o->round_size = 64;
-  o->refine_max_iterations = 100; o->lo_rounds = 4;
-}
+extern "C" void pxr_homography_default_options(pxr_homography_options* o) { pxr::pair_default_options(o); }
 
 extern "C" int pxr_homography(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
                               const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,

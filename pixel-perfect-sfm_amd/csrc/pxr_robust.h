@@ -1,12 +1,14 @@
-// pxr_robust.h -- the device core the batched robust estimators share (pxr_abspose.hip, pxr_twoview.hip; pxr_triangulate.hip takes
-// the constants and the compaction kernel): the counter-hash samples, the hypothesis key and its selection across a workgroup, the
-// stop rule, the fixed-order workgroup sum, the damped Cholesky solve, the quaternion update and the compaction of usable records.
+// pxr_robust.h -- the device core the batched robust estimators share (pxr_abspose.hip, pxr_twoview.hip, pxr_homography.hip,
+// pxr_fundamental.hip; pxr_triangulate.hip takes the constants and the compaction kernel): the counter-hash samples, the
+// hypothesis key and its selection across a workgroup, the stop rule, the fixed-order workgroup sum, the damped Cholesky solve,
+// the Levenberg-Marquardt loop, the quaternion update and the compaction of usable records.
 // Everything here is a function of its arguments alone -- no random state, every choice a comparison of keys -- which is what
 // makes an estimator built from it a function of the item's own data, bit for bit, alone or inside any batch (DESIGN.md sections
 // 19 and 21).  __shared__ arrays are declared by the kernels and handed down as pointers.
-// Not here: the Levenberg-Marquardt and local-optimisation loops of the two refine kernels.  Both kernels sit at 256 VGPRs with
-// spills, and either loop written once as a template over the estimator's pieces costs each of them spill registers (DESIGN.md
-// section 21, "the shared core"); the loops are built from block_sum, solve_damped and quat_plus below and stay with their kernels.
+// Not here: the Levenberg-Marquardt and local-optimisation loops of k_abs_refine and k_tv_refine.  Both kernels sit at 256 VGPRs
+// with spills, and either loop taken from a template over the estimator's pieces costs each of them spill registers (DESIGN.md
+// section 21, "the shared core"); their loops are built from block_sum, solve_damped and quat_plus below and stay written out in
+// their kernels.  k_hg_refine and k_fm_refine take lm_refine from here and their local optimisation from pxr_pairs.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -261,6 +263,49 @@ __device__ __forceinline__ bool solve_damped(const double (&acc)[D * (D + 1) / 2
     ok = ok && isfinite(d[i]);
   }
   return ok;
+}
+
+// Levenberg-Marquardt over D parameters on a state of NS doubles, refined in place: sums(x, acc) forms the normal equations at
+// x (acc as solve_damped takes it), plus(x, d, x1) moves it.  lambda from 1e-4, x 0.1 (not below 1e-12) on a kept step, x 10 on
+// a refused or unsolvable one, until lambda > 1e12 (sections 19, 21 and 22).  Every lane holds the same sums, so every lane takes
+// the same decisions and ends with the same state.
+constexpr double LM_STEP_TOL = 1e-12;                  // a refinement stops at a step of this norm
+constexpr double LM_COST_SLACK = 1e-12;                // a step is kept unless the cost grows by more than this fraction
+template <int D, int NS, class Sums, class Plus>
+__device__ __forceinline__ void lm_refine(int max_iterations, double (&x)[NS], Sums sums, Plus plus) {
+  constexpr int NA = D * (D + 1) / 2 + D + 1;
+  double acc[NA];
+  sums(x, acc);
+  if (!isfinite(acc[NA - 1])) return;
+  double lambda = 1e-4;
+  for (int it = 0; it < max_iterations; ++it) {
+    double d[D], x1[NS];
+    if (!solve_damped<D>(acc, lambda, d)) {
+      lambda *= 10.0;
+      if (lambda > 1e12) break;
+      continue;
+    }
+    double cur[NA];                                       // the sums at x, kept while the trial's are formed
+#pragma unroll
+    for (int c = 0; c < NA; ++c) cur[c] = acc[c];
+    const double cost = acc[NA - 1];
+    plus(x, d, x1);
+    sums(x1, acc);
+    if (acc[NA - 1] <= cost + LM_COST_SLACK * cost) {
+#pragma unroll
+      for (int j = 0; j < NS; ++j) x[j] = x1[j];
+      lambda = fmax(lambda * 0.1, 1e-12);
+    } else {
+#pragma unroll
+      for (int c = 0; c < NA; ++c) acc[c] = cur[c];
+      lambda *= 10.0;
+      if (lambda > 1e12) break;
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < D; ++j) s += d[j] * d[j];
+    if (sqrt(s) <= LM_STEP_TOL) break;
+  }
 }
 
 // ---- records -------------------------------------------------------------------------------------------------------------------------

@@ -7,11 +7,10 @@
 // points), decompose it, refine the pose on its inliers.  Like the absolute-pose estimator (pxr_abspose.hip, DESIGN.md section
 // 19) it has no random state -- sample h of a pair is a counter-based hash of (seed, h) -- and every choice is a comparison of
 // keys, so the result is a function of the pair's own matches alone, bit for bit, alone or inside any batch.
+// Records, the opening of a pair and the host side of a call are those of pxr_pairs.h, shared with the homography and
+// fundamental-matrix estimators.
 //
-//   k_tv_bearings    one lane per match: its pair (binary search of the offsets), undistort both sides -> record (u1, v1, u2, v2)
-//   k_compact_records<4>  (pxr_robust.h) one lane per pair: the usable records of a pair moved to the front of its slice (in
-//                    order), positions kept
-//   k_tv_hypotheses  the estimator's samples: one workgroup of 256 lanes per pair, the first TV_LDS records staged in LDS; a round
+//   k_tv_hypotheses  the estimator's samples: one workgroup of 256 lanes per pair, the first PAIR_LDS records staged in LDS; a round
 //                    of samples per wavefront, a sample per lane, every lane scoring its own essential matrices against all records
 //   k_tv_refine      the winner's decomposition, local optimisation and final classification; with a pose prior, only the last
 //
@@ -27,24 +26,15 @@
 // is in registers for the scoring walk, which is the larger share of the work from a few hundred matches on.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
-#include <vector>
 
-#include "pxr_batch.h"
 #include "pxr_device.h"
-#include "pxr_internal.h"
-#include "pxr_robust.h"
-#include "pxr_undistort.h"
+#include "pxr_pairs.h"
 
 namespace pxr {
 
-constexpr int TV_THREADS = 256;
-constexpr int TV_WAVES = TV_THREADS / 64;
-constexpr int TV_REC = 4;                              // doubles per record: u1, v1, u2, v2 (normalised image points)
-constexpr int TV_LDS = PXR_TWOVIEW_LDS_MATCHES;        // records of a pair staged in LDS (32 B each); the rest is read from global memory (L2)
 constexpr int TV_ACC = 21;                             // the refinement's sums: H (15, upper triangle by rows), g (5), cost
-constexpr int TV_CHUNK = 7;                            // of which this many cross the workgroup at a time (TV_THREADS x TV_CHUNK doubles of LDS)
+constexpr int TV_CHUNK = 7;                            // of which this many cross the workgroup at a time (PAIR_THREADS x TV_CHUNK doubles of LDS)
 constexpr int TV_DEG = 10;                             // degree of the polynomial in z
 constexpr int TV_BISECT = 64;                          // bisection steps per root
 constexpr int TV_NEWTON = 4;                           // Newton steps per root, each kept only inside the bisection's last interval
@@ -367,45 +357,12 @@ __device__ __forceinline__ double tv_sampson(const double* E, const double* r) {
   return (N * N) / D;
 }
 
-// ---- kernel A: records -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TV_THREADS) void k_tv_bearings(int64_t n_matches, int32_t n_pairs, const int64_t* __restrict__ offsets,
-                                                            const int32_t* __restrict__ pair_camera, const int32_t* __restrict__ cam_model,
-                                                            const double* __restrict__ cam_params, const double* __restrict__ xy1,
-                                                            const double* __restrict__ xy2, double* __restrict__ rec,
-                                                            uint8_t* __restrict__ valid, uint8_t* __restrict__ inlier, double* __restrict__ err) {
-  const int64_t i = (int64_t)blockIdx.x * TV_THREADS + threadIdx.x;
-  if (i >= n_matches) return;
-  int lo = 0, hi = n_pairs;                            // the pair p with offsets[p] <= i < offsets[p + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) / 2;
-    if (offsets[mid] <= i) lo = mid; else hi = mid;
-  }
-  double uv[4];
-  bool ok = true;
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int cam = pair_camera[2 * (size_t)lo + side];
-    double k[PXR_KPAD];
-#pragma unroll
-    for (int j = 0; j < PXR_KPAD; ++j) k[j] = cam_params[(size_t)cam * PXR_KPAD + j];
-    const double* xy = side == 0 ? xy1 : xy2;
-    const double x = xy[2 * i], y = xy[2 * i + 1];
-    ok = isfinite(x) && isfinite(y) && ok;
-    ok = image_to_world(cam_model[cam], k, x, y, uv[2 * side], uv[2 * side + 1]) && ok;
-  }
-  double* r = rec + (size_t)i * TV_REC;
-  r[0] = uv[0]; r[1] = uv[1]; r[2] = uv[2]; r[3] = uv[3];
-  valid[i] = ok ? 1 : 0;
-  inlier[i] = 0;                                       // what a match keeps unless its pair gets a pose
-  err[i] = quiet_nan();
-}
-
 // ---- kernel B: the estimator -------------------------------------------------------------------------------------------------------
 struct TvArgs {
   const int64_t* offsets; const int32_t* pair_camera; const int32_t* cam_model; const double* cam_params;
   const double* prior_qvec; const double* prior_tvec;   // both null: estimate; else [n_pairs][4] / [n_pairs][3]
   const int32_t* order;        // [n_pairs] pairs by descending match count
-  const double* rec;           // [n_matches][TV_REC], compacted per pair
+  const double* rec;           // [n_matches][PAIR_REC], compacted per pair
   const int32_t* pos;          // [n_matches]
   const int32_t* n_valid;      // [n_pairs]
   int32_t* winner;             // [n_pairs][3] the best key: count (-1: none), sample, root
@@ -416,39 +373,16 @@ struct TvArgs {
   double* qvec; double* tvec; double* E; int32_t* status; int32_t* n_inliers; int32_t* n_trials; uint8_t* inlier; double* err;
 };
 
-struct TvPair {                // what every lane of the workgroup knows about its pair
-  const double* sh; const double* g; int n; int64_t o0;
-  double thr, thr2;
-  __device__ __forceinline__ const double* rec(int j) const { return j < TV_LDS ? sh + j * TV_REC : g + (size_t)j * TV_REC; }
-};
-
-// what every lane of a workgroup needs of its pair; false: fewer than five usable matches
-__device__ __forceinline__ bool tv_open_pair(const TvArgs& a, int pi, double* sh_rec, TvPair& P) {
-  P.o0 = a.offsets[pi];
-  P.n = a.n_valid[pi];
-  if (P.n < 5) return false;
-  P.g = a.rec + (size_t)P.o0 * TV_REC;
-  P.sh = sh_rec;
-  for (int x = threadIdx.x; x < min(P.n, TV_LDS) * TV_REC; x += TV_THREADS) sh_rec[x] = P.g[x];
-  const int cam1 = a.pair_camera[2 * (size_t)pi], cam2 = a.pair_camera[2 * (size_t)pi + 1];
-  const double f1 = mean_focal(a.cam_model[cam1], a.cam_params + (size_t)cam1 * PXR_KPAD);
-  const double f2 = mean_focal(a.cam_model[cam2], a.cam_params + (size_t)cam2 * PXR_KPAD);
-  P.thr = 0.5 * (a.o.max_error / f1 + a.o.max_error / f2);
-  P.thr2 = P.thr * P.thr;
-  __syncthreads();
-  return true;
-}
-
 // Every branch that encloses a barrier or a cross-lane operation is uniform over the workgroup; the hypothesis loop, where the
 // lanes meet different root counts, has none.
-__global__ __launch_bounds__(TV_THREADS) void k_tv_hypotheses(const TvArgs a) {
-  __shared__ double sh_rec[TV_LDS * TV_REC];
-  __shared__ double sh_ksum[TV_WAVES];
-  __shared__ int sh_kint[TV_WAVES][3];
+__global__ __launch_bounds__(PAIR_THREADS) void k_tv_hypotheses(const TvArgs a) {
+  __shared__ double sh_rec[PAIR_LDS * PAIR_REC];
+  __shared__ double sh_ksum[PAIR_WAVES];
+  __shared__ int sh_kint[PAIR_WAVES][3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int pi = a.order[blockIdx.x];
-  TvPair P;
-  if (!tv_open_pair(a, pi, sh_rec, P)) {
+  PairRecords P;
+  if (!open_pair<PairThreshold::BothCameras>(a, pi, 5, sh_rec, P)) {
     if (tid == 0) { a.status[pi] = 1; a.n_inliers[pi] = 0; a.n_trials[pi] = 0; }
     return;
   }
@@ -463,7 +397,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_hypotheses(const TvArgs a) {
     return trials_needed(a.o.confidence, a.o.min_num_trials, a.max_trials, cnt, (w * w) * (w * w) * w);
   };
   for (int pass = 0;; ++pass) {
-    const int round = pass * TV_WAVES + wave;
+    const int round = pass * PAIR_WAVES + wave;
     HypKey mine = {-1, 0.0, 0x7fffffff, TV_DEG};
     if ((int64_t)round * a.o.round_size < a.max_trials) {
       for (int s = lane; s < a.o.round_size; s += 64) {
@@ -501,11 +435,11 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_hypotheses(const TvArgs a) {
     if (lane == 0) { sh_ksum[wave] = mine.sum; sh_kint[wave][0] = mine.cnt; sh_kint[wave][1] = mine.h; sh_kint[wave][2] = mine.root; }
     __syncthreads();
     bool stop = false;
-    for (int w = 0; w < TV_WAVES && !stop; ++w) {       // the rounds in order; the stop rule at every round boundary
-      if ((int64_t)(pass * TV_WAVES + w) * a.o.round_size >= a.max_trials) { stop = true; break; }
+    for (int w = 0; w < PAIR_WAVES && !stop; ++w) {       // the rounds in order; the stop rule at every round boundary
+      if ((int64_t)(pass * PAIR_WAVES + w) * a.o.round_size >= a.max_trials) { stop = true; break; }
       const HypKey key = {sh_kint[w][0], sh_ksum[w], sh_kint[w][1], sh_kint[w][2]};
       if (key.beats(best)) best = key;
-      done = (pass * TV_WAVES + w + 1) * a.o.round_size;
+      done = (pass * PAIR_WAVES + w + 1) * a.o.round_size;
       stop = (double)done >= need(best.cnt);
     }
     __syncthreads();
@@ -597,7 +531,7 @@ __device__ __forceinline__ void tv_tangent_basis(const double* t, double b1[3], 
 
 // H = sum J^t J, g = sum J^t r, cost = sum r^2 over the records of `mask`; r = x2^t E x1 / sqrt(D) the signed Sampson residual of
 // E = [t]x R(q), J = dr / d(rotation tangent (3), a, b): R(d) = R(2 d) R, t(a, b) = (t + a b1 + b b2) / |.|
-__device__ __forceinline__ void tv_normal_equations(const TvPair& P, const uint8_t* mask, const double* q, const double* t,
+__device__ __forceinline__ void tv_normal_equations(const PairRecords& P, const uint8_t* mask, const double* q, const double* t,
                                                     double (&acc)[TV_ACC], double* sh_part, double* sh_tot) {
 #pragma unroll
   for (int c = 0; c < TV_ACC; ++c) acc[c] = 0.0;
@@ -614,7 +548,7 @@ __device__ __forceinline__ void tv_normal_equations(const TvPair& P, const uint8
   }
   tv_essential_of_pose(R, b1, dE[3]);
   tv_essential_of_pose(R, b2, dE[4]);
-  for (int j = threadIdx.x; j < P.n; j += TV_THREADS) {
+  for (int j = threadIdx.x; j < P.n; j += PAIR_THREADS) {
     if (!mask[P.o0 + j]) continue;
     const double* r = P.rec(j);
     const double u1 = r[0], v1 = r[1], u2 = r[2], v2 = r[3];
@@ -643,7 +577,7 @@ __device__ __forceinline__ void tv_normal_equations(const TvPair& P, const uint8
     }
     acc[20] += res * res;
   }
-  block_sum<TV_THREADS, TV_CHUNK>(acc, sh_part, sh_tot);
+  block_sum<PAIR_THREADS, TV_CHUNK>(acc, sh_part, sh_tot);
 }
 
 // x (+) d: QuaternionManifold::Plus [upstream Ceres manifold.cc] on q as section 19 moves it (q re-normalised); t along its
@@ -661,7 +595,7 @@ __device__ __forceinline__ void tv_pose_plus(const double* q0, const double* t0,
 
 // Levenberg-Marquardt on the records of `mask`, (q, t) refined in place.  Every lane holds the same sums, so every lane takes
 // the same decisions and ends with the same pose.
-__device__ __forceinline__ void tv_refine(const TvArgs& a, const TvPair& P, const uint8_t* mask, double q[4], double t[3],
+__device__ __forceinline__ void tv_refine(const TvArgs& a, const PairRecords& P, const uint8_t* mask, double q[4], double t[3],
                                           double* sh_part, double* sh_tot) {
   double acc[TV_ACC];
   tv_normal_equations(P, mask, q, t, acc, sh_part, sh_tot);
@@ -696,15 +630,15 @@ __device__ __forceinline__ void tv_refine(const TvArgs& a, const TvPair& P, cons
   }
 }
 
-__global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
-  __shared__ double sh_rec[TV_LDS * TV_REC];
-  __shared__ double sh_part[TV_THREADS * TV_CHUNK];
+__global__ __launch_bounds__(PAIR_THREADS) void k_tv_refine(const TvArgs a) {
+  __shared__ double sh_rec[PAIR_LDS * PAIR_REC];
+  __shared__ double sh_part[PAIR_THREADS * TV_CHUNK];
   __shared__ double sh_tot[TV_ACC];
   const int tid = threadIdx.x;
   const int pi = a.order[blockIdx.x];
   const bool prior = a.prior_qvec != nullptr;
-  TvPair P;
-  if (!tv_open_pair(a, pi, sh_rec, P)) {                 // status 1: written by k_tv_hypotheses unless that did not run
+  PairRecords P;
+  if (!open_pair<PairThreshold::BothCameras>(a, pi, 5, sh_rec, P)) {   // status 1: written by k_tv_hypotheses unless that did not run
     if (prior && tid == 0) { a.status[pi] = 1; a.n_inliers[pi] = 0; a.n_trials[pi] = 0; }
     return;
   }
@@ -736,7 +670,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
     const bool have = tv_horn(E0, t, Ra, Rb);
     double front[5] = {0.0, 0.0, 0.0, 0.0, 0.0};         // poses (Ra, t) (Ra, -t) (Rb, t) (Rb, -t); the inlier count
     const double tm[3] = {-t[0], -t[1], -t[2]};
-    for (int j = tid; j < n; j += TV_THREADS) {
+    for (int j = tid; j < n; j += PAIR_THREADS) {
       const double* r = P.rec(j);
       const bool in = tv_sampson(E0, r) <= thr2;
       a.mask_a[P.o0 + j] = in ? 1 : 0;                   // (a lane reads back only what it wrote: j = tid mod 256)
@@ -746,7 +680,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
       }
       front[4] += in ? 1.0 : 0.0;
     }
-    block_sum<TV_THREADS, TV_CHUNK>(front, sh_part, sh_tot);
+    block_sum<PAIR_THREADS, TV_CHUNK>(front, sh_part, sh_tot);
     if (!have) {
       if (tid == 0) { a.status[pi] = 3; a.n_inliers[pi] = 0; }
       return;
@@ -771,13 +705,13 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
       quat_to_rotation(q1, R1);
       tv_essential_of_pose(R1, t1, E1);
       double cc[2] = {0.0, 0.0};                          // inliers of the refined pose; how many memberships changed
-      for (int j = tid; j < n; j += TV_THREADS) {
+      for (int j = tid; j < n; j += PAIR_THREADS) {
         const bool in = tv_sampson(E1, P.rec(j)) <= thr2;
         nxt[P.o0 + j] = in ? 1 : 0;
         cc[0] += in ? 1.0 : 0.0;
         cc[1] += (in != (cur[P.o0 + j] != 0)) ? 1.0 : 0.0;
       }
-      block_sum<TV_THREADS, TV_CHUNK>(cc, sh_part, sh_tot);
+      block_sum<PAIR_THREADS, TV_CHUNK>(cc, sh_part, sh_tot);
       if (cc[0] < (double)cur_cnt) break;                 // fewer inliers: the pose before it stays
 #pragma unroll
       for (int j = 0; j < 4; ++j) q[j] = q1[j];
@@ -793,8 +727,8 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
   quat_to_rotation(q, R);
   tv_essential_of_pose(R, t, E);
   double fin[1] = {0.0};
-  for (int j = tid; j < n; j += TV_THREADS) fin[0] += tv_sampson(E, P.rec(j)) <= thr2 ? 1.0 : 0.0;
-  block_sum<TV_THREADS, TV_CHUNK>(fin, sh_part, sh_tot);
+  for (int j = tid; j < n; j += PAIR_THREADS) fin[0] += tv_sampson(E, P.rec(j)) <= thr2 ? 1.0 : 0.0;
+  block_sum<PAIR_THREADS, TV_CHUNK>(fin, sh_part, sh_tot);
   const int n_in = (int)fin[0];
   const int need = max(a.o.min_num_inliers, (int)ceil(a.o.min_inlier_ratio * (double)n));
   if (n_in < need) {
@@ -802,7 +736,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_tv_refine(const TvArgs a) {
     return;
   }
   const double to_px = a.o.max_error / P.thr;
-  for (int j = tid; j < n; j += TV_THREADS) {
+  for (int j = tid; j < n; j += PAIR_THREADS) {
     const double e2 = tv_sampson(E, P.rec(j));
     const int64_t i = P.o0 + a.pos[P.o0 + j];
     a.err[i] = sqrt(e2) * to_px;
@@ -827,92 +761,26 @@ static int two_view_geometry(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pai
                              const double* d_cam_params, const double* d_prior_qvec, const double* d_prior_tvec,
                              const pxr_two_view_options* o, double* d_qvec, double* d_tvec, double* d_E, int32_t* d_status,
                              int32_t* d_n_inliers, int32_t* d_n_trials, uint8_t* d_inlier, double* d_err, double* h_ms) {
-  const char* fn = "pxr_two_view_geometry";
-  PXR_REQUIRE(ctx && o, "%s: NULL argument", fn);
-  PXR_REQUIRE(n_pairs >= 0 && n_matches >= 0 && n_cameras >= 0, "%s: negative size", fn);
-  PXR_REQUIRE(n_matches < ((int64_t)1 << 31), "%s: more than 2^31 matches", fn);
-  PXR_REQUIRE(n_pairs == 0 || (d_pair_offsets && d_pair_camera && d_qvec && d_tvec && d_E && d_status && d_n_inliers && d_n_trials &&
-                               d_cam_model && d_cam_params), "%s: NULL pair / camera array", fn);
-  PXR_REQUIRE(n_matches == 0 || (d_xy1 && d_xy2 && d_inlier && d_err), "%s: NULL match array", fn);
-  PXR_REQUIRE((d_prior_qvec == nullptr) == (d_prior_tvec == nullptr), "%s: prior_qvec and prior_tvec go together", fn);
-  PXR_REQUIRE(o->max_error > 0.0 && o->confidence > 0.0 && o->confidence < 1.0 && o->min_inlier_ratio >= 0.0 && o->min_inlier_ratio <= 1.0 &&
-                  o->min_num_inliers >= 0 && o->min_num_trials >= 0 && o->max_num_trials >= 1 && o->max_num_trials <= (1 << 20) &&
-                  o->round_size >= 1 && o->round_size <= (1 << 20) && o->refine_max_iterations >= 0 && o->lo_rounds >= 0,
-              "%s: option out of range", fn);
-  if (h_ms) h_ms[0] = h_ms[1] = h_ms[2] = h_ms[3] = 0.0;
-  if (n_pairs == 0) {
-    PXR_REQUIRE(n_matches == 0, "%s: pair_offsets ends at 0, not at n_matches = %lld", fn, (long long)n_matches);
-    return PXR_OK;
-  }
-  PXR_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int64_t T = n_pairs, N = n_matches;
-
-  // offsets and cameras are validated on a host copy, which also gives the processing order: pairs by descending match count
-  // (a stable counting sort), so that the longest start first
-  std::vector<int64_t> off;
-  std::vector<int32_t> order, pcam((size_t)T * 2);
-  PXR_HIP(hipMemcpyAsync(pcam.data(), d_pair_camera, sizeof(int32_t) * (size_t)T * 2, hipMemcpyDeviceToHost, st));
-  const auto cameras_in_range = [&](int64_t t) {
-    for (int side = 0; side < 2; ++side)
-      PXR_REQUIRE(pcam[2 * t + side] >= 0 && pcam[2 * t + side] < n_cameras, "%s: pair %lld names a camera outside [0, n_cameras = %d)", fn,
-                  (long long)t, (int)n_cameras);
-    return (int)PXR_OK;
-  };
-  if (int rc = batch_order(ctx, {fn, "pair_offsets", "pair", "n_matches"}, false, d_pair_offsets, T, N, off, order, cameras_in_range)) return rc;
-
-  Carver cv;
-  const size_t o_rec = cv.take((size_t)N * TV_REC, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
-  const size_t o_ma = cv.take((size_t)N, 1), o_mb = cv.take((size_t)N, 1), o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4);
-  const size_t o_win = cv.take((size_t)T * 3, 4), o_winE = cv.take((size_t)T * 9, 8);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  double* rec = (double*)(ws + o_rec);
-  uint8_t* valid = (uint8_t*)(ws + o_valid);
-  int32_t* pos = (int32_t*)(ws + o_pos);
-  int32_t* n_valid = (int32_t*)(ws + o_nv);
-  int32_t* d_order = (int32_t*)(ws + o_order);
-
-  StageTimer<5> timer(st, h_ms);                         // bearings | compact | hypotheses | refine
-  if (int rc = timer.create(fn)) return rc;
-
-  auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
-  int rc = hip_check(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-  if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (`order` may go out of scope)
-  if (rc != PXR_OK) return rc;
-  timer.mark(0);
-  if (N > 0)
-    hipLaunchKernelGGL(k_tv_bearings, blocks(N, TV_THREADS), dim3(TV_THREADS), 0, st, N, n_pairs, d_pair_offsets, d_pair_camera,
-                       d_cam_model, d_cam_params, d_xy1, d_xy2, rec, valid, d_inlier, d_err);
-  timer.mark(1);
-  hipLaunchKernelGGL(k_compact_records<TV_REC>, blocks(T, TV_THREADS), dim3(TV_THREADS), 0, st, T, d_pair_offsets, rec, valid, pos, n_valid);
-  timer.mark(2);
+  const PairCall c = {"pxr_two_view_geometry", ctx, n_pairs, d_pair_offsets, n_matches, d_xy1, d_xy2, d_pair_camera, n_cameras, d_cam_model,
+                      d_cam_params, o, d_status, d_n_inliers, d_n_trials, d_inlier, d_err, h_ms};
+  const bool priors_paired = (d_prior_qvec == nullptr) == (d_prior_tvec == nullptr);
+  PairBatch b;
+  if (int rc = open_pair_batch(c, d_qvec && d_tvec && d_E, priors_paired ? nullptr : "prior_qvec and prior_tvec go together", 3, b)) return rc;
+  if (n_pairs == 0) return PXR_OK;
   TvArgs a;
-  a.offsets = d_pair_offsets; a.pair_camera = d_pair_camera; a.cam_model = d_cam_model; a.cam_params = d_cam_params;
+  fill_pair_args(a, c, b);
+  a.winner_E = b.winner_model;
   a.prior_qvec = d_prior_qvec; a.prior_tvec = d_prior_tvec;
-  a.order = d_order; a.rec = rec; a.pos = pos; a.n_valid = n_valid; a.mask_a = (uint8_t*)(ws + o_ma); a.mask_b = (uint8_t*)(ws + o_mb);
-  a.o = *o;
-  a.max_trials = (int32_t)(((int64_t)o->max_num_trials + o->round_size - 1) / o->round_size * o->round_size);
-  a.qvec = d_qvec; a.tvec = d_tvec; a.E = d_E; a.status = d_status; a.n_inliers = d_n_inliers; a.n_trials = d_n_trials;
-  a.inlier = d_inlier; a.err = d_err;
-  a.winner = (int32_t*)(ws + o_win); a.winner_E = (double*)(ws + o_winE);
-  if (!d_prior_qvec) hipLaunchKernelGGL(k_tv_hypotheses, dim3((unsigned)T), dim3(TV_THREADS), 0, st, a);
-  timer.mark(3);
-  hipLaunchKernelGGL(k_tv_refine, dim3((unsigned)T), dim3(TV_THREADS), 0, st, a);
-  timer.mark(4);
-  rc = hip_check(hipGetLastError(), "k_tv_refine launch");
-  const int from[4] = {0, 1, 2, 3};
-  return rc == PXR_OK ? timer.read(from, 4) : rc;
+  a.qvec = d_qvec; a.tvec = d_tvec; a.E = d_E;
+  if (!d_prior_qvec) hipLaunchKernelGGL(k_tv_hypotheses, dim3((unsigned)n_pairs), dim3(PAIR_THREADS), 0, ctx->stream, a);
+  b.timer->mark(3);
+  hipLaunchKernelGGL(k_tv_refine, dim3((unsigned)n_pairs), dim3(PAIR_THREADS), 0, ctx->stream, a);
+  return close_pair_batch(b, "k_tv_refine launch");
 }
 
 }  // namespace pxr
 
-extern "C" void pxr_two_view_default_options(pxr_two_view_options* o) {
-  if (!o) return;
-  o->max_error = 4.0; o->min_inlier_ratio = 0.25; o->confidence = 0.999;
-  o->seed = 0; o->min_num_inliers = 15; o->min_num_trials = 64; o->max_num_trials = 10000; o->round_size = 64;
-  o->refine_max_iterations = 100; o->lo_rounds = 4;
-}
+extern "C" void pxr_two_view_default_options(pxr_two_view_options* o) { pxr::pair_default_options(o); }
 
 extern "C" int pxr_two_view_geometry(pxr_ctx* ctx, int32_t n_pairs, const int64_t* d_pair_offsets, int64_t n_matches, const double* d_xy1,
                                      const double* d_xy2, const int32_t* d_pair_camera, int32_t n_cameras, const int32_t* d_cam_model,

@@ -101,8 +101,8 @@ class AbsposeOptions(C.Structure):
 ABSPOSE_LDS_CORR = 1024      # PXR_ABSPOSE_LDS_CORR
 
 
-class TwoViewOptions(C.Structure):
-    """pxr_two_view_options"""
+class PairOptions(C.Structure):
+    """pxr_pair_options: one struct under the three names of the header"""
     _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double), ("seed", C.c_uint64),
                 ("min_num_inliers", C.c_int32), ("min_num_trials", C.c_int32), ("max_num_trials", C.c_int32),
                 ("round_size", C.c_int32), ("refine_max_iterations", C.c_int32), ("lo_rounds", C.c_int32)]
@@ -111,14 +111,7 @@ class TwoViewOptions(C.Structure):
 TWOVIEW_LDS_MATCHES = 1024   # PXR_TWOVIEW_LDS_MATCHES
 
 
-class HomographyOptions(C.Structure):
-    """pxr_homography_options"""
-    _fields_ = list(TwoViewOptions._fields_)
-
-
-class FundamentalOptions(C.Structure):
-    """pxr_fundamental_options"""
-    _fields_ = list(TwoViewOptions._fields_)
+TwoViewOptions = HomographyOptions = FundamentalOptions = PairOptions   # pxr_two_view_options, pxr_homography_options, pxr_fundamental_options
 
 
 class MatchOptions(C.Structure):

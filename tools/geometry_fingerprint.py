@@ -1,8 +1,9 @@
 """One SHA-256 per case over every output of the batched geometry stages -- absolute pose, two-view geometry (estimating, and
-with a pose prior), triangulation, descriptor matching, homography estimation -- timings excluded.
+with a pose prior), triangulation, descriptor matching, homography and fundamental-matrix estimation -- timings excluded.
 
-A refactor of pxr_abspose.hip, pxr_twoview.hip, pxr_triangulate.hip, pxr_match.hip, pxr_homography.hip or of the headers they share (pxr_robust.h,
-pxr_batch.h) must leave every line of this output unchanged: run it before and after on the same machine and compare.  Only the
+A refactor of pxr_abspose.hip, pxr_twoview.hip, pxr_triangulate.hip, pxr_match.hip, pxr_homography.hip, pxr_fundamental.hip or of
+what they share (pxr_robust.h, pxr_batch.h, pxr_pairs.h) must leave every line of this output unchanged: run it
+before and after on the same machine and compare.  Only the
 public engine API is used, and the seeded generators the tests use (tests/*_cases.py, the repository's own oracle for the
 camera models).
 
@@ -40,6 +41,11 @@ def twoview(ctx, batch):
 def homography(ctx, batch):
     from pixsfm_amd.engine import HomographyProblem
     return digest(HomographyProblem(ctx, batch).estimate())
+
+
+def fundamental(ctx, batch):
+    from pixsfm_amd.engine import FundamentalProblem
+    return digest(FundamentalProblem(ctx, batch).estimate())
 
 
 def triangulation(ctx, scene):
@@ -82,6 +88,10 @@ def cases(ctx):
     planes = hc.boundary_inputs()
     yield "homography_boundaries", lambda: homography(ctx, planes)
     yield "homography_eleven_models", lambda: homography(ctx, hc.eleven_models_pairs()[0])
+    import fundamental_cases as fc
+    uncalibrated = fc.boundary_inputs()
+    yield "fundamental_boundaries", lambda: fundamental(ctx, uncalibrated)
+    yield "fundamental_eleven_models", lambda: fundamental(ctx, fc.eleven_models_pairs()[0])
 
 
 if __name__ == "__main__":
