@@ -772,6 +772,45 @@ int pxr_match_descriptors_timed(pxr_ctx* ctx, int32_t n_images, const int64_t* d
                                 const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches,
                                 double* h_kernel_ms);
 
+/* ---- incremental mapping: visibility (triangulated tracks in, per-image scores and 2D-3D pairs out) ----
+ * The stage of the reference's main entry point that produces poses: PixSfM.reconstruction (pixsfm/refine_hloc.py:133-146)
+ * hands it to hloc.reconstruction.main, i.e. COLMAP's incremental mapper.  The arithmetic of a mapper is the stages above
+ * (pxr_two_view_geometry, pxr_triangulate_tracks, pxr_absolute_pose, pxr_ba_solve_geometric); this is the device step between
+ * triangulation and registration, for all candidate images at once: [upstream COLMAP 3.8] IncrementalMapper::FindNextImages
+ * with VisibilityPyramid's score, and the 2D-3D gathering at the head of IncrementalMapper::RegisterNextImage -- as remembered,
+ * parity unpinned.  All arrays are device pointers.
+ *   view                 tracks in CSR form over the observations, images and cameras (qvec / tvec / cam_model / cam_params are not read)
+ *   d_obs_track          [n_obs] the track of every observation
+ *   d_image_obs_offsets  [n_images + 1], d_image_obs [n_obs]: the image-major transpose of the CSR -- image i owns the
+ *                        observation indices d_image_obs[offsets[i] .. offsets[i+1]), ascending
+ *   d_xyz, d_status      [n_tracks][3], [n_tracks] exactly as pxr_triangulate_tracks writes them
+ *   d_image_mask         [n_images] non-zero = candidate
+ *   d_cam_size           [n_cameras][2] width, height in pixels
+ *   pyramid_levels       L, 1 <= L <= 6
+ * Observation o of a candidate image is VISIBLE iff d_status[d_obs_track[o]] == 0, that track's xyz is finite and the
+ * observation's xy is finite.  Its finest cell is cx = clamp((int)floor(x 2^L / width), 0, 2^L - 1), cy likewise with the
+ * height; at level l = 1 .. L it occupies cell (cx >> (L - l), cy >> (L - l)).
+ * Outputs: d_n_visible[i] the visible observations of image i; d_score[i] = sum over l of 4^l (distinct occupied cells at
+ * level l); both 0 for an image that is masked out.  d_corr_offsets [n_images + 1] = the exclusive scan of d_n_visible;
+ * d_corr_obs / d_corr_xy / d_corr_xyz (capacity n_obs rows) hold, for every image in turn, its visible observations in
+ * ascending observation order: the observation index, its keypoint, the point of its track; *h_n_corr their number.
+ * (n_images, d_corr_offsets, *h_n_corr, d_corr_xy, d_corr_xyz, view->d_image_camera) is an argument set of pxr_absolute_pose:
+ * an image that is no candidate is a query without correspondences.
+ * PXR_EINVAL (nothing launched on the outputs, which stay untouched): either offsets array not monotone or not ending at n_obs,
+ * d_image_obs not that transpose, a track / image / camera index out of range, a camera size that is not positive,
+ * pyramid_levels out of range.  Synchronises the context's stream. */
+int pxr_mapper_visibility(pxr_ctx* ctx, const pxr_tri_view* view, const int64_t* d_obs_track, const int64_t* d_image_obs_offsets,
+                          const int64_t* d_image_obs, const double* d_xyz, const int32_t* d_status, const uint8_t* d_image_mask,
+                          const int32_t* d_cam_size, int32_t pyramid_levels, int32_t* d_n_visible, int64_t* d_score,
+                          int64_t* d_corr_offsets, int64_t* d_corr_obs, double* d_corr_xy, double* d_corr_xyz, int64_t* h_n_corr);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[4] = validation, count, scan, write. */
+int pxr_mapper_visibility_timed(pxr_ctx* ctx, const pxr_tri_view* view, const int64_t* d_obs_track,
+                                const int64_t* d_image_obs_offsets, const int64_t* d_image_obs, const double* d_xyz,
+                                const int32_t* d_status, const uint8_t* d_image_mask, const int32_t* d_cam_size,
+                                int32_t pyramid_levels, int32_t* d_n_visible, int64_t* d_score, int64_t* d_corr_offsets,
+                                int64_t* d_corr_obs, double* d_corr_xy, double* d_corr_xyz, int64_t* h_n_corr,
+                                double* h_kernel_ms);
+
 /* ---- BA reference extraction -----------------------------------------------------------
  * Replaces ReferenceExtractor::Run (bundle_adjustment/src/reference_extractor.h:125-318) +
  * RobustMeanIRLS (base/src/irls_optim.h:24-71) for N_NODES = 1: per point, descriptors of all

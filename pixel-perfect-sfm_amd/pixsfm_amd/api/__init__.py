@@ -23,3 +23,5 @@ from .matching import DescriptorMatcher, pairs_2d3d_from_matches  # noqa: F401,E
 from .two_view import TwoViewVerifier, essential_matrix_estimation  # noqa: F401,E402
 from .homography import TwoViewClassifier, homography_matrix_estimation, two_view_config  # noqa: F401,E402
 from .fundamental import fundamental_matrix_estimation, two_view_config_uncalibrated  # noqa: F401,E402
+from . import mapping  # noqa: F401,E402
+from .mapping import IncrementalMapper  # noqa: F401,E402

@@ -900,6 +900,25 @@ class AbsolutePoseProblem:
         }
         self.kernel_ms = None
 
+    @classmethod
+    def from_device(cls, ctx, query_offsets, n_corr, xy, xyz, query_camera, cam_model, cam_params):
+        """The same problem over arrays that already live on the device (DeviceArray each; nothing is copied): query_offsets
+        (n_queries + 1) int64, xy / xyz with at least n_corr rows, query_camera (n_queries) int32, cam_model (n_cameras) int32,
+        cam_params (n_cameras, KPAD).  What MapperScene.visibility returns goes in as it is."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.n_queries = int(query_offsets.shape[0]) - 1
+        self.n_corr = int(n_corr)
+        self.n_cameras = int(cam_model.shape[0])
+        if self.n_queries < 0 or int(query_camera.shape[0]) != self.n_queries:
+            raise ValueError("query_camera must hold one camera per query")
+        if int(xy.shape[0]) < self.n_corr or int(xyz.shape[0]) < self.n_corr:
+            raise ValueError("xy and xyz must hold one row per correspondence")
+        self.d = {"query_offsets": query_offsets, "xy": xy, "xyz": xyz, "query_camera": query_camera, "cam_model": cam_model,
+                  "cam_params": cam_params}
+        self.kernel_ms = None
+        return self
+
     def estimate(self, qvec=None, tvec=None, timed=False, **options):
         """Run the kernels (pxr_absolute_pose) with abspose_options(**options).  Returns the device arrays (qvec (n_queries, 4),
         tvec (n_queries, 3), status, n_inliers, n_trials (n_queries,) int32, inlier (n_corr,) uint8, err (n_corr,) float64).
@@ -1181,3 +1200,114 @@ class MatchProblem:
         else:
             check(ctx.lib.pxr_match_descriptors(*args), "pxr_match_descriptors")
         return d_m, d_s, d_n
+
+
+def image_major_transpose(obs_image, n_images):
+    """The image-major transpose of a track-major observation list: (image_obs_offsets (n_images + 1,) int64, image_obs (n_obs,)
+    int64) -- image i owns the observation indices image_obs[offsets[i]:offsets[i + 1]], ascending."""
+    obs_image = np.asarray(obs_image, dtype=np.int64).reshape(-1)
+    if len(obs_image) and (obs_image.min() < 0 or obs_image.max() >= n_images):
+        raise ValueError("an observation names an image outside [0, %d)" % n_images)
+    offsets = np.zeros(n_images + 1, dtype=np.int64)
+    np.cumsum(np.bincount(obs_image, minlength=n_images), out=offsets[1:])
+    return offsets, np.argsort(obs_image, kind="stable").astype(np.int64)
+
+
+def restrict_tracks(track_offsets, obs_image, registered):
+    """The track CSR that keeps only the observations in registered images (registered: (n_images,) bool).  The track count is
+    unchanged -- a track may become empty -- so track indices stay what they are.  Returns (track_offsets (n_tracks + 1,) int64,
+    obs_index: the kept observations as indices into the full list, ascending)."""
+    keep = np.asarray(registered, dtype=bool)[np.asarray(obs_image, dtype=np.int64)]
+    before = np.zeros(len(keep) + 1, dtype=np.int64)
+    np.cumsum(keep, out=before[1:])
+    return before[np.asarray(track_offsets, dtype=np.int64)], np.flatnonzero(keep).astype(np.int64)
+
+
+class MapperScene:
+    """The flat arrays of a scene that an incremental mapper keeps on the device for all of its rounds (pxr_mapper_visibility):
+    every observation of every track with its image and keypoint, the image-major transpose, images, cameras and their sizes.
+
+    problem: the dict of TriangulationProblem (track_offsets, obs_image, obs_xy, image_camera, cam_model, cam_params; qvec / tvec
+    are not needed) plus cam_size (n_cameras x 2: width, height).  ctx None: host arrays only (restricted_tracks works,
+    visibility does not).
+    """
+
+    def __init__(self, ctx, problem):
+        self.ctx = ctx
+        g = problem
+        self.track_offsets = np.ascontiguousarray(g["track_offsets"], dtype=np.int64).reshape(-1)
+        if len(self.track_offsets) < 1:
+            raise ValueError("track_offsets must hold n_tracks + 1 entries")
+        self.n_tracks = len(self.track_offsets) - 1
+        self.obs_image = np.ascontiguousarray(np.asarray(g["obs_image"]).reshape(-1), dtype=np.int32)
+        self.n_obs = len(self.obs_image)
+        self.obs_xy = np.ascontiguousarray(g["obs_xy"], dtype=np.float64).reshape(-1, 2)
+        if len(self.obs_xy) != self.n_obs:
+            raise ValueError("obs_xy must hold one keypoint per observation")
+        self.image_camera = np.ascontiguousarray(g["image_camera"], dtype=np.int32).reshape(-1)
+        self.n_images = len(self.image_camera)
+        self.cam_model = np.ascontiguousarray(g["cam_model"], dtype=np.int32).reshape(-1)
+        self.n_cameras = len(self.cam_model)
+        self.cam_size = np.ascontiguousarray(g["cam_size"], dtype=np.int32).reshape(-1, 2)
+        if len(self.cam_size) != self.n_cameras:
+            raise ValueError("cam_size must hold one (width, height) per camera")
+        self.obs_track = np.repeat(np.arange(self.n_tracks, dtype=np.int64), np.diff(self.track_offsets))
+        if len(self.obs_track) != self.n_obs:
+            raise ValueError("track_offsets must end at the number of observations")
+        self.image_obs_offsets, self.image_obs = image_major_transpose(self.obs_image, self.n_images)
+        self.kernel_ms = None
+        if ctx is None:
+            return
+        self.d = {
+            "track_offsets": ctx.to_device(self.track_offsets, np.int64),
+            "obs_image": ctx.to_device(self.obs_image, np.int32),
+            "obs_xy": ctx.to_device(self.obs_xy, np.float64),
+            "obs_track": ctx.to_device(self.obs_track, np.int64),
+            "image_obs_offsets": ctx.to_device(self.image_obs_offsets, np.int64),
+            "image_obs": ctx.to_device(self.image_obs, np.int64),
+            "image_camera": ctx.to_device(self.image_camera, np.int32),
+            "cam_model": ctx.to_device(self.cam_model, np.int32),
+            "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
+            "cam_size": ctx.to_device(self.cam_size, np.int32),
+        }
+        d = self.d
+        self.view = _lib.TriView(self.n_tracks, d["track_offsets"].ptr, self.n_obs, d["obs_image"].ptr, d["obs_xy"].ptr,
+                                 self.n_images, d["image_camera"].ptr, None, None, self.n_cameras, d["cam_model"].ptr,
+                                 d["cam_params"].ptr)
+
+    def restricted_tracks(self, registered):
+        """restrict_tracks on this scene, as the problem dict entries of TriangulationProblem: track_offsets, obs_image, obs_xy,
+        and obs_index (the kept observations as indices into the scene's list)."""
+        offsets, obs_index = restrict_tracks(self.track_offsets, self.obs_image, registered)
+        return dict(track_offsets=offsets, obs_index=obs_index, obs_image=self.obs_image[obs_index], obs_xy=self.obs_xy[obs_index])
+
+    def visibility(self, xyz, status, image_mask, levels=6, timed=False, out=None):
+        """Run the kernels (pxr_mapper_visibility).  xyz (n_tracks, 3) float64 and status (n_tracks,) int32: device arrays as
+        TriangulationProblem.triangulate returns them; image_mask (n_images,) host array, non-zero = candidate.  Returns a dict
+        of device arrays: n_visible (n_images,) int32, score (n_images,) int64, corr_offsets (n_images + 1,) int64, corr_obs
+        (n_obs,) int64, corr_xy (n_obs, 2), corr_xyz (n_obs, 3) -- the first n_corr rows are written -- and n_corr (int).
+        out: a dict of these six device arrays to write into.
+        timed: also keep the kernels' HIP-event times in self.kernel_ms {"check", "count", "scan", "write"} (milliseconds)."""
+        ctx, d = self.ctx, self.d
+        mask = np.ascontiguousarray(image_mask, dtype=np.uint8).reshape(-1)
+        if len(mask) != self.n_images:
+            raise ValueError("image_mask must hold one entry per image")
+        if tuple(xyz.shape) != (self.n_tracks, 3) or tuple(status.shape) != (self.n_tracks,):
+            raise ValueError("xyz and status must hold one row per track")
+        d_mask = ctx.to_device(mask, np.uint8)
+        out = dict(out) if out is not None else dict(
+            n_visible=ctx.empty((self.n_images,), np.int32), score=ctx.empty((self.n_images,), np.int64),
+            corr_offsets=ctx.empty((self.n_images + 1,), np.int64), corr_obs=ctx.empty((max(self.n_obs, 1),), np.int64),
+            corr_xy=ctx.empty((max(self.n_obs, 1), 2), np.float64), corr_xyz=ctx.empty((max(self.n_obs, 1), 3), np.float64))
+        n_corr = C.c_int64()
+        args = (ctx.handle, C.byref(self.view), d["obs_track"].ptr, d["image_obs_offsets"].ptr, d["image_obs"].ptr, xyz.ptr, status.ptr,
+                d_mask.ptr, d["cam_size"].ptr, int(levels), out["n_visible"].ptr, out["score"].ptr, out["corr_offsets"].ptr,
+                out["corr_obs"].ptr, out["corr_xy"].ptr, out["corr_xyz"].ptr, C.byref(n_corr))
+        if timed:
+            ms = (C.c_double * 4)()
+            check(ctx.lib.pxr_mapper_visibility_timed(*args, ms), "pxr_mapper_visibility_timed")
+            self.kernel_ms = dict(zip(("check", "count", "scan", "write"), (float(x) for x in ms)))
+        else:
+            check(ctx.lib.pxr_mapper_visibility(*args), "pxr_mapper_visibility")
+        out["n_corr"] = int(n_corr.value)
+        return out
