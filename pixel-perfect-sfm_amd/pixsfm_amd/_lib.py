@@ -166,49 +166,28 @@ _SIGNATURES = {
                                      C.c_void_p]),
     "pxr_triangulate_tracks": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.POINTER(TriOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
-    "pxr_triangulate_tracks_timed": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.POINTER(TriOptions), C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_abspose_default_options": (None, [C.POINTER(AbsposeOptions)]),
     "pxr_absolute_pose": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.POINTER(AbsposeOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pxr_absolute_pose_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                          C.c_void_p, C.c_void_p, C.POINTER(AbsposeOptions), C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_two_view_default_options": (None, [C.POINTER(TwoViewOptions)]),
     "pxr_two_view_geometry": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TwoViewOptions), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pxr_two_view_geometry_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TwoViewOptions),
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_homography_default_options": (None, [C.POINTER(HomographyOptions)]),
     "pxr_homography": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.POINTER(HomographyOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pxr_homography_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                       C.c_void_p, C.c_void_p, C.POINTER(HomographyOptions), C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_fundamental_default_options": (None, [C.POINTER(FundamentalOptions)]),
     "pxr_fundamental": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.POINTER(FundamentalOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pxr_fundamental_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.POINTER(FundamentalOptions), C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "pxr_match_default_options": (None, [C.POINTER(MatchOptions)]),
     "pxr_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p, C.c_void_p]),
-    "pxr_match_descriptors_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
-                                              C.c_void_p, C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.POINTER(C.c_double)]),
     "pxr_mapper_visibility": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_int64)]),
-    "pxr_mapper_visibility_timed": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "pxr_ba_compute_references": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BaView), C.POINTER(InterpCfg),
                                             C.POINTER(Loss), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pxr_costmap_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
@@ -254,6 +233,10 @@ _SIGNATURES = {
     "pxr_comm_force": (C.c_int, [C.c_void_p, C.c_int]),
     "pxr_comm_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
 }
+# every *_timed entry point: the arguments of its plain twin, then the array that takes the stages' HIP-event times
+for _name in ("pxr_triangulate_tracks", "pxr_absolute_pose", "pxr_two_view_geometry", "pxr_homography", "pxr_fundamental",
+              "pxr_match_descriptors", "pxr_mapper_visibility"):
+    _SIGNATURES[_name + "_timed"] = (_SIGNATURES[_name][0], _SIGNATURES[_name][1] + [C.POINTER(C.c_double)])
 LINEAR_AUTO, LINEAR_DIRECT, LINEAR_ITERATIVE = 0, 1, 2
 COMM_ID_BYTES = 128
 

@@ -16,7 +16,6 @@ import numpy as np
 
 from ..engine import FundamentalProblem, fundamental_options
 from . import two_view as _tv
-from .keypoint_adjustment import default_context
 
 _DEFAULTS = {name: p.default for name, p in inspect.signature(fundamental_options).parameters.items()}
 _OPTION_KEYS = tuple(_DEFAULTS)
@@ -24,17 +23,14 @@ _NAMES = ("F", "status", "n_inliers", "n_trials", "inlier", "err")
 
 
 def fundamental_engine_options(options=None):
-    """The keyword arguments of engine.fundamental_options for an option dict (a nested "ransac" dict, as pycolmap groups them,
-    is flattened).  Unknown keys raise ValueError."""
-    opts = dict(options or {})
-    ransac = opts.pop("ransac", None) or {}
-    out = {}
-    for k, v in list(dict(ransac).items()) + list(opts.items()):
-        if k not in _OPTION_KEYS:
-            raise ValueError("unknown fundamental option %r (known: %s)" % (k, ", ".join(_OPTION_KEYS)))
-        out[k] = v
-    fundamental_options(**out)                # fail early on a value ctypes cannot take
-    return out
+    """The keyword arguments of engine.fundamental_options for an option dict (two_view._engine_options).  Unknown keys raise
+    ValueError."""
+    return _tv._engine_options(options, _OPTION_KEYS, "fundamental", fundamental_options)
+
+
+def _estimate(ctx, batch, opts):
+    """The seam to the GPU: host arrays {F, status, n_inliers, n_trials, inlier, err}."""
+    return _tv._run(FundamentalProblem, _NAMES, ctx, batch, opts)
 
 
 def two_view_config_uncalibrated(e_ok, n_e, f_ok, n_f, h_ok, n_h, n_r, both_trusted, max_H_inlier_ratio=0.8, min_E_F_inlier_ratio=0.95):
@@ -83,16 +79,10 @@ def conditioning_camera(points):
     return Camera(0, 0, 1, 1, [f, float(c[0]), float(c[1])])
 
 
-def _calibration_matrix(camera):
-    k = camera.params
-    if camera.model_id == 0:
-        return np.array([[k[0], 0.0, k[1]], [0.0, k[0], k[2]], [0.0, 0.0, 1.0]])
-    return np.array([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]])
-
-
 def fundamental_in_pixels(F, camera1, camera2):
     """F_px = K2^-t F K1^-1 of two pinhole-family cameras, scaled to unit Frobenius norm: x2_px^t F_px x1_px = 0."""
-    Fp = np.linalg.inv(_calibration_matrix(camera2)).T @ np.asarray(F, dtype=np.float64).reshape(3, 3) @ np.linalg.inv(_calibration_matrix(camera1))
+    K1, K2 = _tv._calibration_matrix(camera1), _tv._calibration_matrix(camera2)
+    Fp = np.linalg.inv(K2).T @ np.asarray(F, dtype=np.float64).reshape(3, 3) @ np.linalg.inv(K1)
     return Fp / np.linalg.norm(Fp)
 
 
@@ -103,17 +93,11 @@ def fundamental_matrix_estimation(points1, points2, options=None, camera1=None, 
     are pixels (COLMAP convention), "F" relates the normalised planes of the cameras (unit Frobenius norm), and for two
     pinhole-family cameras (SIMPLE_PINHOLE, PINHOLE) "F_pixels" = K2^-t F K1^-1 (unit norm) is returned too."""
     opts = fundamental_engine_options(options)
-    xy1, xy2 = np.asarray(points1, dtype=np.float64).reshape(-1, 2), np.asarray(points2, dtype=np.float64).reshape(-1, 2)
-    if len(xy1) != len(xy2):
-        raise ValueError("points1 and points2 must have the same length")
+    xy1, xy2 = _tv._points(points1, points2)
     if (camera1 is None) != (camera2 is None):
         raise ValueError("camera1 and camera2 go together")
     cams = [conditioning_camera(xy1), conditioning_camera(xy2)] if camera1 is None else [camera1, camera2]
-    index, model, params = _tv._camera_table(cams)
-    batch = dict(pair_offsets=np.array([0, len(xy1)], np.int64), xy1=xy1, xy2=xy2, pair_camera=index.reshape(1, 2), cam_model=model,
-                 cam_params=params)
-    ctx = ctx or default_context()
-    res = {k: a.download() for k, a in zip(_NAMES, FundamentalProblem(ctx, batch).estimate(**opts))}
+    res = _estimate(ctx, _tv._single_pair_batch(xy1, xy2, cams), opts)
     if res["status"][0] != 0:
         return {"success": False}
     F = res["F"][0].reshape(3, 3).copy()

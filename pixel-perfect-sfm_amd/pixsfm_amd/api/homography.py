@@ -15,10 +15,9 @@ import inspect
 
 import numpy as np
 
-from ..engine import FundamentalProblem, HomographyProblem, TwoViewProblem, homography_options
+from ..engine import HomographyProblem, homography_options
 from . import fundamental as _fm
 from . import two_view as _tv
-from .keypoint_adjustment import default_context
 
 _DEFAULTS = {name: p.default for name, p in inspect.signature(homography_options).parameters.items()}
 _OPTION_KEYS = tuple(_DEFAULTS)
@@ -27,17 +26,14 @@ CONFIGS = ("CALIBRATED", "PLANAR", "PANORAMIC", "DEGENERATE", "UNCALIBRATED", "P
 
 
 def homography_engine_options(options=None):
-    """The keyword arguments of engine.homography_options for an option dict (a nested "ransac" dict, as pycolmap groups them,
-    is flattened).  Unknown keys raise ValueError."""
-    opts = dict(options or {})
-    ransac = opts.pop("ransac", None) or {}
-    out = {}
-    for k, v in list(dict(ransac).items()) + list(opts.items()):
-        if k not in _OPTION_KEYS:
-            raise ValueError("unknown homography option %r (known: %s)" % (k, ", ".join(_OPTION_KEYS)))
-        out[k] = v
-    homography_options(**out)                 # fail early on a value ctypes cannot take
-    return out
+    """The keyword arguments of engine.homography_options for an option dict (two_view._engine_options).  Unknown keys raise
+    ValueError."""
+    return _tv._engine_options(options, _OPTION_KEYS, "homography", homography_options)
+
+
+def _estimate(ctx, batch, opts):
+    """The seam to the GPU: host arrays {H, rot_qvec, status, n_inliers, n_rot_inliers, n_trials, inlier, err}."""
+    return _tv._run(HomographyProblem, _NAMES, ctx, batch, opts)
 
 
 def two_view_config(e_success, n_e, h_success, n_h, n_r, max_H_inlier_ratio=0.8):
@@ -61,13 +57,6 @@ def _identity_camera():
     return Camera(0, 0, 1, 1, [1.0, 0.0, 0.0])
 
 
-def _calibration_matrix(camera):
-    k = camera.params
-    if camera.model_id == 0:
-        return np.array([[k[0], 0.0, k[1]], [0.0, k[0], k[2]], [0.0, 0.0, 1.0]])
-    return np.array([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]])
-
-
 def homography_matrix_estimation(points1, points2, options=None, camera1=None, camera2=None, ctx=None):
     """pycolmap.homography_matrix_estimation's shape: {"success", "H" (3, 3), "num_inliers", "inliers"}, or {"success": False}.
     points: (n, 2).  Without cameras the points are used as they are (the stand-in is an identity SIMPLE_PINHOLE camera), so
@@ -75,23 +64,17 @@ def homography_matrix_estimation(points1, points2, options=None, camera1=None, c
     H maps the normalised plane of camera 1 to that of camera 2 (unit Frobenius norm), and for two pinhole-family cameras
     (SIMPLE_PINHOLE, PINHOLE) "H_pixels" = K2 H K1^-1 is returned too."""
     opts = homography_engine_options(options)
-    xy1, xy2 = np.asarray(points1, dtype=np.float64).reshape(-1, 2), np.asarray(points2, dtype=np.float64).reshape(-1, 2)
-    if len(xy1) != len(xy2):
-        raise ValueError("points1 and points2 must have the same length")
+    xy1, xy2 = _tv._points(points1, points2)
     if (camera1 is None) != (camera2 is None):
         raise ValueError("camera1 and camera2 go together")
     cams = [_identity_camera()] * 2 if camera1 is None else [camera1, camera2]
-    index, model, params = _tv._camera_table(cams)
-    batch = dict(pair_offsets=np.array([0, len(xy1)], np.int64), xy1=xy1, xy2=xy2, pair_camera=index.reshape(1, 2), cam_model=model,
-                 cam_params=params)
-    ctx = ctx or default_context()
-    res = {k: a.download() for k, a in zip(_NAMES, HomographyProblem(ctx, batch).estimate(**opts))}
+    res = _estimate(ctx, _tv._single_pair_batch(xy1, xy2, cams), opts)
     if res["status"][0] != 0:
         return {"success": False}
     H = res["H"][0].reshape(3, 3).copy()
     out = {"success": True, "H": H, "num_inliers": int(res["n_inliers"][0]), "inliers": [bool(x) for x in res["inlier"]]}
     if camera1 is not None and camera1.model_id in (0, 1) and camera2.model_id in (0, 1):
-        out["H_pixels"] = _calibration_matrix(camera2) @ H @ np.linalg.inv(_calibration_matrix(camera1))
+        out["H_pixels"] = _tv._calibration_matrix(camera2) @ H @ np.linalg.inv(_tv._calibration_matrix(camera1))
     return out
 
 
@@ -144,26 +127,14 @@ class TwoViewClassifier:
             raise ValueError("pairs, matches and scores must have the same length")
         if not pairs:
             return [], (None if scores is None else []), []
-        xy1, xy2, cams = [], [], []
-        for (a, b), m in zip(pairs, matches):
-            for n in (a, b):
-                if n not in keypoints or n not in cameras:
-                    raise KeyError("no keypoints or camera for image %r" % (n,))
-            m = np.asarray(m).reshape(-1, 2).astype(np.int64)
-            xy1.append(np.asarray(keypoints[a], dtype=np.float64)[m[:, 0], :2])
-            xy2.append(np.asarray(keypoints[b], dtype=np.float64)[m[:, 1], :2])
-            cams += [cameras[a], cameras[b]]
-        index, model, params = _tv._camera_table(cams)
-        off = np.concatenate([[0], np.cumsum([len(a) for a in xy1])]).astype(np.int64)
-        batch = dict(pair_offsets=off, xy1=np.concatenate(xy1).reshape(-1, 2), xy2=np.concatenate(xy2).reshape(-1, 2),
-                     pair_camera=index.reshape(-1, 2), cam_model=model, cam_params=params)
-        ctx = self.ctx or default_context()
-        prob = TwoViewProblem(ctx, batch)
-        res_e = {k: a.download() for k, a in zip(_tv._NAMES, prob.estimate(**self.conf["two_view"]))}
-        res_h = {k: a.download() for k, a in zip(_NAMES, HomographyProblem(ctx, prob).estimate(**self.conf["homography"]))}
+        # one batch for the two or three seams: the first uploads it, the others share its device arrays
+        batch = _tv._multi_pair_batch(pairs, matches, keypoints, cameras, (keypoints, cameras), "no keypoints or camera for image %r")
+        off = batch["pair_offsets"]
+        res_e = _tv._estimate(self.ctx, batch, self.conf["two_view"])
+        res_h = _estimate(self.ctx, batch, self.conf["homography"])
         with_f = self.conf["fundamental"] is not None
         if with_f:
-            res_f = {k: a.download() for k, a in zip(_fm._NAMES, FundamentalProblem(ctx, prob).estimate(**self.conf["fundamental"]))}
+            res_f = _fm._estimate(self.ctx, batch, self.conf["fundamental"])
             trusted = dict(prior_focal_length or {})
         out_m, out_s, geoms = [], [], []
         for p, m in enumerate(matches):
@@ -183,8 +154,8 @@ class TwoViewClassifier:
                 keep = which["inlier"][off[p]:off[p + 1]].astype(bool) if which else np.zeros(len(keep), bool)
             if g["config"] not in self.conf["keep"]:
                 keep = np.zeros(len(keep), bool)
-            out_m.append(np.asarray(m).reshape(-1, 2)[keep])
-            if scores is not None:
-                out_s.append(np.asarray(scores[p]).reshape(-1)[keep])
+            kept = _tv._masked(m, None if scores is None else scores[p], keep)
+            out_m.append(kept[0])
+            out_s.append(kept[1])
             geoms.append(g)
         return out_m, (out_s if scores is not None else None), geoms

@@ -23,24 +23,44 @@ _OPTION_KEYS = tuple(_DEFAULTS)
 _NAMES = ("qvec", "tvec", "E", "status", "n_inliers", "n_trials", "inlier", "err")
 
 
-def two_view_engine_options(options=None):
-    """The keyword arguments of engine.two_view_options for an option dict (a nested "ransac" dict, as pycolmap groups them, is
-    flattened).  Unknown keys raise ValueError."""
+def _engine_options(options, keys, what, builder):
+    """The keyword arguments of an engine option builder for an option dict (a nested "ransac" dict, as pycolmap groups them, is
+    flattened).  A key outside `keys` raises ValueError, which names the estimator as `what`."""
     opts = dict(options or {})
     ransac = opts.pop("ransac", None) or {}
     out = {}
     for k, v in list(dict(ransac).items()) + list(opts.items()):
-        if k not in _OPTION_KEYS:
-            raise ValueError("unknown two-view option %r (known: %s)" % (k, ", ".join(_OPTION_KEYS)))
+        if k not in keys:
+            raise ValueError("unknown %s option %r (known: %s)" % (what, k, ", ".join(keys)))
         out[k] = v
-    two_view_options(**out)                   # fail early on a value ctypes cannot take
+    builder(**out)                            # fail early on a value ctypes cannot take
     return out
 
 
-def _estimate(ctx, batch, opts):
-    """The one place that touches the GPU: host arrays {qvec, tvec, E, status, n_inliers, n_trials, inlier, err}."""
+def two_view_engine_options(options=None):
+    """The keyword arguments of engine.two_view_options for an option dict (_engine_options).  Unknown keys raise ValueError."""
+    return _engine_options(options, _OPTION_KEYS, "two-view", two_view_options)
+
+
+class _Batch(dict):
+    """A host pair batch that remembers the pair problem that uploaded it, so that the estimators run after the first share
+    its device arrays (a pose prior is uploaded only by that first one)."""
+    problem = None
+
+
+def _run(problem_cls, names, ctx, batch, opts):
+    """Construct a pair problem over `batch` -- over the upload a _Batch remembers, when it does -- run it and download its
+    outputs: host arrays by name.  Nothing else in the two-view api modules touches the GPU."""
     ctx = ctx or default_context()
-    return {k: a.download() for k, a in zip(_NAMES, TwoViewProblem(ctx, batch).estimate(**opts))}
+    prob = problem_cls(ctx, getattr(batch, "problem", None) or batch)
+    if isinstance(batch, _Batch):
+        batch.problem = prob
+    return {k: a.download() for k, a in zip(names, prob.estimate(**opts))}
+
+
+def _estimate(ctx, batch, opts):
+    """The seam to the GPU: host arrays {qvec, tvec, E, status, n_inliers, n_trials, inlier, err}."""
+    return _run(TwoViewProblem, _NAMES, ctx, batch, opts)
 
 
 def _camera_table(cameras):
@@ -56,6 +76,52 @@ def _camera_table(cameras):
     for i, c in enumerate(table):
         params[i, :len(c.params)] = c.params
     return np.array(index, np.int32), np.array([c.model_id for c in table], np.int32), params
+
+
+def _calibration_matrix(camera):
+    """K of a SIMPLE_PINHOLE or PINHOLE camera."""
+    k = camera.params
+    if camera.model_id == 0:
+        return np.array([[k[0], 0.0, k[1]], [0.0, k[0], k[2]], [0.0, 0.0, 1.0]])
+    return np.array([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]])
+
+
+def _points(points1, points2):
+    """The two point lists of one pair as (n, 2) float64 arrays of one length."""
+    xy1, xy2 = np.asarray(points1, dtype=np.float64).reshape(-1, 2), np.asarray(points2, dtype=np.float64).reshape(-1, 2)
+    if len(xy1) != len(xy2):
+        raise ValueError("points1 and points2 must have the same length")
+    return xy1, xy2
+
+
+def _single_pair_batch(xy1, xy2, cameras):
+    """The batch of one pair: its matches (n, 2) + (n, 2) under the two cameras."""
+    index, model, params = _camera_table(cameras)
+    return dict(pair_offsets=np.array([0, len(xy1)], np.int64), xy1=xy1, xy2=xy2, pair_camera=index.reshape(1, 2), cam_model=model,
+                cam_params=params)
+
+
+def _multi_pair_batch(pairs, matches, keypoints, cameras, required, missing):
+    """The batch of a list of pairs from per-image keypoints and cameras and per-pair matches.  Every image of a pair must be
+    a key of each of the dicts `required`, or KeyError(`missing` % name)."""
+    xy1, xy2, cams = [], [], []
+    for (a, b), m in zip(pairs, matches):
+        for n in (a, b):
+            if any(n not in table for table in required):
+                raise KeyError(missing % (n,))
+        m = np.asarray(m).reshape(-1, 2).astype(np.int64)
+        xy1.append(np.asarray(keypoints[a], dtype=np.float64)[m[:, 0], :2])
+        xy2.append(np.asarray(keypoints[b], dtype=np.float64)[m[:, 1], :2])
+        cams += [cameras[a], cameras[b]]
+    index, model, params = _camera_table(cams)
+    off = np.concatenate([[0], np.cumsum([len(a) for a in xy1])]).astype(np.int64)
+    return _Batch(pair_offsets=off, xy1=np.concatenate(xy1).reshape(-1, 2), xy2=np.concatenate(xy2).reshape(-1, 2),
+                  pair_camera=index.reshape(-1, 2), cam_model=model, cam_params=params)
+
+
+def _masked(matches, scores, keep):
+    """The matches (M, 2) and the scores ((M,), or None) of one pair that the mask `keep` selects."""
+    return np.asarray(matches).reshape(-1, 2)[keep], None if scores is None else np.asarray(scores).reshape(-1)[keep]
 
 
 def _relative_pose(pose1, pose2):
@@ -77,13 +143,8 @@ def essential_matrix_estimation(points1, points2, camera1, camera2, options=None
     """pycolmap.essential_matrix_estimation's shape: {"success", "E" (3, 3), "qvec", "tvec", "num_inliers", "inliers"}, or
     {"success": False}.  points: (n, 2) pixels (COLMAP convention); the pose is that of camera 2 relative to camera 1, |t| = 1."""
     opts = two_view_engine_options(options)
-    xy1, xy2 = np.asarray(points1, dtype=np.float64).reshape(-1, 2), np.asarray(points2, dtype=np.float64).reshape(-1, 2)
-    if len(xy1) != len(xy2):
-        raise ValueError("points1 and points2 must have the same length")
-    index, model, params = _camera_table([camera1, camera2])
-    batch = dict(pair_offsets=np.array([0, len(xy1)], np.int64), xy1=xy1, xy2=xy2, pair_camera=index.reshape(1, 2), cam_model=model,
-                 cam_params=params)
-    return _geometry(_estimate(ctx, batch, opts), 0, 0, len(xy1))
+    xy1, xy2 = _points(points1, points2)
+    return _geometry(_estimate(ctx, _single_pair_batch(xy1, xy2, [camera1, camera2]), opts), 0, 0, len(xy1))
 
 
 class TwoViewVerifier:
@@ -112,19 +173,9 @@ class TwoViewVerifier:
             raise ValueError("pairs, matches and scores must have the same length")
         if not pairs:
             return [], (None if scores is None else []), []
-        xy1, xy2, cams = [], [], []
-        for (a, b), m in zip(pairs, matches):
-            for n in (a, b):
-                if n not in keypoints or n not in cameras or (poses is not None and n not in poses):
-                    raise KeyError("no keypoints, camera or pose for image %r" % (n,))
-            m = np.asarray(m).reshape(-1, 2).astype(np.int64)
-            xy1.append(np.asarray(keypoints[a], dtype=np.float64)[m[:, 0], :2])
-            xy2.append(np.asarray(keypoints[b], dtype=np.float64)[m[:, 1], :2])
-            cams += [cameras[a], cameras[b]]
-        index, model, params = _camera_table(cams)
-        off = np.concatenate([[0], np.cumsum([len(a) for a in xy1])]).astype(np.int64)
-        batch = dict(pair_offsets=off, xy1=np.concatenate(xy1).reshape(-1, 2), xy2=np.concatenate(xy2).reshape(-1, 2),
-                     pair_camera=index.reshape(-1, 2), cam_model=model, cam_params=params)
+        required = (keypoints, cameras) if poses is None else (keypoints, cameras, poses)
+        batch = _multi_pair_batch(pairs, matches, keypoints, cameras, required, "no keypoints, camera or pose for image %r")
+        off = batch["pair_offsets"]
         if poses is not None:
             rel = [_relative_pose(poses[a], poses[b]) for a, b in pairs]
             batch["prior_qvec"] = np.array([r[0] for r in rel]).reshape(-1, 4)
@@ -132,9 +183,8 @@ class TwoViewVerifier:
         res = _estimate(self.ctx, batch, self.conf)
         out_m, out_s, geoms = [], [], []
         for p, m in enumerate(matches):
-            keep = res["inlier"][off[p]:off[p + 1]].astype(bool)
-            out_m.append(np.asarray(m).reshape(-1, 2)[keep])
-            if scores is not None:
-                out_s.append(np.asarray(scores[p]).reshape(-1)[keep])
+            kept = _masked(m, None if scores is None else scores[p], res["inlier"][off[p]:off[p + 1]].astype(bool))
+            out_m.append(kept[0])
+            out_s.append(kept[1])
             geoms.append(_geometry(res, p, off[p], off[p + 1]))
         return out_m, (out_s if scores is not None else None), geoms

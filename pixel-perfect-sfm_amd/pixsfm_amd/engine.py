@@ -486,7 +486,126 @@ def _linear_solver_id(name):
     return table[key]
 
 
-class BAProblem:
+def _padded_cam_params(cam_params, n_cameras):
+    """cam_params as (n_cameras, KPAD), zero-padded.  A 2-D array of n_cameras rows (or of one row, for every camera) is taken
+    as it is, anything else -- a flat list, one camera's parameters -- is reshaped to n_cameras rows."""
+    out = np.zeros((n_cameras, KPAD))
+    cp = np.asarray(cam_params, dtype=np.float64)
+    if cp.ndim != 2 or cp.shape[0] not in (1, n_cameras):
+        cp = cp.reshape(n_cameras, -1)
+    out[:, :cp.shape[1]] = cp
+    return out
+
+
+def _csr_offsets(offsets, name, rows):
+    """The offsets of a CSR list as a flat int64 array: `name` must hold `rows` + 1 entries, at least one."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    if len(offsets) < 1:
+        raise ValueError("%s must hold %s + 1 entries" % (name, rows))
+    return offsets
+
+
+def _start(values, rows, width):
+    """The host array an output starts from: the caller's (rows, width), or NaN -- what a row without a result keeps."""
+    return np.full((rows, width), np.nan) if values is None else np.asarray(values, dtype=np.float64).reshape(rows, width)
+
+
+def _launch(ctx, name, args, stages, timed):
+    """Call the entry point `name`, or with `timed` its twin `name`_timed, which also fills one HIP-event time per stage.
+    Returns {stage: milliseconds}, or None for an untimed call."""
+    if not timed:
+        check(getattr(ctx.lib, name)(*args), name)
+        return None
+    ms = (C.c_double * len(stages))()
+    check(getattr(ctx.lib, name + "_timed")(*args, ms), name + "_timed")
+    return dict(zip(stages, (float(x) for x in ms)))
+
+
+_ROBUST_STAGES = ("records", "compact", "hypotheses", "refine")     # the kernels of abspose and of the three pair estimators
+
+
+class _BABase:
+    """What the featuremetric and the geometric bundle-adjustment problems share: the device arrays of poses, cameras and
+    points behind one pxr_ba_view, the records of the last evaluation, and the host side of a solve."""
+
+    def _upload(self, ctx, g, **more):
+        """Counts, the shared device arrays of problem dict `g` plus `more`, the record buffer and the view."""
+        self.ctx = ctx
+        self.n_obs = len(g["obs_image"])
+        self.n_images = len(g["image_camera"])
+        self.n_cameras = len(g["cam_model"])
+        self.n_points = len(g["xyz"])
+        self.d = {
+            "obs_image": ctx.to_device(g["obs_image"], np.int32),
+            "obs_point": ctx.to_device(g["obs_point"], np.int32),
+            "image_camera": ctx.to_device(g["image_camera"], np.int32),
+            "qvec": ctx.to_device(g["qvec"], np.float64),
+            "tvec": ctx.to_device(g["tvec"], np.float64),
+            "cam_model": ctx.to_device(g["cam_model"], np.int32),
+            "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
+            "xyz": ctx.to_device(g["xyz"], np.float64),
+            **more,
+        }
+        self.rec = ctx.empty((self.n_obs, OBS_REC), np.float64)
+        self.view = self._view()
+
+    def _view(self):
+        d = self.d
+        patch, refs = d.get("obs_patch"), d.get("refs")
+        return BaView(self.n_obs, d["obs_image"].ptr, d["obs_point"].ptr, patch.ptr if patch is not None else None,
+                      self.n_images, d["image_camera"].ptr, d["qvec"].ptr, d["tvec"].ptr,
+                      self.n_cameras, d["cam_model"].ptr, d["cam_params"].ptr,
+                      self.n_points, d["xyz"].ptr, refs.ptr if refs is not None else None)
+
+    def _solve(self, name, head, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, options, allreduce):
+        """The entry point `name` over its leading arguments `head` and what every BA solve takes after them: the loss, the
+        constant masks (checked against the problem's dimensions), the options, the all-reduce callback and the summary."""
+        pc = np.ascontiguousarray(pose_const, dtype=np.uint8)
+        tm = np.ascontiguousarray(tvec_const_mask, dtype=np.uint8)
+        cm = np.ascontiguousarray(cam_const_mask, dtype=np.uint16)
+        ptc = np.ascontiguousarray(point_const, dtype=np.uint8)
+        if len(pc) != self.n_images or len(tm) != self.n_images or len(cm) != self.n_cameras \
+                or len(ptc) != self.n_points:
+            raise ValueError("parameterisation arrays do not match the problem dimensions")
+        opts = options or lm_options()
+        summ = _lib.LMSummary()
+        cb = None
+        if allreduce is not None:
+            def _cb(user, ptr, count):
+                try:
+                    allreduce(ptr, count)
+                    return 0
+                except Exception as e:  # noqa: BLE001 -- must not unwind through C
+                    import sys
+                    print("all-reduce callback failed: %r" % (e,), file=sys.stderr)
+                    return 1
+            cb = _lib.ALLREDUCE_FN(_cb)
+        check(getattr(self.ctx.lib, name)(*head, C.byref(loss), pc.ctypes.data, tm.ctypes.data, cm.ctypes.data, ptc.ctypes.data,
+                                          C.byref(opts), C.cast(cb, C.c_void_p) if cb else None, None, C.byref(summ)), name)
+        return summ.as_dict()
+
+    def projection_jacobian(self, out=None):
+        """The 2 x (10+K) projection Jacobian P of every observation (k_jac) -- for the geometric problem the Jacobian of the
+        residual block itself; `out` re-uses a device array."""
+        P = out if out is not None else self.ctx.empty((self.n_obs, 2, 10 + KPAD), np.float64)
+        check(self.ctx.lib.pxr_ba_projection_jacobian(self.ctx.handle, C.byref(self.view), P.ptr),
+              "pxr_ba_projection_jacobian")
+        return P
+
+    def params(self):
+        """Download (qvec, tvec, cam_params, xyz)."""
+        d = self.d
+        return d["qvec"].download(), d["tvec"].download(), d["cam_params"].download(), d["xyz"].download()
+
+    def cost(self, loss):
+        """Sum of 0.5 rho(|r|^2) over the records of the last eval()."""
+        out = C.c_double()
+        check(self.ctx.lib.pxr_ba_cost(self.ctx.handle, self.rec.ptr, self.n_obs, C.byref(loss), C.byref(out)),
+              "pxr_ba_cost")
+        return out.value
+
+
+class BAProblem(_BABase):
     """Device-resident flat arrays of a bundle-adjustment problem (pxr_ba_view).
 
     problem: dict with obs_image, obs_point, obs_patch, image_camera, qvec, tvec,
@@ -495,36 +614,10 @@ class BAProblem:
     """
 
     def __init__(self, ctx, arena, problem):
-        self.ctx, self.arena = ctx, arena
+        self.arena = arena
         g = problem
-        self.n_obs = len(g["obs_image"])
-        self.n_images = len(g["image_camera"])
-        self.n_cameras = len(g["cam_model"])
-        self.n_points = len(g["xyz"])
-        cam_params = np.zeros((self.n_cameras, KPAD))
-        cp = np.asarray(g["cam_params"], dtype=np.float64)
-        cam_params[:, :cp.shape[1]] = cp
-        self.d = {
-            "obs_image": ctx.to_device(g["obs_image"], np.int32),
-            "obs_point": ctx.to_device(g["obs_point"], np.int32),
-            "obs_patch": ctx.to_device(g["obs_patch"], np.int64),
-            "image_camera": ctx.to_device(g["image_camera"], np.int32),
-            "qvec": ctx.to_device(g["qvec"], np.float64),
-            "tvec": ctx.to_device(g["tvec"], np.float64),
-            "cam_model": ctx.to_device(g["cam_model"], np.int32),
-            "cam_params": ctx.to_device(cam_params, np.float64),
-            "xyz": ctx.to_device(g["xyz"], np.float64),
-            "refs": ctx.to_device(g["refs"], np.float64) if g.get("refs") is not None else None,
-        }
-        self.rec = ctx.empty((self.n_obs, OBS_REC), np.float64)
-        self.view = self._view()
-
-    def _view(self):
-        d = self.d
-        return BaView(self.n_obs, d["obs_image"].ptr, d["obs_point"].ptr, d["obs_patch"].ptr,
-                      self.n_images, d["image_camera"].ptr, d["qvec"].ptr, d["tvec"].ptr,
-                      self.n_cameras, d["cam_model"].ptr, d["cam_params"].ptr,
-                      self.n_points, d["xyz"].ptr, d["refs"].ptr if d["refs"] is not None else None)
+        self._upload(ctx, g, obs_patch=ctx.to_device(g["obs_patch"], np.int64),
+                     refs=ctx.to_device(g["refs"], np.float64) if g.get("refs") is not None else None)
 
     def extract_costmaps(self, loss, as_gradientfield=True, apply_sqrt=False, dtype=None, out=None, first_out=0,
                          upsampling_factor=1.0, compute_cross_derivative=False, cfg=None):
@@ -591,13 +684,6 @@ class BAProblem:
                                             self.rec.ptr, C.byref(built) if sync else None), "pxr_ba_eval_gram")
         return self.rec, (built.value if sync else None)
 
-    def projection_jacobian(self, out=None):
-        """The 2 x (10+K) projection Jacobian P of every observation (k_jac); `out` re-uses a device array."""
-        P = out if out is not None else self.ctx.empty((self.n_obs, 2, 10 + KPAD), np.float64)
-        check(self.ctx.lib.pxr_ba_projection_jacobian(self.ctx.handle, C.byref(self.view), P.ptr),
-              "pxr_ba_projection_jacobian")
-        return P
-
     def solve(self, cfg, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, options=None,
               allreduce=None):
         """Run the GPU LM (pxr_ba_solve); parameters are refined in place on the device.
@@ -606,32 +692,8 @@ class BAProblem:
         over the ranks (see parallel.make_allreduce); None for one GPU.
         Returns the summary dict; use params() to fetch the refined parameters.
         """
-        ctx = self.ctx
-        pc = np.ascontiguousarray(pose_const, dtype=np.uint8)
-        tm = np.ascontiguousarray(tvec_const_mask, dtype=np.uint8)
-        cm = np.ascontiguousarray(cam_const_mask, dtype=np.uint16)
-        ptc = np.ascontiguousarray(point_const, dtype=np.uint8)
-        if len(pc) != self.n_images or len(tm) != self.n_images or len(cm) != self.n_cameras \
-                or len(ptc) != self.n_points:
-            raise ValueError("parameterisation arrays do not match the problem dimensions")
-        opts = options or lm_options()
-        summ = _lib.LMSummary()
-        cb = None
-        if allreduce is not None:
-            def _cb(user, ptr, count):
-                try:
-                    allreduce(ptr, count)
-                    return 0
-                except Exception as e:  # noqa: BLE001 -- must not unwind through C
-                    import sys
-                    print("all-reduce callback failed: %r" % (e,), file=sys.stderr)
-                    return 1
-            cb = _lib.ALLREDUCE_FN(_cb)
-        check(ctx.lib.pxr_ba_solve(ctx.handle, self.arena.handle, C.byref(self.view), C.byref(cfg), C.byref(loss),
-                                   pc.ctypes.data, tm.ctypes.data, cm.ctypes.data, ptc.ctypes.data,
-                                   C.byref(opts), C.cast(cb, C.c_void_p) if cb else None, None, C.byref(summ)),
-              "pxr_ba_solve")
-        return summ.as_dict()
+        head = (self.ctx.handle, self.arena.handle, C.byref(self.view), C.byref(cfg))
+        return self._solve("pxr_ba_solve", head, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, options, allreduce)
 
     def compute_references(self, cfg, loss, iters=100, keep_mean=False, keep_observations=False):
         """ReferenceExtractor.run on the GPU: fills this problem's `refs` in place (device) and
@@ -648,19 +710,8 @@ class BAProblem:
                                                 self.obs_desc.ptr if self.obs_desc else None), "pxr_ba_compute_references")
         return ref_obs.download(), (mean.download() if mean else None)
 
-    def params(self):
-        """Download (qvec, tvec, cam_params, xyz)."""
-        d = self.d
-        return d["qvec"].download(), d["tvec"].download(), d["cam_params"].download(), d["xyz"].download()
 
-    def cost(self, loss):
-        out = C.c_double()
-        check(self.ctx.lib.pxr_ba_cost(self.ctx.handle, self.rec.ptr, self.n_obs, C.byref(loss), C.byref(out)),
-              "pxr_ba_cost")
-        return out.value
-
-
-class GeometricBAProblem:
+class GeometricBAProblem(_BABase):
     """Device-resident flat arrays of a geometric (reprojection-error) bundle-adjustment problem: the pxr_ba_view without a
     patch arena plus the observed keypoints (GeometricBundleOptimizer::AddResiduals, geometric_bundle_optimizer.h:39-88).
 
@@ -668,35 +719,12 @@ class GeometricBAProblem:
     """
 
     def __init__(self, ctx, problem):
-        self.ctx = ctx
         g = problem
-        self.n_obs = len(g["obs_image"])
-        self.n_images = len(g["image_camera"])
-        self.n_cameras = len(g["cam_model"])
-        self.n_points = len(g["xyz"])
         obs_xy = np.ascontiguousarray(g["obs_xy"], dtype=np.float64).reshape(-1, 2)
-        if len(obs_xy) != self.n_obs:
+        if len(obs_xy) != len(g["obs_image"]):
             raise ValueError("obs_xy must hold one keypoint per observation")
-        cam_params = np.zeros((self.n_cameras, KPAD))
-        cp = np.asarray(g["cam_params"], dtype=np.float64)
-        cam_params[:, :cp.shape[1]] = cp
-        self.d = {
-            "obs_image": ctx.to_device(g["obs_image"], np.int32),
-            "obs_point": ctx.to_device(g["obs_point"], np.int32),
-            "obs_xy": ctx.to_device(obs_xy, np.float64),
-            "image_camera": ctx.to_device(g["image_camera"], np.int32),
-            "qvec": ctx.to_device(g["qvec"], np.float64),
-            "tvec": ctx.to_device(g["tvec"], np.float64),
-            "cam_model": ctx.to_device(g["cam_model"], np.int32),
-            "cam_params": ctx.to_device(cam_params, np.float64),
-            "xyz": ctx.to_device(g["xyz"], np.float64),
-        }
-        self.rec = ctx.empty((self.n_obs, OBS_REC), np.float64)
+        self._upload(ctx, g, obs_xy=ctx.to_device(obs_xy, np.float64))
         self.res = ctx.empty((self.n_obs, 2), np.float64)
-        d = self.d
-        self.view = BaView(self.n_obs, d["obs_image"].ptr, d["obs_point"].ptr, None, self.n_images, d["image_camera"].ptr,
-                           d["qvec"].ptr, d["tvec"].ptr, self.n_cameras, d["cam_model"].ptr, d["cam_params"].ptr,
-                           self.n_points, d["xyz"].ptr, None)
 
     def eval(self, residuals=True):
         """Launch the reprojection-residual kernel (pxr_ba_geom_eval).  Returns device arrays (rec, res): the 8-double
@@ -712,54 +740,12 @@ class GeometricBAProblem:
         r = res.download()
         return np.hypot(r[:, 0], r[:, 1])
 
-    def projection_jacobian(self, out=None):
-        """The 2 x (10+K) projection Jacobian of every observation -- here the Jacobian of the residual block itself."""
-        P = out if out is not None else self.ctx.empty((self.n_obs, 2, 10 + KPAD), np.float64)
-        check(self.ctx.lib.pxr_ba_projection_jacobian(self.ctx.handle, C.byref(self.view), P.ptr),
-              "pxr_ba_projection_jacobian")
-        return P
-
     def solve(self, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, options=None, allreduce=None):
         """Run the GPU LM (pxr_ba_solve_geometric); parameters are refined in place on the device.  Arguments as
         BAProblem.solve without the interpolation configuration.  Returns the summary dict."""
-        ctx = self.ctx
-        pc = np.ascontiguousarray(pose_const, dtype=np.uint8)
-        tm = np.ascontiguousarray(tvec_const_mask, dtype=np.uint8)
-        cm = np.ascontiguousarray(cam_const_mask, dtype=np.uint16)
-        ptc = np.ascontiguousarray(point_const, dtype=np.uint8)
-        if len(pc) != self.n_images or len(tm) != self.n_images or len(cm) != self.n_cameras \
-                or len(ptc) != self.n_points:
-            raise ValueError("parameterisation arrays do not match the problem dimensions")
-        opts = options or lm_options()
-        summ = _lib.LMSummary()
-        cb = None
-        if allreduce is not None:
-            def _cb(user, ptr, count):
-                try:
-                    allreduce(ptr, count)
-                    return 0
-                except Exception as e:  # noqa: BLE001 -- must not unwind through C
-                    import sys
-                    print("all-reduce callback failed: %r" % (e,), file=sys.stderr)
-                    return 1
-            cb = _lib.ALLREDUCE_FN(_cb)
-        check(ctx.lib.pxr_ba_solve_geometric(ctx.handle, C.byref(self.view), self.d["obs_xy"].ptr, C.byref(loss),
-                                             pc.ctypes.data, tm.ctypes.data, cm.ctypes.data, ptc.ctypes.data,
-                                             C.byref(opts), C.cast(cb, C.c_void_p) if cb else None, None, C.byref(summ)),
-              "pxr_ba_solve_geometric")
-        return summ.as_dict()
-
-    def params(self):
-        """Download (qvec, tvec, cam_params, xyz)."""
-        d = self.d
-        return d["qvec"].download(), d["tvec"].download(), d["cam_params"].download(), d["xyz"].download()
-
-    def cost(self, loss):
-        """Sum of 0.5 rho(|r|^2) over the records of the last eval()."""
-        out = C.c_double()
-        check(self.ctx.lib.pxr_ba_cost(self.ctx.handle, self.rec.ptr, self.n_obs, C.byref(loss), C.byref(out)),
-              "pxr_ba_cost")
-        return out.value
+        head = (self.ctx.handle, C.byref(self.view), self.d["obs_xy"].ptr)
+        return self._solve("pxr_ba_solve_geometric", head, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, options,
+                           allreduce)
 
 
 def tri_options(min_tri_angle=1.5, max_angle_error=2.0, max_reproj_error=4.0, min_track_len=2, max_hypotheses=256):
@@ -767,13 +753,6 @@ def tri_options(min_tri_angle=1.5, max_angle_error=2.0, max_reproj_error=4.0, mi
     reprojection error in pixels) and the bound on the two-view hypotheses per track."""
     return _lib.TriOptions(float(min_tri_angle), float(max_angle_error), float(max_reproj_error), int(min_track_len),
                            int(max_hypotheses))
-
-
-def _padded_cam_params(cam_params, n_cameras):
-    out = np.zeros((n_cameras, KPAD))
-    cp = np.asarray(cam_params, dtype=np.float64).reshape(n_cameras, -1)
-    out[:, :cp.shape[1]] = cp
-    return out
 
 
 def image_to_world(ctx, cam_model, cam_params, xy, cam_index=None):
@@ -809,9 +788,7 @@ class TriangulationProblem:
     def __init__(self, ctx, problem):
         self.ctx = ctx
         g = problem
-        offsets = np.ascontiguousarray(g["track_offsets"], dtype=np.int64).reshape(-1)
-        if len(offsets) < 1:
-            raise ValueError("track_offsets must hold n_tracks + 1 entries")
+        offsets = _csr_offsets(g["track_offsets"], "track_offsets", "n_tracks")
         self.n_tracks = len(offsets) - 1
         self.n_obs = len(g["obs_image"])
         self.n_images = len(g["image_camera"])
@@ -843,18 +820,11 @@ class TriangulationProblem:
         {"check", "rays", "compact", "tracks"} (milliseconds)."""
         ctx = self.ctx
         opts = tri_options(**options)
-        init = np.full((self.n_tracks, 3), np.nan) if xyz is None else np.asarray(xyz, dtype=np.float64).reshape(self.n_tracks, 3)
-        d_xyz = ctx.to_device(init, np.float64)
+        d_xyz = ctx.to_device(_start(xyz, self.n_tracks, 3), np.float64)
         d_status, d_ninl = ctx.empty((self.n_tracks,), np.int32), ctx.empty((self.n_tracks,), np.int32)
         d_inl, d_err = ctx.empty((self.n_obs,), np.uint8), ctx.empty((self.n_obs,), np.float64)
-        if timed:
-            ms = (C.c_double * 4)()
-            check(ctx.lib.pxr_triangulate_tracks_timed(ctx.handle, C.byref(self.view), C.byref(opts), d_xyz.ptr, d_status.ptr,
-                                                       d_ninl.ptr, d_inl.ptr, d_err.ptr, ms), "pxr_triangulate_tracks_timed")
-            self.kernel_ms = dict(zip(("check", "rays", "compact", "tracks"), (float(x) for x in ms)))
-        else:
-            check(ctx.lib.pxr_triangulate_tracks(ctx.handle, C.byref(self.view), C.byref(opts), d_xyz.ptr, d_status.ptr,
-                                                 d_ninl.ptr, d_inl.ptr, d_err.ptr), "pxr_triangulate_tracks")
+        args = (ctx.handle, C.byref(self.view), C.byref(opts), d_xyz.ptr, d_status.ptr, d_ninl.ptr, d_inl.ptr, d_err.ptr)
+        self.kernel_ms = _launch(ctx, "pxr_triangulate_tracks", args, ("check", "rays", "compact", "tracks"), timed) or self.kernel_ms
         return d_xyz, d_status, d_ninl, d_inl, d_err
 
 
@@ -878,9 +848,7 @@ class AbsolutePoseProblem:
     def __init__(self, ctx, problem):
         self.ctx = ctx
         g = problem
-        offsets = np.ascontiguousarray(g["query_offsets"], dtype=np.int64).reshape(-1)
-        if len(offsets) < 1:
-            raise ValueError("query_offsets must hold n_queries + 1 entries")
+        offsets = _csr_offsets(g["query_offsets"], "query_offsets", "n_queries")
         self.n_queries = len(offsets) - 1
         xy = np.ascontiguousarray(g["xy"], dtype=np.float64).reshape(-1, 2)
         xyz = np.ascontiguousarray(g["xyz"], dtype=np.float64).reshape(-1, 3)
@@ -926,46 +894,44 @@ class AbsolutePoseProblem:
         keep the kernels' HIP-event times in self.kernel_ms {"records", "compact", "hypotheses", "refine"} (milliseconds)."""
         ctx, d, T, N = self.ctx, self.d, self.n_queries, self.n_corr
         opts = abspose_options(**options)
-        q0 = np.full((T, 4), np.nan) if qvec is None else np.asarray(qvec, dtype=np.float64).reshape(T, 4)
-        t0 = np.full((T, 3), np.nan) if tvec is None else np.asarray(tvec, dtype=np.float64).reshape(T, 3)
-        d_q, d_t = ctx.to_device(q0, np.float64), ctx.to_device(t0, np.float64)
+        d_q, d_t = ctx.to_device(_start(qvec, T, 4), np.float64), ctx.to_device(_start(tvec, T, 3), np.float64)
         d_status, d_ninl, d_ntr = ctx.empty((T,), np.int32), ctx.empty((T,), np.int32), ctx.empty((T,), np.int32)
         d_inl, d_err = ctx.empty((N,), np.uint8), ctx.empty((N,), np.float64)
         args = (ctx.handle, T, d["query_offsets"].ptr, N, d["xy"].ptr, d["xyz"].ptr, d["query_camera"].ptr, self.n_cameras,
                 d["cam_model"].ptr, d["cam_params"].ptr, C.byref(opts), d_q.ptr, d_t.ptr, d_status.ptr, d_ninl.ptr, d_ntr.ptr,
                 d_inl.ptr, d_err.ptr)
-        if timed:
-            ms = (C.c_double * 4)()
-            check(ctx.lib.pxr_absolute_pose_timed(*args, ms), "pxr_absolute_pose_timed")
-            self.kernel_ms = dict(zip(("records", "compact", "hypotheses", "refine"), (float(x) for x in ms)))
-        else:
-            check(ctx.lib.pxr_absolute_pose(*args), "pxr_absolute_pose")
+        self.kernel_ms = _launch(ctx, "pxr_absolute_pose", args, _ROBUST_STAGES, timed) or self.kernel_ms
         return d_q, d_t, d_status, d_ninl, d_ntr, d_inl, d_err
 
 
 def two_view_options(max_error=4.0, min_inlier_ratio=0.25, min_num_inliers=15, confidence=0.999, min_num_trials=64,
                      max_num_trials=10000, round_size=64, seed=0, refine_max_iterations=100, lo_rounds=4):
-    """pxr_two_view_options: COLMAP 3.8's two-view geometry values as remembered (parity unpinned), and the estimator's own
-    min_num_trials, round_size, seed, refine_max_iterations and lo_rounds."""
-    return _lib.TwoViewOptions(float(max_error), float(min_inlier_ratio), float(confidence), int(seed), int(min_num_inliers),
-                               int(min_num_trials), int(max_num_trials), int(round_size), int(refine_max_iterations), int(lo_rounds))
+    """pxr_pair_options, the one struct the header also names pxr_two_view_options, pxr_homography_options and
+    pxr_fundamental_options: COLMAP 3.8's two-view geometry values as remembered (parity unpinned), and the estimators' own
+    min_num_trials, round_size, seed, refine_max_iterations and lo_rounds.  homography_options and fundamental_options are this
+    function: the same fields and defaults, for the homography and the fundamental-matrix estimator."""
+    return _lib.PairOptions(float(max_error), float(min_inlier_ratio), float(confidence), int(seed), int(min_num_inliers),
+                            int(min_num_trials), int(max_num_trials), int(round_size), int(refine_max_iterations), int(lo_rounds))
 
 
-class TwoViewProblem:
-    """Device-resident flat arrays of a batch of image pairs (pxr_two_view_geometry): the matches of every pair in CSR form,
-    two cameras per pair.
+homography_options = fundamental_options = two_view_options
+
+
+class _PairProblem:
+    """Device-resident flat arrays of a batch of image pairs: the matches of every pair in CSR form, two cameras per pair.
 
     batch: dict with pair_offsets (n_pairs + 1), xy1 / xy2 (n_matches x 2, image pixels, COLMAP convention), pair_camera
-    (n_pairs x 2), cam_model, cam_params (n_cams x <= KPAD), and optionally prior_qvec (n_pairs x 4) + prior_tvec (n_pairs x 3):
-    the pose of camera 2 relative to camera 1, which switches the estimator to known-pose verification.
+    (n_pairs x 2), cam_model, cam_params (n_cams x <= KPAD).  Any pair problem in place of the dict shares its device arrays:
+    several estimators on one upload.
     """
 
     def __init__(self, ctx, batch):
-        self.ctx = ctx
+        self.ctx, self.kernel_ms = ctx, None
+        if isinstance(batch, _PairProblem):
+            self.n_pairs, self.n_matches, self.n_cameras, self.d = batch.n_pairs, batch.n_matches, batch.n_cameras, batch.d
+            return
         g = batch
-        offsets = np.ascontiguousarray(g["pair_offsets"], dtype=np.int64).reshape(-1)
-        if len(offsets) < 1:
-            raise ValueError("pair_offsets must hold n_pairs + 1 entries")
+        offsets = _csr_offsets(g["pair_offsets"], "pair_offsets", "n_pairs")
         self.n_pairs = len(offsets) - 1
         xy1 = np.ascontiguousarray(g["xy1"], dtype=np.float64).reshape(-1, 2)
         xy2 = np.ascontiguousarray(g["xy2"], dtype=np.float64).reshape(-1, 2)
@@ -976,8 +942,6 @@ class TwoViewProblem:
         pair_camera = np.ascontiguousarray(g["pair_camera"], dtype=np.int32).reshape(-1, 2)
         if len(pair_camera) != self.n_pairs:
             raise ValueError("pair_camera must hold two cameras per pair")
-        if (g.get("prior_qvec") is None) != (g.get("prior_tvec") is None):
-            raise ValueError("prior_qvec and prior_tvec go together")
         self.d = {
             "pair_offsets": ctx.to_device(offsets, np.int64),
             "xy1": ctx.to_device(xy1, np.float64),
@@ -986,11 +950,40 @@ class TwoViewProblem:
             "cam_model": ctx.to_device(g["cam_model"], np.int32),
             "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
         }
-        self.has_prior = g.get("prior_qvec") is not None
-        if self.has_prior:
-            self.d["prior_qvec"] = ctx.to_device(np.asarray(g["prior_qvec"], dtype=np.float64).reshape(self.n_pairs, 4), np.float64)
-            self.d["prior_tvec"] = ctx.to_device(np.asarray(g["prior_tvec"], dtype=np.float64).reshape(self.n_pairs, 3), np.float64)
-        self.kernel_ms = None
+
+    def _estimate(self, name, options, starts, n_counts, timed, prior=()):
+        """Run the entry point `name` with two_view_options(**options).  starts: (host array or None, width) per model output,
+        each starting from _start; n_counts: its per-pair int32 outputs; prior: what goes between the batch and the options.
+        Returns the device arrays (model outputs, counts, inlier (n_matches,) uint8, err (n_matches,) float64)."""
+        ctx, d, T, N = self.ctx, self.d, self.n_pairs, self.n_matches
+        opts = two_view_options(**options)
+        models = [ctx.to_device(_start(a, T, w), np.float64) for a, w in starts]
+        counts = [ctx.empty((T,), np.int32) for _ in range(n_counts)]
+        d_inl, d_err = ctx.empty((N,), np.uint8), ctx.empty((N,), np.float64)
+        args = (ctx.handle, T, d["pair_offsets"].ptr, N, d["xy1"].ptr, d["xy2"].ptr, d["pair_camera"].ptr, self.n_cameras,
+                d["cam_model"].ptr, d["cam_params"].ptr, *prior, C.byref(opts), *(a.ptr for a in models), *(a.ptr for a in counts),
+                d_inl.ptr, d_err.ptr)
+        self.kernel_ms = _launch(ctx, name, args, _ROBUST_STAGES, timed) or self.kernel_ms
+        return (*models, *counts, d_inl, d_err)
+
+
+class TwoViewProblem(_PairProblem):
+    """The pair batch of pxr_two_view_geometry: the batch dict of every pair problem, and optionally prior_qvec (n_pairs x 4) +
+    prior_tvec (n_pairs x 3): the pose of camera 2 relative to camera 1, which switches the estimator to known-pose
+    verification.
+    """
+
+    def __init__(self, ctx, batch):
+        prior = None
+        if not isinstance(batch, _PairProblem):
+            prior = (batch.get("prior_qvec"), batch.get("prior_tvec"))
+            if (prior[0] is None) != (prior[1] is None):
+                raise ValueError("prior_qvec and prior_tvec go together")
+        super().__init__(ctx, batch)
+        if prior is not None and prior[0] is not None:
+            self.d["prior_qvec"] = ctx.to_device(np.asarray(prior[0], dtype=np.float64).reshape(self.n_pairs, 4), np.float64)
+            self.d["prior_tvec"] = ctx.to_device(np.asarray(prior[1], dtype=np.float64).reshape(self.n_pairs, 3), np.float64)
+        self.has_prior = "prior_qvec" in self.d
 
     def estimate(self, qvec=None, tvec=None, E=None, timed=False, **options):
         """Run the kernels (pxr_two_view_geometry) with two_view_options(**options).  Returns the device arrays (qvec (n_pairs, 4),
@@ -998,68 +991,12 @@ class TwoViewProblem:
         (n_matches,) float64).  qvec / tvec / E: host arrays the outputs start from -- rows of pairs without a pose keep them
         (default: NaN).  timed: also keep the kernels' HIP-event times in self.kernel_ms {"records", "compact", "hypotheses",
         "refine"} (milliseconds)."""
-        ctx, d, T, N = self.ctx, self.d, self.n_pairs, self.n_matches
-        opts = two_view_options(**options)
-        start = lambda a, w: np.full((T, w), np.nan) if a is None else np.asarray(a, dtype=np.float64).reshape(T, w)
-        d_q, d_t, d_E = (ctx.to_device(start(a, w), np.float64) for a, w in ((qvec, 4), (tvec, 3), (E, 9)))
-        d_status, d_ninl, d_ntr = ctx.empty((T,), np.int32), ctx.empty((T,), np.int32), ctx.empty((T,), np.int32)
-        d_inl, d_err = ctx.empty((N,), np.uint8), ctx.empty((N,), np.float64)
-        prior = (d["prior_qvec"].ptr, d["prior_tvec"].ptr) if self.has_prior else (None, None)
-        args = (ctx.handle, T, d["pair_offsets"].ptr, N, d["xy1"].ptr, d["xy2"].ptr, d["pair_camera"].ptr, self.n_cameras,
-                d["cam_model"].ptr, d["cam_params"].ptr, prior[0], prior[1], C.byref(opts), d_q.ptr, d_t.ptr, d_E.ptr, d_status.ptr,
-                d_ninl.ptr, d_ntr.ptr, d_inl.ptr, d_err.ptr)
-        if timed:
-            ms = (C.c_double * 4)()
-            check(ctx.lib.pxr_two_view_geometry_timed(*args, ms), "pxr_two_view_geometry_timed")
-            self.kernel_ms = dict(zip(("records", "compact", "hypotheses", "refine"), (float(x) for x in ms)))
-        else:
-            check(ctx.lib.pxr_two_view_geometry(*args), "pxr_two_view_geometry")
-        return d_q, d_t, d_E, d_status, d_ninl, d_ntr, d_inl, d_err
+        prior = (self.d["prior_qvec"].ptr, self.d["prior_tvec"].ptr) if self.has_prior else (None, None)
+        return self._estimate("pxr_two_view_geometry", options, ((qvec, 4), (tvec, 3), (E, 9)), 3, timed, prior)
 
 
-def homography_options(max_error=4.0, min_inlier_ratio=0.25, min_num_inliers=15, confidence=0.999, min_num_trials=64,
-                       max_num_trials=10000, round_size=64, seed=0, refine_max_iterations=100, lo_rounds=4):
-    """pxr_homography_options: the fields and defaults of two_view_options, as the homography estimator's own struct."""
-    return _lib.HomographyOptions(float(max_error), float(min_inlier_ratio), float(confidence), int(seed), int(min_num_inliers),
-                                  int(min_num_trials), int(max_num_trials), int(round_size), int(refine_max_iterations), int(lo_rounds))
-
-
-class HomographyProblem:
-    """Device-resident flat arrays of a batch of image pairs (pxr_homography): the batch dict of TwoViewProblem without a pose
-    prior -- pair_offsets (n_pairs + 1), xy1 / xy2 (n_matches x 2, image pixels, COLMAP convention), pair_camera (n_pairs x 2),
-    cam_model, cam_params (n_cams x <= KPAD).  A TwoViewProblem in place of the dict shares its device arrays: both estimators
-    on one upload.
-    """
-
-    def __init__(self, ctx, batch):
-        self.ctx = ctx
-        self.kernel_ms = None
-        if isinstance(batch, TwoViewProblem):
-            self.n_pairs, self.n_matches, self.n_cameras, self.d = batch.n_pairs, batch.n_matches, batch.n_cameras, batch.d
-            return
-        g = batch
-        offsets = np.ascontiguousarray(g["pair_offsets"], dtype=np.int64).reshape(-1)
-        if len(offsets) < 1:
-            raise ValueError("pair_offsets must hold n_pairs + 1 entries")
-        self.n_pairs = len(offsets) - 1
-        xy1 = np.ascontiguousarray(g["xy1"], dtype=np.float64).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(g["xy2"], dtype=np.float64).reshape(-1, 2)
-        if len(xy1) != len(xy2):
-            raise ValueError("xy1 and xy2 must hold one row per match")
-        self.n_matches = len(xy1)
-        self.n_cameras = len(g["cam_model"])
-        pair_camera = np.ascontiguousarray(g["pair_camera"], dtype=np.int32).reshape(-1, 2)
-        if len(pair_camera) != self.n_pairs:
-            raise ValueError("pair_camera must hold two cameras per pair")
-        self.d = {
-            "pair_offsets": ctx.to_device(offsets, np.int64),
-            "xy1": ctx.to_device(xy1, np.float64),
-            "xy2": ctx.to_device(xy2, np.float64),
-            "pair_camera": ctx.to_device(pair_camera, np.int32),
-            "cam_model": ctx.to_device(g["cam_model"], np.int32),
-            "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
-        }
-        self.kernel_ms = None
+class HomographyProblem(_PairProblem):
+    """The pair batch of pxr_homography: the batch dict of every pair problem; a pose prior is not used."""
 
     def estimate(self, H=None, rot_qvec=None, timed=False, **options):
         """Run the kernels (pxr_homography) with homography_options(**options).  Returns the device arrays (H (n_pairs, 9),
@@ -1067,57 +1004,19 @@ class HomographyProblem:
         (n_matches,) float64).  H / rot_qvec: host arrays the outputs start from -- rows of pairs without a homography keep them
         (default: NaN).  timed: also keep the kernels' HIP-event times in self.kernel_ms {"records", "compact", "hypotheses",
         "refine"} (milliseconds)."""
-        ctx, d, T, N = self.ctx, self.d, self.n_pairs, self.n_matches
-        opts = homography_options(**options)
-        start = lambda a, w: np.full((T, w), np.nan) if a is None else np.asarray(a, dtype=np.float64).reshape(T, w)
-        d_H, d_q = (ctx.to_device(start(a, w), np.float64) for a, w in ((H, 9), (rot_qvec, 4)))
-        d_status, d_ninl, d_nrot, d_ntr = (ctx.empty((T,), np.int32) for _ in range(4))
-        d_inl, d_err = ctx.empty((N,), np.uint8), ctx.empty((N,), np.float64)
-        args = (ctx.handle, T, d["pair_offsets"].ptr, N, d["xy1"].ptr, d["xy2"].ptr, d["pair_camera"].ptr, self.n_cameras,
-                d["cam_model"].ptr, d["cam_params"].ptr, C.byref(opts), d_H.ptr, d_q.ptr, d_status.ptr, d_ninl.ptr, d_nrot.ptr,
-                d_ntr.ptr, d_inl.ptr, d_err.ptr)
-        if timed:
-            ms = (C.c_double * 4)()
-            check(ctx.lib.pxr_homography_timed(*args, ms), "pxr_homography_timed")
-            self.kernel_ms = dict(zip(("records", "compact", "hypotheses", "refine"), (float(x) for x in ms)))
-        else:
-            check(ctx.lib.pxr_homography(*args), "pxr_homography")
-        return d_H, d_q, d_status, d_ninl, d_nrot, d_ntr, d_inl, d_err
+        return self._estimate("pxr_homography", options, ((H, 9), (rot_qvec, 4)), 4, timed)
 
 
-def fundamental_options(max_error=4.0, min_inlier_ratio=0.25, min_num_inliers=15, confidence=0.999, min_num_trials=64,
-                        max_num_trials=10000, round_size=64, seed=0, refine_max_iterations=100, lo_rounds=4):
-    """pxr_fundamental_options: the fields and defaults of two_view_options, as the fundamental-matrix estimator's own struct."""
-    return _lib.FundamentalOptions(float(max_error), float(min_inlier_ratio), float(confidence), int(seed), int(min_num_inliers),
-                                   int(min_num_trials), int(max_num_trials), int(round_size), int(refine_max_iterations), int(lo_rounds))
-
-
-class FundamentalProblem(HomographyProblem):
-    """Device-resident flat arrays of a batch of image pairs (pxr_fundamental): the batch dict of HomographyProblem.  The cameras
-    are the ones the records are normalised with -- for an uncalibrated pair, conditioning transforms.  A TwoViewProblem in place
-    of the dict shares its device arrays: all three estimators on one upload.
-    """
+class FundamentalProblem(_PairProblem):
+    """The pair batch of pxr_fundamental: the batch dict of every pair problem.  The cameras are the ones the records are
+    normalised with -- for an uncalibrated pair, conditioning transforms."""
 
     def estimate(self, F=None, timed=False, **options):
         """Run the kernels (pxr_fundamental) with fundamental_options(**options).  Returns the device arrays (F (n_pairs, 9),
         status, n_inliers, n_trials (n_pairs,) int32, inlier (n_matches,) uint8, err (n_matches,) float64).  F: a host array the
         output starts from -- rows of pairs without a fundamental matrix keep it (default: NaN).  timed: also keep the kernels'
         HIP-event times in self.kernel_ms {"records", "compact", "hypotheses", "refine"} (milliseconds)."""
-        ctx, d, T, N = self.ctx, self.d, self.n_pairs, self.n_matches
-        opts = fundamental_options(**options)
-        d_F = ctx.to_device(np.full((T, 9), np.nan) if F is None else np.asarray(F, dtype=np.float64).reshape(T, 9), np.float64)
-        d_status, d_ninl, d_ntr = (ctx.empty((T,), np.int32) for _ in range(3))
-        d_inl, d_err = ctx.empty((N,), np.uint8), ctx.empty((N,), np.float64)
-        args = (ctx.handle, T, d["pair_offsets"].ptr, N, d["xy1"].ptr, d["xy2"].ptr, d["pair_camera"].ptr, self.n_cameras,
-                d["cam_model"].ptr, d["cam_params"].ptr, C.byref(opts), d_F.ptr, d_status.ptr, d_ninl.ptr, d_ntr.ptr, d_inl.ptr,
-                d_err.ptr)
-        if timed:
-            ms = (C.c_double * 4)()
-            check(ctx.lib.pxr_fundamental_timed(*args, ms), "pxr_fundamental_timed")
-            self.kernel_ms = dict(zip(("records", "compact", "hypotheses", "refine"), (float(x) for x in ms)))
-        else:
-            check(ctx.lib.pxr_fundamental(*args), "pxr_fundamental")
-        return d_F, d_status, d_ninl, d_ntr, d_inl, d_err
+        return self._estimate("pxr_fundamental", options, ((F, 9),), 3, timed)
 
 
 MATCH_CONFS = {            # hloc's match_features confs for its NearestNeighbor matcher
@@ -1146,7 +1045,7 @@ class MatchProblem:
             desc = descriptors if isinstance(descriptors, DeviceArray) else np.ascontiguousarray(descriptors, dtype=np.float32)
             if len(desc.shape) != 2:
                 raise ValueError("descriptors must be (n_total, D)")
-            offsets = np.ascontiguousarray(image_offsets, dtype=np.int64).reshape(-1)
+            offsets = _csr_offsets(image_offsets, "image_offsets", "n_images")
             self.dim = int(desc.shape[1])
             self.d_desc = desc if isinstance(desc, DeviceArray) else ctx.to_device(desc, np.float32)
         else:
@@ -1163,8 +1062,6 @@ class MatchProblem:
                 dst = C.c_void_p(self.d_desc.ptr.value + int(first) * row)
                 h = np.ascontiguousarray(d.download() if isinstance(d, DeviceArray) else d, dtype=np.float32)
                 check(ctx.lib.pxr_memcpy_h2d(ctx.handle, dst, h.ctypes.data, h.nbytes), "pxr_memcpy_h2d")
-        if len(offsets) < 1:
-            raise ValueError("image_offsets must hold n_images + 1 entries")
         self.image_offsets = offsets
         self.n_images = len(offsets) - 1
         self.n_total = int(self.d_desc.shape[0])
@@ -1193,12 +1090,7 @@ class MatchProblem:
                                                       ctx.empty((self.n_pairs,), np.int32))
         args = (ctx.handle, self.n_images, self.d_offsets.ptr, self.n_total, self.dim, self.d_desc.ptr, self.n_pairs, self.d_pairs.ptr,
                 self.d_pair_offsets.ptr, C.byref(opts), d_m.ptr, d_s.ptr, d_n.ptr)
-        if timed:
-            ms = (C.c_double * 3)()
-            check(ctx.lib.pxr_match_descriptors_timed(*args, ms), "pxr_match_descriptors_timed")
-            self.kernel_ms = dict(zip(("tiles", "columns", "mutual"), (float(x) for x in ms)))
-        else:
-            check(ctx.lib.pxr_match_descriptors(*args), "pxr_match_descriptors")
+        self.kernel_ms = _launch(ctx, "pxr_match_descriptors", args, ("tiles", "columns", "mutual"), timed) or self.kernel_ms
         return d_m, d_s, d_n
 
 
@@ -1235,9 +1127,7 @@ class MapperScene:
     def __init__(self, ctx, problem):
         self.ctx = ctx
         g = problem
-        self.track_offsets = np.ascontiguousarray(g["track_offsets"], dtype=np.int64).reshape(-1)
-        if len(self.track_offsets) < 1:
-            raise ValueError("track_offsets must hold n_tracks + 1 entries")
+        self.track_offsets = _csr_offsets(g["track_offsets"], "track_offsets", "n_tracks")
         self.n_tracks = len(self.track_offsets) - 1
         self.obs_image = np.ascontiguousarray(np.asarray(g["obs_image"]).reshape(-1), dtype=np.int32)
         self.n_obs = len(self.obs_image)
@@ -1303,11 +1193,6 @@ class MapperScene:
         args = (ctx.handle, C.byref(self.view), d["obs_track"].ptr, d["image_obs_offsets"].ptr, d["image_obs"].ptr, xyz.ptr, status.ptr,
                 d_mask.ptr, d["cam_size"].ptr, int(levels), out["n_visible"].ptr, out["score"].ptr, out["corr_offsets"].ptr,
                 out["corr_obs"].ptr, out["corr_xy"].ptr, out["corr_xyz"].ptr, C.byref(n_corr))
-        if timed:
-            ms = (C.c_double * 4)()
-            check(ctx.lib.pxr_mapper_visibility_timed(*args, ms), "pxr_mapper_visibility_timed")
-            self.kernel_ms = dict(zip(("check", "count", "scan", "write"), (float(x) for x in ms)))
-        else:
-            check(ctx.lib.pxr_mapper_visibility(*args), "pxr_mapper_visibility")
+        self.kernel_ms = _launch(ctx, "pxr_mapper_visibility", args, ("check", "count", "scan", "write"), timed) or self.kernel_ms
         out["n_corr"] = int(n_corr.value)
         return out

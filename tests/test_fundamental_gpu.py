@@ -202,13 +202,13 @@ def test_classifier_without_the_fundamental_matrix_is_unchanged(ctx):
     kps, cams, pairs, matches, scores, _ = _scene(batch)
     off = batch["pair_offsets"]
     launched = []
-    import pixsfm_amd.api.homography as mod
-    real = mod.FundamentalProblem
-    mod.FundamentalProblem = lambda *a, **k: launched.append(a) or real(*a, **k)
+    import pixsfm_amd.api.fundamental as mod               # its _estimate is the classifier's only way to pxr_fundamental
+    real = mod._estimate
+    mod._estimate = lambda *a, **k: launched.append(a) or real(*a, **k)
     try:
         outs = [TwoViewClassifier.create(conf, ctx=ctx).classify_pairs(kps, cams, pairs, matches, scores) for conf in ({}, {"fundamental": None})]
     finally:
-        mod.FundamentalProblem = real
+        mod._estimate = real
     assert not launched
     for m, s, geoms in outs:
         for p, g in enumerate(geoms):

@@ -132,3 +132,62 @@ def test_api_argument_errors():
         c.classify_pairs({}, {}, [("a", "b")], [])
     with pytest.raises(KeyError, match="'b'"):
         c.classify_pairs({"a": pts}, {"a": cam, "b": cam}, [("a", "b")], [np.zeros((0, 2), int)])
+
+
+def test_classifier_batch_assembly_and_selection(monkeypatch):
+    """classify_pairs without a GPU: the three seams (_estimate of api.two_view, api.homography and api.fundamental) are replaced
+    by fakes that record the batch they are handed and return chosen results.  3 pairs over 3 images with 0, 1 and 5 matches."""
+    from pixsfm_amd.api import TwoViewClassifier, TwoViewVerifier, fundamental, homography, two_view
+    from pixsfm_amd.api.reconstruction import Camera
+    rng = np.random.default_rng(12)
+    cam1, cam2 = Camera(1, 1, 1000, 960, [1200.0, 1180, 500, 480]), Camera(2, 2, 1000, 960, [1100.0, 500, 480, 0.01])
+    keypoints = {n: rng.uniform(0, 900, (7, 3)) for n in "abc"}                  # a third column (a scale, say) is not read
+    cameras = {"a": cam1, "b": cam2, "c": cam1}
+    pairs = [("a", "b"), ("b", "c"), ("a", "c")]
+    matches = [np.zeros((0, 2), np.uint64), np.array([[3, 6]], np.uint64), np.array([[0, 1], [1, 0], [2, 5], [6, 6], [4, 3]], np.uint64)]
+    scores = [np.zeros(0, np.float32), np.array([0.5], np.float32), np.linspace(0.1, 0.9, 5).astype(np.float32)]
+    nan = np.full((3, 9), np.nan)
+    mask_e, mask_f, mask_h = np.array([1, 1, 0, 1, 1, 1], np.uint8), np.array([1, 0, 1, 1, 1, 1], np.uint8), np.array([0, 1, 1, 0, 1, 1], np.uint8)
+    results = {       # pair 0: nothing succeeds; pair 1: F alone; pair 2: E with as many inliers as F, H fails
+        "E": dict(qvec=nan[:, :4], tvec=nan[:, :3], E=nan, status=np.array([1, 1, 0]), n_inliers=np.array([0, 0, 4]), n_trials=np.zeros(3, int),
+                  inlier=mask_e, err=np.zeros(6)),
+        "H": dict(H=nan, rot_qvec=nan[:, :4], status=np.array([1, 1, 1]), n_inliers=np.array([0, 0, 4]), n_rot_inliers=np.zeros(3, int),
+                  n_trials=np.zeros(3, int), inlier=mask_h, err=np.zeros(6)),
+        "F": dict(F=nan, status=np.array([1, 0, 0]), n_inliers=np.array([0, 1, 4]), n_trials=np.zeros(3, int), inlier=mask_f, err=np.zeros(6)),
+    }
+    seen = []
+    for model, module in (("E", two_view), ("H", homography), ("F", fundamental)):
+        monkeypatch.setattr(module, "_estimate", lambda ctx, batch, opts, model=model: seen.append((model, batch, dict(opts))) or results[model])
+
+    out_m, out_s, geoms = TwoViewClassifier.create({"fundamental": {}, "homography": {"seed": 3}}).classify_pairs(keypoints, cameras, pairs, matches, scores)
+    assert [s[0] for s in seen] == ["E", "H", "F"] and seen[1][2]["seed"] == 3 and seen[0][2]["seed"] == 0
+    expect = dict(pair_offsets=np.array([0, 0, 1, 6]), xy1=np.concatenate([keypoints["b"][[3], :2], keypoints["a"][[0, 1, 2, 6, 4], :2]]),
+                  xy2=np.concatenate([keypoints["c"][[6], :2], keypoints["c"][[1, 0, 5, 6, 3], :2]]),
+                  pair_camera=np.array([[0, 1], [1, 0], [0, 0]]), cam_model=np.array([1, 2]),
+                  cam_params=np.array([[1200.0, 1180, 500, 480] + [0.0] * 8, [1100.0, 500, 480, 0.01] + [0.0] * 8]))
+    for _, batch, _ in seen:
+        assert set(batch) == set(expect)
+        for k, v in expect.items():
+            assert np.array_equal(batch[k], v) and np.asarray(batch[k]).shape == v.shape, k
+    assert seen[0][1] is seen[1][1] and seen[0][1] is seen[2][1]                   # one batch, so one upload, for the three
+    # the class, and the matches and scores of the model that decided it
+    assert [g["config"] for g in geoms] == ["DEGENERATE", "UNCALIBRATED", "CALIBRATED"]
+    assert out_m[0].shape == (0, 2) and out_s[0].shape == (0,)
+    assert np.array_equal(out_m[1], matches[1]) and np.array_equal(out_s[1], scores[1])                       # F's mask: [1]
+    keep_e = mask_e[1:].astype(bool)
+    assert np.array_equal(out_m[2], matches[2][keep_e]) and np.array_equal(out_s[2], scores[2][keep_e]) and out_m[2].dtype == np.uint64
+    assert geoms[2]["success"] and geoms[2]["inliers"] == keep_e.tolist() and geoms[2]["num_inliers_F"] == 4 and geoms[1]["F"].shape == (3, 3)
+    # a class outside "keep" keeps no match; without scores there are none to return
+    out_m, out_s, geoms = TwoViewClassifier.create({"fundamental": {}, "keep": ("CALIBRATED",)}).classify_pairs(keypoints, cameras, pairs, matches, scores)
+    assert geoms[1]["config"] == "UNCALIBRATED" and out_m[1].shape == (0, 2) and out_s[1].shape == (0,) and len(out_m[2]) == 4
+    assert TwoViewClassifier.create({"fundamental": {}}).classify_pairs(keypoints, cameras, pairs, matches)[1] is None
+    # without "fundamental": two seams, and the model with more inliers decides (E on a tie)
+    del seen[:]
+    out_m, _, geoms = TwoViewClassifier.create().classify_pairs(keypoints, cameras, pairs, matches)
+    assert [s[0] for s in seen] == ["E", "H"] and geoms[2]["config"] == "CALIBRATED" and np.array_equal(out_m[2], matches[2][keep_e])
+    # TwoViewVerifier.verify_pairs builds the same batch from the same input
+    del seen[:]
+    TwoViewVerifier.create().verify_pairs(keypoints, cameras, pairs, matches, scores)
+    assert [s[0] for s in seen] == ["E"] and set(seen[0][1]) == set(expect)
+    for k, v in expect.items():
+        assert np.array_equal(seen[0][1][k], v), k

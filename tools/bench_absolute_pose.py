@@ -22,11 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pixel-perfect-sfm_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-
-def stats(values):
-    v = sorted(float(x) for x in values)
-    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1], "all": [round(x, 5) for x in values]}
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 def main():
@@ -40,20 +36,12 @@ def main():
     args = ap.parse_args()
 
     import abspose_cases as ac
+    from _bench_runs import stats, timed_runs
     from pixsfm_amd.engine import AbsolutePoseProblem, Context
     batch = ac.make_queries([args.correspondences] * args.queries, (2, 1, 4), seed=7, p_outlier=args.outliers)
     ctx = Context(0)
     prob = AbsolutePoseProblem(ctx, batch)
-    prob.estimate()                                                      # warm-up
-    ctx.sync()
-    kernels, wall = {}, []
-    for _ in range(args.repeats):
-        t0 = time.perf_counter()
-        out = prob.estimate(timed=True)
-        ctx.sync()
-        wall.append(1e3 * (time.perf_counter() - t0))
-        for name, ms in prob.kernel_ms.items():
-            kernels.setdefault(name, []).append(ms)
+    out, kernels, wall = timed_runs(ctx, prob.estimate, args.repeats)
     q, t, status, n_inl, n_trials, inl = (a.download() for a in out[:6])
     ok = status == 0
     d = np.array([ac.pose_distance(batch["gt_qvec"][i], batch["gt_tvec"][i], q[i], t[i]) for i in np.flatnonzero(ok)])

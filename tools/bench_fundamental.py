@@ -38,7 +38,8 @@ def main():
     import fundamental_cases as fc
     import homography_cases as hc
     import twoview_cases as tv
-    from bench_homography import summary, timed_runs
+    from _bench_runs import timed_runs
+    from bench_homography import summary
     from pixsfm_amd.engine import Context, FundamentalProblem, HomographyProblem, TwoViewProblem
     kinds = [("planar", "rotation", "general")[p % 3] for p in range(args.pairs)]
     # the batch of bench_homography.py: outliers uniform in the image, no minimum distance
@@ -47,9 +48,9 @@ def main():
     ctx = Context(0)
     prob_e = TwoViewProblem(ctx, batch)
     prob_h, prob_f = HomographyProblem(ctx, prob_e), FundamentalProblem(ctx, prob_e)
-    out_f, kern_f, wall_f = timed_runs(ctx, prob_f, args.repeats)
-    out_h, kern_h, wall_h = timed_runs(ctx, prob_h, args.repeats)
-    out_e, kern_e, wall_e = timed_runs(ctx, prob_e, args.repeats)
+    out_f, kern_f, wall_f = timed_runs(ctx, prob_f.estimate, args.repeats)
+    out_h, kern_h, wall_h = timed_runs(ctx, prob_h.estimate, args.repeats)
+    out_e, kern_e, wall_e = timed_runs(ctx, prob_e.estimate, args.repeats)
     res = {k: a.download() for k, a in zip(fc.NAMES, out_f)}
     res_h = {k: a.download() for k, a in zip(hc.NAMES, out_h)}
     res_e = {k: a.download() for k, a in zip(tv.NAMES, out_e)}

@@ -22,25 +22,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pixel-perfect-sfm_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def stats(values):
-    v = sorted(float(x) for x in values)
-    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1], "all": [round(x, 5) for x in values]}
-
-
-def timed_runs(ctx, prob, repeats):
-    prob.estimate()                                                      # warm-up
-    ctx.sync()
-    kernels, wall = {}, []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        out = prob.estimate(timed=True)
-        ctx.sync()
-        wall.append(1e3 * (time.perf_counter() - t0))
-        for name, ms in prob.kernel_ms.items():
-            kernels.setdefault(name, []).append(ms)
-    return out, kernels, wall
+from _bench_runs import stats, timed_runs  # noqa: E402
 
 
 def summary(n_pairs, kernels, wall, n_trials, status):
@@ -72,8 +57,8 @@ def main():
     ctx = Context(0)
     prob_e = TwoViewProblem(ctx, batch)
     prob_h = HomographyProblem(ctx, prob_e)
-    out_h, kern_h, wall_h = timed_runs(ctx, prob_h, args.repeats)
-    out_e, kern_e, wall_e = timed_runs(ctx, prob_e, args.repeats)
+    out_h, kern_h, wall_h = timed_runs(ctx, prob_h.estimate, args.repeats)
+    out_e, kern_e, wall_e = timed_runs(ctx, prob_e.estimate, args.repeats)
     res = {k: a.download() for k, a in zip(hc.NAMES, out_h)}
     res_e = {k: a.download() for k, a in zip(tv.NAMES, out_e)}
     ok = res["status"] == 0

@@ -18,13 +18,15 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in ("tests", "oracle", "pixel-perfect-sfm_amd"):
+for p in ("tools", "tests", "oracle", "pixel-perfect-sfm_amd"):
     sys.path.insert(0, os.path.join(ROOT, p))
 
 
+from _bench_runs import stats as _stats, timed_runs  # noqa: E402
+
+
 def stats(values):
-    v = sorted(float(x) for x in values)
-    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1]}
+    return _stats(values, keep_all=False)
 
 
 def make_scene(n_cams, n_tracks, track_len, sigma, p_outlier, seed):
@@ -63,16 +65,7 @@ def main():
     scene = make_scene(args.cams, args.tracks, args.track_len, 0.5, args.outliers, seed=7)
     ctx = Context(0)
     prob = TriangulationProblem(ctx, scene)
-    prob.triangulate()                                                   # warm-up
-    ctx.sync()
-    kernels, wall = {}, []
-    for _ in range(args.repeats):
-        t0 = time.perf_counter()
-        out = prob.triangulate(timed=True)
-        ctx.sync()
-        wall.append(1e3 * (time.perf_counter() - t0))
-        for name, ms in prob.kernel_ms.items():
-            kernels.setdefault(name, []).append(ms)
+    out, kernels, wall = timed_runs(ctx, prob.triangulate, args.repeats)
     xyz, status, n_inl = out[0].download(), out[1].download(), out[2].download()
     ok = status == 0
     gpu_ms = sum(stats(v)["median"] for v in kernels.values())

@@ -20,11 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pixel-perfect-sfm_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-
-def stats(values):
-    v = sorted(float(x) for x in values)
-    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1], "all": [round(x, 5) for x in values]}
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 def main():
@@ -38,21 +34,13 @@ def main():
     args = ap.parse_args()
 
     import twoview_cases as tv
+    from _bench_runs import stats, timed_runs
     from pixsfm_amd.engine import Context, TwoViewProblem
     # outliers uniform in the image, no minimum distance: the generator's distance test is a Python loop over the outliers
     batch = tv.make_pairs([args.matches] * args.pairs, (1, 2, 8), seed=7, p_outlier=args.outliers, min_outlier_sampson=None)
     ctx = Context(0)
     prob = TwoViewProblem(ctx, batch)
-    prob.estimate()                                                      # warm-up
-    ctx.sync()
-    kernels, wall = {}, []
-    for _ in range(args.repeats):
-        t0 = time.perf_counter()
-        out = prob.estimate(timed=True)
-        ctx.sync()
-        wall.append(1e3 * (time.perf_counter() - t0))
-        for name, ms in prob.kernel_ms.items():
-            kernels.setdefault(name, []).append(ms)
+    out, kernels, wall = timed_runs(ctx, prob.estimate, args.repeats)
     res = {k: a.download() for k, a in zip(tv.NAMES, out)}
     status, n_trials = res["status"], res["n_trials"]
     ok = status == 0
