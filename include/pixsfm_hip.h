@@ -141,6 +141,105 @@ int pxr_dsift_dense(pxr_ctx* ctx, const void* d_image, int image_dtype, int h, i
 int pxr_dsift_extract(pxr_ctx* ctx, pxr_arena* a, int64_t first, int64_t n, const void* d_image, int image_dtype, int h,
                       int w, int spatial_bin_size, int rootsift, double clipval, const double* d_keypoints, double image_w,
                       double image_h, int l2_normalize);
+/* ---- SIFT: keypoints and descriptors of one grey image (csrc/pxr_sift.hip) ----
+ * The sparse sibling of dsift: what hloc's `sift` configuration or a COLMAP SIFT database hands to the reference.  Restated from
+ * Lowe's paper and VLFeat's sift.c as remembered -- parity with VLFeat / COLMAP is unpinned.  This comment
+ * is the specification; tests/sift_cases.py transcribes it in numpy float64.  Coordinates are pixel indices (pixel centres at
+ * integers, x along columns, y along rows); angles run from x towards y.
+ *  Input      h x w row-major, PXR_U8 (the float32 quotient (float)u / 255.0f) or PXR_F32.  One image per call.
+ *  Octaves    octave first_octave starts from the image (0) or from its doubling (-1): u(2i) = I(i), u(2i+1) = (I(i) +
+ *             I(min(i+1, n-1))) / 2 along x, then along y, so coordinates scale by exactly 0.5.  Octave o+1 is (h_o+1)/2 x (w_o+1)/2:
+ *             its level 0 is level S of octave o at even indices.  Automatic count: octaves while min(h_o, w_o) >= 16, at most 8
+ *             (an image smaller than that has no octave and no feature); num_octaves > 0 takes the first num_octaves of them.
+ *  Levels     s = 0 .. S+2 with sigma(s) = sigma0 2^(s/S) in the octave's pixels.  Level 0 of the first octave blurs the (doubled)
+ *             input by sqrt(sigma0^2 - (sigma_in 2^-first_octave)^2); level s blurs level s-1 by sigma0 sqrt(2^(2s/S) - 2^(2(s-1)/S)).
+ *  Blur       by sigma: rows (along x), then columns; radius r = int(4 sigma + 0.5) <= 18 (else PXR_EINVAL); weights
+ *             exp(-x^2 / 2 sigma^2) divided by their sum (added in ascending x) in float64 on the host, rounded to float32; borders
+ *             replicated; the float32 sum acc = 0, acc = acc + w[k] v[k] for k = -r .. r in that order, product and sum each
+ *             rounded once.  (scipy.ndimage.gaussian_filter1d(truncate=4, mode="nearest") up to rounding.)
+ *  Pyramid    d_pyramid: plane (k, s) of octave index k = o - first_octave is h_k x w_k float32 at float offset
+ *             offsets[k] + s h_k w_k, offsets[k] = sum over k' < k of (S+3) h_k' w_k' (pxr_sift_pyramid_layout reports sizes and
+ *             offsets for 8 octaves, pxr_sift_pyramid_bytes the total).  Everything below reads it as float32 and computes in float64.
+ *  Detection  D(s) = G(s+1) - G(s), s = 0 .. S+1.  A candidate is a sample at s in 1 .. S, at least one pixel inside the border,
+ *             with |D| > 0.8 peak_threshold, strictly above or strictly below all 26 neighbours.  Refinement at (X, Y) = (xi, yi):
+ *             gradient and Hessian of D in (x, y, s) by central differences (mixed terms: a quarter of the four diagonal samples),
+ *             H d = -g by Gaussian elimination with partial pivoting (the first largest pivot; a zero pivot rejects).  While fewer
+ *             than max_refine_steps moves were made: X moves by +-1 if d_x > 0.6 / < -0.6 and stays in [1, w-2], Y likewise (s never
+ *             moves); if either moved, repeat at the new (X, Y).  Accept iff |d_x|, |d_y|, |d_s| < 1.5, 0 <= s + d_s <= S+1,
+ *             |D + g.d / 2| > peak_threshold, and the spatial Hessian has det > 0 and ((e+1)^2 / e) det - tr^2 > 0, e = edge_threshold.
+ *             Keypoint: x = (X + d_x) 2^o, y = (Y + d_y) 2^o, sigma = sigma0 2^(o + (s + d_s) / S), response |D + g.d / 2|, record
+ *             (o, s, xi, yi) = the extremum's own sample (before any move), which is unique and orders the output.
+ *             peak_threshold < 0 stands for 0.02 / S.
+ *  Orientation on level min(max(floor(s + d_s + 0.5), 0), S+2) of the keypoint's octave, in its pixels (xo, yo, sigma_oct):
+ *             sigma_w = 1.5 sigma_oct, R = floor(3 sigma_w); the integer samples (px, py) within R of (floor(xo+0.5), floor(yo+0.5))
+ *             in both axes that lie in [1, w-2] x [1, h-2] and have d^2 = (px-xo)^2 + (py-yo)^2 < R^2 + 0.5, rows first.  Gradient by
+ *             central differences / 2, angle a = atan2(gy, gx) in [0, 2 pi); a sample adds |g| exp(-d^2 / 2 sigma_w^2) at the bin
+ *             coordinate 36 a / 2 pi - 0.5, split linearly over the two nearest of 36 circular bins.  Six circular passes of
+ *             (a + b + c) / 3.  A peak is a bin above both neighbours and >= 0.8 of the maximum; theta = 2 pi (i + di + 0.5) / 36
+ *             with di = -(h+ - h-) / (2 (h+ + h- - 2 h0)).  At most max_num_orientations peaks by (height descending, bin
+ *             ascending), each a feature; features are ordered by (keypoint, rank).  upright: one feature, theta = 0.
+ *  Descriptor of (x, y, sigma, theta) alone: t = S log2(sigma / sigma0), octave o = floor((t - 0.5) / S) clamped to the pyramid's
+ *             octaves, level floor(t - o S + 0.5) (outside 0 .. S+2: not valid; a keypoint of pxr_sift_detect never is).  Bin width b = magnif sigma_oct, W = floor(sqrt(2) b 2.5 + 0.5);
+ *             samples as above within W (no circular cut).  (nx, ny) = the offset rotated by -theta, divided by b; a sample adds
+ *             |g| exp(-(nx^2 + ny^2) / 8) (a window of sigma = 2 bins) at the bin coordinates (ny + 1.5, nx + 1.5, 8 ((a - theta)
+ *             mod 2 pi) / 2 pi), trilinearly over 4 x 4 x 8 bins (the last circular; shares outside the 4 x 4 are dropped).  Then
+ *             L2-normalise, clamp at clip, L2 again; normalization 1 (L1_ROOT, "rootsift"): divide by the L1 norm, square root.
+ *             A zero histogram is not valid.  Output float32 (n, 128), unit L2 norm, channel = by * 32 + bx * 8 + bo: the layout
+ *             pxr_match_descriptors takes.  No uint8 quantisation.
+ *  All sums over samples run in sample order, whatever the lane: two runs give the same bits in every output. */
+typedef struct {
+  int32_t first_octave;          /* -1  (hloc's and COLMAP's default); {-1, 0}                              */
+  int32_t num_octaves;           /* 0   automatic                                                          */
+  int32_t octave_resolution;     /* 3   S in {2, 3, 4}                                                     */
+  int32_t max_refine_steps;      /* 5   0 .. 16                                                            */
+  int32_t max_num_orientations;  /* 2   1 .. 4                                                             */
+  int32_t upright;               /* 0                                                                      */
+  int32_t normalization;         /* 1   0 = L2, 1 = L1_ROOT                                                */
+  int32_t reserved;              /* 0                                                                      */
+  double sigma0;                 /* 1.6                                                                    */
+  double sigma_in;               /* 0.5                                                                    */
+  double peak_threshold;         /* -1  = 0.02 / S                                                         */
+  double edge_threshold;         /* 10                                                                     */
+  double magnif;                 /* 3                                                                      */
+  double clip;                   /* 0.2                                                                    */
+} pxr_sift_options;
+/* Writes the defaults above. */
+void pxr_sift_default_options(pxr_sift_options* options);
+/* Every entry point below returns PXR_EINVAL, with nothing launched and every output untouched, for: h or w < 1 (or > 16384), an
+ * option outside the range given above, sigma0 <= sigma_in 2^-first_octave, num_octaves above the automatic count, a blur radius
+ * above 18, a negative capacity or n, a NULL pointer that is needed. */
+/* The layout: *h_n_octaves, h_sizes [8][2] (h_k, w_k; 0 past the last octave), h_offsets [8] (in floats).  Host arrays. */
+int pxr_sift_pyramid_layout(int h, int w, const pxr_sift_options* options, int32_t* h_n_octaves, int32_t* h_sizes, int64_t* h_offsets);
+int pxr_sift_pyramid_bytes(int h, int w, const pxr_sift_options* options, int64_t* h_bytes);
+/* Fills d_pyramid (pxr_sift_pyramid_bytes of device memory) from the image on the device; asynchronous on the context's stream. */
+int pxr_sift_pyramid(pxr_ctx* ctx, const void* d_image, int image_dtype, int h, int w, const pxr_sift_options* options, float* d_pyramid);
+/* The same, and the HIP-event time of all its kernels in milliseconds: h_kernel_ms[1]. */
+int pxr_sift_pyramid_timed(pxr_ctx* ctx, const void* d_image, int image_dtype, int h, int w, const pxr_sift_options* options,
+                           float* d_pyramid, double* h_kernel_ms);
+/* Keypoints with orientations, in ascending (o, s, yi, xi), then rank of the orientation: d_keypoints double [capacity][4]
+ * (x, y, sigma, theta), d_record int32 [capacity][4] (o, s, xi, yi), d_response float32 [capacity].  Writes the first
+ * min(*h_n_found, capacity) features and never a byte past capacity; *h_n_found is always the number found.  With capacity = 0
+ * the three arrays may be NULL.  Synchronises the context's stream. */
+int pxr_sift_detect(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const pxr_sift_options* options, int64_t capacity,
+                    double* d_keypoints, int32_t* d_record, float* d_response, int64_t* h_n_found);
+/* The same, and h_kernel_ms[5] = count, scan, write, orient, emit. */
+int pxr_sift_detect_timed(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const pxr_sift_options* options, int64_t capacity,
+                          double* d_keypoints, int32_t* d_record, float* d_response, int64_t* h_n_found, double* h_kernel_ms);
+/* Rows d_index[i] (NULL: i) of the n_in rows pxr_sift_detect wrote, i < n, split into what the Python layer returns: d_keypoints_out
+ * double [n][4], d_xy double [n][2] = (x + offset, y + offset) (offset 0.5: COLMAP's convention, pixel centres at +0.5), d_scales
+ * double [n], d_orientations double [n], d_scores float32 [n] (needs d_response).  An output that is NULL is not written; a row
+ * whose index lies outside [0, n_in) is left untouched.  Asynchronous. */
+int pxr_sift_gather(pxr_ctx* ctx, int64_t n, int64_t n_in, const int64_t* d_index, const double* d_keypoints, const float* d_response,
+                    double offset, double* d_keypoints_out, double* d_xy, double* d_scales, double* d_orientations, float* d_scores);
+/* Descriptors of the given keypoints double [n][4] (x, y, sigma, theta) -- those of pxr_sift_detect, or keypoints that moved since:
+ * d_descriptors float32 [n][128], d_valid uint8 [n].  A keypoint that is not finite, has sigma <= 0, a scale outside the pyramid
+ * or an empty window gets zeros and valid = 0; it never faults and leaves its neighbours alone.  Asynchronous. */
+int pxr_sift_describe(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const pxr_sift_options* options, int64_t n,
+                      const double* d_keypoints, float* d_descriptors, uint8_t* d_valid);
+/* The same, and h_kernel_ms[1]. */
+int pxr_sift_describe_timed(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const pxr_sift_options* options, int64_t n,
+                            const double* d_keypoints, float* d_descriptors, uint8_t* d_valid, double* h_kernel_ms);
+
 void* pxr_arena_data(pxr_arena* a);     /* device pointer of patch 0 */
 int32_t* pxr_arena_corners(pxr_arena* a); /* device int32[n][2] */
 double* pxr_arena_scales(pxr_arena* a);   /* device double[n][2] */

@@ -122,6 +122,17 @@ class MatchOptions(C.Structure):
 
 MATCH_MAX_DIM = 512          # PXR_MATCH_MAX_DIM
 
+
+class SiftOptions(C.Structure):
+    """pxr_sift_options"""
+    _fields_ = [("first_octave", C.c_int32), ("num_octaves", C.c_int32), ("octave_resolution", C.c_int32),
+                ("max_refine_steps", C.c_int32), ("max_num_orientations", C.c_int32), ("upright", C.c_int32),
+                ("normalization", C.c_int32), ("reserved", C.c_int32), ("sigma0", C.c_double), ("sigma_in", C.c_double),
+                ("peak_threshold", C.c_double), ("edge_threshold", C.c_double), ("magnif", C.c_double), ("clip", C.c_double)]
+
+
+SIFT_MAX_OCTAVES = 8
+
 # every symbol include/pixsfm_hip.h declares (checked by tests/test_cabi_and_host.py)
 _SIGNATURES = {
     "pxr_version": (C.c_int, []),
@@ -146,6 +157,16 @@ _SIGNATURES = {
     "pxr_dsift_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "pxr_dsift_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "pxr_sift_default_options": (None, [C.POINTER(SiftOptions)]),
+    "pxr_sift_pyramid_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(SiftOptions), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "pxr_sift_pyramid_bytes": (C.c_int, [C.c_int, C.c_int, C.POINTER(SiftOptions), C.POINTER(C.c_int64)]),
+    "pxr_sift_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SiftOptions), C.c_void_p]),
+    "pxr_sift_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(SiftOptions), C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.POINTER(C.c_int64)]),
+    "pxr_sift_describe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(SiftOptions), C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "pxr_sift_gather": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "pxr_arena_data": (C.c_void_p, [C.c_void_p]),
     "pxr_arena_corners": (C.c_void_p, [C.c_void_p]),
     "pxr_arena_scales": (C.c_void_p, [C.c_void_p]),
@@ -235,7 +256,7 @@ _SIGNATURES = {
 }
 # every *_timed entry point: the arguments of its plain twin, then the array that takes the stages' HIP-event times
 for _name in ("pxr_triangulate_tracks", "pxr_absolute_pose", "pxr_two_view_geometry", "pxr_homography", "pxr_fundamental",
-              "pxr_match_descriptors", "pxr_mapper_visibility"):
+              "pxr_match_descriptors", "pxr_mapper_visibility", "pxr_sift_pyramid", "pxr_sift_detect", "pxr_sift_describe"):
     _SIGNATURES[_name + "_timed"] = (_SIGNATURES[_name][0], _SIGNATURES[_name][1] + [C.POINTER(C.c_double)])
 LINEAR_AUTO, LINEAR_DIRECT, LINEAR_ITERATIVE = 0, 1, 2
 COMM_ID_BYTES = 128

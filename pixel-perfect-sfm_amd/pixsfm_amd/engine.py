@@ -179,6 +179,11 @@ class DeviceArray:
         check(self.ctx.lib.pxr_memcpy_d2h(self.ctx.handle, out.ctypes.data, self.ptr, self.nbytes), "pxr_memcpy_d2h")
         return out
 
+    def __array__(self, dtype=None, copy=None):
+        """np.asarray(device array): a download."""
+        a = self.download()
+        return a if dtype is None else a.astype(dtype, copy=False)
+
     def free(self):
         if getattr(self, "ptr", None) and self.ctx.handle:
             self.ctx.lib.pxr_free(self.ctx.handle, self.ptr)
@@ -1196,3 +1201,110 @@ class MapperScene:
         self.kernel_ms = _launch(ctx, "pxr_mapper_visibility", args, ("check", "count", "scan", "write"), timed) or self.kernel_ms
         out["n_corr"] = int(n_corr.value)
         return out
+
+
+# ---- SIFT ------------------------------------------------------------------------------------------------------------------------
+def sift_options(**options):
+    """pxr_sift_options: the library's defaults (pxr_sift_default_options) with `options` over them.  peak_threshold < 0 (the
+    default) stands for 0.02 / octave_resolution.  An unknown name is a ValueError."""
+    o = _lib.SiftOptions()
+    _lib.load().pxr_sift_default_options(C.byref(o))
+    names = {k: t for k, t in _lib.SiftOptions._fields_ if k != "reserved"}
+    for k, v in options.items():
+        if k not in names:
+            raise ValueError("unknown SIFT option %r (known: %s)" % (k, ", ".join(sorted(names))))
+        setattr(o, k, float(v) if names[k] is C.c_double else int(v))
+    return o
+
+
+def _rows(array, n):
+    """The first n rows of a device array, as the same buffer under a smaller shape."""
+    array.shape = (int(n),) + tuple(array.shape[1:])
+    array.nbytes = int(np.prod(array.shape, dtype=np.int64)) * array.dtype.itemsize
+    return array
+
+
+class SiftPyramid:
+    """The Gaussian scale space of one grey image on the device (pxr_sift_pyramid), and the stages that read it.
+
+    grey: (h, w) uint8 (value / 255) or float32, host array or device tensor.  options: sift_options(**options).
+    kernel_ms collects the HIP-event times of the timed calls {"pyramid", "count", "scan", "write", "orient", "emit", "describe"}."""
+
+    def __init__(self, ctx, grey, timed=False, **options):
+        self.ctx = ctx
+        self.options = sift_options(**options)
+        img = _grey_on_device(ctx, grey)
+        self.h, self.w = img.h, img.w
+        n_oct, sizes, offsets = C.c_int32(), np.zeros((_lib.SIFT_MAX_OCTAVES, 2), np.int32), np.zeros(_lib.SIFT_MAX_OCTAVES, np.int64)
+        check(ctx.lib.pxr_sift_pyramid_layout(self.h, self.w, C.byref(self.options), C.byref(n_oct), sizes.ctypes.data,
+                                              offsets.ctypes.data), "pxr_sift_pyramid_layout")
+        nbytes = C.c_int64()
+        check(ctx.lib.pxr_sift_pyramid_bytes(self.h, self.w, C.byref(self.options), C.byref(nbytes)), "pxr_sift_pyramid_bytes")
+        self.n_octaves, self.sizes, self.offsets = int(n_oct.value), sizes[:n_oct.value], offsets[:n_oct.value]
+        self.levels = self.options.octave_resolution + 3
+        self.d_pyramid = ctx.empty((max(nbytes.value // 4, 1),), np.float32)
+        self.kernel_ms = {}
+        args = (ctx.handle, img.ptr, img.dtype, self.h, self.w, C.byref(self.options), self.d_pyramid.ptr)
+        self.kernel_ms.update(_launch(ctx, "pxr_sift_pyramid", args, ("pyramid",), timed) or {})
+        ctx.sync()                                      # (the image may be a temporary upload)
+
+    def level(self, k, s):
+        """Plane (octave index k, level s) as a host (h_k, w_k) float32 array."""
+        h, w = (int(v) for v in self.sizes[k])
+        flat = self.d_pyramid.download()
+        first = int(self.offsets[k]) + s * h * w
+        return flat[first:first + h * w].reshape(h, w)
+
+    def octaves(self):
+        """[octave: (S + 3, h_k, w_k) float32] on the host."""
+        flat = self.d_pyramid.download()
+        return [flat[int(o):int(o) + self.levels * int(h) * int(w)].reshape(self.levels, int(h), int(w))
+                for o, (h, w) in zip(self.offsets, self.sizes)]
+
+    def detect(self, capacity=None, timed=False, out=None):
+        """pxr_sift_detect.  Returns (keypoints (n, 4) float64 x, y, sigma, theta in pixel indices, record (n, 4) int32 o, s, xi,
+        yi, response (n,) float32) as device arrays of the rows written, and the number found.  capacity=None: a first guess, and
+        a second run when more were found; out: the three device arrays (capacity rows) to write into."""
+        ctx = self.ctx
+        guess = capacity is None
+        cap = max(4096, self.h * self.w // 32) if guess else int(capacity)
+        while True:
+            kp, rec, resp = out if out is not None else (ctx.empty((max(cap, 0), 4), np.float64), ctx.empty((max(cap, 0), 4), np.int32),
+                                                         ctx.empty((max(cap, 0),), np.float32))
+            found = C.c_int64(-1)
+            args = (ctx.handle, self.d_pyramid.ptr, self.h, self.w, C.byref(self.options), cap, kp.ptr, rec.ptr, resp.ptr, C.byref(found))
+            self.kernel_ms.update(_launch(ctx, "pxr_sift_detect", args, ("count", "scan", "write", "orient", "emit"), timed) or {})
+            if not guess or found.value <= cap or out is not None:
+                break
+            cap = int(found.value)
+        n = min(int(found.value), cap)
+        if out is None:
+            kp, rec, resp = _rows(kp, n), _rows(rec, n), _rows(resp, n)
+        return kp, rec, resp, int(found.value)
+
+    def gather(self, keypoints, response=None, index=None, offset=0.0):
+        """pxr_sift_gather: rows `index` (host int64 array; None: all) of detect()'s arrays as device arrays (keypoints (n, 4),
+        xy (n, 2) + offset, scales (n,), orientations (n,), scores (n,) or None)."""
+        ctx = self.ctx
+        n_in = int(keypoints.shape[0])
+        d_index = None if index is None else ctx.to_device(np.ascontiguousarray(index, dtype=np.int64).reshape(-1), np.int64)
+        n = n_in if index is None else int(d_index.shape[0])
+        kp, xy, sc, th = ctx.empty((n, 4), np.float64), ctx.empty((n, 2), np.float64), ctx.empty((n,), np.float64), ctx.empty((n,), np.float64)
+        scores = ctx.empty((n,), np.float32) if response is not None else None
+        check(ctx.lib.pxr_sift_gather(ctx.handle, n, n_in, d_index.ptr if d_index is not None else None, keypoints.ptr,
+                                      response.ptr if response is not None else None, float(offset), kp.ptr, xy.ptr, sc.ptr, th.ptr,
+                                      scores.ptr if scores is not None else None), "pxr_sift_gather")
+        ctx.sync()                                      # (d_index may go out of scope)
+        return kp, xy, sc, th, scores
+
+    def describe(self, keypoints, timed=False, out=None):
+        """pxr_sift_describe of (n, 4) x, y, sigma, theta (pixel indices; a device array is used in place).  Returns the device
+        arrays (descriptors (n, 128) float32, valid (n,) uint8)."""
+        ctx = self.ctx
+        kp = keypoints if isinstance(keypoints, DeviceArray) else ctx.to_device(np.asarray(keypoints, dtype=np.float64).reshape(-1, 4), np.float64)
+        n = int(kp.shape[0])
+        desc, valid = out if out is not None else (ctx.empty((n, 128), np.float32), ctx.empty((n,), np.uint8))
+        args = (ctx.handle, self.d_pyramid.ptr, self.h, self.w, C.byref(self.options), n, kp.ptr, desc.ptr, valid.ptr)
+        self.kernel_ms.update(_launch(ctx, "pxr_sift_describe", args, ("describe",), timed) or {})
+        ctx.sync()
+        return desc, valid
