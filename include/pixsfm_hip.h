@@ -871,6 +871,72 @@ int pxr_match_descriptors_timed(pxr_ctx* ctx, int32_t n_images, const int64_t* d
                                 const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches,
                                 double* h_kernel_ms);
 
+/* ---- image retrieval (local descriptors in, a VLAD global descriptor per image and the image pairs to match out) --------
+ * What picks the image pairs: hloc's pairs_from_retrieval over global descriptors (examples/sfm+loc_aachen.py; pixsfm/localize.py
+ * reads its output through parse_retrieval).  hloc's retrieval models need weights and stay out; this is the classical weight-free
+ * one: VLAD (Jegou et al. 2010) with intra-normalisation (Arandjelovic & Zisserman 2013) over a vocabulary learned by spherical
+ * k-means from the scene's own descriptors.  Parity with hloc and with COLMAP's vocabulary tree is unpinned; the specification
+ * below is this library's own and reproduces bit for bit (csrc/pxr_retrieval.hip).
+ *
+ * d_desc is (n_total, dim) float32 row-major, image m owning rows [d_image_offsets[m], d_image_offsets[m+1]), as for
+ * pxr_match_descriptors.  1 <= dim <= PXR_VLAD_MAX_DIM, 1 <= n_clusters K <= PXR_VLAD_MAX_CLUSTERS, K dim <=
+ * PXR_VLAD_MAX_GLOBAL_DIM, n_total < 2^30.  Descriptors are expected to be L2-normalised.  A row is VALID iff every entry is finite
+ * and |x| <= 1; an invalid row is assigned -1 and contributes to no sum.  All d_ arrays are device pointers.  Integer sums have no
+ * order; every floating-point chain has the one order stated; nothing is contracted.
+ *   1 similarity  sim(a, b) = the float32 value of  s = 0; for k ascending: s = fmaf(a[k], b[k], s)  (the chain of
+ *                 pxr_match_descriptors; k is padded with zeros, which changes no value).  A NaN never wins a comparison.
+ *   2 assignment  assign[i] = the c with the largest sim(x_i, C_c), ties to the lowest c; -1 for an invalid row or when every
+ *                 similarity is NaN.  Centroids C: (K, dim) float32.
+ *   3 sums        q(x) = llrint((double)x 2^32).  S[g][c][k] = sum of q(x_i[k]) over the valid rows i of group g with assign[i] = c,
+ *                 as int64; cnt[g][c] the number of such rows.  A group is the training set (training) or an image (aggregation).
+ *   4 vocabulary  (pxr_vocab_train) n_train = min(n_total, max_train); the training set is rows t_j = floor(j n_total / n_train),
+ *                 j < n_train.  Initial centroid c = training row floor(c n_train / K), copied.  n_iterations times: assign the
+ *                 training set (2), sum (3), then for every c with cnt[c] > 0: s_k = (double)S[c][k], n2 = sum_k s_k s_k in double
+ *                 in ascending k, and if n2 > 0: C[c][k] = (float)(s_k / sqrt(n2)).  A cluster that is empty or has n2 = 0 keeps
+ *                 its centroid.  Outputs: d_centroids (K, dim), d_counts (K) the cnt of the last iteration, *h_n_empty the number of
+ *                 zeros among them (n_iterations = 0: the initial centroids, all counts 0, *h_n_empty = K).  No random state: a
+ *                 function of the input alone.  Evenly spread initial rows can be duplicates; the later duplicate loses every tie
+ *                 and stays empty.  Requires K <= n_train.
+ *   5 VLAD        (pxr_vlad_aggregate) per image m and centroid c: v_k = (double)S[m][c][k] 2^-32 - (double)cnt[m][c] (double)C[c][k];
+ *                 b2 = sum_k v_k v_k in double, ascending k.  A block with cnt = 0 or b2 = 0 is all zeros; nne[m] is the number of
+ *                 other blocks; G[m][c dim + k] = (float)(v_k / (sqrt(b2) sqrt((double)nne[m]))): every non-empty block has norm
+ *                 1 / sqrt(nne), the row has norm 1.  Outputs: d_global (n_images, K dim) float32; d_assign (n_total) int32 or NULL;
+ *                 d_counts (n_images, K) int32 or NULL.  An image without valid descriptors gives a zero row.
+ *   6 selection   (pxr_retrieval_topk) d_query (n_query, dim), d_db (n_db, dim) float32, 1 <= dim <= PXR_VLAD_MAX_GLOBAL_DIM;
+ *                 d_query_self int32[n_query] or NULL: the database index that is the query itself, -1 for none; d_mask
+ *                 uint8[n_query][n_db] or NULL, 0 = excluded; min_score applies iff it is finite.  Entry (i, j) is a CANDIDATE iff it
+ *                 is not masked, j != self, sim is not NaN, and sim >= (float)min_score when that applies.  Row i of the outputs:
+ *                 its candidates by (sim descending, j ascending), cut at num_matched: d_top_index int32[n_query][num_matched]
+ *                 padded with -1, d_top_sim float32 padded with 0, d_n_found int32[n_query].  The n_query x n_db similarity matrix
+ *                 is kept in the context's workspace.
+ * PXR_EINVAL (nothing launched, outputs untouched): image offsets not starting at 0, not monotone or not ending at n_total; dim,
+ * n_clusters, their product or n_total out of range; n_iterations < 0; max_train < 1; n_clusters > n_train; num_matched < 1; a NaN
+ * min_score.  pxr_vocab_train and pxr_vlad_aggregate synchronise the context's stream (the offsets are validated on a host copy, the
+ * counts are read back); pxr_retrieval_topk only queues its kernels. */
+#define PXR_VLAD_MAX_DIM 512
+#define PXR_VLAD_MAX_CLUSTERS 256
+#define PXR_VLAD_MAX_GLOBAL_DIM 32768
+int pxr_vocab_train(pxr_ctx* ctx, int64_t n_total, int32_t dim, const float* d_desc, int32_t n_clusters, int32_t n_iterations,
+                    int64_t max_train, float* d_centroids, int32_t* d_counts, int32_t* h_n_empty);
+/* The same, and the HIP-event times of its kernels in milliseconds, summed over the iterations: h_kernel_ms[4] = gather (with the
+ * initial centroids), assign, accumulate, update. */
+int pxr_vocab_train_timed(pxr_ctx* ctx, int64_t n_total, int32_t dim, const float* d_desc, int32_t n_clusters, int32_t n_iterations,
+                          int64_t max_train, float* d_centroids, int32_t* d_counts, int32_t* h_n_empty, double* h_kernel_ms);
+int pxr_vlad_aggregate(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                       const float* d_desc, int32_t n_clusters, const float* d_centroids, float* d_global, int32_t* d_assign,
+                       int32_t* d_counts);
+/* h_kernel_ms[3] = assign, accumulate, finalise. */
+int pxr_vlad_aggregate_timed(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                             const float* d_desc, int32_t n_clusters, const float* d_centroids, float* d_global, int32_t* d_assign,
+                             int32_t* d_counts, double* h_kernel_ms);
+int pxr_retrieval_topk(pxr_ctx* ctx, int32_t n_query, int32_t n_db, int32_t dim, const float* d_query, const float* d_db,
+                       const int32_t* d_query_self, const uint8_t* d_mask, int32_t num_matched, double min_score,
+                       int32_t* d_top_index, float* d_top_sim, int32_t* d_n_found);
+/* h_kernel_ms[2] = similarity, select. */
+int pxr_retrieval_topk_timed(pxr_ctx* ctx, int32_t n_query, int32_t n_db, int32_t dim, const float* d_query, const float* d_db,
+                             const int32_t* d_query_self, const uint8_t* d_mask, int32_t num_matched, double min_score,
+                             int32_t* d_top_index, float* d_top_sim, int32_t* d_n_found, double* h_kernel_ms);
+
 /* ---- incremental mapping: visibility (triangulated tracks in, per-image scores and 2D-3D pairs out) ----
  * The stage of the reference's main entry point that produces poses: PixSfM.reconstruction (pixsfm/refine_hloc.py:133-146)
  * hands it to hloc.reconstruction.main, i.e. COLMAP's incremental mapper.  The arithmetic of a mapper is the stages above

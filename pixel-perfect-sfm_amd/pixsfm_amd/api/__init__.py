@@ -27,3 +27,6 @@ from . import mapping  # noqa: F401,E402
 from .mapping import IncrementalMapper  # noqa: F401,E402
 from . import sift  # noqa: F401,E402
 from .sift import SiftExtractor  # noqa: F401,E402
+from . import retrieval  # noqa: F401,E402
+from .retrieval import (GlobalDescriptorExtractor, pairs_from_exhaustive, pairs_from_retrieval,  # noqa: F401,E402
+                        unique_pairs)

@@ -1036,15 +1036,15 @@ def match_options(ratio_threshold=0.0, distance_threshold=0.0, do_mutual_check=T
     return _lib.MatchOptions(float(ratio_threshold or 0.0), float(distance_threshold or 0.0), int(bool(do_mutual_check)), 0)
 
 
-class MatchProblem:
-    """Device-resident descriptors of a set of images and a list of image pairs (pxr_match_descriptors).
+class DescriptorSet:
+    """Device-resident descriptors of a set of images, as pxr_match_descriptors and pxr_vlad_aggregate take them: d_desc (n_total, D)
+    float32, image_offsets (n_images + 1) on the host and d_offsets on the device.
 
     descriptors: a list of (n, D) float32 host arrays or DeviceArrays (one per image; n may be 0), or one (n_total, D) array
     with image_offsets (n_images + 1), which is used in place when it is a DeviceArray (a DeviceArray inside a list is staged
-    through the host).  pairs: (n_pairs, 2) image indices.  Every image is uploaded once, however many pairs name it.
-    """
+    through the host).  Every image is uploaded once."""
 
-    def __init__(self, ctx, descriptors, pairs, image_offsets=None):
+    def __init__(self, ctx, descriptors, image_offsets=None):
         self.ctx = ctx
         if image_offsets is not None:
             desc = descriptors if isinstance(descriptors, DeviceArray) else np.ascontiguousarray(descriptors, dtype=np.float32)
@@ -1070,6 +1070,23 @@ class MatchProblem:
         self.image_offsets = offsets
         self.n_images = len(offsets) - 1
         self.n_total = int(self.d_desc.shape[0])
+        self.d_offsets = ctx.to_device(offsets, np.int64)
+
+
+class MatchProblem:
+    """Device-resident descriptors of a set of images and a list of image pairs (pxr_match_descriptors).
+
+    descriptors: a list of (n, D) float32 host arrays or DeviceArrays (one per image; n may be 0), or one (n_total, D) array
+    with image_offsets (n_images + 1), which is used in place when it is a DeviceArray (a DeviceArray inside a list is staged
+    through the host).  pairs: (n_pairs, 2) image indices.  Every image is uploaded once, however many pairs name it.
+    """
+
+    def __init__(self, ctx, descriptors, pairs, image_offsets=None):
+        self.ctx = ctx
+        d = descriptors if isinstance(descriptors, DescriptorSet) else DescriptorSet(ctx, descriptors, image_offsets)
+        self.dim, self.d_desc, self.image_offsets, self.n_images, self.n_total, self.d_offsets = (d.dim, d.d_desc, d.image_offsets, d.n_images,
+                                                                                                   d.n_total, d.d_offsets)
+        offsets = self.image_offsets
         self.pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         self.n_pairs = len(self.pairs)
         counts = np.diff(offsets)
@@ -1078,7 +1095,6 @@ class MatchProblem:
         rows = np.zeros(self.n_pairs, dtype=np.int64)
         rows[in_range] = counts[first[in_range]]
         self.pair_offsets = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-        self.d_offsets = ctx.to_device(offsets, np.int64)
         self.d_pairs = ctx.to_device(self.pairs, np.int32)
         self.d_pair_offsets = ctx.to_device(self.pair_offsets, np.int64)
         self.kernel_ms = None
@@ -1308,3 +1324,84 @@ class SiftPyramid:
         self.kernel_ms.update(_launch(ctx, "pxr_sift_describe", args, ("describe",), timed) or {})
         ctx.sync()
         return desc, valid
+
+
+def _device_descriptors(ctx, descriptors, image_offsets=None):
+    """A DescriptorSet of a list of (n, D) arrays, one per image, or of one (n_total, D) array with image_offsets (None: one image)."""
+    flat = isinstance(descriptors, (DeviceArray, np.ndarray))
+    if flat and image_offsets is None:
+        image_offsets = [0, int(descriptors.shape[0])]
+    return DescriptorSet(ctx, descriptors, image_offsets)
+
+
+class VladVocabulary:
+    """The centroids of a VLAD vocabulary on the device (pxr_vocab_train, pxr_vlad_aggregate).
+
+    centroids: (K, D) float32, a host array or a DeviceArray (used in place).  After train(): counts (K,) int32, the rows of the
+    training set per centroid in the last iteration, and n_empty, the zeros among them."""
+
+    def __init__(self, ctx, centroids):
+        self.ctx = ctx
+        self.d_centroids = centroids if isinstance(centroids, DeviceArray) else ctx.to_device(np.asarray(centroids), np.float32)
+        if len(self.d_centroids.shape) != 2 or self.d_centroids.dtype != np.float32:
+            raise ValueError("centroids must be (K, D) float32")
+        self.n_clusters, self.dim = (int(s) for s in self.d_centroids.shape)
+        self.counts = self.n_empty = self.kernel_ms = None
+
+    @classmethod
+    def train(cls, ctx, descriptors, n_clusters=64, n_iterations=10, max_train=262144, timed=False):
+        """Spherical k-means over the descriptors (a list of (n, D) arrays or one (n_total, D) array): a function of the input
+        alone, no random state.  timed: kernel_ms {"gather", "assign", "accumulate", "update"}, summed over the iterations."""
+        d = _device_descriptors(ctx, descriptors)
+        K = int(n_clusters)
+        d_c, d_cnt = ctx.empty((max(K, 0), d.dim), np.float32), ctx.empty((max(K, 0),), np.int32)
+        n_empty = C.c_int32(-1)
+        args = (ctx.handle, d.n_total, d.dim, d.d_desc.ptr, K, int(n_iterations), int(max_train), d_c.ptr, d_cnt.ptr, C.byref(n_empty))
+        ms = _launch(ctx, "pxr_vocab_train", args, ("gather", "assign", "accumulate", "update"), timed)
+        voc = cls(ctx, d_c)
+        voc.counts, voc.n_empty, voc.kernel_ms = d_cnt.download(), int(n_empty.value), ms
+        return voc
+
+    @property
+    def centroids(self):
+        return self.d_centroids.download()
+
+    def aggregate(self, descriptors_by_image, image_offsets=None, timed=False, details=False):
+        """The VLAD global descriptors of a list of (n, D) arrays (or of one (n_total, D) array with image_offsets): a device
+        array (n_images, K * D) float32.  details: also the device arrays assign (n_total,) int32 and counts (n_images, K) int32.
+        timed: kernel_ms {"assign", "accumulate", "finalise"}."""
+        ctx = self.ctx
+        d = _device_descriptors(ctx, descriptors_by_image, image_offsets)
+        if d.n_total and d.dim != self.dim:
+            raise ValueError("descriptors of dimension %d for a vocabulary of dimension %d" % (d.dim, self.dim))
+        g = ctx.empty((d.n_images, self.n_clusters * self.dim), np.float32)
+        d_a = ctx.empty((d.n_total,), np.int32) if details else None
+        d_n = ctx.empty((d.n_images, self.n_clusters), np.int32) if details else None
+        args = (ctx.handle, d.n_images, d.d_offsets.ptr, d.n_total, self.dim, d.d_desc.ptr, self.n_clusters, self.d_centroids.ptr, g.ptr,
+                d_a.ptr if details else None, d_n.ptr if details else None)
+        self.kernel_ms = _launch(ctx, "pxr_vlad_aggregate", args, ("assign", "accumulate", "finalise"), timed) or self.kernel_ms
+        ctx.sync()                                      # (the uploaded descriptors may go out of scope)
+        return (g, d_a, d_n) if details else g
+
+
+def retrieval_topk(ctx, query, db, num_matched, query_self=None, mask=None, min_score=None, timed=False):
+    """pxr_retrieval_topk: per row of query (n_query, Dg) its num_matched most similar rows of db (n_db, Dg), by (similarity
+    descending, index ascending).  query / db: float32 host arrays or DeviceArrays (one object for both: uploaded once).
+    query_self (n_query,) int32: the db row that is the query itself (-1: none), never returned; mask (n_query, n_db): 0 = excluded;
+    min_score: the smallest similarity kept.  Returns the device arrays (top_index (n_query, num_matched) int32 padded with -1,
+    top_sim float32 padded with 0, n_found (n_query,) int32), and with timed also {"similarity", "select"} in milliseconds."""
+    d_q = query if isinstance(query, DeviceArray) else ctx.to_device(np.asarray(query), np.float32)
+    d_db = d_q if db is query else (db if isinstance(db, DeviceArray) else ctx.to_device(np.asarray(db), np.float32))
+    if len(d_q.shape) != 2 or len(d_db.shape) != 2 or d_q.shape[1] != d_db.shape[1]:
+        raise ValueError("query and db must be (n, Dg) arrays of one Dg")
+    nq, ndb, k = int(d_q.shape[0]), int(d_db.shape[0]), int(num_matched)
+    d_self = None if query_self is None else ctx.to_device(np.asarray(query_self).reshape(-1), np.int32)
+    d_mask = None if mask is None else ctx.to_device(np.asarray(mask).astype(bool).reshape(-1), np.uint8)
+    if (d_self is not None and d_self.shape[0] != nq) or (d_mask is not None and d_mask.shape[0] != nq * ndb):
+        raise ValueError("query_self must be (n_query,) and mask (n_query, n_db)")
+    top, sim, found = ctx.empty((nq, max(k, 0)), np.int32), ctx.empty((nq, max(k, 0)), np.float32), ctx.empty((nq,), np.int32)
+    args = (ctx.handle, nq, ndb, int(d_q.shape[1]), d_q.ptr, d_db.ptr, d_self.ptr if d_self is not None else None,
+            d_mask.ptr if d_mask is not None else None, k, float("inf") if min_score is None else float(min_score), top.ptr, sim.ptr, found.ptr)
+    ms = _launch(ctx, "pxr_retrieval_topk", args, ("similarity", "select"), timed)
+    ctx.sync()                                          # (the uploaded arrays may go out of scope)
+    return (top, sim, found, ms) if timed else (top, sim, found)
