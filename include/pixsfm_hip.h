@@ -488,6 +488,44 @@ int pxr_ba_solve_geometric(pxr_ctx* ctx, const pxr_ba_view* view, const double* 
                            const pxr_lm_options* options, pxr_allreduce_fn allreduce, void* allreduce_user,
                            pxr_lm_summary* summary);
 
+/* ---- covariance of a bundle adjustment (pose, intrinsics and point uncertainty) ------------------
+ * What ceres::Covariance / COLMAP's EstimateBACovariance give: blocks of inv(H), H = J~^T J~ the Gauss-Newton matrix the LM loop
+ * linearises at the parameters in `view` -- the same corrector, the same tangent columns in the same order (per image 3
+ * rotation columns, then the variable tvec components; then per camera the variable intrinsics), no LM diagonal.
+ *   Sigma_c = inv(S),  S = U - W inv(V) W^T the reduced camera matrix;
+ *   Sigma_p = inv(V_p) + Y_p Sigma_c[cols(p), cols(p)] Y_p^T,  Y_p = inv(V_p) W_p^T, for a variable point p.
+ * d_rec [n_obs][8]: the records of an evaluation at these parameters -- pxr_ba_eval (with Jacobians, on feature or cost-map
+ * patches) or pxr_ba_geom_eval: the entry takes records, not a residual type; the caller evaluates first.  Nothing in `view` is
+ * written.  The parameterisation arrays are those of pxr_ba_solve.
+ * ROTATION UNITS: the rotation tangent is the solver's own, delta of QuaternionManifold::Plus, q <- (cos|d|, sin|d| d/|d|) * q:
+ * the HALF-angle vector.  A rotation covariance in radians is 4 x the rotation block (2 x the rotation-translation block).
+ * Outputs (device pointers, each may be NULL):
+ *   d_cov_cameras    [n_c][n_c], n_c = summary->num_camera_unknowns, the dense Sigma_c in column order (not touched when n_c = 0)
+ *   d_cov_pose       [n_images][6][6] in the order (rotation tangent, tx, ty, tz); rows and columns of constant components
+ *                    (a constant pose, a tvec component under the mask) are zero
+ *   d_cov_intrinsics [n_cameras][PXR_KPAD][PXR_KPAD], rows and columns of constant parameters zero
+ *   d_cov_points     [n_points][3][3]; zero for a constant point and for a point without observation; NaN for a SINGULAR point:
+ *                    one whose 3 x 3 block V_p meets, in its Cholesky factorisation, a pivot not above 64 u times its diagonal
+ *                    entry (u = 2^-53; a point seen from one image).  Such points are counted and left out of S, as constant.
+ * summary->info: 0, or the 1-based column at which S is rank deficient -- a gauge that is not fixed: the first pivot of the
+ * Cholesky factorisation of the power-of-two scaled S that is not positive, or not above 64 n_c u times its diagonal entry.
+ * The call then returns 0 and the outputs are unspecified.
+ * Sums are those of the solver (fixed point in the deterministic mode); the new kernels use no atomics on floating-point
+ * numbers: two calls give the same bits.  Not available on a context with several ranks (PXR_EINVAL). */
+typedef struct {
+  int32_t num_camera_unknowns;
+  int32_t info;                    /* pivot index of a rank-deficient S, else 0 */
+  int64_t num_singular_points;     /* variable points whose 3x3 block V is not positive definite */
+  double ms_linearise, ms_factor_inverse, ms_points;
+} pxr_cov_summary;
+
+int pxr_ba_covariance(pxr_ctx* ctx, const pxr_ba_view* view, const double* d_rec /* [n_obs][8] */, const pxr_loss* loss,
+                      const uint8_t* h_pose_const, const uint8_t* h_tvec_const_mask, const uint16_t* h_cam_const_mask,
+                      const uint8_t* h_point_const,
+                      double* d_cov_cameras /* [n_c][n_c] or NULL */, double* d_cov_pose /* [n_images][6][6] or NULL */,
+                      double* d_cov_intrinsics /* [n_cameras][PXR_KPAD][PXR_KPAD] or NULL */,
+                      double* d_cov_points /* [n_points][3][3] or NULL */, pxr_cov_summary* summary);
+
 /* ---- track triangulation (known poses in, points and tracks out) ------------------------------
  * The middle stage of the reference's pipeline between keypoint adjustment and bundle adjustment, which PixSfM.triangulation
  * hands to COLMAP: pycolmap.triangulate_points as called by hloc.triangulation.main from pixsfm/refine_hloc.py:112-114.
@@ -1178,6 +1216,15 @@ int pxr_ka_build_edges(int64_t n_nodes, const int32_t* node_image, const int32_t
  * by the factor); d_b: right-hand side -> solution.  *h_info = 0 or the 1-based index of the
  * first non-positive pivot. */
 int pxr_dense_spd_solve(pxr_ctx* ctx, double* d_a, int n, double* d_b, int* h_info);
+
+/* Dense SPD inverse (the covariance of a reduced camera system, what ceres::Covariance's dense path
+ * computes): the Cholesky factorisation of pxr_dense_spd_solve, then T = inv(L) by block columns and
+ * inv(A) = T^T T in 64 x 64 fp64 MFMA tiles; no atomics, the same bits every run.
+ * d_a: n x n row-major, UPPER triangle filled (the strictly lower part is ignored).  On return the FULL
+ * symmetric inverse (symmetric bit for bit).
+ * *h_info: 0, or the 1-based index of the first non-positive pivot.  In that case d_a is unspecified and
+ * the return value is 0.  n may not exceed 18 * PXR_MAX_IMAGES_DIRECT (PXR_EINVAL). */
+int pxr_dense_spd_inverse(pxr_ctx* ctx, double* d_a, int n, int* h_info);
 
 #ifdef __cplusplus
 }

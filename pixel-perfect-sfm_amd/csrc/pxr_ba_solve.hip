@@ -37,6 +37,7 @@
 #include <thread>
 #include <vector>
 
+#include "pxr_ba_cov.h"
 #include "pxr_ba_driver.h"
 #include "pxr_ba_pcg.h"
 
@@ -336,6 +337,45 @@ __global__ __launch_bounds__(256) void k_pinv(int64_t n_points, const int* __res
   To[0] = c00 * id; To[1] = c01 * id; To[2] = c02 * id;
   To[3] = (a00 * a22 - a02 * a02) * id; To[4] = (a01 * a02 - a00 * a12) * id;
   To[5] = (a00 * a11 - a01 * a01) * id;
+}
+
+// ---- K_pinv_checked: T_p = V_p^-1 for the covariance (pxr_ba_cov.hip), by a 3 x 3 Cholesky that can say no -------------------------
+// A pivot that is not above 64 u times its diagonal entry is not distinguishable from zero in a V_p summed in floating point: the
+// point is SINGULAR (a point seen from one image, a track without parallax) -- flag 1, T_p = 0, so that the Schur kernels leave
+// it out of S as they leave a constant point out.  No damping, no determinant formula: the inverse comes from the factor.
+__global__ __launch_bounds__(256) void k_pinv_checked(int64_t n_points, const int* __restrict__ pt_var, const double* __restrict__ V,
+                                                      double* __restrict__ T, int* __restrict__ singular, unsigned long long* __restrict__ n_singular) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_points) return;
+  double* To = T + 6 * p;
+  singular[p] = 0;
+  if (!pt_var[p]) { for (int j = 0; j < 6; ++j) To[j] = 0.0; return; }
+  const double tiny = 64.0 * 1.1102230246251565e-16;
+  const double a00 = V[6 * p], a01 = V[6 * p + 1], a02 = V[6 * p + 2], a11 = V[6 * p + 3], a12 = V[6 * p + 4], a22 = V[6 * p + 5];
+  bool ok = a00 > 0.0 && isfinite(a00);
+  const double l00 = sqrt(ok ? a00 : 1.0);
+  const double l10 = a01 / l00, l20 = a02 / l00;
+  const double d1 = a11 - l10 * l10;
+  ok = ok && d1 > tiny * a11;
+  const double l11 = sqrt(ok ? d1 : 1.0);
+  const double l21 = (a12 - l20 * l10) / l11;
+  const double d2 = a22 - l20 * l20 - l21 * l21;
+  ok = ok && d2 > tiny * a22;
+  if (!ok) {
+    for (int j = 0; j < 6; ++j) To[j] = 0.0;
+    singular[p] = 1;
+    atomicAdd(n_singular, 1ull);                   // (a count: exact in any order)
+    return;
+  }
+  const double l22 = sqrt(d2);
+  // M = inv(L) (lower), T = M^T M
+  const double m00 = 1.0 / l00, m11 = 1.0 / l11, m22 = 1.0 / l22;
+  const double m10 = -l10 * m00 * m11;
+  const double m21 = -l21 * m11 * m22;
+  const double m20 = -(l20 * m00 + l21 * m10) * m22;
+  To[0] = m00 * m00 + m10 * m10 + m20 * m20; To[1] = m10 * m11 + m20 * m21; To[2] = m20 * m22;
+  To[3] = m11 * m11 + m21 * m21; To[4] = m21 * m22;
+  To[5] = m22 * m22;
 }
 
 // the accepted candidate becomes the current point: four arrays, ONE launch (four hipMemcpyAsync cost four dispatches)
@@ -1220,6 +1260,7 @@ struct LmSolve {
   int move_columns();
   bool cols_pow2 = false;
   int gradient_below_tolerance(bool* below);
+  int reduced_system_direct(double inv_radius);
   int reduced_step_direct(double inv_radius);
   int reduced_step_iterative(double inv_radius, bool* ok, double* inexact_correction);
   int candidate(double inv_radius, double inexact_correction, Candidate* c);
@@ -1229,6 +1270,9 @@ struct LmSolve {
   int finish(int termination);                              // leaves final_radius alone
   int finish(int termination, double final_radius);
   void phase(int k);
+  // the covariance (pxr_ba_cov.hip): the caller brings the records -- nothing is evaluated, no parameter is touched
+  bool records_only = false;
+  int covariance_system(const double* rec, int* singular, unsigned long long* n_singular, CovSystem* out);
 };
 
 // the collective: the caller's callback if given, else the context's RCCL communicator (pxr_comm_init)
@@ -1476,7 +1520,7 @@ int LmSolve::setup() {
 
   cur_q = const_cast<double*>(view->d_qvec); cur_t = const_cast<double*>(view->d_tvec);
   cur_k = const_cast<double*>(view->d_cam_params); cur_X = const_cast<double*>(view->d_xyz);
-  hipLaunchKernelGGL(k_normalize_q, dim3(nblk(n_img)), dim3(256), 0, st, n_img, cur_q);
+  if (!records_only) hipLaunchKernelGGL(k_normalize_q, dim3(nblk(n_img)), dim3(256), 0, st, n_img, cur_q);
 
   dv.v = *view;
   dv.pose_off = sx.d_pose_off.p; dv.pose_dim = sx.d_pose_dim.p; dv.tmask = sx.d_tmask.p;
@@ -1490,12 +1534,12 @@ int LmSolve::setup() {
   //  needs no care: with reference descriptors the functor ignores the bounds check, feature_reference.h:128-136.)
   // (InterpolationConfig.use_float_simd asks for the reference's ALL-fp32 splines: the Gram-matrix paths -- exact fp64 algebra -- would
   // silently compute something finer; a solve with that flag keeps the texel kernels, which have the fp32 arithmetic bit for bit)
-  gram_cache = !m.geom && ctx->gram_cache && gram_eval_supported(arena, view) && cfg->use_float_simd == 0;
+  gram_cache = !records_only && !m.geom && ctx->gram_cache && gram_eval_supported(arena, view) && cfg->use_float_simd == 0;
   // The Gram-matrix kernel of the inner iterations keeps its matrices in the same cache from call to call (it writes back what
   // it builds), whether or not the LM loop evaluates from them: the same numbers as without a cache, fewer builds.  (That kernel
   // is built without the six extended camera models -- their forward-mode duals cost ~100 registers: a problem that uses one
   // keeps the packed kernel for every point.)
-  gram_inner = !m.geom && opt->use_inner_iterations != 0 && arena->dtype != PXR_F64 && (arena->C == 128 || arena->C == 64) &&
+  gram_inner = !records_only && !m.geom && opt->use_inner_iterations != 0 && arena->dtype != PXR_F64 && (arena->C == 128 || arena->C == 64) &&
                !knobs.inner_packed && cfg->use_float_simd == 0;
   for (int c = 0; c < n_cam; ++c) gram_inner = gram_inner && sx.cam_model[c] <= PXR_OPENCV;
   inner_cache = gram_inner && gram_eval_supported(arena, view) && !knobs.inner_no_cache;
@@ -1575,8 +1619,8 @@ int LmSolve::reduced_step_iterative(double inv_radius, bool* ok, double* inexact
   hipLaunchKernelGGL(k_finish_camera_step, dim3(nblk(n_c)), dim3(256), 0, st, n_c, ws.xsol.p, gc, ws.damp_c.p, inv_radius, ws.delta_c.p, scal_rep, limb_arg);
   return from_rank0(ws.delta_c.p, n_c);
 }
-// Schur complement (dense) + Cholesky
-int LmSolve::reduced_step_direct(double inv_radius) {
+// Schur complement (dense): [S + D_c / radius | rhs] in ws.S ...
+int LmSolve::reduced_system_direct(double inv_radius) {
   const double schur_scale = m.det_fixed ? lin_scale : 0.0;    // the SAME grid as U's: re-quantising the finished U is exact
   hipLaunchKernelGGL(k_copy_upper_add_diag, dim3(nblk((int64_t)n_c * ldS)), dim3(256), 0, st, n_c, ws.U.p, (const double*)nullptr, 0.0, (const double*)nullptr, ws.S.p, 1, schur_scale);
   if (knobs.schur_lds) {
@@ -1598,6 +1642,11 @@ int LmSolve::reduced_step_direct(double inv_radius) {
   phase(1);
   // the fixed-point slots back to doubles (deterministic mode), rhs += g_c (global), S += D_c / radius: one pass
   hipLaunchKernelGGL(k_copy_upper_add_diag, dim3(nblk((int64_t)n_c * ldS)), dim3(256), 0, st, n_c, ws.U.p, ws.damp_c.p, inv_radius, gc, ws.S.p, 0, schur_scale);
+  return PXR_OK;
+}
+// ... + Cholesky
+int LmSolve::reduced_step_direct(double inv_radius) {
+  RC(reduced_system_direct(inv_radius));
   // row-major upper == column-major lower; the pivot check is read back with the scalars of
   // this attempt (no extra host synchronisation): a failed factorisation = invalid step.
   RC(chol_factor_solve(st, ws.S.p, n_c, d_info, ws.linv.p, ws.xsol.p, /*zero_info=*/false));     // (the attempt's first kernel cleared the info word)
@@ -1833,6 +1882,65 @@ int LmSolve::run() {
             "backsub+update %.2f eval+cost %.2f linearize %.2f other %.2f\n", sum->iterations, ph_ms[0], ph_ms[1],
             ph_ms[2], ph_ms[3], ph_ms[4], ph_ms[5], ph_ms[6], ph_ms[7]);
   return finish(sum->termination, radius);
+}
+
+// ---- the covariance's linear algebra up to the factor of S (pxr_ba_cov.hip has the rest) -------------------------------------------
+// The linearisation of the LM loop at the caller's records, WITHOUT damping: columns moved into [1/4, 1) by powers of two alone
+// (scale_c starts at 1 and only k_column_pow2 touches it: S_scaled = D S D exactly, the covariance is D inv(S_scaled) D without a
+// rounding), points unscaled, T_p = inv(V_p) from k_pinv_checked, then reduced_system_direct at 1 / radius = 0: the Schur
+// complement on the grid of the deterministic mode, in the layout chol_factor_solve takes.
+int LmSolve::covariance_system(const double* rec, int* singular, unsigned long long* n_singular, CovSystem* out) {
+  double hs[kScalSlots];
+  RC(zero_scalars());
+  hipLaunchKernelGGL(k_cost_limbs, dim3(1024), dim3(256), 0, st, rec, n_obs, *loss, slimb + SCAL_COST * PXR_LIMBS);
+  LAUNCH_CHECK("cost");
+  RC(read_scalars(hs));
+  cost = hs[SCAL_COST];
+  PXR_REQUIRE(std::isfinite(cost), "pxr_ba_covariance: the records do not give a finite cost");
+  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.scale_c.p);
+  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.pow_c.p);
+  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.damp_c.p);
+  hipLaunchKernelGGL(k_fill, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, 1.0, ws.scale_p.p);
+  RC(linearize_checked(rec, std::ldexp(1.0, 32), cost));
+  if (n_c > 0 && !lin_not_finite) {
+    if (m.det_fixed) RC(resolve_small_columns(rec));
+    if (!lin_not_finite) {
+      RC(move_columns());
+      RC(linearize_checked(rec, 1.0 / 8.0, cost));
+    }
+  }
+  PXR_REQUIRE(!lin_not_finite, "pxr_ba_covariance: the Jacobian at these parameters is not finite");
+  RC(zero_scalars());
+  PXR_HIP(hipMemsetAsync(n_singular, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_pinv_checked, dim3(nblk(n_pts)), dim3(256), 0, st, n_pts, sx.d_pt_var.p, ws.V.p, ws.T.p, singular, n_singular);
+  LAUNCH_CHECK("k_pinv_checked");
+  if (n_c > 0) RC(reduced_system_direct(0.0));
+  out->dv = dv; out->n_c = n_c; out->DC = DC;
+  out->aug = ws.S.p; out->linv = ws.linv.p; out->xsol = ws.xsol.p; out->d_info = d_info; out->scratch = ws.U.p;
+  out->W = ws.W.p; out->T = ws.T.p; out->pt_ptr = sx.d_pt_ptr.p; out->pt_obs = sx.d_pt_obs.p;
+  out->deterministic = m.det_fixed;
+  return PXR_OK;
+}
+
+int ba_cov_system(pxr_ctx* ctx, const pxr_ba_view* view, const double* d_rec, const pxr_loss* loss, const uint8_t* h_pose_const,
+                  const uint8_t* h_tvec_const_mask, const uint16_t* h_cam_const_mask, const uint8_t* h_point_const, int* d_singular,
+                  unsigned long long* d_n_singular, const std::function<int(const CovSystem&)>& then) {
+  const SolveKnobs knobs;
+  const SetupClock clock{knobs.verbose};
+  ArenaScope arena_scope(ctx, knobs.arena);
+  pxr_lm_options opt;
+  std::memset(&opt, 0, sizeof(opt));
+  opt.jacobi_scaling = 1; opt.linear_solver = PXR_LINEAR_DIRECT; opt.min_lm_diagonal = 1e-6; opt.max_lm_diagonal = 1e32;
+  pxr_lm_summary sum;
+  std::memset(&sum, 0, sizeof(sum));
+  LmSolve s{ctx, nullptr, view, nullptr, nullptr, loss, h_pose_const, h_tvec_const_mask, h_cam_const_mask, h_point_const, &opt, nullptr, nullptr, &sum,
+            knobs, ctx->stream, clock};
+  s.records_only = true;
+  RC(s.setup());
+  PXR_REQUIRE(!s.m.multi, "pxr_ba_covariance: not available with a communicator (several ranks)");
+  CovSystem sys;
+  RC(s.covariance_system(d_rec, d_singular, d_n_singular, &sys));
+  return then(sys);
 }
 
 static int ba_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* view, const pxr_interp_cfg* cfg, const double* d_obs_xy,

@@ -16,6 +16,7 @@ U8 = 3            # grey images of the dense-SIFT producer (pxr_dsift_*)
 CAMERA_MODEL_IDS = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4, "OPENCV_FISHEYE": 5,
                     "FULL_OPENCV": 6, "FOV": 7, "SIMPLE_RADIAL_FISHEYE": 8, "RADIAL_FISHEYE": 9, "THIN_PRISM_FISHEYE": 10}
 LOSS_IDS = {"trivial": 0, "cauchy": 1, "huber": 2, "soft_l1": 3}
+CAMERA_NUM_PARAMS = (3, 4, 4, 5, 8, 8, 12, 5, 4, 5, 12)     # by model id [upstream COLMAP camera_models.h]
 
 
 class PixsfmHipError(RuntimeError):
@@ -59,6 +60,15 @@ class LMSummary(C.Structure):
                 ("total_ms", C.c_double), ("setup_ms", C.c_double), ("linear_solver", C.c_int32),
                 ("collective_kib", C.c_int32), ("linear_iterations", C.c_int64), ("accumulation", C.c_int32),
                 ("initial_us", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class CovSummary(C.Structure):
+    """pxr_cov_summary"""
+    _fields_ = [("num_camera_unknowns", C.c_int32), ("info", C.c_int32), ("num_singular_points", C.c_int64),
+                ("ms_linearise", C.c_double), ("ms_factor_inverse", C.c_double), ("ms_points", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -232,6 +242,9 @@ _SIGNATURES = {
     "pxr_ka_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(KaView), C.POINTER(InterpCfg), C.POINTER(Loss),
                                C.c_double, C.POINTER(LMOptions), C.c_void_p, C.POINTER(LMSummary)]),
     "pxr_dense_spd_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "pxr_dense_spd_inverse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "pxr_ba_covariance": (C.c_int, [C.c_void_p, C.POINTER(BaView), C.c_void_p, C.POINTER(Loss), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CovSummary)]),
     "pxr_graph_track_labels": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int64)]),
     "pxr_graph_score_labels": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -30,3 +30,5 @@ from .sift import SiftExtractor  # noqa: F401,E402
 from . import retrieval  # noqa: F401,E402
 from .retrieval import (GlobalDescriptorExtractor, pairs_from_exhaustive, pairs_from_retrieval,  # noqa: F401,E402
                         unique_pairs)
+from . import covariance  # noqa: F401,E402
+from .covariance import BACovariance, estimate_ba_covariance  # noqa: F401,E402

@@ -363,7 +363,9 @@ class QueryBundleOptimizer:
         self.ctx = ctx
         self.last_summary = None
 
-    def run(self, qvec, tvec, camera, points3D, fmap, references, inliers=None, patch_idxs=None):
+    def _problem(self, qvec, tvec, camera, points3D, fmap, references, inliers, patch_idxs):
+        """The QBA problem at (qvec, tvec, camera): (BAProblem, arena, camera mask, number of residual blocks), or None when no
+        residual is added -- one image, every point constant."""
         n = len(points3D)
         if len(references) != n:
             raise ValueError("references.size() != points3D.size()")          # THROW_CHECK_EQ, :100 / :141 / :183
@@ -376,11 +378,10 @@ class QueryBundleOptimizer:
                 raise ValueError("%s must be a float64 numpy array of %d values (refined in place)" % (name, k))
         rows, patches, xyz, refs = _qba_observations(points3D, fmap, references, inliers, patch_idxs)
         if not patches:
-            return False
+            return None
         ctx = self.ctx or default_context()
         arena = features.to_arena(ctx, patches)
         m = len(patches)
-        o, s = self.options, self.options['solver']
         q = qvec.reshape(4)
         params = np.zeros((1, 12))
         params[0, :len(camera.params)] = camera.params
@@ -389,9 +390,16 @@ class QueryBundleOptimizer:
                     qvec=q.reshape(1, 4).copy(), tvec=tvec.reshape(1, 3).copy(),
                     cam_model=np.array([camera.model_id], np.int32), cam_params=params,
                     xyz=np.array(xyz), refs=np.array(refs))
-        ba = BAProblem(ctx, arena, prob)
+        return BAProblem(ctx, arena, prob), arena, _qba_camera_mask(camera, self.options), m
+
+    def run(self, qvec, tvec, camera, points3D, fmap, references, inliers=None, patch_idxs=None):
+        built = self._problem(qvec, tvec, camera, points3D, fmap, references, inliers, patch_idxs)
+        if built is None:
+            return False
+        ba, arena, cam_mask, m = built
+        ctx = ba.ctx
+        o, s = self.options, self.options['solver']
         K = len(camera.params)
-        cam_mask = _qba_camera_mask(camera, o)
         lm = lm_options(max_iterations=s['max_num_iterations'], function_tolerance=s['function_tolerance'],
                         gradient_tolerance=s['gradient_tolerance'], parameter_tolerance=s['parameter_tolerance'],
                         max_consecutive_invalid_steps=s['max_num_consecutive_invalid_steps'],
@@ -413,6 +421,28 @@ class QueryBundleOptimizer:
         self.last_summary = summary
         arena.close()
         return True
+
+    def covariance(self, qvec, tvec, camera, points3D, fmap, references, inliers=None, patch_idxs=None):
+        """The 6 x 6 covariance of the query pose at (qvec, tvec) -- rotation in radians about the camera axes, then the
+        translation -- from the problem run() solves (every point constant: the inverse of the pose block of J~^T J~, with the
+        refined intrinsics marginalised when the options refine any); None when no residual is added.  Raises ValueError when the
+        correspondences do not determine the pose."""
+        from .covariance import half_angle_to_radians
+        built = self._problem(qvec, tvec, camera, points3D, fmap, references, inliers, patch_idxs)
+        if built is None:
+            return None
+        ba, arena, cam_mask, m = built
+        o = self.options
+        try:
+            ba.eval(self.interpolation.to_engine(), with_jacobian=True)
+            cov = ba.covariance(make_loss(o['loss']['name'], o['loss']['params']), np.zeros(1, np.uint8), np.zeros(1, np.uint8),
+                                np.array([cam_mask], np.uint16), np.ones(m, np.uint8))
+        finally:
+            arena.close()
+        if cov["summary"]["info"] != 0:
+            raise ValueError("the query pose is not determined by its %d correspondences (rank deficient at column %d)"
+                             % (m, cov["summary"]["info"]))
+        return half_angle_to_radians(cov["pose"][0])
 
 
 class QueryBundleAdjuster:
@@ -443,6 +473,13 @@ class QueryBundleAdjuster:
         for level in resolve_level_indices(self.conf['level_indices'], len(fmaps)):
             self.refine(qvec, tvec, camera, points3D, fmaps[level], references[level], inliers=inliers,
                         point2D_idxs=point2D_idxs)
+
+    def covariance(self, qvec, tvec, camera, points3D, fmaps, references, inliers=None, point2D_idxs=None):
+        """QueryBundleOptimizer.covariance on the LAST level refine_multilevel refines (the finest by default)."""
+        assert len(fmaps) == len(references)
+        level = list(resolve_level_indices(self.conf['level_indices'], len(fmaps)))[-1]
+        return self.solver.covariance(qvec, tvec, camera, points3D, fmaps[level], references[level], inliers=inliers,
+                                      patch_idxs=point2D_idxs)
 
 
 # ---- PnP ---------------------------------------------------------------------------------------------------------------------------
@@ -679,7 +716,11 @@ class QueryLocalizer:
             self.references = [self.reference_extractor.run(labels, reconstruction, dense_features.fset(i))
                                for i in range(dense_features.num_levels)]
 
-    def localize(self, keypoints, pnp_point2D_idxs, pnp_points3D_id, query_camera, image_path=None, query_fmaps=None):
+    def localize(self, keypoints, pnp_point2D_idxs, pnp_points3D_id, query_camera, image_path=None, query_fmaps=None,
+                 return_covariance=False):
+        """return_covariance: adds "covariance" to a successful result -- the 6 x 6 covariance of the final pose, (rotation in
+        radians about the camera axes, translation), from the query bundle adjustment's problem at that pose (every point
+        constant, residuals of unit variance).  Needs the features QKA / QBA work on."""
         assert len(pnp_point2D_idxs) == len(pnp_points3D_id)
         conf = self.conf
         require_feats = conf["QKA"]["apply"] or conf["QBA"]["apply"]
@@ -737,6 +778,13 @@ class QueryLocalizer:
             self.query_bundle_adjuster.refine_multilevel(pose_dict["qvec"], pose_dict["tvec"], query_camera, pnp_points3D,
                                                          query_fmaps, query_references, inliers=inliers,
                                                          point2D_idxs=pnp_point2D_idxs)
+
+        if return_covariance:
+            if not require_feats:
+                raise ValueError("return_covariance needs the query's features: apply QKA or QBA, or pass query_fmaps")
+            pose_dict["covariance"] = self.query_bundle_adjuster.covariance(pose_dict["qvec"], pose_dict["tvec"], query_camera,
+                                                                            pnp_points3D, query_fmaps, query_references,
+                                                                            inliers=inliers, point2D_idxs=pnp_point2D_idxs)
 
         # We recompute the inliers from the final pose
         errors = compute_reprojection_errors(pnp_points2D, pnp_points3D, pose_dict["qvec"], pose_dict["tvec"], query_camera)

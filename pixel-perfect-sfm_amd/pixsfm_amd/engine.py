@@ -441,6 +441,19 @@ def nearest_references(ctx, arena, cfg, keypoints, patch_idx, cand_ptr, cand_des
     return best.download(), dist.download(), (out.download() if out else None)
 
 
+def dense_spd_inverse(ctx, a):
+    """The inverse of a symmetric positive definite matrix (pxr_dense_spd_inverse): `a` is a DeviceArray (n, n), inverted in
+    place, or a host array, of which only the upper triangle is read.  Returns (info, inverse): info is 0, or the 1-based
+    index of the first non-positive pivot -- the inverse then holds nothing meaningful.  The result is symmetric bit for bit
+    and the same on every run."""
+    d = a if isinstance(a, DeviceArray) else ctx.to_device(np.ascontiguousarray(a, dtype=np.float64), np.float64)
+    if len(d.shape) != 2 or d.shape[0] != d.shape[1] or d.shape[0] < 1:
+        raise ValueError("dense_spd_inverse takes a square matrix")
+    info = C.c_int(0)
+    check(ctx.lib.pxr_dense_spd_inverse(ctx.handle, d.ptr, int(d.shape[0]), C.byref(info)), "pxr_dense_spd_inverse")
+    return info.value, (d if d is a else d.download())
+
+
 def interp_cfg(l2_normalize=True, use_float_simd=False, check_bounds=False, mode="BICUBIC", nodes=None,
                ncc_normalize=False, **_):
     """InterpolationConfig (pixsfm/base/main.py:1-7).  Only the hot-path configuration is accepted."""
@@ -529,6 +542,26 @@ def _launch(ctx, name, args, stages, timed):
 _ROBUST_STAGES = ("records", "compact", "hypotheses", "refine")     # the kernels of abspose and of the three pair estimators
 
 
+def column_layout(pose_const, tvec_const_mask, cam_const_mask, cam_model):
+    """The columns of the reduced camera system (block_layout, csrc/pxr_ba_structure.h): per image 3 rotation columns and the
+    variable tvec components, then per camera the variable intrinsics.  Returns pose_off / pose_dim (per image), intr_off /
+    intr_dim (per camera), pose_slots / intr_slots (per block: the component 0..5 of (rotation, t) / the parameter index of every
+    column) and n_c."""
+    off = 0
+    pose_off, pose_dim, pose_slots = [], [], []
+    for const, tm in zip(pose_const, tvec_const_mask):
+        slots = [] if const else [0, 1, 2] + [3 + k for k in range(3) if not (int(tm) >> k) & 1]
+        pose_off.append(off); pose_dim.append(len(slots)); pose_slots.append(slots)
+        off += len(slots)
+    intr_off, intr_dim, intr_slots = [], [], []
+    for mask, model in zip(cam_const_mask, cam_model):
+        slots = [k for k in range(_lib.CAMERA_NUM_PARAMS[int(model)]) if not (int(mask) >> k) & 1]
+        intr_off.append(off); intr_dim.append(len(slots)); intr_slots.append(slots)
+        off += len(slots)
+    return {"pose_off": pose_off, "pose_dim": pose_dim, "pose_slots": pose_slots, "intr_off": intr_off, "intr_dim": intr_dim,
+            "intr_slots": intr_slots, "n_c": off}
+
+
 class _BABase:
     """What the featuremetric and the geometric bundle-adjustment problems share: the device arrays of poses, cameras and
     points behind one pxr_ba_view, the records of the last evaluation, and the host side of a solve."""
@@ -562,9 +595,8 @@ class _BABase:
                       self.n_cameras, d["cam_model"].ptr, d["cam_params"].ptr,
                       self.n_points, d["xyz"].ptr, refs.ptr if refs is not None else None)
 
-    def _solve(self, name, head, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, options, allreduce):
-        """The entry point `name` over its leading arguments `head` and what every BA solve takes after them: the loss, the
-        constant masks (checked against the problem's dimensions), the options, the all-reduce callback and the summary."""
+    def _masks(self, pose_const, tvec_const_mask, cam_const_mask, point_const):
+        """The constant masks as the arrays the C entry points take, checked against the problem's dimensions."""
         pc = np.ascontiguousarray(pose_const, dtype=np.uint8)
         tm = np.ascontiguousarray(tvec_const_mask, dtype=np.uint8)
         cm = np.ascontiguousarray(cam_const_mask, dtype=np.uint16)
@@ -572,6 +604,12 @@ class _BABase:
         if len(pc) != self.n_images or len(tm) != self.n_images or len(cm) != self.n_cameras \
                 or len(ptc) != self.n_points:
             raise ValueError("parameterisation arrays do not match the problem dimensions")
+        return pc, tm, cm, ptc
+
+    def _solve(self, name, head, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, options, allreduce):
+        """The entry point `name` over its leading arguments `head` and what every BA solve takes after them: the loss, the
+        constant masks (checked against the problem's dimensions), the options, the all-reduce callback and the summary."""
+        pc, tm, cm, ptc = self._masks(pose_const, tvec_const_mask, cam_const_mask, point_const)
         opts = options or lm_options()
         summ = _lib.LMSummary()
         cb = None
@@ -588,6 +626,34 @@ class _BABase:
         check(getattr(self.ctx.lib, name)(*head, C.byref(loss), pc.ctypes.data, tm.ctypes.data, cm.ctypes.data, ptc.ctypes.data,
                                           C.byref(opts), C.cast(cb, C.c_void_p) if cb else None, None, C.byref(summ)), name)
         return summ.as_dict()
+
+    def covariance(self, loss, pose_const, tvec_const_mask, cam_const_mask, point_const, rec=None, cameras=False):
+        """Covariance of the parameters at the current point (pxr_ba_covariance): blocks of the inverse of the Gauss-Newton
+        matrix the solver linearises, from the records `rec` (default: those of the last eval() -- evaluate first, with
+        Jacobians).  Returns a dict of numpy arrays: "pose" (n_images, 6, 6) in the order (rotation tangent, tx, ty, tz) with
+        the rotation in the solver's HALF-angle units, "intrinsics" (n_cameras, KPAD, KPAD), "points" (n_points, 3, 3; NaN for
+        a singular point), with `cameras` also "cameras" (n_c, n_c) and "columns" (column_layout), and "summary".  Rows and columns
+        of constant parameters are zero.  summary["info"] > 0: the reduced camera matrix is rank deficient at that column (a gauge
+        is not fixed) and the arrays hold nothing meaningful."""
+        pc, tm, cm, ptc = self._masks(pose_const, tvec_const_mask, cam_const_mask, point_const)
+        ctx = self.ctx
+        cols = column_layout(pc, tm, cm, self.d["cam_model"].download())
+        n_c = cols["n_c"]
+        pose = ctx.empty((self.n_images, 6, 6), np.float64)
+        intr = ctx.empty((self.n_cameras, KPAD, KPAD), np.float64)
+        pts = ctx.empty((self.n_points, 3, 3), np.float64)
+        dense = ctx.empty((max(n_c, 1), max(n_c, 1)), np.float64) if cameras else None
+        summ = _lib.CovSummary()
+        check(ctx.lib.pxr_ba_covariance(ctx.handle, C.byref(self.view), (self.rec if rec is None else rec).ptr, C.byref(loss),
+                                        pc.ctypes.data, tm.ctypes.data, cm.ctypes.data, ptc.ctypes.data,
+                                        dense.ptr if dense else None, pose.ptr, intr.ptr, pts.ptr, C.byref(summ)), "pxr_ba_covariance")
+        out = {"pose": pose.download(), "intrinsics": intr.download(), "points": pts.download(), "summary": summ.as_dict()}
+        if summ.num_camera_unknowns != n_c:
+            raise RuntimeError("column layout mismatch: %d columns here, %d in the library" % (n_c, summ.num_camera_unknowns))
+        if cameras:
+            out["cameras"] = dense.download()[:n_c, :n_c]
+            out["columns"] = cols
+        return out
 
     def projection_jacobian(self, out=None):
         """The 2 x (10+K) projection Jacobian P of every observation (k_jac) -- for the geometric problem the Jacobian of the
