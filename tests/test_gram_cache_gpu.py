@@ -6,7 +6,11 @@ stencil: with G = T T^t (16 x 16) and D = T ref the record is a set of quadratic
 The cache path must give pxr_ba_eval's records up to the rounding of the reference's fp32 horizontal pass
 (cubic_hermite_spline_simd.h; the algebra on G is exact in fp64), rebuild exactly the observations whose projection left
 their cell, and steer the LM loop to the same solution.  The inner iterations keep their matrices in the same cache from
-call to call in EVERY mode: that must not change a bit."""
+call to call in EVERY mode: that must not change a bit.
+
+The comparisons here cannot see below the fp32 pass's rounding (~1e-7).  tests/test_gram_records_gpu.py holds the same records
+to a long-double reference of the Gram path's own arithmetic and a derived bound of a few hundred roundings (tests/gram_cases.py),
+at placed positions, clamped stencils, small batches and chosen sets of flagged observations."""
 import numpy as np
 import pytest
 
