@@ -975,6 +975,48 @@ int pxr_retrieval_topk_timed(pxr_ctx* ctx, int32_t n_query, int32_t n_db, int32_
                              const int32_t* d_query_self, const uint8_t* d_mask, int32_t num_matched, double min_score,
                              int32_t* d_top_index, float* d_top_sim, int32_t* d_n_found, double* h_kernel_ms);
 
+/* ---- reconstruction evaluation on point clouds (two clouds in, nearest neighbours and voxel-averaged fractions out) --------
+ * What says how good a model is: the reference's pixsfm/eval/eth3d.  triangulation.py:19-52 hands the sparse cloud and a laser
+ * scan to ETH3D's multi-view-evaluation program (Schoeps et al. 2017), which reports accuracy (model against scan) and
+ * completeness (scan against model) at 1 / 2 / 5 cm; localization.py:113-157 computes pose errors and their AUC (host code here:
+ * pixsfm_amd/api/evaluation.py).  Both directions of the cloud half are nearest-neighbour queries followed by an average over
+ * occupied voxels, so that a densely sampled wall does not outvote a sparsely sampled one.  That program's occlusion and
+ * free-space meshes are not modelled and parity with it is unpinned; the specification below is this library's own and
+ * reproduces bit for bit (csrc/pxr_cloud.hip).
+ *
+ * Clouds are (n, 3) float64 row-major device pointers.  A point is VALID iff its three coordinates are finite.  Nothing is
+ * contracted; integer sums have no order.
+ *   1 nearest     (pxr_cloud_nearest) 0 <= n_ref < 2^31, 0 <= n_query < 2^31, max_dist finite and > 0.
+ *                 d2(q, r) = ((dx dx + dy dy) + dz dz) in float64 with dx = q.x - r.x (and so on).  r is a CANDIDATE of q iff both
+ *                 are valid and d2 <= max_dist max_dist (one float64 multiplication).  Per query: the candidate with the smallest
+ *                 d2, ties to the lowest reference index, in d_nn_index int32[n_query] and d_nn_dist2 float64[n_query]; without a
+ *                 candidate -1 and +inf.  A function of the two arrays alone: equal to the brute-force search bit for bit,
+ *                 whatever the order the grid inside is built or walked in.
+ *   2 voxels      (pxr_cloud_voxel_fractions) 0 <= n < 2^30, 1 <= n_tol <= PXR_CLOUD_MAX_TOLERANCES, tolerances finite and > 0,
+ *                 voxel_size v finite and >= 0.  The valid point i lies in voxel (floor(x / v), floor(y / v), floor(z / v)), division
+ *                 and floor in float64; within_t(i) iff d_dist2[i] <= t t (the +inf of a query without a candidate never is).  Per
+ *                 occupied voxel: n_v points, w_v[t] of them within, q_v[t] = llrint(((double)w_v[t] / (double)n_v) 2^32).
+ *                 h_fraction[t] = ((double)(sum over the voxels of q_v[t], as int64)) 2^-32 / (double)n_voxels; *h_n_voxels the
+ *                 number of occupied voxels.  Without a valid point: NaN and 0.  v = 0: every valid point is its own voxel, the
+ *                 result is exactly (double)W[t] / (double)n_valid.
+ * PXR_EINVAL (nothing launched, outputs untouched): a size, max_dist, a tolerance, n_tol or voxel_size outside the limits above; a
+ * NULL array of a non-empty cloud.  One check is made ON THE DEVICE and therefore AFTER the launch: every voxel component must
+ * satisfy |floor(x / v)| < 2^20 (the key packs into 63 bits); otherwise pxr_cloud_voxel_fractions returns PXR_EINVAL with
+ * h_fraction and h_n_voxels untouched.  Both calls take their scratch from the context's workspace and queue on its stream;
+ * pxr_cloud_nearest only queues its kernels, pxr_cloud_voxel_fractions synchronises the stream to return its host values. */
+#define PXR_CLOUD_MAX_TOLERANCES 8
+int pxr_cloud_nearest(pxr_ctx* ctx, int64_t n_ref, const double* d_ref_xyz, int64_t n_query, const double* d_query_xyz,
+                      double max_dist, int32_t* d_nn_index, double* d_nn_dist2);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[2] = grid (count, scan, fill), query. */
+int pxr_cloud_nearest_timed(pxr_ctx* ctx, int64_t n_ref, const double* d_ref_xyz, int64_t n_query, const double* d_query_xyz,
+                            double max_dist, int32_t* d_nn_index, double* d_nn_dist2, double* h_kernel_ms);
+int pxr_cloud_voxel_fractions(pxr_ctx* ctx, int64_t n, const double* d_xyz, const double* d_dist2, double voxel_size, int32_t n_tol,
+                              const double* h_tolerances, double* h_fraction, int64_t* h_n_voxels);
+/* h_kernel_ms[2] = insert, reduce. */
+int pxr_cloud_voxel_fractions_timed(pxr_ctx* ctx, int64_t n, const double* d_xyz, const double* d_dist2, double voxel_size,
+                                    int32_t n_tol, const double* h_tolerances, double* h_fraction, int64_t* h_n_voxels,
+                                    double* h_kernel_ms);
+
 /* ---- incremental mapping: visibility (triangulated tracks in, per-image scores and 2D-3D pairs out) ----
  * The stage of the reference's main entry point that produces poses: PixSfM.reconstruction (pixsfm/refine_hloc.py:133-146)
  * hands it to hloc.reconstruction.main, i.e. COLMAP's incremental mapper.  The arithmetic of a mapper is the stages above

@@ -32,3 +32,6 @@ from .retrieval import (GlobalDescriptorExtractor, pairs_from_exhaustive, pairs_
                         unique_pairs)
 from . import covariance  # noqa: F401,E402
 from .covariance import BACovariance, estimate_ba_covariance  # noqa: F401,E402
+from . import evaluation  # noqa: F401,E402
+from .evaluation import (Sim3, align_reconstructions, compare_reconstructions, compute_auc, compute_pose_error,  # noqa: F401,E402
+                         compute_recall, evaluate_point_cloud, export_PLY, read_ply_points)

@@ -1471,3 +1471,43 @@ def retrieval_topk(ctx, query, db, num_matched, query_self=None, mask=None, min_
     ms = _launch(ctx, "pxr_retrieval_topk", args, ("similarity", "select"), timed)
     ctx.sync()                                          # (the uploaded arrays may go out of scope)
     return (top, sim, found, ms) if timed else (top, sim, found)
+
+
+def _device_cloud(ctx, xyz, name):
+    """A cloud as pxr_cloud_nearest takes it: (n, 3) float64 on the device.  A DeviceArray is used in place."""
+    d = xyz if isinstance(xyz, DeviceArray) else ctx.to_device(np.asarray(xyz, dtype=np.float64).reshape(-1, 3), np.float64)
+    if len(d.shape) != 2 or d.shape[1] != 3 or d.dtype != np.float64:
+        raise ValueError("%s must be (n, 3) float64" % name)
+    return d
+
+
+def cloud_nearest(ctx, ref, query, max_dist, timed=False):
+    """pxr_cloud_nearest: per row of query (n_query, 3) the nearest row of ref (n_ref, 3) within max_dist, ties to the lowest
+    index -- the brute-force search bit for bit.  ref / query: float64 host arrays or DeviceArrays (one object for both:
+    uploaded once).  Returns the device arrays (index (n_query,) int32, -1 without a candidate; dist2 (n_query,) float64, +inf
+    without one), and with timed also {"grid", "query"} in milliseconds."""
+    d_r = _device_cloud(ctx, ref, "ref")
+    d_q = d_r if query is ref else _device_cloud(ctx, query, "query")
+    nq = int(d_q.shape[0])
+    index, dist2 = ctx.empty((nq,), np.int32), ctx.empty((nq,), np.float64)
+    args = (ctx.handle, int(d_r.shape[0]), d_r.ptr, nq, d_q.ptr, float(max_dist), index.ptr, dist2.ptr)
+    ms = _launch(ctx, "pxr_cloud_nearest", args, ("grid", "query"), timed)
+    ctx.sync()                                          # (the uploaded arrays may go out of scope)
+    return (index, dist2, ms) if timed else (index, dist2)
+
+
+def cloud_voxel_fractions(ctx, xyz, dist2, voxel_size, tolerances, timed=False):
+    """pxr_cloud_voxel_fractions: the fraction of the points of xyz (n, 3) whose dist2 (n,) is within each tolerance, averaged
+    over the occupied voxels of side voxel_size (0: over the points).  xyz / dist2: float64 host arrays or DeviceArrays.
+    Returns (fractions (n_tol,) float64, n_voxels), and with timed also {"insert", "reduce"} in milliseconds."""
+    d_x = _device_cloud(ctx, xyz, "xyz")
+    d_d = dist2 if isinstance(dist2, DeviceArray) else ctx.to_device(np.asarray(dist2, dtype=np.float64).reshape(-1), np.float64)
+    if d_d.dtype != np.float64 or int(np.prod(d_d.shape)) != d_x.shape[0]:
+        raise ValueError("dist2 must be (n,) float64, one entry per point")
+    tol = np.ascontiguousarray(tolerances, dtype=np.float64).reshape(-1)
+    frac = np.full(len(tol), np.nan)
+    n_voxels = C.c_int64(0)
+    args = (ctx.handle, int(d_x.shape[0]), d_x.ptr, d_d.ptr, float(voxel_size), len(tol), tol.ctypes.data_as(C.POINTER(C.c_double)),
+            frac.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n_voxels))
+    ms = _launch(ctx, "pxr_cloud_voxel_fractions", args, ("insert", "reduce"), timed)
+    return (frac, int(n_voxels.value), ms) if timed else (frac, int(n_voxels.value))
