@@ -909,6 +909,44 @@ int pxr_match_descriptors_timed(pxr_ctx* ctx, int32_t n_images, const int64_t* d
                                 const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches,
                                 double* h_kernel_ms);
 
+/* ---- guided descriptor matching (nearest neighbours among the candidates that agree with a pair's two-view model) --------
+ * COLMAP's guided matching: once a pair has a model, it is matched again and only candidates that agree with the model compete,
+ * so a look-alike off the epipolar line no longer enters the ratio test.
+ * The batch is pxr_match_descriptors' plus d_xy (n_total x 2 float64, row-aligned with d_desc: the keypoint of every descriptor in
+ * the frame the models live in -- the normalised plane for the E, F and H of this library) and per pair a kind (int32), a model M
+ * (9 float64, row-major) and a threshold thr (float64, in the units of d_xy).  The specification is exactly pxr_match_descriptors'
+ * with one added rule: AN INADMISSIBLE (i, j) NEVER WINS A COMPARISON -- it is treated exactly as a NaN similarity, forward and
+ * backward.  Admissibility is computed in float64, every operation rounded once in the order written (no contraction); a
+ * comparison with a NaN is false.  With (x, y) = xy_a[i], (u, v) = xy_b[j]:
+ *   PXR_GUIDE_EPIPOLAR    per row     l0 = (M00 x + M01 y) + M02,  l1 = (M10 x + M11 y) + M12,  l2 = (M20 x + M21 y) + M22,
+ *                                     ra = l0 l0 + l1 l1
+ *                         per column  m0 = (M00 u + M10 v) + M20,  m1 = (M01 u + M11 v) + M21,  cb = m0 m0 + m1 m1
+ *                         per entry   t = (u l0 + v l1) + l2,  den = ra + cb;  admissible iff den > 0 and t t <= (thr thr) den.
+ *                         This is the Sampson test of pxr_two_view_geometry step 4 without the division; it may differ from that
+ *                         estimator's d_inlier for an error within an ulp of thr^2.
+ *   PXR_GUIDE_HOMOGRAPHY  per row     X = (M00 x + M01 y) + M02, Y and Wd likewise from rows 1 and 2 of M;  px = X / Wd,
+ *                                     py = Y / Wd;  the row is valid iff Wd > 0
+ *                         per entry   dx = px - u,  dy = py - v;  admissible iff valid and dx dx + dy dy <= thr thr.
+ *                         This is the forward transfer error in image 2, as pxr_homography scores it (the gate is one-sided).
+ * Consequences: a row with no admissible column gets -1.  A row with exactly one admissible column has s2 = -inf, d2 = +inf and so
+ * passes the ratio test.  The skip of the ratio test when na == 1 or nb == 1 is unchanged.  Records belong to the pair, not the
+ * image: the same image pair may appear twice with different models.  thr = +inf is allowed and admits every entry with den > 0
+ * (epipolar) or a valid row (homography).  A model with an entry that is not finite is not an error: nothing is admissible for it.
+ * PXR_EINVAL (nothing launched, outputs untouched): everything pxr_match_descriptors rejects, a kind outside {0, 1}, a threshold
+ * that is NaN or negative (kinds and thresholds are checked on a host copy). */
+#define PXR_GUIDE_EPIPOLAR   0   /* x_b^t M x_a = 0 : E or F */
+#define PXR_GUIDE_HOMOGRAPHY 1   /* x_b ~ M x_a          : H  */
+int pxr_match_guided(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                     const float* d_desc, const double* d_xy, int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets,
+                     const int32_t* d_pair_kind, const double* d_pair_model, const double* d_pair_thr,
+                     const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[4] = records, tiles, columns, mutual. */
+int pxr_match_guided_timed(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                           const float* d_desc, const double* d_xy, int32_t n_pairs, const int32_t* d_pairs,
+                           const int64_t* d_pair_offsets, const int32_t* d_pair_kind, const double* d_pair_model,
+                           const double* d_pair_thr, const pxr_match_options* options, int32_t* d_matches0, float* d_scores0,
+                           int32_t* d_n_matches, double* h_kernel_ms);
+
 /* ---- image retrieval (local descriptors in, a VLAD global descriptor per image and the image pairs to match out) --------
  * What picks the image pairs: hloc's pairs_from_retrieval over global descriptors (examples/sfm+loc_aachen.py; pixsfm/localize.py
  * reads its output through parse_retrieval).  hloc's retrieval models need weights and stay out; this is the classical weight-free

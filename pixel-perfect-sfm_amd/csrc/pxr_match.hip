@@ -17,6 +17,10 @@
 // k_match_columns  one lane per (pair, column): merges the strips' partials, applies the tests, writes m1.
 // k_match_mutual   one workgroup per (pair, strip), one lane per row: the mutual check, matches0 / scores0, one integer add per
 //                  workgroup to n_matches.
+// pxr_match_guided is the same three kernels with a geometric gate in the tile kernel's epilogue: an entry
+// that the pair's two-view model does not admit is masked like a NaN similarity.  k_guided_records computes, once per (pair, row)
+// and (pair, column), everything of the gate that depends on one side only; the tile loop has one text, a template over the
+// argument struct (MatchArgs / GuidedMatchArgs).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,6 +50,7 @@ struct MatchPair {       // one pair, as the host laid it out
 };
 
 struct MatchArgs {
+  static constexpr bool guided = false;
   const float* desc;
   const MatchPair* pairs;
   const MatchItem* items;
@@ -57,6 +62,18 @@ struct MatchArgs {
   int32_t n_pairs, dim, kp;    // kp: k pairs (instructions per tile), a multiple of MT_KSTEP
   float r2, t2;
   int32_t use_ratio, use_dist, mutual;
+};
+
+struct GuidedMatchArgs : MatchArgs {   // pxr_match_guided: the gate's arrays on top; the unguided kernels keep the argument they had
+  static constexpr bool guided = true;
+  const int64_t* row_prefix;   // [n_pairs + 1]: d_pair_offsets
+  const double* xy;            // n_total x 2
+  const int32_t* kind;         // per pair
+  const double* model;         // per pair 9, row-major
+  const double* thr;           // per pair
+  double* rec_row;             // 4 doubles per output row (at pair.out + row), see k_guided_records
+  double* rec_col;             // 4 doubles per column (at pair.col + column)
+  int64_t n_rows;
 };
 
 struct Top2 { float s1; int32_t i1; float s2; };
@@ -96,10 +113,61 @@ __device__ __forceinline__ int32_t match_tests(const Top2& t, bool ratio_on, boo
   return t.i1;
 }
 
-// KP: k pairs a wavefront can hold (registers of A fragments); the LDS tiles are sized by it too
-template <int KP>
-__global__ __launch_bounds__(MT_THREADS) void k_match_tiles(const MatchArgs a) {
+// The records of the geometric gate of pxr_match_guided, one lane per (pair, row) and per (pair, column), float64, every operation
+// rounded once in the order of the specification (include/pixsfm_hip.h):
+//   epipolar    row (l0, l1, l2, ra)    column (u, v, cb, -)
+//   homography  row (px, py, valid, -)  column (u, v, -, -)       valid: 1.0 or 0.0
+// A model with an entry that is not finite gives NaN records (valid = 0): nothing is admissible for it.
+__global__ __launch_bounds__(256) void k_guided_records(const GuidedMatchArgs a) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= a.n_rows + a.n_cols) return;
+  const bool is_row = g < a.n_rows;
+  const int64_t* prefix = is_row ? a.row_prefix : a.col_prefix;
+  const int64_t e = is_row ? g : g - a.n_rows;
+  int lo = 0, hi = a.n_pairs;                 // the pair with prefix[pair] <= e < prefix[pair + 1]
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (prefix[mid] <= e) lo = mid; else hi = mid; }
+  const MatchPair p = a.pairs[lo];
+  const double* M = a.model + 9 * (int64_t)lo;
+  bool finite = true;
+  for (int k = 0; k < 9; ++k) finite = finite && isfinite(M[k]);
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const int64_t src = is_row ? p.a_row + (e - p.out) : p.b_row + (e - p.col);
+  const double x = a.xy[2 * src], y = a.xy[2 * src + 1];
+  double r0 = nan, r1 = nan, r2 = nan, r3 = nan;
+  if (a.kind[lo] == PXR_GUIDE_EPIPOLAR) {
+    if (is_row && finite) {
+      r0 = (M[0] * x + M[1] * y) + M[2];
+      r1 = (M[3] * x + M[4] * y) + M[5];
+      r2 = (M[6] * x + M[7] * y) + M[8];
+      r3 = r0 * r0 + r1 * r1;
+    } else if (finite) {
+      const double m0 = (M[0] * x + M[3] * y) + M[6];
+      const double m1 = (M[1] * x + M[4] * y) + M[7];
+      r0 = x; r1 = y; r2 = m0 * m0 + m1 * m1; r3 = 0.0;
+    }
+  } else {
+    if (is_row) {
+      r2 = 0.0;
+      if (finite) {
+        const double X = (M[0] * x + M[1] * y) + M[2];
+        const double Y = (M[3] * x + M[4] * y) + M[5];
+        const double Wd = (M[6] * x + M[7] * y) + M[8];
+        r0 = X / Wd; r1 = Y / Wd; r2 = Wd > 0.0 ? 1.0 : 0.0; r3 = 0.0;
+      }
+    } else if (finite) { r0 = x; r1 = y; r2 = 0.0; r3 = 0.0; }
+  }
+  double* out = (is_row ? a.rec_row : a.rec_col) + 4 * e;
+  out[0] = r0; out[1] = r1; out[2] = r2; out[3] = r3;
+}
+
+// KP: k pairs a wavefront can hold (registers of A fragments); the LDS tiles are sized by it too.  Args = GuidedMatchArgs (GUIDED): an
+// entry that the pair's model does not admit is masked like a NaN similarity; the strip's 128 row records sit in LDS for the whole
+// sweep (the 32 lanes of a half read the same row: a broadcast), the lane's one column record per tile in registers.
+template <int KP, class Args>
+__global__ __launch_bounds__(MT_THREADS) void k_match_tiles(const Args a) {
+  constexpr bool GUIDED = Args::guided;
   __shared__ float bs[2][KP * 64];
+  __shared__ double row_rec[GUIDED ? MT_ROWS * 4 : 1];
   __shared__ float cp_s1[2][4][MT_COLS];
   __shared__ int32_t cp_i1[2][4][MT_COLS];
   __shared__ float cp_s2[2][4][MT_COLS];
@@ -165,6 +233,17 @@ __global__ __launch_bounds__(MT_THREADS) void k_match_tiles(const MatchArgs a) {
   for (int r = 0; r < 16; ++r) { rt[r].s1 = NEG; rt[r].i1 = -1; rt[r].s2 = NEG; }
 
   if (n_tiles > 0) { fetch(0); stash(0); }
+  int kind = 0;
+  double thr2 = 0.0;
+  if constexpr (GUIDED) {
+    kind = a.kind[it.pair];
+    const double thr = a.thr[it.pair];
+    thr2 = thr * thr;
+    for (int e = tid; e < MT_ROWS * 4; e += MT_THREADS) {       // rows past the pair's end are masked by row < p.na below
+      const int row = it.strip * MT_ROWS + (e >> 2);
+      row_rec[e] = row < p.na ? a.rec_row[4 * (p.out + row) + (e & 3)] : 0.0;
+    }
+  }
   __syncthreads();
 
   const int row_base = it.strip * MT_ROWS + w * 32 + 4 * h;     // + (r & 3) + 8 (r >> 2): the rows of this lane's accumulators
@@ -172,6 +251,13 @@ __global__ __launch_bounds__(MT_THREADS) void k_match_tiles(const MatchArgs a) {
     const int buf = t & 1;
     const bool more = t + 1 < n_tiles;
     if (more) fetch(t + 1);
+
+    double cu = 0.0, cv = 0.0, ccb = 0.0;                       // the column's record: in flight under the instructions below
+    if constexpr (GUIDED) {
+      const int jc = t * MT_COLS + c;
+      const double* cr = a.rec_col + 4 * (p.col + (jc < p.nb ? jc : 0));
+      cu = cr[0]; cv = cr[1]; ccb = cr[2];
+    }
 
     f32x16 acc;
 #pragma unroll
@@ -196,6 +282,19 @@ __global__ __launch_bounds__(MT_THREADS) void k_match_tiles(const MatchArgs a) {
       const int row = row_base + (r & 3) + 8 * (r >> 2);
       float v = acc[r];
       v = (col_ok && row < p.na && v == v) ? v : NEG;           // outside the pair, or NaN: never wins
+      if constexpr (GUIDED) {                                   // nor does an entry the model does not admit
+        const double* rr = &row_rec[4 * (w * 32 + 4 * h + (r & 3) + 8 * (r >> 2))];
+        bool adm;
+        if (kind == PXR_GUIDE_EPIPOLAR) {
+          const double tt = (cu * rr[0] + cv * rr[1]) + rr[2];
+          const double den = rr[3] + ccb;
+          adm = den > 0.0 && tt * tt <= thr2 * den;
+        } else {
+          const double dx = rr[0] - cu, dy = rr[1] - cv;
+          adm = rr[2] > 0.0 && dx * dx + dy * dy <= thr2;
+        }
+        v = adm ? v : NEG;
+      }
       top2_push(rt[r], v, j);
       top2_push(ct, v, row);
     }
@@ -267,10 +366,14 @@ __global__ __launch_bounds__(MT_ROWS) void k_match_mutual(const MatchArgs a) {
   if (threadIdx.x == 0 && total > 0) atomicAdd(&a.n_matches[it.pair], total);
 }
 
+struct GuideIn { const double* d_xy; const int32_t* d_kind; const double* d_model; const double* d_thr; };
+
+// gd: the geometric gate of pxr_match_guided, or NULL for pxr_match_descriptors.  h_ms: [3] = tiles, columns, mutual without a gate,
+// [4] = records, tiles, columns, mutual with one.
 int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim, const float* d_desc,
                       int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets, const pxr_match_options* o,
-                      int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches, double* h_ms) {
-  const char* fn = "pxr_match_descriptors";
+                      int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches, double* h_ms, const GuideIn* gd = nullptr) {
+  const char* fn = gd ? "pxr_match_guided" : "pxr_match_descriptors";
   PXR_REQUIRE(ctx && o, "%s: NULL argument", fn);
   PXR_REQUIRE(n_images >= 0 && n_total >= 0 && n_pairs >= 0, "%s: negative size", fn);
   PXR_REQUIRE(dim >= 1 && dim <= PXR_MATCH_MAX_DIM, "%s: dim = %d is outside [1, %d]", fn, (int)dim, PXR_MATCH_MAX_DIM);
@@ -280,7 +383,11 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
   PXR_REQUIRE(n_images == 0 || d_image_offsets, "%s: NULL d_image_offsets", fn);
   PXR_REQUIRE(n_total == 0 || d_desc, "%s: NULL d_desc", fn);
   PXR_REQUIRE(n_pairs == 0 || (d_pairs && d_pair_offsets && d_n_matches), "%s: NULL d_pairs / d_pair_offsets / d_n_matches", fn);
-  if (h_ms) h_ms[0] = h_ms[1] = h_ms[2] = 0.0;
+  if (gd) {
+    PXR_REQUIRE(n_total == 0 || gd->d_xy, "%s: NULL d_xy", fn);
+    PXR_REQUIRE(n_pairs == 0 || (gd->d_kind && gd->d_model && gd->d_thr), "%s: NULL d_pair_kind / d_pair_model / d_pair_thr", fn);
+  }
+  if (h_ms) for (int k = 0; k < (gd ? 4 : 3); ++k) h_ms[k] = 0.0;
   PXR_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
 
@@ -292,7 +399,18 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
     PXR_HIP(hipMemcpyAsync(pairs.data(), d_pairs, sizeof(int32_t) * pairs.size(), hipMemcpyDeviceToHost, st));
     PXR_HIP(hipMemcpyAsync(pair_off.data(), d_pair_offsets, sizeof(int64_t) * pair_off.size(), hipMemcpyDeviceToHost, st));
   }
+  std::vector<int32_t> kinds(gd ? (size_t)n_pairs : 0);
+  std::vector<double> thrs(gd ? (size_t)n_pairs : 0);
+  if (gd && n_pairs > 0) {
+    PXR_HIP(hipMemcpyAsync(kinds.data(), gd->d_kind, sizeof(int32_t) * kinds.size(), hipMemcpyDeviceToHost, st));
+    PXR_HIP(hipMemcpyAsync(thrs.data(), gd->d_thr, sizeof(double) * thrs.size(), hipMemcpyDeviceToHost, st));
+  }
   PXR_HIP(hipStreamSynchronize(st));
+  for (size_t p = 0; p < kinds.size(); ++p) {
+    PXR_REQUIRE(kinds[p] == PXR_GUIDE_EPIPOLAR || kinds[p] == PXR_GUIDE_HOMOGRAPHY, "%s: d_pair_kind[%d] = %d is neither PXR_GUIDE_EPIPOLAR nor "
+                "PXR_GUIDE_HOMOGRAPHY", fn, (int)p, (int)kinds[p]);
+    PXR_REQUIRE(thrs[p] >= 0.0, "%s: d_pair_thr[%d] is NaN or negative", fn, (int)p);
+  }
   PXR_REQUIRE(off[0] == 0, "%s: d_image_offsets[0] = %lld, not 0", fn, (long long)off[0]);
   for (int32_t m = 0; m < n_images; ++m)
     PXR_REQUIRE(off[m + 1] >= off[m], "%s: d_image_offsets is not monotone at image %d", fn, (int)m);
@@ -332,10 +450,11 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
   const size_t o_pairs = cv.take(hp.size(), sizeof(MatchPair)), o_items = cv.take(items.size(), sizeof(MatchItem));
   const size_t o_colp = cv.take(col_prefix.size(), 8), o_m1 = cv.take((size_t)cols, 4);
   const size_t o_s1 = cv.take((size_t)parts, 4), o_i1 = cv.take((size_t)parts, 4), o_s2 = cv.take((size_t)parts, 4);
+  const size_t o_rrow = cv.take(gd ? (size_t)rows * 4 : 0, 8), o_rcol = cv.take(gd ? (size_t)cols * 4 : 0, 8);
   if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
   char* ws = static_cast<char*>(ctx->d_workspace);
 
-  MatchArgs a;
+  GuidedMatchArgs a{};
   a.desc = d_desc;
   a.pairs = (const MatchPair*)(ws + o_pairs); a.items = (const MatchItem*)(ws + o_items); a.col_prefix = (const int64_t*)(ws + o_colp);
   a.part_s1 = (float*)(ws + o_s1); a.part_i1 = (int32_t*)(ws + o_i1); a.part_s2 = (float*)(ws + o_s2);
@@ -346,8 +465,13 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
   a.r2 = (float)(o->ratio_threshold * o->ratio_threshold);
   a.t2 = (float)(o->distance_threshold * o->distance_threshold);
   a.use_ratio = o->ratio_threshold > 0.0; a.use_dist = o->distance_threshold > 0.0; a.mutual = mutual;
+  if (gd) {
+    a.row_prefix = d_pair_offsets; a.xy = gd->d_xy; a.kind = gd->d_kind; a.model = gd->d_model; a.thr = gd->d_thr;
+    a.rec_row = (double*)(ws + o_rrow); a.rec_col = (double*)(ws + o_rcol); a.n_rows = rows;
+  }
+  const MatchArgs& au = a;                               // what the unguided kernels take
 
-  StageTimer<4> timer(st, h_ms);                         // tiles | columns | mutual
+  StageTimer<5> timer(st, h_ms);                         // records (with a gate) | tiles | columns | mutual
   if (int rc = timer.create(fn)) return rc;
 
   int rc = hip_check(hipMemcpyAsync(ws + o_pairs, hp.data(), sizeof(MatchPair) * hp.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
@@ -358,18 +482,28 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
   if (rc != PXR_OK) return rc;
 
   const dim3 grid((unsigned)items.size());
-  timer.mark(0);
-  if (a.kp <= 64) hipLaunchKernelGGL(k_match_tiles<64>, grid, dim3(MT_THREADS), 0, st, a);
-  else if (a.kp <= 128) hipLaunchKernelGGL(k_match_tiles<128>, grid, dim3(MT_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(k_match_tiles<256>, grid, dim3(MT_THREADS), 0, st, a);
+  if (gd) {
+    timer.mark(0);
+    hipLaunchKernelGGL(k_guided_records, dim3((unsigned)((rows + cols + 255) / 256)), dim3(256), 0, st, a);
+  }
   timer.mark(1);
-  if (mutual && cols > 0) hipLaunchKernelGGL(k_match_columns, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, a);
+  if (gd) {
+    if (a.kp <= 64) hipLaunchKernelGGL((k_match_tiles<64, GuidedMatchArgs>), grid, dim3(MT_THREADS), 0, st, a);
+    else if (a.kp <= 128) hipLaunchKernelGGL((k_match_tiles<128, GuidedMatchArgs>), grid, dim3(MT_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((k_match_tiles<256, GuidedMatchArgs>), grid, dim3(MT_THREADS), 0, st, a);
+  } else {
+    if (a.kp <= 64) hipLaunchKernelGGL((k_match_tiles<64, MatchArgs>), grid, dim3(MT_THREADS), 0, st, au);
+    else if (a.kp <= 128) hipLaunchKernelGGL((k_match_tiles<128, MatchArgs>), grid, dim3(MT_THREADS), 0, st, au);
+    else hipLaunchKernelGGL((k_match_tiles<256, MatchArgs>), grid, dim3(MT_THREADS), 0, st, au);
+  }
   timer.mark(2);
-  hipLaunchKernelGGL(k_match_mutual, grid, dim3(MT_ROWS), 0, st, a);
+  if (mutual && cols > 0) hipLaunchKernelGGL(k_match_columns, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, au);
   timer.mark(3);
+  hipLaunchKernelGGL(k_match_mutual, grid, dim3(MT_ROWS), 0, st, au);
+  timer.mark(4);
   rc = hip_check(hipGetLastError(), "k_match_mutual launch");
-  const int from[3] = {0, 1, 2};
-  return rc == PXR_OK ? timer.read(from, 3) : rc;
+  const int from[4] = {0, 1, 2, 3};
+  return rc == PXR_OK ? (gd ? timer.read(from, 4) : timer.read(from + 1, 3)) : rc;
 }
 
 }  // namespace
@@ -394,4 +528,24 @@ extern "C" int pxr_match_descriptors_timed(pxr_ctx* ctx, int32_t n_images, const
   PXR_REQUIRE(h_kernel_ms, "pxr_match_descriptors_timed: NULL h_kernel_ms");
   return pxr::match_descriptors(ctx, n_images, d_image_offsets, n_total, dim, d_desc, n_pairs, d_pairs, d_pair_offsets, options,
                                 d_matches0, d_scores0, d_n_matches, h_kernel_ms);
+}
+
+extern "C" int pxr_match_guided(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim, const float* d_desc,
+                                const double* d_xy, int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets,
+                                const int32_t* d_pair_kind, const double* d_pair_model, const double* d_pair_thr,
+                                const pxr_match_options* options, int32_t* d_matches0, float* d_scores0, int32_t* d_n_matches) {
+  const pxr::GuideIn gd = {d_xy, d_pair_kind, d_pair_model, d_pair_thr};
+  return pxr::match_descriptors(ctx, n_images, d_image_offsets, n_total, dim, d_desc, n_pairs, d_pairs, d_pair_offsets, options,
+                                d_matches0, d_scores0, d_n_matches, nullptr, &gd);
+}
+
+extern "C" int pxr_match_guided_timed(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offsets, int64_t n_total, int32_t dim,
+                                      const float* d_desc, const double* d_xy, int32_t n_pairs, const int32_t* d_pairs,
+                                      const int64_t* d_pair_offsets, const int32_t* d_pair_kind, const double* d_pair_model,
+                                      const double* d_pair_thr, const pxr_match_options* options, int32_t* d_matches0, float* d_scores0,
+                                      int32_t* d_n_matches, double* h_kernel_ms) {
+  PXR_REQUIRE(h_kernel_ms, "pxr_match_guided_timed: NULL h_kernel_ms");
+  const pxr::GuideIn gd = {d_xy, d_pair_kind, d_pair_model, d_pair_thr};
+  return pxr::match_descriptors(ctx, n_images, d_image_offsets, n_total, dim, d_desc, n_pairs, d_pairs, d_pair_offsets, options,
+                                d_matches0, d_scores0, d_n_matches, h_kernel_ms, &gd);
 }

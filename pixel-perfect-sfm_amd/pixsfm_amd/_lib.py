@@ -216,6 +216,9 @@ _SIGNATURES = {
     "pxr_match_default_options": (None, [C.POINTER(MatchOptions)]),
     "pxr_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pxr_match_guided": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MatchOptions), C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "pxr_vocab_train": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_int32)]),
     "pxr_vlad_aggregate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
@@ -278,10 +281,11 @@ _SIGNATURES = {
 }
 # every *_timed entry point: the arguments of its plain twin, then the array that takes the stages' HIP-event times
 for _name in ("pxr_triangulate_tracks", "pxr_absolute_pose", "pxr_two_view_geometry", "pxr_homography", "pxr_fundamental",
-              "pxr_match_descriptors", "pxr_mapper_visibility", "pxr_sift_pyramid", "pxr_sift_detect", "pxr_sift_describe",
+              "pxr_match_descriptors", "pxr_match_guided", "pxr_mapper_visibility", "pxr_sift_pyramid", "pxr_sift_detect", "pxr_sift_describe",
               "pxr_vocab_train", "pxr_vlad_aggregate", "pxr_retrieval_topk", "pxr_cloud_nearest", "pxr_cloud_voxel_fractions"):
     _SIGNATURES[_name + "_timed"] = (_SIGNATURES[_name][0], _SIGNATURES[_name][1] + [C.POINTER(C.c_double)])
 LINEAR_AUTO, LINEAR_DIRECT, LINEAR_ITERATIVE = 0, 1, 2
+GUIDE_EPIPOLAR, GUIDE_HOMOGRAPHY = 0, 1      # PXR_GUIDE_*: the kind of a pair's model in pxr_match_guided
 COMM_ID_BYTES = 128
 
 _lib = None

@@ -19,7 +19,7 @@ from .localization import (QueryBundleAdjuster, QueryBundleOptimizer, QueryKeypo
 from .extract import (FeatureExtractor, extract_patchdata_from_graph, features_from_graph,  # noqa: F401,E402
                       features_from_image_list, features_from_reconstruction)
 from .triangulation import TrackTriangulator  # noqa: F401,E402
-from .matching import DescriptorMatcher, pairs_2d3d_from_matches  # noqa: F401,E402
+from .matching import DescriptorMatcher, guided_model, guided_threshold, pairs_2d3d_from_matches  # noqa: F401,E402
 from .two_view import TwoViewVerifier, essential_matrix_estimation  # noqa: F401,E402
 from .homography import TwoViewClassifier, homography_matrix_estimation, two_view_config  # noqa: F401,E402
 from .fundamental import fundamental_matrix_estimation, two_view_config_uncalibrated  # noqa: F401,E402

@@ -1145,9 +1145,11 @@ class MatchProblem:
     descriptors: a list of (n, D) float32 host arrays or DeviceArrays (one per image; n may be 0), or one (n_total, D) array
     with image_offsets (n_images + 1), which is used in place when it is a DeviceArray (a DeviceArray inside a list is staged
     through the host).  pairs: (n_pairs, 2) image indices.  Every image is uploaded once, however many pairs name it.
+    keypoints (run_guided only): per image an (n, 2) float64 array in the frame of the pairs' models, or one (n_total, 2) array
+    (a DeviceArray is used in place), row-aligned with the descriptors.
     """
 
-    def __init__(self, ctx, descriptors, pairs, image_offsets=None):
+    def __init__(self, ctx, descriptors, pairs, image_offsets=None, keypoints=None):
         self.ctx = ctx
         d = descriptors if isinstance(descriptors, DescriptorSet) else DescriptorSet(ctx, descriptors, image_offsets)
         self.dim, self.d_desc, self.image_offsets, self.n_images, self.n_total, self.d_offsets = (d.dim, d.d_desc, d.image_offsets, d.n_images,
@@ -1164,6 +1166,41 @@ class MatchProblem:
         self.d_pairs = ctx.to_device(self.pairs, np.int32)
         self.d_pair_offsets = ctx.to_device(self.pair_offsets, np.int64)
         self.kernel_ms = None
+        self.d_xy = None
+        if isinstance(keypoints, DeviceArray):
+            self.d_xy = keypoints
+        elif keypoints is not None:
+            if not isinstance(keypoints, np.ndarray):
+                keypoints = [np.asarray(k, dtype=np.float64).reshape(-1, 2) for k in keypoints]
+                keypoints = np.concatenate(keypoints) if keypoints else np.empty((0, 2))
+            self.d_xy = ctx.to_device(np.asarray(keypoints, dtype=np.float64).reshape(-1, 2), np.float64)
+        if self.d_xy is not None and tuple(self.d_xy.shape) != (self.n_total, 2):
+            raise ValueError("keypoints must hold one (x, y) per descriptor: (%d, 2), not %s" % (self.n_total, tuple(self.d_xy.shape)))
+
+    def _outputs(self, out):
+        ctx, n_rows = self.ctx, int(self.pair_offsets[-1])
+        return out if out is not None else (ctx.empty((n_rows,), np.int32), ctx.empty((n_rows,), np.float32),
+                                            ctx.empty((self.n_pairs,), np.int32))
+
+    def run_guided(self, kinds, models, thresholds, timed=False, out=None, **options):
+        """Run the guided kernels (pxr_match_guided): per pair a kind (_lib.GUIDE_EPIPOLAR / GUIDE_HOMOGRAPHY), a 3 x 3 model and a
+        threshold in the keypoints' units; only candidates the model admits compete.  Needs `keypoints`.  Returns what run returns;
+        timed keeps self.kernel_ms {"records", "tiles", "columns", "mutual"}."""
+        ctx = self.ctx
+        if self.d_xy is None:
+            raise ValueError("run_guided needs the keypoints of the images (MatchProblem(..., keypoints=...))")
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32).reshape(-1)
+        models = np.ascontiguousarray(models, dtype=np.float64).reshape(-1, 9)
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        if not (len(kinds) == len(models) == len(thresholds) == self.n_pairs):
+            raise ValueError("kinds, models and thresholds must hold one entry per pair (%d)" % self.n_pairs)
+        opts = match_options(**options)
+        d_m, d_s, d_n = self._outputs(out)
+        d_kind, d_model, d_thr = ctx.to_device(kinds, np.int32), ctx.to_device(models, np.float64), ctx.to_device(thresholds, np.float64)
+        args = (ctx.handle, self.n_images, self.d_offsets.ptr, self.n_total, self.dim, self.d_desc.ptr, self.d_xy.ptr, self.n_pairs,
+                self.d_pairs.ptr, self.d_pair_offsets.ptr, d_kind.ptr, d_model.ptr, d_thr.ptr, C.byref(opts), d_m.ptr, d_s.ptr, d_n.ptr)
+        self.kernel_ms = _launch(ctx, "pxr_match_guided", args, ("records", "tiles", "columns", "mutual"), timed) or self.kernel_ms
+        return d_m, d_s, d_n
 
     def run(self, timed=False, out=None, **options):
         """Run the kernels (pxr_match_descriptors) with match_options(**options).  Returns the device arrays (matches0
@@ -1172,9 +1209,7 @@ class MatchProblem:
         self.kernel_ms {"tiles", "columns", "mutual"} (milliseconds)."""
         ctx = self.ctx
         opts = match_options(**options)
-        n_rows = int(self.pair_offsets[-1])
-        d_m, d_s, d_n = out if out is not None else (ctx.empty((n_rows,), np.int32), ctx.empty((n_rows,), np.float32),
-                                                      ctx.empty((self.n_pairs,), np.int32))
+        d_m, d_s, d_n = self._outputs(out)
         args = (ctx.handle, self.n_images, self.d_offsets.ptr, self.n_total, self.dim, self.d_desc.ptr, self.n_pairs, self.d_pairs.ptr,
                 self.d_pair_offsets.ptr, C.byref(opts), d_m.ptr, d_s.ptr, d_n.ptr)
         self.kernel_ms = _launch(ctx, "pxr_match_descriptors", args, ("tiles", "columns", "mutual"), timed) or self.kernel_ms
