@@ -1,21 +1,3 @@
-// csrc/pxr_abspose.hip as host code over the workgroup stand-in runtime of workgroup/hip/hip_runtime.h (see there).
-#include <cstdarg>
-#include <cstdio>
-
-#include "workgroup/hip/hip_runtime.h"
-uint3e threadIdx, blockIdx, blockDim;
-EmuBlock emu_block;
-#include "pxr_internal.h"
-static thread_local char g_err[512];
-namespace pxr {
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-}  // namespace pxr
-extern "C" const char* emu_last_error() { return g_err; }
-extern "C" pxr_ctx* emu_ctx() { return new pxr_ctx(); }
+// csrc/pxr_abspose.hip as host code over the stand-in runtime (on_host.h, hip/hip_runtime.h).
+#include "on_host.h"
 #include "pxr_abspose.hip"

@@ -1,32 +1,8 @@
-// csrc/pxr_cloud.hip as host code over the stand-in runtime of matrix/hip/hip_runtime.h (see there), plus the one primitive that
-// file lacks: the 64-bit compare-and-swap (lanes run one after another here, so a plain read-compare-write states it).
+// csrc/pxr_cloud.hip as host code over the stand-in runtime (on_host.h, hip/hip_runtime.h).
 // With -DCLOUD_ON_HOST_MAIN: a stand-alone program (for -fsanitize=address,undefined builds) that runs both entry points on
 // synthetic clouds (command line: n_ref n_query max_dist voxel_size) with every array allocated at its exact size -- rows that are
 // not valid in both clouds, points on cell faces, duplicates -- checks the result against the brute-force search and prints counts.
-#include <cstdarg>
-#include <cstdio>
-
-#include "matrix/hip/hip_runtime.h"
-uint3e threadIdx, blockIdx, blockDim;
-EmuBlock emu_block;
-inline unsigned long long atomicCAS(unsigned long long* p, unsigned long long expected, unsigned long long desired) {
-  const unsigned long long was = *p;
-  if (was == expected) *p = desired;
-  return was;
-}
-#include "pxr_internal.h"
-static thread_local char g_err[512];
-namespace pxr {
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-}  // namespace pxr
-extern "C" const char* emu_last_error() { return g_err; }
-extern "C" pxr_ctx* emu_ctx() { return new pxr_ctx(); }
+#include "on_host.h"
 #include "pxr_cloud.hip"
 
 #ifdef CLOUD_ON_HOST_MAIN
@@ -48,10 +24,10 @@ int main(int argc, char** argv) {
   std::vector<double> ref, query;
   fill(ref, n_ref);
   fill(query, n_query);
-  pxr_ctx ctx;
+  pxr_ctx* ctx = emu_ctx();
   std::vector<int32_t> idx((size_t)n_query);
   std::vector<double> d2((size_t)n_query);
-  int rc = pxr_cloud_nearest(&ctx, n_ref, ref.data(), n_query, query.data(), max_dist, idx.data(), d2.data());
+  int rc = pxr_cloud_nearest(ctx, n_ref, ref.data(), n_query, query.data(), max_dist, idx.data(), d2.data());
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
   int64_t found = 0, wrong = 0;
   const double m2 = max_dist * max_dist;
@@ -73,11 +49,11 @@ int main(int argc, char** argv) {
   const double tol[3] = {0.5 * max_dist, max_dist, 2.0 * max_dist};
   double frac[3] = {-7.0, -7.0, -7.0};
   int64_t n_vox = -7;
-  rc = pxr_cloud_voxel_fractions(&ctx, n_query, query.data(), d2.data(), voxel, 3, tol, frac, &n_vox);
+  rc = pxr_cloud_voxel_fractions(ctx, n_query, query.data(), d2.data(), voxel, 3, tol, frac, &n_vox);
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
   printf("queries %lld found %lld wrong %lld voxels %lld fraction %.17g\n", (long long)n_query, (long long)found, (long long)wrong,
          (long long)n_vox, frac[2]);
-  free(ctx.d_workspace);
+  emu_ctx_free(ctx);
   return 0;
 }
 #endif

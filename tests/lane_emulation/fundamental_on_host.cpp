@@ -1,26 +1,8 @@
-// csrc/pxr_fundamental.hip as host code over the workgroup stand-in runtime of workgroup/hip/hip_runtime.h (see there).
+// csrc/pxr_fundamental.hip as host code over the stand-in runtime (on_host.h, hip/hip_runtime.h).
 // With -DFUNDAMENTAL_ON_HOST_MAIN: a stand-alone program (for -fsanitize=address,undefined builds) that runs synthetic pairs of
 // the match counts given on the command line -- 0 is an empty pair -- through a focal length stated 0.7 times too long on odd
 // pairs, and prints every pair's status, inliers and trials.
-#include <cstdarg>
-#include <cstdio>
-
-#include "workgroup/hip/hip_runtime.h"
-uint3e threadIdx, blockIdx, blockDim;
-EmuBlock emu_block;
-#include "pxr_internal.h"
-static thread_local char g_err[512];
-namespace pxr {
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-}  // namespace pxr
-extern "C" const char* emu_last_error() { return g_err; }
-extern "C" pxr_ctx* emu_ctx() { return new pxr_ctx(); }
+#include "on_host.h"
 #include "pxr_fundamental.hip"
 
 #ifdef FUNDAMENTAL_ON_HOST_MAIN
@@ -61,8 +43,7 @@ int main(int argc, char** argv) {
   if (rc) { printf("error %d: %s\n", rc, emu_last_error()); return 1; }
   for (int32_t p = 0; p < T; ++p)
     printf("pair %d: %lld matches, status %d, %d inliers, %d trials\n", p, (long long)(off[p + 1] - off[p]), st[p], ni[p], nt[p]);
-  if (ctx->d_workspace) free(ctx->d_workspace);
-  delete ctx;
+  emu_ctx_free(ctx);
   return 0;
 }
 #endif

@@ -1,4 +1,4 @@
-// csrc/pxr_match.hip as host code over the stand-in runtime of matrix/hip/hip_runtime.h, for pxr_match_guided
+// csrc/pxr_match.hip as host code over the stand-in runtime (on_host.h, hip/hip_runtime.h), for pxr_match_guided
 // (tests/test_guided_matching_lanes_cpu.py): the translation unit of match_on_host.cpp, which exports every entry point of the file.
 // With -DGUIDED_ON_HOST_MAIN: a stand-alone program (for -fsanitize=address,undefined builds) that runs pxr_match_guided on one
 // pair of (1, 1, 1), one of (129, 65, 128) and a batch over images of 0, 1, 33, 129 and 200 descriptors with the empty image on
@@ -60,12 +60,12 @@ int run(pxr_ctx* ctx, const Batch& b, const std::vector<int32_t>& pairs, const c
 
 int main() {
   std::mt19937_64 rng(5);
-  pxr_ctx ctx;
+  pxr_ctx* ctx = emu_ctx();
   int bad = 0;
-  bad |= run(&ctx, make_batch({1, 1}, 1, rng), {0, 1, 1, 0}, "1x1x1");
-  bad |= run(&ctx, make_batch({129, 65}, 128, rng), {0, 1, 0, 1}, "129x65x128");
-  bad |= run(&ctx, make_batch({0, 1, 33, 129, 200}, 128, rng), {4, 4, 3, 4, 3, 4, 4, 3, 0, 2, 2, 0, 1, 3}, "batch");
-  free(ctx.d_workspace);
+  bad |= run(ctx, make_batch({1, 1}, 1, rng), {0, 1, 1, 0}, "1x1x1");
+  bad |= run(ctx, make_batch({129, 65}, 128, rng), {0, 1, 0, 1}, "129x65x128");
+  bad |= run(ctx, make_batch({0, 1, 33, 129, 200}, 128, rng), {4, 4, 3, 4, 3, 4, 4, 3, 0, 2, 2, 0, 1, 3}, "batch");
+  emu_ctx_free(ctx);
   return bad;
 }
 #endif

@@ -1,27 +1,9 @@
-// csrc/pxr_mapper.hip as host code over the workgroup stand-in runtime of workgroup/hip/hip_runtime.h (see there).
+// csrc/pxr_mapper.hip as host code over the stand-in runtime (on_host.h, hip/hip_runtime.h).
 // With -DMAPPING_ON_HOST_MAIN: a stand-alone program (for -fsanitize=address,undefined builds) that runs one scene whose images
 // have the observation counts given on the command line -- every third observation on a track without a point, every seventh
 // with a keypoint that is not finite, the second image masked out -- with every array allocated at its exact size, and prints
 // per image the visible count, the score and the offset.
-#include <cstdarg>
-#include <cstdio>
-
-#include "workgroup/hip/hip_runtime.h"
-uint3e threadIdx, blockIdx, blockDim;
-EmuBlock emu_block;
-#include "pxr_internal.h"
-static thread_local char g_err[512];
-namespace pxr {
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-}  // namespace pxr
-extern "C" const char* emu_last_error() { return g_err; }
-extern "C" pxr_ctx* emu_ctx() { return new pxr_ctx(); }
+#include "on_host.h"
 #include "pxr_mapper.hip"
 
 #ifdef MAPPING_ON_HOST_MAIN
@@ -64,9 +46,9 @@ int main(int argc, char** argv) {
   std::vector<int64_t> score(n_images), corr_off(n_images + 1), corr_obs(n_obs);
   std::vector<double> corr_xy(2 * n_obs), corr_xyz(3 * n_obs);
   int64_t n_corr = -1;
-  pxr_ctx ctx;
+  pxr_ctx* ctx = emu_ctx();
   for (int levels : {1, 6}) {
-    const int rc = pxr_mapper_visibility(&ctx, &v, obs_track.data(), image_off.data(), image_obs.data(), xyz.data(), status.data(),
+    const int rc = pxr_mapper_visibility(ctx, &v, obs_track.data(), image_off.data(), image_obs.data(), xyz.data(), status.data(),
                                          mask.data(), cam_size.data(), levels, n_visible.data(), score.data(), corr_off.data(),
                                          corr_obs.data(), corr_xy.data(), corr_xyz.data(), &n_corr);
     if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
@@ -75,7 +57,7 @@ int main(int argc, char** argv) {
              n_visible[i], (long long)score[i], (long long)corr_off[i]);
     printf("L %d total %lld\n", levels, (long long)n_corr);
   }
-  free(ctx.d_workspace);
+  emu_ctx_free(ctx);
   return 0;
 }
 #endif

@@ -1,26 +1,8 @@
-// csrc/pxr_retrieval.hip as host code over the stand-in runtime of matrix/hip/hip_runtime.h (see there).
+// csrc/pxr_retrieval.hip as host code over the stand-in runtime (on_host.h, hip/hip_runtime.h).
 // With -DRETRIEVAL_ON_HOST_MAIN: a stand-alone program (for -fsanitize=address,undefined builds) that trains a vocabulary, aggregates
 // and selects on synthetic descriptors (command line: n_images rows_per_image dim n_clusters num_matched) with every array allocated
 // at its exact size -- images of different sizes, one of them empty, one row that is not valid -- and prints the counts.
-#include <cstdarg>
-#include <cstdio>
-
-#include "matrix/hip/hip_runtime.h"
-uint3e threadIdx, blockIdx, blockDim;
-EmuBlock emu_block;
-#include "pxr_internal.h"
-static thread_local char g_err[512];
-namespace pxr {
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-}  // namespace pxr
-extern "C" const char* emu_last_error() { return g_err; }
-extern "C" pxr_ctx* emu_ctx() { return new pxr_ctx(); }
+#include "on_host.h"
 #include "pxr_retrieval.hip"
 
 #ifdef RETRIEVAL_ON_HOST_MAIN
@@ -44,18 +26,18 @@ int main(int argc, char** argv) {
     for (int k = 0; k < dim; ++k) desc[(size_t)i * dim + k] = (float)(desc[(size_t)i * dim + k] / std::sqrt(n2 > 0 ? n2 : 1.0));
   }
   if (n_total > 3) desc[(size_t)3 * dim] = std::numeric_limits<float>::quiet_NaN();
-  pxr_ctx ctx;
+  pxr_ctx* ctx = emu_ctx();
   std::vector<float> C((size_t)K * dim), G((size_t)n_images * K * dim);
   std::vector<int32_t> cnt((size_t)K), assign((size_t)n_total), counts((size_t)n_images * K);
   int32_t n_empty = -1;
-  int rc = pxr_vocab_train(&ctx, n_total, dim, desc.data(), K, 2, n_total - 5, C.data(), cnt.data(), &n_empty);
+  int rc = pxr_vocab_train(ctx, n_total, dim, desc.data(), K, 2, n_total - 5, C.data(), cnt.data(), &n_empty);
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
-  rc = pxr_vlad_aggregate(&ctx, n_images, off.data(), n_total, dim, desc.data(), K, C.data(), G.data(), assign.data(), counts.data());
+  rc = pxr_vlad_aggregate(ctx, n_images, off.data(), n_total, dim, desc.data(), K, C.data(), G.data(), assign.data(), counts.data());
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
   std::vector<int32_t> self((size_t)n_images), top((size_t)n_images * num_matched), found((size_t)n_images);
   std::vector<float> top_sim((size_t)n_images * num_matched);
   for (int m = 0; m < n_images; ++m) self[(size_t)m] = m;
-  rc = pxr_retrieval_topk(&ctx, n_images, n_images, K * dim, G.data(), G.data(), self.data(), nullptr, num_matched,
+  rc = pxr_retrieval_topk(ctx, n_images, n_images, K * dim, G.data(), G.data(), self.data(), nullptr, num_matched,
                           std::numeric_limits<double>::infinity(), top.data(), top_sim.data(), found.data());
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
   int64_t n_assigned = 0, n_counted = 0, n_found = 0;
@@ -64,7 +46,7 @@ int main(int argc, char** argv) {
   for (int32_t f : found) n_found += f;
   printf("rows %lld assigned %lld counted %lld empty %d found %lld\n", (long long)n_total, (long long)n_assigned, (long long)n_counted,
          (int)n_empty, (long long)n_found);
-  free(ctx.d_workspace);
+  emu_ctx_free(ctx);
   return 0;
 }
 #endif

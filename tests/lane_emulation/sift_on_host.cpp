@@ -1,28 +1,10 @@
-// csrc/pxr_sift.hip as host code over the workgroup stand-in runtime of workgroup/hip/hip_runtime.h (see there).
+// csrc/pxr_sift.hip as host code over the stand-in runtime (on_host.h, hip/hip_runtime.h).
 // With -DSIFT_ON_HOST_MAIN: a stand-alone program (for -fsanitize=address,undefined builds) that runs pyramid, detect and describe
 // on a synthetic h x w image (command line: h w first_octave capacity) with every array allocated at its exact size -- the
 // pyramid at pxr_sift_pyramid_bytes, the outputs at `capacity` rows, below the number found when capacity is small -- and prints
 // the counts.  The keypoints given to describe include one that is not finite, one with a negative sigma, one far outside the
 // image and one whose window is larger than its octave.
-#include <cstdarg>
-#include <cstdio>
-
-#include "workgroup/hip/hip_runtime.h"
-uint3e threadIdx, blockIdx, blockDim;
-EmuBlock emu_block;
-#include "pxr_internal.h"
-static thread_local char g_err[512];
-namespace pxr {
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-}  // namespace pxr
-extern "C" const char* emu_last_error() { return g_err; }
-extern "C" pxr_ctx* emu_ctx() { return new pxr_ctx(); }
+#include "on_host.h"
 #include "pxr_sift.hip"
 
 #ifdef SIFT_ON_HOST_MAIN
@@ -41,17 +23,17 @@ int main(int argc, char** argv) {
   pxr_sift_default_options(&opt);
   opt.first_octave = first;
   int64_t bytes = -1;
-  pxr_ctx ctx;
+  pxr_ctx* ctx = emu_ctx();
   int rc = pxr_sift_pyramid_bytes(h, w, &opt, &bytes);
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
   std::vector<float> pyramid((size_t)bytes / 4);
-  rc = pxr_sift_pyramid(&ctx, image.data(), PXR_U8, h, w, &opt, pyramid.data());
+  rc = pxr_sift_pyramid(ctx, image.data(), PXR_U8, h, w, &opt, pyramid.data());
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
   std::vector<double> kp((size_t)capacity * 4);
   std::vector<int32_t> rec((size_t)capacity * 4);
   std::vector<float> resp((size_t)capacity);
   int64_t found = -1;
-  rc = pxr_sift_detect(&ctx, pyramid.data(), h, w, &opt, capacity, kp.data(), rec.data(), resp.data(), &found);
+  rc = pxr_sift_detect(ctx, pyramid.data(), h, w, &opt, capacity, kp.data(), rec.data(), resp.data(), &found);
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
   const int64_t n = std::min(found, capacity);
   std::vector<double> q(kp.begin(), kp.begin() + 4 * n);
@@ -67,13 +49,13 @@ int main(int argc, char** argv) {
   const int64_t nq = n + 5;
   std::vector<float> desc((size_t)nq * 128);
   std::vector<uint8_t> valid((size_t)nq);
-  rc = pxr_sift_describe(&ctx, pyramid.data(), h, w, &opt, nq, q.data(), desc.data(), valid.data());
+  rc = pxr_sift_describe(ctx, pyramid.data(), h, w, &opt, nq, q.data(), desc.data(), valid.data());
   if (rc) { printf("error %d: %s\n", rc, g_err); return 1; }
   int64_t n_valid = 0;
   for (int64_t i = 0; i < n; ++i) n_valid += valid[i];
   printf("found %lld written %lld valid %lld extra %d %d %d %d %d\n", (long long)found, (long long)n, (long long)n_valid, valid[n], valid[n + 1],
          valid[n + 2], valid[n + 3], valid[n + 4]);
-  free(ctx.d_workspace);
+  emu_ctx_free(ctx);
   return 0;
 }
 #endif

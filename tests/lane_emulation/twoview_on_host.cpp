@@ -1,25 +1,7 @@
-// csrc/pxr_twoview.hip as host code over the workgroup stand-in runtime of workgroup/hip/hip_runtime.h (see there).
+// csrc/pxr_twoview.hip as host code over the stand-in runtime (on_host.h, hip/hip_runtime.h).
 // With -DTWOVIEW_ON_HOST_MAIN: a stand-alone program (for -fsanitize=address,undefined builds) that runs synthetic pairs of the
 // match counts given on the command line -- 0 is an empty pair -- and prints every pair's status, inliers and trials.
-#include <cstdarg>
-#include <cstdio>
-
-#include "workgroup/hip/hip_runtime.h"
-uint3e threadIdx, blockIdx, blockDim;
-EmuBlock emu_block;
-#include "pxr_internal.h"
-static thread_local char g_err[512];
-namespace pxr {
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-}  // namespace pxr
-extern "C" const char* emu_last_error() { return g_err; }
-extern "C" pxr_ctx* emu_ctx() { return new pxr_ctx(); }
+#include "on_host.h"
 #include "pxr_twoview.hip"
 
 #ifdef TWOVIEW_ON_HOST_MAIN
@@ -61,8 +43,7 @@ int main(int argc, char** argv) {
                              &o, q.data(), t.data(), E.data(), st.data(), ni.data(), nt.data(), inl.data(), err.data());
   if (rc) { printf("error %d: %s\n", rc, emu_last_error()); return 1; }
   for (int32_t p = 0; p < T; ++p) printf("pair %d with its pose given: status %d, %d inliers, %d trials\n", p, st[p], ni[p], nt[p]);
-  if (ctx->d_workspace) free(ctx->d_workspace);
-  delete ctx;
+  emu_ctx_free(ctx);
   return 0;
 }
 #endif

@@ -1,47 +1,23 @@
-"""The source of the absolute-pose kernels, run lane by lane on the CPU: csrc/pxr_abspose.hip is compiled as host C++ over a
-stand-in runtime (tests/lane_emulation/workgroup: a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through an
+"""The source of the absolute-pose kernels, run lane by lane on the CPU: csrc/pxr_abspose.hip is compiled as host C++ over the
+stand-in runtime of tests/lane_emulation (a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through an
 exchange buffer) and held to the numpy reference like the GPU test does -- the sample hash, the P3P solver, the keys and the
 stop rule across the four wavefronts of a workgroup, the workgroup sums of the refinement, the compaction and the host-side
 validation are checked without a GPU.  What only hardware can show (LDS behaviour, occupancy, the device's libm) stays with
 tests/test_abspose_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import abspose_cases as ac
+import lanes
 import triangulation_cases as tc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
+from lanes import p as _p
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = _clang()       # the device headers use clang's vector types: the compiler that hipcc drives, as a plain host compiler
-    assert cxx, "no clang++ next to hipcc"
-    out = str(tmp_path_factory.mktemp("lanes") / "libabs_lanes.so")
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off",
-                           "-I", os.path.join(HERE, "workgroup"), "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "abspose_on_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return lanes.load(tmp_path_factory, "abspose_on_host.cpp")
 
 
 def _run(emu, batch, qvec=None, tvec=None, **options):
@@ -59,8 +35,7 @@ def _run(emu, batch, qvec=None, tvec=None, **options):
     inl, err = np.full(N, 9, np.uint8), np.full(N, -1.0)
     rc = lib.pxr_absolute_pose(ctx, C.c_int32(T), _p(off), C.c_int64(N), _p(xy), _p(xyz), _p(qc), C.c_int32(len(cm)), _p(cm), _p(cp),
                                C.byref(opts), _p(q), _p(t), _p(st), _p(ni), _p(nt), _p(inl), _p(err))
-    if rc:
-        raise ValueError("%d: %s" % (rc, lib.emu_last_error().decode()))
+    lanes.check(lib, rc)
     return dict(qvec=q, tvec=t, status=st, n_inliers=ni, n_trials=nt, inlier=inl, err=err)
 
 

@@ -1,51 +1,24 @@
 """The source of the cloud kernels, run lane by lane on the CPU: csrc/pxr_cloud.hip is compiled as host C++ over the stand-in
-runtime of tests/lane_emulation/matrix and held to the brute-force statement of tests/cloud_cases.py bit for bit, on every case of
+runtime of tests/lane_emulation and held to the brute-force statement of tests/cloud_cases.py bit for bit, on every case of
 the GPU test -- the cell coordinates and their hash, count / scan / fill of the buckets, the walk over the 27 cells with its
 tie-break, the voxel keys, the compare-and-swap inserts with their probing, the fixed-point sums and the host-side validation are
 checked without a GPU.  The host's float64 division is correctly rounded, as numpy's is; whether the device's is stays with
 tests/test_cloud_gpu.py.  Lanes run one after another here: what the integer atomics do under real concurrency does too."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import cloud_cases as cc
+import lanes
+from lanes import p as _p
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
 SENTINEL = -7
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
-
-
-def _compile(out, *flags):
-    cxx = _clang()       # the compiler that hipcc drives, as a plain host compiler (the stand-in runtime uses its vector types)
-    assert cxx, "no clang++ next to hipcc"
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", "-Wno-psabi", *flags,
-                           "-I", os.path.join(HERE, "matrix"), "-I", HERE, "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "cloud_on_host.cpp"), "-o", out])
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("lanes") / "libcloud_lanes.so")
-    _compile(out, "-shared")
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return lanes.load(tmp_path_factory, "cloud_on_host.cpp")
 
 
 def _nearest(emu, ref, query, max_dist, n_ref=None, n_query=None):
@@ -111,15 +84,10 @@ def test_sanitized_stand_alone_program(tmp_path):
     """The same translation unit with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone host
     program whose arrays have their exact sizes: both entry points on lattice clouds with rows that are not valid, checked
     against the brute-force search inside the program."""
-    exe = str(tmp_path / "cloud_asan")
-    _compile(exe, "-DCLOUD_ON_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
     for args in (("300", "257", "0.25", "0.5"), ("65", "64", "1", "0"), ("1", "1", "0.1", "0.1"), ("0", "5", "0.1", "0.1"), ("4100", "70", "0.5", "0.25")):
-        res = subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                             env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-        assert res.returncode == 0, res.stdout + res.stderr
-        assert "runtime error" not in res.stderr and "ERROR: AddressSanitizer" not in res.stderr, res.stderr
-        w = res.stdout.split()
+        stdout = lanes.sanitized(tmp_path, "cloud_on_host.cpp", "CLOUD_ON_HOST_MAIN", *args)
+        w = stdout.split()
         queries, found, wrong, voxels = int(w[1]), int(w[3]), int(w[5]), int(w[7])
-        assert queries == int(args[1]) and wrong == 0 and 0 <= found <= queries and 0 <= voxels <= queries, res.stdout
+        assert queries == int(args[1]) and wrong == 0 and 0 <= found <= queries and 0 <= voxels <= queries, stdout
         if int(args[0]) >= 300:
-            assert found > 0, res.stdout
+            assert found > 0, stdout

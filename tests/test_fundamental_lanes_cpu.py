@@ -1,50 +1,22 @@
 """The source of the fundamental-matrix kernels, run lane by lane on the CPU: csrc/pxr_fundamental.hip is compiled as host C++ over
-the stand-in runtime of tests/lane_emulation/workgroup (a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through an
+the stand-in runtime of tests/lane_emulation (a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through an
 exchange buffer) and held to the numpy reference like the GPU test does -- the sample hash at seven indices, the seven-point
 solver with its cubic and Sturm chain, the keys and the stop rule across the four wavefronts of a workgroup, the workgroup sums of
 the rank-2 refinement, the compaction and the host-side validation are checked without a GPU.  What only hardware can show (LDS
 and scratch behaviour, occupancy, the device's libm) stays with tests/test_fundamental_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import fundamental_cases as fc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
-
-
-def _compile(out, *extra):
-    cxx = _clang()       # the device headers use clang's vector types: the compiler that hipcc drives, as a plain host compiler
-    assert cxx, "no clang++ next to hipcc"
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", *extra,
-                           "-I", os.path.join(HERE, "workgroup"), "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "fundamental_on_host.cpp"), "-o", out])
+import lanes
+from lanes import p as _p
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("lanes") / "libfm_lanes.so")
-    _compile(out, "-shared")
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return lanes.load(tmp_path_factory, "fundamental_on_host.cpp")
 
 
 def _run(emu, batch, F=None, **options):
@@ -61,8 +33,7 @@ def _run(emu, batch, F=None, **options):
     inl, err = np.full(N, 9, np.uint8), np.full(N, -1.0)
     rc = lib.pxr_fundamental(ctx, C.c_int32(T), _p(off), C.c_int64(N), _p(xy1), _p(xy2), _p(pc), C.c_int32(len(cm)), _p(cm), _p(cp),
                              C.byref(opts), _p(Fm), _p(st), _p(ni), _p(nt), _p(inl), _p(err))
-    if rc:
-        raise ValueError("%d: %s" % (rc, lib.emu_last_error().decode()))
+    lanes.check(lib, rc)
     return dict(F=Fm, status=st, n_inliers=ni, n_trials=nt, inlier=inl, err=err)
 
 
@@ -102,14 +73,9 @@ def test_status_codes_and_validation(emu):
 def test_sanitized_stand_alone_program(tmp_path):
     """The same translation unit with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone
     host program: empty pairs, pairs of 7, 8, 17, 70 and S + 1 matches, the odd ones through a focal length x 0.7."""
-    exe = str(tmp_path / "fundamental_asan")
-    _compile(exe, "-DFUNDAMENTAL_ON_HOST_MAIN", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
     counts = [0, 7, 8, 0, 70, 70, fc.LDS_MATCHES + 1, 17, 0]
-    res = subprocess.run([exe] + [str(c) for c in counts], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stderr
-    lines = [ln for ln in res.stdout.split("\n") if ln.startswith("pair")]
+    stdout = lanes.sanitized(tmp_path, "fundamental_on_host.cpp", "FUNDAMENTAL_ON_HOST_MAIN", *counts)
+    lines = [ln for ln in stdout.split("\n") if ln.startswith("pair")]
     assert len(lines) == len(counts)
     assert "pair 0: 0 matches, status 1, 0 inliers, 0 trials" in lines
     assert any(ln.startswith("pair 6: 1025 matches, status 0") for ln in lines)

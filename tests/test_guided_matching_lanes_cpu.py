@@ -1,46 +1,26 @@
 """The source of the guided matching kernels, run lane by lane on the CPU: csrc/pxr_match.hip compiled as host C++ over the
-stand-in runtime of tests/lane_emulation/matrix (as tests/test_matching_lanes_cpu.py does for the unguided entry point) and held
+stand-in runtime of tests/lane_emulation (as tests/test_matching_lanes_cpu.py does for the unguided entry point) and held
 to the reference of tests/guided_matching_cases.py bit for bit -- the records, the gate in the tile loop's epilogue on both the
 row and the column side, the LDS row records at the strip edges, the host-side validation -- without a GPU.  The same translation
 unit runs once more with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone host program."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import guided_matching_cases as gc
+import lanes
 import matching_cases as mc
-from test_matching_lanes_cpu import _clang, _equal
-from test_matching_lanes_cpu import _p as _p_array
+from lanes import p as _p
+from test_matching_lanes_cpu import _equal
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
 SHAPES = [(1, 1, 4), (1, 37, 128), (37, 1, 128), (33, 31, 128), (129, 65, 128), (70, 90, 130)]
 SENTINEL = -7
 
 
-def _compile(out, *flags):
-    cxx = _clang()       # the kernels use clang's vector types: the compiler that hipcc drives, as a plain host compiler
-    assert cxx, "no clang++ next to hipcc"
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", *flags,
-                           "-I", os.path.join(HERE, "matrix"), "-I", HERE, "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "guided_on_host.cpp"), "-o", out])
-
-
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("guided_lanes") / "libguided_lanes.so")
-    _compile(out, "-shared")
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return None if a is None else _p_array(a)
+    return lanes.load(tmp_path_factory, "match_on_host.cpp")          # the build that tests/test_matching_lanes_cpu.py uses
 
 
 def guided_call(call, descs, xy, pairs, kinds, models, thrs, offsets=None, dim=None, null=(), reserved=0, **options):
@@ -75,7 +55,7 @@ def _run(emu, *args, **kw):
     rc, m, s, n = guided_call(call, *args, **kw)
     if rc:
         assert (m == SENTINEL).all() and (s == SENTINEL).all() and (n == SENTINEL).all(), "an error wrote to the outputs"
-        raise ValueError("%d: %s" % (rc, lib.emu_last_error().decode()))
+    lanes.check(lib, rc)
     return m, s, n
 
 
@@ -147,13 +127,9 @@ def test_validation(emu):
 def test_sanitized_stand_alone_program(tmp_path):
     """The same translation unit with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone host
     program whose arrays have their exact sizes: (1, 1, 1), (129, 65, 128) and the batch with the empty images, both kinds."""
-    exe = str(tmp_path / "guided_asan")
-    _compile(exe, "-DGUIDED_ON_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stderr
-    lines = res.stdout.strip().split("\n")
-    assert len(lines) == 3 and all("error" not in ln for ln in lines), res.stdout
+    stdout = lanes.sanitized(tmp_path, "guided_on_host.cpp", "GUIDED_ON_HOST_MAIN")
+    lines = stdout.strip().split("\n")
+    assert len(lines) == 3 and all("error" not in ln for ln in lines), stdout
     counts = [int(w) for w in lines[2].split(":")[1].split()]
-    assert lines[2].startswith("batch") and len(counts) == 7, res.stdout
-    assert counts[4:6] == [0, 0] and counts[0] > 0, res.stdout          # an empty image on either side; (4, 4) under E keeps some
+    assert lines[2].startswith("batch") and len(counts) == 7, stdout
+    assert counts[4:6] == [0, 0] and counts[0] > 0, stdout          # an empty image on either side; (4, 4) under E keeps some

@@ -1,50 +1,22 @@
 """The source of the mapper's visibility kernels, run lane by lane on the CPU: csrc/pxr_mapper.hip is compiled as host C++ over the
-workgroup stand-in runtime (tests/lane_emulation/workgroup: a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through
+stand-in runtime of tests/lane_emulation (a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through
 an exchange buffer) and held bit for bit to the numpy reference of tests/mapping_cases.py on the shapes of the GPU test -- the
 occupancy words, the workgroup sums, the prefix sums across the four wavefronts and the chunks of a long image, and the host-side
 validation are checked without a GPU.  What only hardware can show (LDS atomics under contention, the device's floor and division)
 stays with tests/test_mapping_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import lanes
 import mapping_cases as mc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
-
-
-def _compile(out, *flags):
-    cxx = _clang()
-    assert cxx, "no clang++ next to hipcc"
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", *flags,
-                           "-I", os.path.join(HERE, "workgroup"), "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "mapping_on_host.cpp"), "-o", out])
+from lanes import p as _p
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("lanes") / "libmap_lanes.so")
-    _compile(out, "-shared")
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return lanes.load(tmp_path_factory, "mapping_on_host.cpp")
 
 
 def _run(emu, scene, xyz, status, mask, levels, **replace):
@@ -70,10 +42,11 @@ def _run(emu, scene, xyz, status, mask, levels, **replace):
                                    _p(status), _p(mask), _p(a["cam_size"]), C.c_int32(levels), _p(out["n_visible"]), _p(out["score"]),
                                    _p(out["corr_offsets"]), _p(out["corr_obs"]), _p(out["corr_xy"]), _p(out["corr_xyz"]),
                                    C.byref(n_corr))
-    if rc:
-        err = ValueError("%d: %s" % (rc, lib.emu_last_error().decode()))
+    try:
+        lanes.check(lib, rc)
+    except ValueError as err:
         err.outputs, err.n_corr = out, n_corr.value
-        raise err
+        raise
     return out, n_corr.value
 
 
@@ -111,19 +84,14 @@ def test_sanitized_stand_alone_program(tmp_path):
     """The same translation unit with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone host
     program whose arrays have their exact sizes: images of 0, 1, 63, 64, 65, 256, 257 and 600 observations, a third of the tracks
     without a point, a seventh of the keypoints not finite, one image masked out."""
-    exe = str(tmp_path / "mapping_asan")
-    _compile(exe, "-DMAPPING_ON_HOST_MAIN", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
     counts = [65, 300, 0, 1, 63, 64, 256, 257, 600]
-    res = subprocess.run([exe] + [str(c) for c in counts], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stderr
+    stdout = lanes.sanitized(tmp_path, "mapping_on_host.cpp", "MAPPING_ON_HOST_MAIN", *counts)
     for levels in (1, 6):
-        rows = [ln.split() for ln in res.stdout.split("\n") if ln.startswith("L %d image" % levels)]
+        rows = [ln.split() for ln in stdout.split("\n") if ln.startswith("L %d image" % levels)]
         assert [int(r[5]) for r in rows] == counts
         visible, score, offset = ([int(r[k]) for r in rows] for k in (7, 9, 11))
         assert visible[1] == 0 and score[1] == 0 and visible[2] == 0                               # masked out; empty
         assert all(0 < v < c for v, c in zip(visible[3:], counts[3:]) if c >= 63)                  # some visible, some not
         assert offset == np.concatenate([[0], np.cumsum(visible)[:-1]]).tolist()
-        assert ("L %d total %d" % (levels, sum(visible))) in res.stdout
+        assert ("L %d total %d" % (levels, sum(visible))) in stdout
         assert all(s <= sum(4 ** l for l in range(1, levels + 1)) * v for s, v in zip(score, visible))

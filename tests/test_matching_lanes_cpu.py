@@ -1,45 +1,21 @@
-"""The source of the matching kernels, run lane by lane on the CPU: csrc/pxr_match.hip is compiled as host C++ over a stand-in
-runtime (tests/lane_emulation/matrix: the workgroup stand-in plus the f32-input MFMA stated as its documented lane maps and fmaf
+"""The source of the matching kernels, run lane by lane on the CPU: csrc/pxr_match.hip is compiled as host C++ over the stand-in
+runtime of tests/lane_emulation (a fibre per lane, the f32-input MFMA stated as its documented lane maps and fmaf
 chain) and held to the reference of tests/matching_cases.py bit for bit, like the GPU test does -- the fragment order of the LDS
 tiles, the masks at the tile edges, the running and merged top-2, the partials across strips, the mutual check and the host-side
 validation are checked without a GPU.  Whether the hardware instruction computes that chain stays with tests/test_matching_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import lanes
 import matching_cases as mc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
+from lanes import p as _p
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = _clang()       # the kernels use clang's vector types: the compiler that hipcc drives, as a plain host compiler
-    assert cxx, "no clang++ next to hipcc"
-    out = str(tmp_path_factory.mktemp("lanes") / "libmatch_lanes.so")
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off",
-                           "-I", os.path.join(HERE, "matrix"), "-I", HERE, "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "match_on_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return lanes.load(tmp_path_factory, "match_on_host.cpp")
 
 
 def _run(emu, descs, pairs, offsets=None, dim=None, **options):
@@ -55,8 +31,7 @@ def _run(emu, descs, pairs, offsets=None, dim=None, **options):
     opts = match_options(**options)
     rc = lib.pxr_match_descriptors(ctx, C.c_int32(len(descs)), _p(off), C.c_int64(len(desc)), C.c_int32(dim), _p(desc), C.c_int32(len(pairs)),
                                    _p(pairs), _p(poff), C.byref(opts), _p(m), _p(s), _p(n))
-    if rc:
-        raise ValueError("%d: %s" % (rc, lib.emu_last_error().decode()))
+    lanes.check(lib, rc)
     return m, s, n
 
 

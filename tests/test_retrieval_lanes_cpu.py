@@ -1,5 +1,5 @@
 """The source of the retrieval kernels, run lane by lane on the CPU: csrc/pxr_retrieval.hip is compiled as host C++ over the
-stand-in runtime of tests/lane_emulation/matrix (the workgroup stand-in plus the f32-input MFMA stated as its documented lane maps
+stand-in runtime of tests/lane_emulation (a fibre per lane, the f32-input MFMA stated as its documented lane maps
 and fmaf chain) and held to the reference of tests/retrieval_cases.py bit for bit, like the GPU test does -- the fragment order
 and the chunks of the LDS tiles, the masks at the edges, the running best and its butterfly, the validity flags, the integer
 atomics across chunks of rows and blocks of centroids, the float64 chains, the rounds of the selection and the host-side
@@ -7,51 +7,18 @@ validation are checked without a GPU.  The host's float64 sqrt and division are 
 device's are, and whether the hardware instruction computes the chain, stays with tests/test_retrieval_gpu.py.  Every shape of
 that test runs here, the largest selection shape (3, 300, 32768, 20) included (about half a minute of emulated instructions)."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import lanes
 import retrieval_cases as rc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
-
-
-def _compile(out, *flags):
-    cxx = _clang()       # the kernels use clang's vector types: the compiler that hipcc drives, as a plain host compiler
-    assert cxx, "no clang++ next to hipcc"
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", "-Wno-psabi", *flags,
-                           "-I", os.path.join(HERE, "matrix"), "-I", HERE, "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "retrieval_on_host.cpp"), "-o", out])
+from lanes import p as _p
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("lanes") / "libretrieval_lanes.so")
-    _compile(out, "-shared")
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _check(emu, code):
-    if code:
-        raise ValueError("%d: %s" % (code, emu[0].emu_last_error().decode()))
+    return lanes.load(tmp_path_factory, "retrieval_on_host.cpp")
 
 
 def _train(emu, X, K, iters, max_train, dim=None):
@@ -96,7 +63,7 @@ def _bits(a):
 def test_assignment_equals_the_reference(emu, shape):
     X, cen = rc.assignment_case(*shape, seed=300 + rc.ASSIGN_SHAPES.index(shape))
     code, _, a, _ = _vlad(emu, [X], cen)
-    _check(emu, code)
+    lanes.check(emu[0], code)
     ref = rc.assign(X, cen)
     assert np.array_equal(a, ref), np.flatnonzero(a != ref)[:8]
     assert a[0] == 0                                                  # of two identical centroids the lowest index
@@ -108,7 +75,7 @@ def test_assignment_equals_the_reference(emu, shape):
 def test_aggregation_equals_the_reference(emu, K, D):
     descs, cen = rc.aggregation_case(K, D, seed=40 + K + D)
     code, G, a, n = _vlad(emu, descs, cen)
-    _check(emu, code)
+    lanes.check(emu[0], code)
     rG, ra, rn = rc.vlad(descs, cen)
     assert np.array_equal(a, ra) and np.array_equal(n, rn)
     assert np.array_equal(_bits(G), _bits(rG)), int((_bits(G) != _bits(rG)).sum())
@@ -119,7 +86,7 @@ def test_aggregation_equals_the_reference(emu, K, D):
     # a batch equals its images run alone
     for k in (2, 5, m):
         code, G1, a1, n1 = _vlad(emu, [descs[k]], cen)
-        _check(emu, code)
+        lanes.check(emu[0], code)
         assert np.array_equal(_bits(G1[0]), _bits(G[k])) and np.array_equal(n1[0], n[k])
 
 
@@ -129,7 +96,7 @@ def test_centroid_blocks_and_row_chunks(emu):
     cen = rc.unit_rows(rng, 40, 256)
     descs = [rc.clustered_rows(rng, 2100, cen), rc.clustered_rows(rng, 3, cen)]
     code, G, a, n = _vlad(emu, descs, cen)
-    _check(emu, code)
+    lanes.check(emu[0], code)
     rG, ra, rn = rc.vlad(descs, cen)
     assert np.array_equal(a, ra) and np.array_equal(n, rn) and np.array_equal(_bits(G), _bits(rG))
 
@@ -138,7 +105,7 @@ def test_centroid_blocks_and_row_chunks(emu):
 def test_training_equals_the_reference(emu, name):
     X, K, iters, max_train = rc.training_case(name)
     code, cen, cnt, empty = _train(emu, X, K, iters, max_train)
-    _check(emu, code)
+    lanes.check(emu[0], code)
     rcen, rcnt, rempty = rc.vocab_train(X, K, iters, max_train)
     assert np.array_equal(cnt, rcnt) and empty == rempty
     assert np.array_equal(_bits(cen), _bits(rcen)), int((_bits(cen) != _bits(rcen)).sum())
@@ -152,7 +119,7 @@ def test_selection_equals_the_reference(emu, shape):
     rng = np.random.default_rng(700 + dim)
     Q, DB = rc.global_rows(rng, nq, dim), rc.global_rows(rng, ndb, dim)
     got = _topk(emu, Q, DB, k)
-    _check(emu, got[0])
+    lanes.check(emu[0], got[0])
     ref = rc.topk(Q, DB, k)
     assert np.array_equal(got[1], ref[0]) and np.array_equal(_bits(got[2]), _bits(ref[1])) and np.array_equal(got[3], ref[2])
 
@@ -170,7 +137,7 @@ def test_selection_rules(emu):
                dict(min_score=-0.1, mask=mask)):
         for k in (1, 3, 20):                                           # 20 > candidates: padding
             got = _topk(emu, DB, DB, k, **kw)
-            _check(emu, got[0])
+            lanes.check(emu[0], got[0])
             ref = rc.topk(DB, DB, k, **kw)
             assert np.array_equal(got[1], ref[0]), (kw.keys(), k)
             assert np.array_equal(_bits(got[2]), _bits(ref[1])) and np.array_equal(got[3], ref[2])
@@ -200,22 +167,17 @@ def test_bad_input_is_refused_and_leaves_the_outputs_untouched(emu):
         code, top, val, found = _topk(emu, X, X, k, **kw)
         assert code == -1 and (top == -7).all() and (val == -7).all() and (found == -7).all(), kw
     with pytest.raises(ValueError, match="pxr_vlad_aggregate.*monotone"):
-        _check(emu, _vlad(emu, [X[:20], X[20:]], cen, offsets=[0, 60, 50])[0])
+        lanes.check(emu[0], _vlad(emu, [X[:20], X[20:]], cen, offsets=[0, 60, 50])[0])
 
 
 def test_sanitized_stand_alone_program(tmp_path):
     """The same translation unit with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone host
     program whose arrays have their exact sizes: training on a strided subset, images of different sizes with an empty one and an
     invalid row, the selection with more neighbours asked for than there are."""
-    exe = str(tmp_path / "retrieval_asan")
-    _compile(exe, "-DRETRIEVAL_ON_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
     for args in (("5", "40", "24", "6", "3"), ("3", "130", "130", "3", "7"), ("4", "33", "7", "33", "1")):
-        res = subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                             env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-        assert res.returncode == 0, res.stdout + res.stderr
-        assert "runtime error" not in res.stderr and "ERROR: AddressSanitizer" not in res.stderr, res.stderr
-        w = res.stdout.split()
+        stdout = lanes.sanitized(tmp_path, "retrieval_on_host.cpp", "RETRIEVAL_ON_HOST_MAIN", *args)
+        w = stdout.split()
         rows, assigned, counted, found = int(w[1]), int(w[3]), int(w[5]), int(w[9])
-        assert assigned == rows - 1 and counted == assigned, res.stdout
+        assert assigned == rows - 1 and counted == assigned, stdout
         n_images, k = int(args[0]), int(args[4])
-        assert 0 < found <= n_images * min(k, n_images - 1), res.stdout
+        assert 0 < found <= n_images * min(k, n_images - 1), stdout

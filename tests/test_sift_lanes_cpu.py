@@ -1,51 +1,23 @@
-"""The source of the SIFT kernels, run lane by lane on the CPU: csrc/pxr_sift.hip is compiled as host C++ over the workgroup stand-in
-runtime (tests/lane_emulation/workgroup: a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through an exchange
+"""The source of the SIFT kernels, run lane by lane on the CPU: csrc/pxr_sift.hip is compiled as host C++ over the stand-in
+runtime of tests/lane_emulation (a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through an exchange
 buffer) and held to the numpy reference of tests/sift_cases.py on small shapes: the tiles and halos of the blur at the edges of
 a level, the count / scan / write of the detection across wavefronts, chunks and blocks, the owner-computes histograms, the
 host-side validation.  The arithmetic here is the host's float32 and float64, so the pyramid is held to the derived bound of
 sift_cases.pass_bound and everything after it to the reference run on the emulation's own pyramid, where only the order of a few
 float64 sums differs.  What only hardware can show stays with tests/test_sift_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import lanes
 import sift_cases as sc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
-
-
-def _compile(out, *flags):
-    cxx = _clang()
-    assert cxx, "no clang++ next to hipcc"
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", *flags,
-                           "-I", os.path.join(HERE, "workgroup"), "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "sift_on_host.cpp"), "-o", out])
+from lanes import p as _p
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("lanes") / "libsift_lanes.so")
-    _compile(out, "-shared")
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return lanes.load(tmp_path_factory, "sift_on_host.cpp")
 
 
 def _options(**kw):
@@ -56,22 +28,17 @@ def _options(**kw):
     return o
 
 
-def _check(emu, rc):
-    if rc:
-        raise ValueError("%d: %s" % (rc, emu[0].emu_last_error().decode()))
-
-
 def _pyramid(emu, image, **kw):
     """The emulation's pyramid as [octave: (S + 3, h, w) float32], through the layout the library reports."""
     lib, ctx = emu
     o = _options(**kw)
     h, w = image.shape
     n_oct, sizes, offs, nbytes = C.c_int32(-1), np.zeros((8, 2), np.int32), np.zeros(8, np.int64), C.c_int64(-1)
-    _check(emu, lib.pxr_sift_pyramid_layout(h, w, C.byref(o), C.byref(n_oct), _p(sizes), _p(offs)))
-    _check(emu, lib.pxr_sift_pyramid_bytes(h, w, C.byref(o), C.byref(nbytes)))
+    lanes.check(lib, lib.pxr_sift_pyramid_layout(h, w, C.byref(o), C.byref(n_oct), _p(sizes), _p(offs)))
+    lanes.check(lib, lib.pxr_sift_pyramid_bytes(h, w, C.byref(o), C.byref(nbytes)))
     flat = np.full(nbytes.value // 4, -7.0, np.float32)
     img = np.ascontiguousarray(image)
-    _check(emu, lib.pxr_sift_pyramid(ctx, _p(img), 3 if img.dtype == np.uint8 else 1, h, w, C.byref(o), _p(flat)))
+    lanes.check(lib, lib.pxr_sift_pyramid(ctx, _p(img), 3 if img.dtype == np.uint8 else 1, h, w, C.byref(o), _p(flat)))
     S = o.octave_resolution
     levels = [flat[offs[k]:offs[k] + (S + 3) * sizes[k, 0] * sizes[k, 1]].reshape(S + 3, sizes[k, 0], sizes[k, 1]) for k in range(n_oct.value)]
     assert sum(lv.size for lv in levels) == flat.size
@@ -82,7 +49,7 @@ def _detect(emu, flat, h, w, o, capacity):
     lib, ctx = emu
     kp, rec, resp = np.full((capacity, 4), -9.0), np.full((capacity, 4), -9, np.int32), np.full(capacity, -9.0, np.float32)
     found = C.c_int64(-9)
-    _check(emu, lib.pxr_sift_detect(ctx, _p(flat), h, w, C.byref(o), C.c_int64(capacity), _p(kp), _p(rec), _p(resp), C.byref(found)))
+    lanes.check(lib, lib.pxr_sift_detect(ctx, _p(flat), h, w, C.byref(o), C.c_int64(capacity), _p(kp), _p(rec), _p(resp), C.byref(found)))
     return kp, rec, resp, found.value
 
 
@@ -90,7 +57,7 @@ def _describe(emu, flat, h, w, o, kp):
     lib, ctx = emu
     kp = np.ascontiguousarray(kp, np.float64).reshape(-1, 4)
     desc, valid = np.full((len(kp), 128), -9.0, np.float32), np.full(len(kp), 9, np.uint8)
-    _check(emu, lib.pxr_sift_describe(ctx, _p(flat), h, w, C.byref(o), C.c_int64(len(kp)), _p(kp), _p(desc), _p(valid)))
+    lanes.check(lib, lib.pxr_sift_describe(ctx, _p(flat), h, w, C.byref(o), C.c_int64(len(kp)), _p(kp), _p(desc), _p(valid)))
     return desc, valid
 
 
@@ -203,15 +170,10 @@ def test_sanitized_stand_alone_program(tmp_path):
     """The same translation unit with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone host
     program whose arrays have their exact sizes: an image smaller than a tile, one with odd halving over two octaves and a
     capacity below the number found, and a capacity of zero."""
-    exe = str(tmp_path / "sift_asan")
-    _compile(exe, "-DSIFT_ON_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
     for args, few in ((("17", "23", "-1", "64"), False), (("33", "37", "0", "3"), True), (("19", "21", "-1", "0"), True)):
-        res = subprocess.run([exe, *args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                             env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-        assert res.returncode == 0, res.stdout + res.stderr
-        assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stderr
-        words = res.stdout.split()
+        stdout = lanes.sanitized(tmp_path, "sift_on_host.cpp", "SIFT_ON_HOST_MAIN", *args)
+        words = stdout.split()
         found, written, valid = int(words[1]), int(words[3]), int(words[5])
-        assert found > 0 and written == min(found, int(args[3])) and valid == written, res.stdout
-        assert (found > int(args[3])) == few, res.stdout
-        assert words[7:] == ["0", "0", "0", "1", "0"], res.stdout          # only the large window in the middle can be described
+        assert found > 0 and written == min(found, int(args[3])) and valid == written, stdout
+        assert (found > int(args[3])) == few, stdout
+        assert words[7:] == ["0", "0", "0", "1", "0"], stdout          # only the large window in the middle can be described

@@ -1,46 +1,22 @@
 """The source of the triangulation kernels, run lane by lane on the CPU: csrc/pxr_triangulate.hip is compiled as host C++
-over a stand-in runtime (tests/lane_emulation: a thread per lane, the 16-lane cross-lane operations through a barrier) and
+over the stand-in runtime of tests/lane_emulation (a fibre per lane; the cross-lane operations of a 16-lane group) and
 held to the numpy reference like the GPU test does -- the estimator's logic, the lane-strided loops, the chunk rotation of the
 acceptance step, the compaction and the host-side validation are checked without a GPU.  What only hardware can show (DPP and
 LDS behaviour, occupancy) stays with tests/test_triangulation_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import lanes
 import pxo
 import triangulation_cases as tc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
+from lanes import p as _p
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    cxx = _clang()       # the device headers use clang's vector types: the compiler that hipcc drives, as a plain host compiler
-    assert cxx, "no clang++ next to hipcc"
-    out = str(tmp_path_factory.mktemp("lanes") / "libtri_lanes.so")
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off", "-I", HERE,
-                           "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(HERE, "triangulate_on_host.cpp"), "-o", out, "-lpthread"])
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return lanes.load(tmp_path_factory, "triangulate_on_host.cpp")
 
 
 def _run(emu, scene, xyz=None):
@@ -59,8 +35,7 @@ def _run(emu, scene, xyz=None):
     st, ni = np.full(T, -9, np.int32), np.full(T, -9, np.int32)
     inl, err = np.full(N, 9, np.uint8), np.full(N, -1.0)
     rc = lib.pxr_triangulate_tracks(ctx, C.byref(view), C.byref(opts), _p(X), _p(st), _p(ni), _p(inl), _p(err))
-    if rc:
-        raise ValueError("%d: %s" % (rc, lib.emu_last_error().decode()))
+    lanes.check(lib, rc)
     return dict(xyz=X, status=st, n_inliers=ni, obs_inlier=inl, obs_err=err)
 
 

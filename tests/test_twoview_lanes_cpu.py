@@ -1,50 +1,22 @@
 """The source of the two-view geometry kernels, run lane by lane on the CPU: csrc/pxr_twoview.hip is compiled as host C++ over
-the stand-in runtime of tests/lane_emulation/workgroup (a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through
+the stand-in runtime of tests/lane_emulation (a fibre per lane, workgroup-wide barriers, the 64-lane shuffles through
 an exchange buffer) and held to the numpy reference like the GPU test does -- the sample hash, the five-point solver, the keys
 and the stop rule across the four wavefronts of a workgroup, Horn's decomposition, the workgroup sums of the refinement, the
 compaction and the host-side validation are checked without a GPU.  What only hardware can show (LDS and scratch behaviour,
 occupancy, the device's libm) stays with tests/test_twoview_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import lanes
 import twoview_cases as tv
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "lane_emulation")
-
-
-def _clang():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cand = [os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
-            shutil.which("clang++")]
-    return next((c for c in cand if c and os.path.exists(c)), None)
-
-
-def _compile(out, *extra):
-    cxx = _clang()       # the device headers use clang's vector types: the compiler that hipcc drives, as a plain host compiler
-    assert cxx, "no clang++ next to hipcc"
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", *extra,
-                           "-I", os.path.join(HERE, "workgroup"), "-I", os.path.join(ROOT, "pixel-perfect-sfm_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "twoview_on_host.cpp"), "-o", out])
+from lanes import p as _p
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("lanes") / "libtv_lanes.so")
-    _compile(out, "-shared")
-    lib = C.CDLL(out)
-    lib.emu_ctx.restype = C.c_void_p
-    lib.emu_last_error.restype = C.c_char_p
-    return lib, C.c_void_p(lib.emu_ctx())
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return lanes.load(tmp_path_factory, "twoview_on_host.cpp")
 
 
 def _run(emu, batch, qvec=None, tvec=None, **options):
@@ -65,8 +37,7 @@ def _run(emu, batch, qvec=None, tvec=None, **options):
     inl, err = np.full(N, 9, np.uint8), np.full(N, -1.0)
     rc = lib.pxr_two_view_geometry(ctx, C.c_int32(T), _p(off), C.c_int64(N), _p(xy1), _p(xy2), _p(pc), C.c_int32(len(cm)), _p(cm), _p(cp),
                                    _p(pq), _p(pt), C.byref(opts), _p(q), _p(t), _p(E), _p(st), _p(ni), _p(nt), _p(inl), _p(err))
-    if rc:
-        raise ValueError("%d: %s" % (rc, lib.emu_last_error().decode()))
+    lanes.check(lib, rc)
     return dict(qvec=q, tvec=t, E=E, status=st, n_inliers=ni, n_trials=nt, inlier=inl, err=err)
 
 
@@ -118,13 +89,8 @@ def test_status_codes_and_validation(emu):
 def test_sanitized_stand_alone_program(tmp_path):
     """The same translation unit with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone
     host program: pairs down to 5 matches, empty pairs, S + 1 matches; with and without a pose prior."""
-    exe = str(tmp_path / "twoview_asan")
-    _compile(exe, "-DTWOVIEW_ON_HOST_MAIN", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
     counts = [0, 5, 6, 0, 17, 70, tv.LDS_MATCHES + 1, 0]
-    res = subprocess.run([exe] + [str(c) for c in counts], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, res.stderr
-    lines = [ln for ln in res.stdout.split("\n") if ln.startswith("pair")]
+    stdout = lanes.sanitized(tmp_path, "twoview_on_host.cpp", "TWOVIEW_ON_HOST_MAIN", *counts)
+    lines = [ln for ln in stdout.split("\n") if ln.startswith("pair")]
     assert len(lines) == 2 * len(counts)
     assert "pair 0: 0 matches, status 1, 0 inliers, 0 trials" in lines and any(ln.startswith("pair 6: 1025 matches, status 0") for ln in lines)
