@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "pxr_ba_driver.h"
+#include "pxr_scan.h"
 
 namespace pxr {
 
@@ -63,32 +64,23 @@ __global__ __launch_bounds__(256) void k_count_indices(int64_t n_obs, const int3
 // is not constant and has an observation, *n_var = how many.  Two launches: the sums of chunks of PT_SCAN_CHUNK points, then
 // every workgroup adds up the chunks before its own and scans its chunk.
 constexpr int PT_SCAN_CHUNK = 2048;
-__device__ __forceinline__ unsigned long long block_sum_256(unsigned long long v, unsigned long long* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if (t < o) sh[t] += sh[t + o]; __syncthreads(); }
-  const unsigned long long r = sh[0];
-  __syncthreads();
-  return r;
-}
 __global__ __launch_bounds__(256) void k_pt_scan_partials(int64_t n_pts, const unsigned long long* __restrict__ cnt, unsigned long long* __restrict__ part) {
-  __shared__ unsigned long long sh[256];
+  __shared__ unsigned long long s_part[256 / 64];
   const int64_t p0 = (int64_t)blockIdx.x * PT_SCAN_CHUNK;
   unsigned long long s = 0;
   for (int j = threadIdx.x; j < PT_SCAN_CHUNK; j += 256) if (p0 + j < n_pts) s += cnt[p0 + j + 1];
-  s = block_sum_256(s, sh);
+  s = block_int_sum<256>(s, s_part);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(256) void k_pt_scan_apply(int64_t n_pts, const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ part,
                                                        const uint8_t* __restrict__ pt_const, int64_t* __restrict__ pt_ptr, int* __restrict__ pt_var,
                                                        unsigned long long* __restrict__ n_var) {
-  __shared__ unsigned long long sh[256];
+  __shared__ unsigned long long s_part[256 / 64];
   constexpr int PER = PT_SCAN_CHUNK / 256;
   const int t = threadIdx.x;
   unsigned long long base = 0;
   for (int g = t; g < (int)blockIdx.x; g += 256) base += part[g];
-  base = block_sum_256(base, sh);
+  base = block_int_sum<256>(base, s_part);
   const int64_t p0 = (int64_t)blockIdx.x * PT_SCAN_CHUNK + (int64_t)t * PER;
   unsigned long long c[PER], mine = 0;
   int nv = 0;
@@ -97,15 +89,8 @@ __global__ __launch_bounds__(256) void k_pt_scan_apply(int64_t n_pts, const unsi
     c[j] = p0 + j < n_pts ? cnt[p0 + j + 1] : 0ull;
     mine += c[j];
   }
-  sh[t] = mine;                                             // inclusive scan of the threads' sums (Hillis-Steele, 8 rounds)
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const unsigned long long add = t >= o ? sh[t - o] : 0ull;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  unsigned long long run = base + sh[t] - mine;
+  unsigned long long chunk_total;
+  unsigned long long run = base + block_exclusive_scan<256>(mine, s_part, chunk_total);
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     if (p0 + j >= n_pts) break;
@@ -115,8 +100,7 @@ __global__ __launch_bounds__(256) void k_pt_scan_apply(int64_t n_pts, const unsi
     pt_var[p0 + j] = v; nv += v;
   }
   if (blockIdx.x == 0 && t == 0) pt_ptr[0] = 0;
-  __syncthreads();
-  const unsigned long long tot = block_sum_256((unsigned long long)nv, sh);
+  const unsigned long long tot = block_int_sum<256>((unsigned long long)nv, s_part);
   if (t == 0 && tot) atomicAdd(n_var, tot);
 }
 __global__ void k_iota(int64_t n, int64_t* __restrict__ out) {

@@ -6,8 +6,8 @@
 // pxr_cloud_nearest: a uniform grid over the reference cloud, kept as a HASHED table of buckets (a power of two >= 2 n_ref of
 // them: a 50 m scene at a 5 cm cell is 10^9 cells, a dense grid is out of the question).
 //   k_cloud_count    one lane per reference point: its cell, the cell's bucket, one integer atomic on the bucket's count.
-//   k_scan_reduce, k_scan_partials, k_scan_apply   the exclusive prefix sums of the counts, in place (chunks of SCAN_CHUNK buckets,
-//                    one workgroup over the chunks' totals, the chunks again).
+//   k_scan_reduce, k_exclusive_scan (pxr_scan.h), k_scan_apply   the exclusive prefix sums of the counts, in place (chunks of
+//                    SCAN_CHUNK buckets, one workgroup over the chunks' totals, the chunks again).
 //   k_cloud_fill     one lane per reference point: a slot from the bucket's cursor (integer atomic), the point and its index copied
 //                    there -- a bucket's points are contiguous for the query.  The cursors end as the buckets' ends: one array
 //                    serves count, offset and end.
@@ -44,6 +44,7 @@
 
 #include "pxr_batch.h"
 #include "pxr_internal.h"
+#include "pxr_scan.h"
 
 namespace pxr {
 namespace {
@@ -99,44 +100,14 @@ __global__ __launch_bounds__(CL_THREADS) void k_cloud_grid(const GridArgs a) {
 }
 
 // ---- exclusive prefix sums over the buckets, in place ------------------------------------------------------------------------------
-// the exclusive prefix of v over the workgroup in lane order, and the workgroup's total
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* s_part, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl(inc, lane >= d ? lane - d : 0, 64);
-    if (lane >= d) inc += up;
-  }
-  __syncthreads();                              // (the previous use of s_part is over)
-  if (lane == 63) s_part[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < CL_THREADS / 64; ++w) { if (w < wave) before += s_part[w]; total += s_part[w]; }
-  return before + inc - v;
-}
-
+// the chunks' totals; k_exclusive_scan in one workgroup turns them into the sums before each chunk; the chunks again
 __global__ __launch_bounds__(CL_THREADS) void k_scan_reduce(const uint32_t* v, int64_t n, uint32_t* partial) {
   __shared__ uint32_t s_part[CL_THREADS / 64];
   const int64_t first = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCAN_PER_LANE;
   uint32_t s = 0;
   for (int k = 0; k < SCAN_PER_LANE; ++k) if (first + k < n) s += v[first + k];
-  uint32_t total;
-  block_scan(s, s_part, total);
+  const uint32_t total = block_int_sum<CL_THREADS>(s, s_part);
   if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// one workgroup: partial[c] becomes the sum of the chunks before c
-__global__ __launch_bounds__(CL_THREADS) void k_scan_partials(uint32_t* partial, int64_t n_chunks) {
-  __shared__ uint32_t s_part[CL_THREADS / 64];
-  const int64_t per = (n_chunks + CL_THREADS - 1) / CL_THREADS, first = (int64_t)threadIdx.x * per;
-  uint32_t s = 0;
-  for (int64_t k = first; k < first + per && k < n_chunks; ++k) s += partial[k];
-  uint32_t total;
-  uint32_t run = block_scan(s, s_part, total);
-  for (int64_t k = first; k < first + per && k < n_chunks; ++k) { const uint32_t c = partial[k]; partial[k] = run; run += c; }
 }
 
 __global__ __launch_bounds__(CL_THREADS) void k_scan_apply(uint32_t* v, int64_t n, const uint32_t* partial) {
@@ -146,7 +117,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_scan_apply(uint32_t* v, int64_t 
 #pragma unroll
   for (int k = 0; k < SCAN_PER_LANE; ++k) { c[k] = first + k < n ? v[first + k] : 0u; s += c[k]; }
   uint32_t total;
-  uint32_t run = partial[blockIdx.x] + block_scan(s, s_part, total);
+  uint32_t run = partial[blockIdx.x] + block_exclusive_scan<CL_THREADS>(s, s_part, total);
 #pragma unroll
   for (int k = 0; k < SCAN_PER_LANE; ++k) { if (first + k < n) v[first + k] = run; run += c[k]; }
 }
@@ -324,7 +295,7 @@ int cloud_nearest(pxr_ctx* ctx, int64_t n_ref, const double* d_ref, int64_t n_qu
     PXR_HIP(hipMemsetAsync(g.bucket, 0, sizeof(uint32_t) * (size_t)buckets, st));
     hipLaunchKernelGGL(k_cloud_grid<false>, dim3(blocks_of(n_ref)), dim3(CL_THREADS), 0, st, g);
     hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)n_chunks), dim3(CL_THREADS), 0, st, (const uint32_t*)g.bucket, (int64_t)buckets, partial);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(CL_THREADS), 0, st, partial, n_chunks);
+    hipLaunchKernelGGL((k_exclusive_scan<CL_THREADS, uint32_t, uint32_t>), dim3(1), dim3(CL_THREADS), 0, st, n_chunks, (const uint32_t*)partial, partial, 0);
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)n_chunks), dim3(CL_THREADS), 0, st, g.bucket, (int64_t)buckets, (const uint32_t*)partial);
     hipLaunchKernelGGL(k_cloud_grid<true>, dim3(blocks_of(n_ref)), dim3(CL_THREADS), 0, st, g);
   }

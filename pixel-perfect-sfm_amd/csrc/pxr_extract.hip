@@ -23,6 +23,7 @@
 #include "pxr_device.h"
 #include "pxr_dispatch.h"
 #include "pxr_internal.h"
+#include "pxr_scan.h"
 
 namespace pxr {
 
@@ -141,19 +142,6 @@ __global__ __launch_bounds__(256) void ex_tile_count(int64_t n, const double* __
   atomicAdd(hist + t, 1);
 }
 
-__global__ __launch_bounds__(1024) void ex_tile_scan(int n_tiles, int* __restrict__ hist /* counts -> first slots */) {
-  __shared__ int part[1024];
-  const int per = (n_tiles + 1023) / 1024, t0 = threadIdx.x * per;
-  int s = 0;
-  for (int i = t0; i < min(n_tiles, t0 + per); ++i) s += hist[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { int run = 0; for (int i = 0; i < 1024; ++i) { const int v = part[i]; part[i] = run; run += v; } }
-  __syncthreads();
-  int run = part[threadIdx.x];
-  for (int i = t0; i < min(n_tiles, t0 + per); ++i) { const int v = hist[i]; hist[i] = run; run += v; }
-}
-
 __global__ __launch_bounds__(256) void ex_tile_scatter(int64_t n, const int* __restrict__ tile_of, int* __restrict__ cursor,
                                                        int* __restrict__ order) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -193,7 +181,8 @@ extern "C" int pxr_arena_extract(pxr_ctx* ctx, pxr_arena* a, int64_t first, int6
     PXR_HIP(hipMemsetAsync(hist, 0, sizeof(int) * n_tiles, ctx->stream));
     const unsigned nb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(ex_tile_count, dim3(nb), dim3(256), 0, ctx->stream, n, d_keypoints, sx, sy, a->H, w, h, tiles_x, tile_of, hist);
-    hipLaunchKernelGGL(ex_tile_scan, dim3(1), dim3(1024), 0, ctx->stream, n_tiles, hist);
+    hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, ctx->stream, (int64_t)n_tiles, (const int*)hist, hist,
+                       0);   // counts -> first slots in place; hist has n_tiles entries: no total
     hipLaunchKernelGGL(ex_tile_scatter, dim3(nb), dim3(256), 0, ctx->stream, n, tile_of, hist, order);
     d_order = order;
   }

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pxr_internal.h"
+#include "pxr_scan.h"
 
 namespace pxr {
 namespace {
@@ -81,20 +82,6 @@ constexpr int kMaxComponentMatches = 32768;   // ~0.3 s of one wavefront; beyond
 __global__ void g_max(int n, const int* __restrict__ cnt, int* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && cnt[i] > 0) atomicMax(out, cnt[i]);
-}
-
-// exclusive scan of a[0..n) in place, a[n] = total: one workgroup, every thread a contiguous chunk
-__global__ __launch_bounds__(1024) void g_scan(int n, int* __restrict__ a) {
-  __shared__ int part[1024];
-  const int per = (n + 1023) / 1024, t0 = threadIdx.x * per, t1 = min(n, t0 + per);
-  int s = 0;
-  for (int i = t0; i < t1; ++i) s += a[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { int run = 0; for (int i = 0; i < 1024; ++i) { const int v = part[i]; part[i] = run; run += v; } a[n] = run; }
-  __syncthreads();
-  int run = part[threadIdx.x];
-  for (int i = t0; i < t1; ++i) { const int v = a[i]; a[i] = run; run += v; }
 }
 
 struct EdgeKey { double sim; int64_t s, d; int e; };
@@ -288,7 +275,7 @@ extern "C" int pxr_graph_labels_device(pxr_ctx* ctx, int64_t n_nodes, const int3
       return set_error(PXR_EUNSUPPORTED, "pxr_graph_labels_device: a connected component holds %d matches (limit %d): label on the host",
                        h_flag[0], kMaxComponentMatches);
   }
-  hipLaunchKernelGGL(g_scan, dim3(1), dim3(1024), 0, st, n, ptr);
+  hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, st, (int64_t)n, (const int*)ptr, ptr, 1);
   PXR_HIP(hipMemcpyAsync(cursor, ptr, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToDevice, st));
   if (m > 0) hipLaunchKernelGGL(g_scatter, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_src, (const int*)comp, cursor, bucket);
   // 3. constrained merges, one wavefront per component
@@ -301,7 +288,7 @@ extern "C" int pxr_graph_labels_device(pxr_ctx* ctx, int64_t n_nodes, const int3
                        d_edge_src, d_edge_dst, d_edge_sim, d_node_image, parent, next, tail, tsize);
   // 4. track ids in node order
   hipLaunchKernelGGL(g_root_flags, dim3(gblk(n)), dim3(256), 0, st, n, (const int*)parent, cursor);
-  hipLaunchKernelGGL(g_scan, dim3(1), dim3(1024), 0, st, n, cursor);
+  hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, st, (int64_t)n, (const int*)cursor, cursor, 1);
   hipLaunchKernelGGL(g_assign, dim3(gblk(n)), dim3(256), 0, st, n, (const int*)parent, (const int*)cursor, d_track_labels);
   int h_tracks = 0;
   PXR_HIP(hipMemcpyAsync(&h_tracks, cursor + n, 4, hipMemcpyDeviceToHost, st));
@@ -312,8 +299,8 @@ extern "C" int pxr_graph_labels_device(pxr_ctx* ctx, int64_t n_nodes, const int3
       hipLaunchKernelGGL(g_count, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_src, (const int*)nullptr, optr);
       hipLaunchKernelGGL(g_count, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_dst, (const int*)nullptr, iptr);
     }
-    hipLaunchKernelGGL(g_scan, dim3(1), dim3(1024), 0, st, n, optr);
-    hipLaunchKernelGGL(g_scan, dim3(1), dim3(1024), 0, st, n, iptr);
+    hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, st, (int64_t)n, (const int*)optr, optr, 1);
+    hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, st, (int64_t)n, (const int*)iptr, iptr, 1);
     PXR_HIP(hipMemcpyAsync(comp, iptr, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, st));     // comp is free now: cursor of the in-lists
     if (m > 0) hipLaunchKernelGGL(g_scatter, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_dst, (const int*)nullptr, comp, ilist);
     hipLaunchKernelGGL(g_scores, dim3(gblk(n)), dim3(256), 0, st, n, (const int*)optr, (const int*)iptr, ilist, d_edge_src, d_edge_dst,

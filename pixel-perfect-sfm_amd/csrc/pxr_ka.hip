@@ -35,6 +35,7 @@
 #include "pxr_dispatch.h"
 #include "pxr_interp.h"
 #include "pxr_internal.h"
+#include "pxr_scan.h"
 
 namespace pxr {
 
@@ -203,22 +204,6 @@ __device__ __forceinline__ double block_sum(double v, double* sh4) {
 #pragma unroll
   for (int k = 1; k < KA_NT / 64; ++k) t += sh4[k];
   return uniform_f64(t);     // every lane holds the sum: in scalar registers it does not compete with the interpolation core's 256
-}
-
-// block-wide exclusive prefix sum over the KA_NT threads (in thread order); total broadcast
-__device__ __forceinline__ int block_excl_scan(int v, int* sh_scan, int& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-  for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(x, off); if (lane >= off) x += y; }
-  __syncthreads();
-  if (lane == 63) sh_scan[w] = x;
-  __syncthreads();
-  int base = 0;
-  for (int k = 0; k < w; ++k) base += sh_scan[k];
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < KA_NT / 64; ++k) total += sh_scan[k];
-  return base + x - v;
 }
 
 // writes of one lane become visible to the other lanes of the same wavefront
@@ -823,9 +808,9 @@ __global__ __launch_bounds__(KA_NT) void ka_setup_kernel(const KaArgs a, KaInfo*
     const int i = base + tid;
     const int c = i < nloc ? cnt[i] : 0;
     int tot;
-    const int e_nodes = block_excl_scan(c, sh_scan, tot) + run_nodes; run_nodes += tot;
-    const int e_h = block_excl_scan(4 * c * c, sh_scan, tot) + run_h; run_h += tot;
-    const int e_c = block_excl_scan(c > 0 ? 1 : 0, sh_scan, tot) + run_c; run_c += tot;
+    const int e_nodes = block_exclusive_scan<KA_NT>(c, sh_scan, tot) + run_nodes; run_nodes += tot;
+    const int e_h = block_exclusive_scan<KA_NT>(4 * c * c, sh_scan, tot) + run_h; run_h += tot;
+    const int e_c = block_exclusive_scan<KA_NT>(c > 0 ? 1 : 0, sh_scan, tot) + run_c; run_c += tot;
     if (c > 0) {
       cstart[i] = e_nodes; hoff[i] = e_h; cidx[i] = e_c;
       p.comp_v0[e_c] = 2 * e_nodes;

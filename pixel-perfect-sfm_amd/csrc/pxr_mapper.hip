@@ -10,7 +10,7 @@
 //                 an image, every observation filed under its own image), obs_track / image_camera in range, camera sizes positive
 //   k_map_count   one workgroup per image: visible observations counted, their pyramid cells marked as bit words in LDS
 //                 (atomicOr), the score summed from the population counts of the words
-//   k_map_scan    one workgroup: corr_offsets = exclusive scan of n_visible
+//   k_exclusive_scan (pxr_scan.h)   corr_offsets = exclusive scan of n_visible
 //   k_map_write   one workgroup per image: the visible observations written in ascending observation order -- a prefix sum over
 //                 the lanes of a wavefront by shuffles, over the wavefronts through LDS, chunk after chunk
 //
@@ -23,6 +23,7 @@
 
 #include "pxr_batch.h"
 #include "pxr_internal.h"
+#include "pxr_scan.h"
 
 namespace pxr {
 
@@ -61,38 +62,6 @@ __device__ __forceinline__ bool map_visible(const MapArgs& a, int64_t o) {
 __device__ __forceinline__ int map_cell(double x, int levels, int size) {
   const double f = floor(x * (double)(1 << levels) / (double)size), top = (double)((1 << levels) - 1);
   return f < 0.0 ? 0 : f > top ? (1 << levels) - 1 : (int)f;
-}
-
-// the sum of v over the workgroup, on every lane (integers: no order to keep)
-__device__ __forceinline__ long long map_block_sum(long long v, long long* s_part) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();                              // (the previous use of s_part is over)
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long sum = 0;
-#pragma unroll
-  for (int w = 0; w < MAP_WAVES; ++w) sum += s_part[w];
-  return sum;
-}
-
-// the exclusive prefix of v over the workgroup in lane order, and the workgroup's total
-__device__ __forceinline__ long long map_block_scan(long long v, long long* s_part, long long& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long up = __shfl(inc, lane >= d ? lane - d : 0, 64);
-    if (lane >= d) inc += up;
-  }
-  __syncthreads();                              // (the previous use of s_part is over)
-  if (lane == 63) s_part[wave] = inc;
-  __syncthreads();
-  long long before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < MAP_WAVES; ++w) { if (w < wave) before += s_part[w]; total += s_part[w]; }
-  return before + inc - v;
 }
 
 // ---- validation --------------------------------------------------------------------------------------------------------------
@@ -146,23 +115,9 @@ __global__ __launch_bounds__(MAP_THREADS) void k_map_count(const MapArgs a) {
     const int first = map_level_first(l), nw = map_level_words(l);
     for (int w = threadIdx.x; w < nw; w += MAP_THREADS) score += ((long long)1 << (2 * l)) * __builtin_popcount((unsigned)s_bits[first + w]);
   }
-  count = map_block_sum(count, s_part);
-  score = map_block_sum(score, s_part);
+  count = block_int_sum<MAP_THREADS>(count, s_part);
+  score = block_int_sum<MAP_THREADS>(score, s_part);
   if (threadIdx.x == 0) { a.n_visible[img] = (int32_t)count; a.score[img] = score; }
-}
-
-// ---- the offsets ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MAP_THREADS) void k_map_scan(int32_t n, const int32_t* __restrict__ n_visible, int64_t* __restrict__ offsets) {
-  __shared__ long long s_part[MAP_WAVES];
-  long long carry = 0;
-  for (int32_t base = 0; base < n; base += MAP_THREADS) {
-    const int32_t i = base + (int32_t)threadIdx.x;
-    long long total;
-    const long long before = map_block_scan(i < n ? (long long)n_visible[i] : 0, s_part, total);
-    if (i < n) offsets[i] = carry + before;
-    carry += total;
-  }
-  if (threadIdx.x == 0) offsets[n] = carry;
 }
 
 // ---- pass 2: the ordered write ---------------------------------------------------------------------------------------------------
@@ -177,7 +132,7 @@ __global__ __launch_bounds__(MAP_THREADS) void k_map_write(const MapArgs a) {
     const int64_t o = k < k1 ? a.image_obs[k] : -1;
     const bool vis = o >= 0 && map_visible(a, o);
     long long total;
-    const long long before = map_block_scan(vis ? 1 : 0, s_part, total);
+    const long long before = block_exclusive_scan<MAP_THREADS>((long long)(vis ? 1 : 0), s_part, total);
     if (vis) {
       const int64_t j = at + before;
       const int64_t t = a.obs_track[o];
@@ -261,7 +216,8 @@ static int mapper_visibility(pxr_ctx* ctx, const pxr_tri_view* v, const int64_t*
   timer.mark(2);
   hipLaunchKernelGGL(k_map_count, dim3((unsigned)I), dim3(MAP_THREADS), 0, st, a);
   timer.mark(3);
-  hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(MAP_THREADS), 0, st, I, d_n_visible, d_corr_offsets);
+  hipLaunchKernelGGL((k_exclusive_scan<MAP_THREADS, int32_t, int64_t>), dim3(1), dim3(MAP_THREADS), 0, st, (int64_t)I, (const int32_t*)d_n_visible,
+                     d_corr_offsets, 1);
   timer.mark(4);
   hipLaunchKernelGGL(k_map_write, dim3((unsigned)I), dim3(MAP_THREADS), 0, st, a);
   timer.mark(5);

@@ -10,7 +10,7 @@
 //   k_sift_detect    <false> counts the keypoints of every block of 1024 DoG samples, <true> writes them behind the block's offset
 //                    in sample order -- count, scan, write: the order (o, s, yi, xi) without an atomic.  The DoG is formed on the
 //                    fly from two levels; the refinement of an extremum runs in float64 on its own lane
-//   k_sift_scan      one workgroup: the exclusive prefix sums (blocks -> keypoints, keypoints -> features)
+//   k_exclusive_scan (pxr_scan.h) the exclusive prefix sums (blocks -> keypoints, keypoints -> features)
 //   k_sift_orient    one wavefront per keypoint: the 36-bin histogram, owner-computes (see below), then lane 0 smooths and picks
 //   k_sift_emit      keypoint x orientation -> feature rows below `capacity`
 //   k_sift_gather    rows of the detector's output by index, split into keypoints, scales, orientations, scores (the bindings)
@@ -27,6 +27,7 @@
 
 #include "pxr_batch.h"
 #include "pxr_internal.h"
+#include "pxr_scan.h"
 
 namespace pxr {
 
@@ -213,25 +214,6 @@ __device__ bool sift_candidate(const SiftDetect& a, int k, int s, int x, int y, 
   return true;
 }
 
-// the exclusive prefix of v over the workgroup in lane order, and the workgroup's total
-__device__ __forceinline__ long long sift_block_scan(long long v, long long* s_part, long long& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long up = __shfl(inc, lane >= d ? lane - d : 0, 64);
-    if (lane >= d) inc += up;
-  }
-  __syncthreads();                              // (the previous use of s_part is over)
-  if (lane == 63) s_part[wave] = inc;
-  __syncthreads();
-  long long before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < SIFT_WAVES; ++w) { if (w < wave) before += s_part[w]; total += s_part[w]; }
-  return before + inc - v;
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(SIFT_THREADS) void k_sift_detect(const SiftDetect a) {
   __shared__ long long s_part[SIFT_WAVES];
@@ -252,7 +234,7 @@ __global__ __launch_bounds__(SIFT_THREADS) void k_sift_detect(const SiftDetect a
       if (x >= 1 && x <= w - 2 && y >= 1 && y <= h - 2) found = sift_candidate(a, k, s, x, y, kp);
     }
     long long total;
-    const long long before = sift_block_scan(found ? 1 : 0, s_part, total);
+    const long long before = block_exclusive_scan<SIFT_THREADS>((long long)(found ? 1 : 0), s_part, total);
     if (WRITE && found) {
       const long long j = at + before;
       if (j < a.kp_cap) {
@@ -264,19 +246,6 @@ __global__ __launch_bounds__(SIFT_THREADS) void k_sift_detect(const SiftDetect a
     at += total;
   }
   if (!WRITE && threadIdx.x == 0) a.block_count[b] = (int32_t)at;
-}
-
-__global__ __launch_bounds__(SIFT_THREADS) void k_sift_scan(int64_t n, const int32_t* __restrict__ counts, int64_t* __restrict__ offsets) {
-  __shared__ long long s_part[SIFT_WAVES];
-  long long carry = 0;
-  for (int64_t base = 0; base < n; base += SIFT_THREADS) {
-    const int64_t i = base + (int64_t)threadIdx.x;
-    long long total;
-    const long long before = sift_block_scan(i < n ? (long long)counts[i] : 0, s_part, total);
-    if (i < n) offsets[i] = carry + before;
-    carry += total;
-  }
-  if (threadIdx.x == 0) offsets[n] = carry;
 }
 
 // ---- orientation and descriptor ---------------------------------------------------------------------------------------------------
@@ -631,7 +600,8 @@ static int sift_detect(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const
     timer.mark(0);
     hipLaunchKernelGGL(k_sift_detect<false>, dim3((unsigned)n_blocks), dim3(SIFT_THREADS), 0, st, a);
     timer.mark(1);
-    hipLaunchKernelGGL(k_sift_scan, dim3(1), dim3(SIFT_THREADS), 0, st, n_blocks, (const int32_t*)a.block_count, (int64_t*)(ws + o_off));
+    hipLaunchKernelGGL((k_exclusive_scan<SIFT_THREADS, int32_t, int64_t>), dim3(1), dim3(SIFT_THREADS), 0, st, n_blocks, (const int32_t*)a.block_count,
+                       (int64_t*)(ws + o_off), 1);
     timer.mark(2);
     if (int rc = hip_check(hipGetLastError(), "k_sift_detect launch")) return rc;
     PXR_HIP(hipMemcpyAsync(&n_kp, a.block_off + n_blocks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -651,7 +621,7 @@ static int sift_detect(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const
     hipLaunchKernelGGL(k_sift_orient, dim3((unsigned)grid), dim3(64), 0, st, d_pyramid, a.L, n_kp, grid, o->upright ? 1 : 0,
                        (int)o->max_num_orientations, (const double*)a.kp, (const int32_t*)a.rec, n_orient, theta);
     timer.mark(4);
-    hipLaunchKernelGGL(k_sift_scan, dim3(1), dim3(SIFT_THREADS), 0, st, n_kp, (const int32_t*)n_orient, feat_off);
+    hipLaunchKernelGGL((k_exclusive_scan<SIFT_THREADS, int32_t, int64_t>), dim3(1), dim3(SIFT_THREADS), 0, st, n_kp, (const int32_t*)n_orient, feat_off, 1);
     const int egrid = (int)std::min<int64_t>(sift_blocks(n_kp), SIFT_MAX_GRID);
     if (capacity > 0)
       hipLaunchKernelGGL(k_sift_emit, dim3((unsigned)egrid), dim3(SIFT_THREADS), 0, st, n_kp, egrid, capacity, (const double*)a.kp,

@@ -168,6 +168,15 @@ def nearest_cases():
             for k, (r, q, md) in cases.items()}
 
 
+def many_chunks_case():
+    """(ref, query, max_dist) with 2^19 + 12 reference points: a table of 2^21 buckets, which the scan cuts into 512 chunks of 4096
+    -- more chunks than the workgroup that scans their totals has threads, so a thread owns two.  Not in NEAREST_CASES: the
+    lane emulation would spend minutes on it; 64 queries keep the brute force at the size of the other cases."""
+    rng = np.random.default_rng(19)
+    ref = rng.uniform(-1, 1, (2 ** 19 + 12, 3))
+    return ref, _near(rng, ref, 64, 0.008), 0.01
+
+
 # ---- voxel cases: name -> (xyz, dist2, voxel_size, tolerances) -------------------------------------------------------------------
 TOL3 = (0.01, 0.02, 0.05)
 TOL8 = (0.005, 0.01, 0.02, 0.03, 0.05, 0.1, 0.2, 0.5)

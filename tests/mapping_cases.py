@@ -104,6 +104,32 @@ def boundary_batch(seed=11):
     return scene, xyz, status, mask, planned
 
 
+@functools.lru_cache(maxsize=None)
+def many_images_batch(n_images):
+    """Many images with a handful of observations each (0 .. 4, a fifth of them on tracks without a point), every tenth image
+    masked out: what the prefix sum over the images' counts can get wrong around the size of its workgroup (256 threads: 255, 256,
+    257 images, and 600 -- three images to a thread).  Returns (scene, xyz, status, image_mask)."""
+    rng = np.random.default_rng(n_images)
+    cam_size = np.array([[640, 480]], np.int32)
+    n_tracks = 40
+    status = np.zeros(n_tracks, np.int32)
+    status[32:] = 1
+    xyz = rng.uniform(-1, 1, (n_tracks, 3))
+    xyz[32:] = np.nan
+    per_image = rng.integers(0, 5, n_images)
+    image = np.repeat(np.arange(n_images), per_image)
+    track = rng.integers(0, n_tracks, len(image))
+    order = np.lexsort((rng.permutation(len(image)), track))         # track-major, images in no order inside a track
+    offsets = np.zeros(n_tracks + 1, np.int64)
+    np.cumsum(np.bincount(track, minlength=n_tracks), out=offsets[1:])
+    scene = dict(track_offsets=offsets, obs_image=image[order].astype(np.int32), obs_xy=rng.uniform(0.0, 480.0, (len(image), 2)),
+                 image_camera=np.zeros(n_images, np.int32), cam_model=np.array([2], np.int32),
+                 cam_params=np.array([[600.0, 320.0, 240.0, 0.01]]), cam_size=cam_size)
+    mask = np.ones(n_images, np.uint8)
+    mask[::10] = 0
+    return scene, xyz, status, mask
+
+
 def bad_inputs(scene):
     """(name, key of the device array to replace, the bad host array, a word of the message) for every class of bad input."""
     off, n_obs = np.asarray(scene["track_offsets"]), len(scene["obs_image"])

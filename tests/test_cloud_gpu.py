@@ -31,6 +31,17 @@ def test_nearest_equals_the_brute_force_search(ctx, name):
     assert index2.tobytes() == index.tobytes() and dist22.tobytes() == dist2.tobytes()
 
 
+def test_nearest_with_more_scan_chunks_than_scan_threads(ctx):
+    """The bucket table is one scan chunk in the size_* cases and two in random_3000x2000, one_cell and spread; here it is 512, so
+    that the one workgroup over the chunks' totals (k_exclusive_scan<256> of csrc/pxr_scan.h, in place) gives two to a thread."""
+    ref, query, max_dist = cc.many_chunks_case()
+    index, dist2 = _nearest(ctx, ref, query, max_dist)
+    r_index, r_dist2 = cc.nearest(ref, query, max_dist)
+    assert (r_index >= 0).sum() > 32
+    assert np.array_equal(index, r_index), np.flatnonzero(index != r_index)[:8]
+    assert dist2.tobytes() == r_dist2.tobytes()
+
+
 def test_pairs_at_exactly_max_dist(ctx):
     for s in cc.EXACT_SCALES:
         for name, (ref, query, max_dist, inside) in cc.exact_pairs(s).items():

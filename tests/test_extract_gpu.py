@@ -196,3 +196,23 @@ def test_map_tile_ordered_extraction_of_many_patches(ctx):
     small.extract(0, t, kps[:1000], size, l2_normalize=True)
     assert np.array_equal(small.download()[0], arena.download(0, 1000)[0])
     arena.close(); small.close()
+
+
+def test_map_tile_order_on_a_map_of_more_than_1024_tiles(ctx):
+    """A 520 x 530 map has 33 x 34 = 1122 tiles of 16 pixels: in the one-workgroup prefix sum over the tile counts
+    (k_exclusive_scan<1024> of csrc/pxr_scan.h) a thread owns two tiles and most of the upper threads none, where the 48 tiles of
+    test_map_tile_ordered_extraction_of_many_patches leave one tile to a thread.  Every patch still lands in its keypoint's slot."""
+    import torch
+    import pxo_extract
+    from pixsfm_amd.engine import PatchArena
+    rng = np.random.default_rng(23)
+    fmap = rng.standard_normal((64, 520, 530), dtype=np.float32)
+    n = 4500
+    size = (2120.0, 2080.0)
+    kps = rng.uniform(-8, 2130, (n, 2))
+    want, corners, scale = pxo_extract.sparse_patches(fmap, kps, size, l2_normalize=False, dtype=np.float16)
+    arena = PatchArena(ctx, n, 16, 16, 64, np.float16)
+    assert arena.extract(0, torch.from_numpy(fmap).cuda(), kps, size, l2_normalize=False) == n
+    patches, c, s = arena.download()
+    assert np.array_equal(c, corners) and np.array_equal(patches, want)
+    arena.close()

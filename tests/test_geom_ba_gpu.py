@@ -194,6 +194,26 @@ def test_auto_selection_follows_the_image_count(ctx):
     assert out[1001]["final_cost"] < out[1001]["initial_cost"]
 
 
+@pytest.mark.parametrize("n_points", [2047, 2048, 2049, 4100])
+def test_point_structure_built_on_the_device_equals_the_host_lists(ctx, monkeypatch, n_points):
+    """The per-point offsets, variable flags and their number come from a two-launch prefix sum over chunks of 2048 points
+    (k_pt_scan_partials / k_pt_scan_apply over csrc/pxr_scan.h): one chunk short of full, exactly full, a second chunk of one
+    point, and three chunks.  PXR_BA_SETUP_HOST=1 builds the same structure with host_lists; the bound is the one
+    tests/test_ba_solve_gpu.py::test_device_built_observation_lists_equal_the_host_ones holds the two paths to."""
+    prob = geom_cases.make_case(n_cams=8, n_points=n_points, obs_per_point=3, seed=n_points, ramp=False)
+    gauge = _gauge(prob)
+    gauge[3][::7] = 1                                                       # constant points: the flags and their count
+    s_dev, p_dev = _solve(ctx, prob, gauge, max_iterations=2, linear_solver="direct")
+    monkeypatch.setenv("PXR_BA_SETUP_HOST", "1")
+    s_host, p_host = _solve(ctx, prob, gauge, max_iterations=2, linear_solver="direct")
+    monkeypatch.delenv("PXR_BA_SETUP_HOST")
+    print("%d points: cost %.15e (device lists) %.15e (host lists)" % (n_points, s_dev["final_cost"], s_host["final_cost"]))
+    assert s_host["iterations"] == s_dev["iterations"] and s_host["num_successful"] == s_dev["num_successful"] >= 1
+    assert abs(s_host["final_cost"] - s_dev["final_cost"]) <= 1e-9 * abs(s_dev["final_cost"])
+    assert all(np.abs(a - b).max() <= 1e-9 * max(1.0, np.abs(b).max()) for a, b in zip(p_host, p_dev))
+    assert np.array_equal(p_dev[3][::7], prob["xyz"][::7])                  # constant points untouched
+
+
 def test_non_finite_initial_evaluation_is_a_failed_solve_not_an_error(ctx):
     """[upstream] "Initial residual and Jacobian evaluation failed": termination FAILURE, the call itself succeeds and the
     parameters stay where they were -- the semantics of pxr_ba_solve."""

@@ -48,14 +48,10 @@ def _flat_random_graph(rng, n_groups, per, n_img, n_matches, n_cross):
     return node_image, src[order], dst[order], sim[order]
 
 
-@pytest.mark.parametrize("n_groups,per,n_matches", [(1500, 12, 60000), (40, 150, 30000)])
-def test_device_labelling_equals_host_labelling_at_size(ctx, n_groups, per, n_matches):
-    """Many small components (the KA regime) and a few large ones (hundreds of nodes, thousands of matches per
-    component: the wavefront's rank sort and the sequential merge run long)."""
+def _device_equals_host(ctx, node_image, src, dst, sim):
+    """Labels, scores and roots of the device against the native host implementation; returns the device inputs and the labels."""
     from pixsfm_amd import _lib
     lib = _lib.load()
-    rng = np.random.default_rng(n_groups)
-    node_image, src, dst, sim = _flat_random_graph(rng, n_groups, per, 40, n_matches, 300)
     n, m = len(node_image), len(src)
     want_l, want_s, want_r = np.empty(n, np.int64), np.empty(n, np.float64), np.empty(n, np.uint8)
     ntr = C.c_int64()
@@ -73,6 +69,19 @@ def test_device_labelling_equals_host_labelling_at_size(ctx, n_groups, per, n_ma
     assert np.array_equal(got_l.download(), want_l)
     assert np.array_equal(got_s.download(), want_s)
     assert np.array_equal(got_r.download(), want_r)
+    return d, want_l
+
+
+@pytest.mark.parametrize("n_groups,per,n_matches", [(1500, 12, 60000), (40, 150, 30000)])
+def test_device_labelling_equals_host_labelling_at_size(ctx, n_groups, per, n_matches):
+    """Many small components (the KA regime) and a few large ones (hundreds of nodes, thousands of matches per
+    component: the wavefront's rank sort and the sequential merge run long)."""
+    from pixsfm_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(n_groups)
+    node_image, src, dst, sim = _flat_random_graph(rng, n_groups, per, 40, n_matches, 300)
+    n, m = len(node_image), len(src)
+    d, want_l = _device_equals_host(ctx, node_image, src, dst, sim)
     # labels only (scores / roots optional), and the argument checks
     only = ctx.empty((n,), np.int64)
     _lib.check(lib.pxr_graph_labels_device(ctx.handle, n, d[0].ptr, m, d[1].ptr, d[2].ptr, d[3].ptr, only.ptr, None, None, None), "labels only")
@@ -80,6 +89,16 @@ def test_device_labelling_equals_host_labelling_at_size(ctx, n_groups, per, n_ma
     bad = ctx.to_device(src[::-1].copy(), np.int64)                   # not in Graph order
     with pytest.raises(_lib.PixsfmHipError):
         _lib.check(lib.pxr_graph_labels_device(ctx.handle, n, d[0].ptr, m, bad.ptr, d[2].ptr, d[3].ptr, only.ptr, None, None, None), "order")
+
+
+@pytest.mark.parametrize("n_groups,per", [(93, 11), (128, 8), (41, 25), (500, 10)])
+def test_device_labelling_around_the_size_of_the_scan_workgroup(ctx, n_groups, per):
+    """1023, 1024, 1025 and 5000 nodes: the four prefix sums over the nodes (k_exclusive_scan<1024> of csrc/pxr_scan.h) with threads
+    that own no element, exactly one each, a short last chunk, and several elements each."""
+    rng = np.random.default_rng(n_groups)
+    node_image, src, dst, sim = _flat_random_graph(rng, n_groups, per, 40, 4 * n_groups * per, 60)
+    assert len(node_image) in (1023, 1024, 1025, 5000)
+    _device_equals_host(ctx, node_image, src, dst, sim)
 
 
 def test_a_giant_component_is_refused_by_the_device_and_labelled_on_the_host(ctx):

@@ -40,6 +40,20 @@ def test_visibility_matches_the_reference_bit_for_bit(ctx, levels):
         assert set(s.kernel_ms) == {"check", "count", "scan", "write"}
 
 
+@pytest.mark.parametrize("n_images", [255, 256, 257, 600])
+def test_offsets_over_many_images_match_the_reference(ctx, n_images):
+    """More images than the boundary batch's 11: the prefix sum of the visible counts (k_exclusive_scan<256> of csrc/pxr_scan.h) at
+    one image to a thread less one, exactly, a second image on the first threads, and three to a thread."""
+    from pixsfm_amd.engine import MapperScene
+    scene, xyz, status, mask = mc.many_images_batch(n_images)
+    ref = mc.visibility_reference(scene, xyz, status, mask, 3)
+    got = MapperScene(ctx, scene).visibility(ctx.to_device(xyz, np.float64), ctx.to_device(status, np.int32), mask, 3)
+    assert got["n_corr"] == ref["n_corr"] > n_images
+    for k in OUTPUTS:
+        a = got[k].download()
+        assert np.array_equal(a if k in OUTPUTS[:3] else a[:ref["n_corr"]], ref[k]), k
+
+
 def test_bad_inputs_are_refused_and_leave_the_outputs_untouched(ctx):
     from pixsfm_amd._lib import PixsfmHipError
     scene, xyz, status, mask, _ = mc.boundary_batch()

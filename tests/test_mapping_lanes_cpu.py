@@ -68,6 +68,14 @@ def test_kernel_source_matches_the_reference_on_the_boundary_batch(emu, levels):
     _equal(got, n_corr, ref)
 
 
+@pytest.mark.parametrize("n_images", [257, 600])
+def test_offsets_over_many_images_match_the_reference(emu, n_images):
+    """More images than the prefix sum over their counts has threads: two and three images to a thread."""
+    scene, xyz, status, mask = mc.many_images_batch(n_images)
+    got, n_corr = _run(emu, scene, xyz, status, mask, 3)
+    _equal(got, n_corr, mc.visibility_reference(scene, xyz, status, mask, 3))
+
+
 def test_bad_inputs_are_refused_and_leave_the_outputs_untouched(emu):
     scene, xyz, status, mask, _ = mc.boundary_batch()
     for name, key, bad, word in mc.bad_inputs(scene):
