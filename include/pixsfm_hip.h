@@ -1276,6 +1276,90 @@ int pxr_ba_build_problem(int32_t n_images, const int32_t* image_camera, const in
                          int64_t* obs_point, uint8_t* image_in_problem, uint8_t* pose_is_const, uint8_t* tvec_mask_out,
                          int32_t* camera_mask, int8_t* point_role);
 
+/* ---- global mapping: rotation averaging and global positioning --------------------
+ * All rotations and centres at once from the verified pairs, instead of growing a model from an initial pair.  Conventions: a
+ * pair p = (i, j) carries the pose of camera j relative to camera i, x_j = R_p x_i + t_p; with image poses x_i = R_i X + t_i and
+ * centres c_i = -R_i^t t_i this is R_p = R_j R_i^t, and the baseline direction in the world b_p = -R_j^t t_p / |t_p| is parallel
+ * to c_j - c_i.  All d_ arrays are device pointers, h_ arguments host pointers.
+ *
+ * pxr_rotation_averaging.  d_pair_image [n_pairs][2] int32, d_pair_qvec [n_pairs][4] (normalised on the way in), d_pair_weight
+ * [n_pairs] >= 0 (for instance the pair's inlier count).  Outputs: d_qvec [n_images][4] (unit, w >= 0), *h_root, *h_iterations,
+ * d_pair_angle [n_pairs] = the residual angle (radians) of every pair under the final rotations.
+ *   1. Root: the image with the largest sum of weights over its pairs (summed in pair order), the first of equals.  R_root = I.
+ *   2. Initial rotations by spanning tree (host): Prim from the root over the pairs of POSITIVE weight, always the heaviest pair
+ *      that leaves the tree (ties: the lower pair index); R_j = R_p R_i or R_i = R_p^t R_j along it.  An image that is not
+ *      reached makes the call fail with PXR_EINVAL.
+ *   3. Iteration it = 0, 1, ...:  e_p = Log(R_j^t R_p R_i), theta_p = |e_p|;  rho_p = w_p / max(theta_p, min_angle) while
+ *      it < l1_iterations (L1 by reweighting), after that rho_p = w_p / (1 + (theta_p / sigma)^2);  solve L w = b, L the graph
+ *      Laplacian of the rho_p with the root's row and column removed, b_j += rho_p e_p, b_i -= rho_p e_p (the three coordinates
+ *      decouple: one (n - 1)^2 matrix, three right-hand sides);  R_k <- R_k Exp(w_k).  Stop once it >= l1_iterations and
+ *      max_k |w_k| < tolerance, or after max_iterations.
+ * Device: a lane per pair for Log and the weights; L and b assembled owner-computes per image row from an image -> pairs list
+ * (no atomics, the same bits every run); the solve is the library's dense fp64 Cholesky, three factor + solve calls per iteration.
+ * PXR_EINVAL, outputs untouched: n_images < 1, n_images - 1 > PXR_MAX_IMAGES_DIRECT, a pair index out of range, a pair with
+ * i == j, a weight negative or not finite, a qvec zero or not finite, an option out of range, images not connected to the root.
+ * PXR_ENUMERIC: a Laplacian that is not positive definite in floating point.  Synchronises the context's stream every iteration. */
+typedef struct {
+  int32_t l1_iterations;    /* 20 */
+  int32_t max_iterations;   /* 40 */
+  double min_angle;         /* 1e-3 radians: the floor of theta in the L1 weights */
+  double sigma;             /* 5.0 degrees: the Cauchy scale after the L1 phase */
+  double tolerance;         /* 1e-10 radians */
+} pxr_rotavg_options;
+void pxr_rotavg_default_options(pxr_rotavg_options* options);
+int pxr_rotation_averaging(pxr_ctx* ctx, int32_t n_images, int32_t n_pairs, const int32_t* d_pair_image, const double* d_pair_qvec,
+                           const double* d_pair_weight, const pxr_rotavg_options* options, double* d_qvec, int32_t* h_root,
+                           int32_t* h_iterations, double* d_pair_angle);
+/* The same, and HIP-event times summed over the iterations: h_kernel_ms[3] = residuals, first assembly, solves (with the two other
+ * assemblies and the update). */
+int pxr_rotation_averaging_timed(pxr_ctx* ctx, int32_t n_images, int32_t n_pairs, const int32_t* d_pair_image, const double* d_pair_qvec,
+                                 const double* d_pair_weight, const pxr_rotavg_options* options, double* d_qvec, int32_t* h_root,
+                                 int32_t* h_iterations, double* d_pair_angle, double* h_kernel_ms);
+
+/* pxr_global_positioning.  view: tracks, observations and cameras as for pxr_triangulate_tracks (offsets start at 0); its d_qvec
+ * holds the averaged rotations, d_tvec is ignored.  Pairs: d_pair_image [n_pairs][2], d_pair_dir [n_pairs][3] = the unit b_p above,
+ * d_pair_weight [n_pairs] >= 0; root: the image whose centre is the origin.  Outputs: d_centre [n_images][3], d_xyz [n_tracks][3]
+ * (written where the status is 0), d_track_status (0 = point written, 1 = fewer than two usable rays or near-singular A_k in the last
+ * round), d_obs_weight [n_obs] and d_pair_weight_out [n_pairs] (the final robust weights, 0 = rejected), *h_status (0 = ok,
+ * 1 = degenerate: the outputs are then unspecified and the return value is still 0), *h_rounds (rounds completed).
+ *   Every observation becomes a world-frame unit ray d = R_i^t (u, v, 1) / |.| with (u, v) its undistorted point; one that cannot
+ *   be undistorted has weight 0 throughout.  P = I - d d^t.  Pairs: P_p = I - b_p b_p^t, w_p = d_pair_weight[p] / max weight times
+ *   a robust factor that starts at 1.  Observation weights start at 1.  Each of `iterations` rounds:
+ *   1. per track A_k = sum w P; the track is valid iff det A_k > min_det; A_k^-1 in closed form (adjugate);
+ *   2. the reduced system over the centres, dense 3n x 3n, upper triangle: S_ii += w P for the observations of valid tracks,
+ *      S_ij -= (w_a P_a) A_k^-1 (w_b P_b) for every ordered pair (a, b) of observations of a valid track (images i, j, a = b
+ *      included), and w_p P_p added to (i, i) and (j, j), subtracted from (i, j) and (j, i);
+ *   3. gauge: c_root = 0 (its rows and columns removed); scale and sign by g^t c = h with g_j += w_p b_p, g_i -= w_p b_p,
+ *      h = sum w_p (the weighted mean baseline length along the pairs' own directions is 1).  The cost is homogeneous, so the
+ *      constrained minimum is y = S^-1 g, c = h y / (g^t y): one Cholesky solve.  A non-positive pivot or g^t y <= 0: degenerate;
+ *   4. X_k = A_k^-1 sum w P c_i;
+ *   5. with v = X_k - c_i, s = |P v| / |v|: w = 1 / (1 + (s / sigma_obs)^2), 0 for an invalid track or v = 0, and from round
+ *      cheirality_from on (counting from 0) 0 where d^t v <= 0; the pairs' robust factors likewise with v = c_j - c_i, sigma_pair.
+ * Device: a track per 16 lanes; everything between two rounds stays on the device, the host reads one word per round.  S is summed
+ * in 64-bit fixed point with integer atomics (every addend is at most 1 in magnitude, the scale comes from the largest number of
+ * addends an entry can receive): the same bits every run.
+ * PXR_EINVAL, outputs untouched: offsets not starting at 0, not monotone or not ending at n_obs; an image, camera, pair or root
+ * index out of range; a pair with i == j; a direction that is not a finite unit vector (to 1e-9); a weight negative or not finite;
+ * n_images - 1 > PXR_MAX_IMAGES_DIRECT (the Cholesky's 3 (n - 1) columns); an option out of range. */
+typedef struct {
+  int32_t iterations;       /* 8 */
+  int32_t cheirality_from;  /* 2: the first round (from 0) whose reweighting rejects what lies behind its camera */
+  double sigma_obs;         /* 1.0 degree */
+  double sigma_pair;        /* 3.0 degrees */
+  double min_det;           /* 1e-12 */
+} pxr_globalpos_options;
+void pxr_globalpos_default_options(pxr_globalpos_options* options);
+int pxr_global_positioning(pxr_ctx* ctx, const pxr_tri_view* view, int32_t n_pairs, const int32_t* d_pair_image, const double* d_pair_dir,
+                           const double* d_pair_weight, int32_t root, const pxr_globalpos_options* options, double* d_centre,
+                           double* d_xyz, int32_t* d_track_status, double* d_obs_weight, double* d_pair_weight_out, int32_t* h_status,
+                           int32_t* h_rounds);
+/* The same, and HIP-event times summed over the rounds: h_kernel_ms[5] = tracks (A_k), contraction (with the pair terms), gauge and
+ * packing, Cholesky, scale and reweighting. */
+int pxr_global_positioning_timed(pxr_ctx* ctx, const pxr_tri_view* view, int32_t n_pairs, const int32_t* d_pair_image,
+                                 const double* d_pair_dir, const double* d_pair_weight, int32_t root,
+                                 const pxr_globalpos_options* options, double* d_centre, double* d_xyz, int32_t* d_track_status,
+                                 double* d_obs_weight, double* d_pair_weight_out, int32_t* h_status, int32_t* h_rounds, double* h_kernel_ms);
+
 /* Residual-block selection of TopologicalKeypointOptimizer::SetUp + AddIntraResiduals (A12,
  * topological_keypoint_optimizer.h:97-175, featuremetric_keypoint_optimizer.h:158-202): intra-track matches,
  * minus keypoint aliases, optionally root edges only, plus root-regularisation blocks; weights = similarity

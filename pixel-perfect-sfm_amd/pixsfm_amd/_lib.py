@@ -100,6 +100,18 @@ class TriOptions(C.Structure):
                 ("min_track_len", C.c_int32), ("max_hypotheses", C.c_int32)]
 
 
+class RotavgOptions(C.Structure):
+    """pxr_rotavg_options"""
+    _fields_ = [("l1_iterations", C.c_int32), ("max_iterations", C.c_int32), ("min_angle", C.c_double), ("sigma", C.c_double),
+                ("tolerance", C.c_double)]
+
+
+class GlobalposOptions(C.Structure):
+    """pxr_globalpos_options"""
+    _fields_ = [("iterations", C.c_int32), ("cheirality_from", C.c_int32), ("sigma_obs", C.c_double), ("sigma_pair", C.c_double),
+                ("min_det", C.c_double)]
+
+
 class AbsposeOptions(C.Structure):
     """pxr_abspose_options"""
     _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
@@ -231,6 +243,13 @@ _SIGNATURES = {
     "pxr_mapper_visibility": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_int64)]),
+    "pxr_rotavg_default_options": (None, [C.POINTER(RotavgOptions)]),
+    "pxr_rotation_averaging": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RotavgOptions),
+                                         C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    "pxr_globalpos_default_options": (None, [C.POINTER(GlobalposOptions)]),
+    "pxr_global_positioning": (C.c_int, [C.c_void_p, C.POINTER(TriView), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.POINTER(GlobalposOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pxr_ba_compute_references": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BaView), C.POINTER(InterpCfg),
                                             C.POINTER(Loss), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pxr_costmap_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
@@ -282,7 +301,8 @@ _SIGNATURES = {
 # every *_timed entry point: the arguments of its plain twin, then the array that takes the stages' HIP-event times
 for _name in ("pxr_triangulate_tracks", "pxr_absolute_pose", "pxr_two_view_geometry", "pxr_homography", "pxr_fundamental",
               "pxr_match_descriptors", "pxr_match_guided", "pxr_mapper_visibility", "pxr_sift_pyramid", "pxr_sift_detect", "pxr_sift_describe",
-              "pxr_vocab_train", "pxr_vlad_aggregate", "pxr_retrieval_topk", "pxr_cloud_nearest", "pxr_cloud_voxel_fractions"):
+              "pxr_vocab_train", "pxr_vlad_aggregate", "pxr_retrieval_topk", "pxr_cloud_nearest", "pxr_cloud_voxel_fractions",
+              "pxr_rotation_averaging", "pxr_global_positioning"):
     _SIGNATURES[_name + "_timed"] = (_SIGNATURES[_name][0], _SIGNATURES[_name][1] + [C.POINTER(C.c_double)])
 LINEAR_AUTO, LINEAR_DIRECT, LINEAR_ITERATIVE = 0, 1, 2
 GUIDE_EPIPOLAR, GUIDE_HOMOGRAPHY = 0, 1      # PXR_GUIDE_*: the kind of a pair's model in pxr_match_guided

@@ -25,6 +25,8 @@ from .homography import TwoViewClassifier, homography_matrix_estimation, two_vie
 from .fundamental import fundamental_matrix_estimation, two_view_config_uncalibrated  # noqa: F401,E402
 from . import mapping  # noqa: F401,E402
 from .mapping import IncrementalMapper  # noqa: F401,E402
+from . import global_mapping  # noqa: F401,E402
+from .global_mapping import GlobalMapper, rotation_averaging  # noqa: F401,E402
 from . import sift  # noqa: F401,E402
 from .sift import SiftExtractor  # noqa: F401,E402
 from . import retrieval  # noqa: F401,E402

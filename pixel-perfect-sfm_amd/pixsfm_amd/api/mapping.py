@@ -52,6 +52,113 @@ def median_triangulation_angle(xyz, centre1, centre2):
     return float(np.median(np.degrees(np.arccos(np.clip(cos, -1.0, 1.0)))))
 
 
+# -- the stages both mappers share (IncrementalMapper here, GlobalMapper in global_mapping.py), on flat arrays -----------------------
+def triangulate_registered(conf, st, registered):
+    """Tracks restricted to the registered images -> (problem, restricted dict, device outputs), or None without observations."""
+    r = st["scene"].restricted_tracks(registered)
+    if len(r["obs_index"]) == 0:
+        return None
+    prob = TriangulationProblem(st["ctx"], dict(track_offsets=r["track_offsets"], obs_image=r["obs_image"], obs_xy=r["obs_xy"],
+                                                image_camera=st["image_camera"], qvec=st["qvec"], tvec=st["tvec"],
+                                                cam_model=st["cam_model"], cam_params=st["cam_params"]))
+    out = prob.triangulate(timed=True, **conf['triangulation'])
+    st["ms"]["triangulate"] += sum(prob.kernel_ms.values())
+    return prob, r, out
+
+
+def retriangulate(conf, st, prob):
+    """The same tracks again from the poses (and intrinsics) of st."""
+    prob.d["qvec"].upload(st["qvec"])
+    prob.d["tvec"].upload(st["tvec"])
+    prob.d["cam_params"].upload(_padded_cam_params(st["cam_params"], len(st["cam_model"])))
+    out = prob.triangulate(timed=True, **conf['triangulation'])
+    st["ms"]["triangulate"] += sum(prob.kernel_ms.values())
+    return out
+
+
+def bundle_adjust(conf, st, registered, r, out):
+    """Global geometric bundle adjustment with trivial loss over the registered images and the tracks with a point: the
+    first image of st["init"] constant, the translation component st["gauge"] of the second constant.  Poses (and intrinsics, if
+    refined) of st are updated.  Returns (GeometricBAProblem, summary, flat index arrays) or None when there is no point."""
+    d_xyz, d_status, _, d_inl, _ = out
+    status, inl, xyz = d_status.download(), d_inl.download().astype(bool), d_xyz.download()
+    sel = np.flatnonzero(inl)
+    if len(sel) == 0:
+        return None
+    obs_track = np.repeat(np.arange(len(status), dtype=np.int64), np.diff(r["track_offsets"]))
+    images = np.flatnonzero(registered)
+    points = np.flatnonzero(status == 0)
+    cams = np.unique(st["image_camera"][images])
+    img_new = np.full(len(registered), -1, np.int32); img_new[images] = np.arange(len(images), dtype=np.int32)
+    pt_new = np.full(len(status), -1, np.int32); pt_new[points] = np.arange(len(points), dtype=np.int32)
+    cam_new = np.full(len(st["cam_model"]), -1, np.int32); cam_new[cams] = np.arange(len(cams), dtype=np.int32)
+    obs_image = img_new[r["obs_image"][sel]]
+    ba = GeometricBAProblem(st["ctx"], dict(obs_image=obs_image, obs_point=pt_new[obs_track[sel]], obs_xy=r["obs_xy"][sel],
+                                            image_camera=cam_new[st["image_camera"][images]], qvec=st["qvec"][images],
+                                            tvec=st["tvec"][images], cam_model=st["cam_model"][cams],
+                                            cam_params=st["cam_params"][cams], xyz=xyz[points]))
+    pose_const = np.zeros(len(images), np.uint8)
+    pose_const[np.bincount(obs_image, minlength=len(images)) == 0] = 1          # an image all of whose observations were filtered
+    pose_const[img_new[st["init"][0]]] = 1
+    tvec_mask = np.zeros(len(images), np.uint8)
+    tvec_mask[img_new[st["init"][1]]] = 1 << st["gauge"]
+    cam_mask = np.zeros(len(cams), np.uint16)
+    for k, c in enumerate(cams):
+        _, n_params, focal, _, _ = CAMERA_MODELS[int(st["cam_model"][c])]
+        mask = (1 << n_params) - 1
+        if conf['ba_refine_focal_length']:
+            for a in focal:
+                mask &= ~(1 << a)
+        cam_mask[k] = mask
+    opts = lm_options(max_iterations=int(conf['ba_max_num_iterations']), linear_solver=linear_solver_for(len(images)))
+    t0 = time.perf_counter()
+    summ = ba.solve(make_loss("trivial", []), pose_const, tvec_mask, cam_mask, np.zeros(len(points), np.uint8), options=opts)
+    st["ms"]["bundle_adjustment_wall"] += 1e3 * (time.perf_counter() - t0)
+    q, t, k, _ = ba.params()
+    st["qvec"][images], st["tvec"][images] = q, t
+    st["cam_params"][cams] = k[:, :st["cam_params"].shape[1]]
+    return ba, summ, dict(sel=sel, obs_track=obs_track, images=images, points=points)
+
+
+def finish(conf, st, skeleton, flat, keypoints, registered, summary):
+    """The end of a reconstruction: triangulate over the registered images, adjust, filter by reprojection error, and build the
+    Reconstruction of the registered images with the tracks that keep two observations.  Fills final_ba,
+    num_filtered_observations, mean_reprojection_error, num_reg_images and num_points3D of `summary`."""
+    prob, r, out = triangulate_registered(conf, st, registered)
+    done = bundle_adjust(conf, st, registered, r, out)
+    rec = Reconstruction()
+    for k, c in enumerate(flat["camera_ids"]):
+        cam = skeleton.cameras[c]
+        rec.add_camera(Camera(c, int(cam.model_id), cam.width, cam.height, st["cam_params"][k, :len(cam.params)].copy()))
+    for k in np.flatnonzero(registered):
+        im = skeleton.images[flat["image_ids"][k]]
+        kp = np.asarray(keypoints[im.name], dtype=np.float64).reshape(-1, 2)
+        rec.add_image(Image(im.image_id, im.name, im.camera_id, st["qvec"][k].copy(), st["tvec"][k].copy(), [Point2D(xy) for xy in kp]))
+    if done is not None:
+        ba, summ, ix = done
+        err = ba.reprojection_errors()
+        xyz = ba.params()[3]
+        keep = err <= float(conf['filter_max_reproj_error'])
+        point_of_obs = np.searchsorted(ix["points"], ix["obs_track"][ix["sel"]])
+        length = np.bincount(point_of_obs[keep], minlength=len(ix["points"]))
+        obs_full = r["obs_index"][ix["sel"]]
+        pid_of_point = np.full(len(ix["points"]), -1, np.int64)
+        for j in np.flatnonzero(length >= 2):
+            pid_of_point[j] = len(rec.points3D) + 1
+            rec.add_point3D(int(pid_of_point[j]), Point3D(xyz[j], Track()))
+        for o, j in zip(obs_full[keep], point_of_obs[keep]):
+            if pid_of_point[j] < 0:
+                continue
+            image_id, f = flat["image_ids"][flat["obs_image"][o]], int(flat["obs_feature"][o])
+            rec.points3D[int(pid_of_point[j])].track.add_element(image_id, f)
+            rec.images[image_id].points2D[f].point3D_id = int(pid_of_point[j])
+        kept = keep & (pid_of_point[point_of_obs] >= 0)
+        summary.update(final_ba=summ, num_filtered_observations=int((~keep).sum()),
+                       mean_reprojection_error=float(err[kept].mean()) if kept.any() else float("nan"))
+    summary.update(num_reg_images=int(registered.sum()), num_points3D=len(rec.points3D))
+    return rec
+
+
 class IncrementalMapper:
     """Verified matches in, registered images and points out -- in place of hloc.reconstruction.main / COLMAP's mapper."""
     default_conf = {
@@ -110,71 +217,7 @@ class IncrementalMapper:
             rec.add_image(Image(k + 1, name, cam_id[id(cam)], [1.0, 0.0, 0.0, 0.0], [0.0, 0.0, 0.0]))
         return rec
 
-    # -- the stages of a round, on flat arrays -------------------------------------------------------------------------------
-    def _triangulate(self, st, registered):
-        """Tracks restricted to the registered images -> (problem, restricted dict, device outputs), or None without observations."""
-        r = st["scene"].restricted_tracks(registered)
-        if len(r["obs_index"]) == 0:
-            return None
-        prob = TriangulationProblem(st["ctx"], dict(track_offsets=r["track_offsets"], obs_image=r["obs_image"], obs_xy=r["obs_xy"],
-                                                    image_camera=st["image_camera"], qvec=st["qvec"], tvec=st["tvec"],
-                                                    cam_model=st["cam_model"], cam_params=st["cam_params"]))
-        out = prob.triangulate(timed=True, **self.conf['triangulation'])
-        st["ms"]["triangulate"] += sum(prob.kernel_ms.values())
-        return prob, r, out
-
-    def _retriangulate(self, st, prob):
-        """The same tracks again from the poses (and intrinsics) of st."""
-        prob.d["qvec"].upload(st["qvec"])
-        prob.d["tvec"].upload(st["tvec"])
-        prob.d["cam_params"].upload(_padded_cam_params(st["cam_params"], len(st["cam_model"])))
-        out = prob.triangulate(timed=True, **self.conf['triangulation'])
-        st["ms"]["triangulate"] += sum(prob.kernel_ms.values())
-        return out
-
-    def _bundle_adjust(self, st, registered, r, out):
-        """Global geometric bundle adjustment with trivial loss over the registered images and the tracks with a point: the
-        first image of the initial pair constant, one translation component of the second constant.  Poses (and intrinsics, if
-        refined) of st are updated.  Returns (GeometricBAProblem, summary, flat index arrays) or None when there is no point."""
-        d_xyz, d_status, _, d_inl, _ = out
-        status, inl, xyz = d_status.download(), d_inl.download().astype(bool), d_xyz.download()
-        sel = np.flatnonzero(inl)
-        if len(sel) == 0:
-            return None
-        obs_track = np.repeat(np.arange(len(status), dtype=np.int64), np.diff(r["track_offsets"]))
-        images = np.flatnonzero(registered)
-        points = np.flatnonzero(status == 0)
-        cams = np.unique(st["image_camera"][images])
-        img_new = np.full(len(registered), -1, np.int32); img_new[images] = np.arange(len(images), dtype=np.int32)
-        pt_new = np.full(len(status), -1, np.int32); pt_new[points] = np.arange(len(points), dtype=np.int32)
-        cam_new = np.full(len(st["cam_model"]), -1, np.int32); cam_new[cams] = np.arange(len(cams), dtype=np.int32)
-        obs_image = img_new[r["obs_image"][sel]]
-        ba = GeometricBAProblem(st["ctx"], dict(obs_image=obs_image, obs_point=pt_new[obs_track[sel]], obs_xy=r["obs_xy"][sel],
-                                                image_camera=cam_new[st["image_camera"][images]], qvec=st["qvec"][images],
-                                                tvec=st["tvec"][images], cam_model=st["cam_model"][cams],
-                                                cam_params=st["cam_params"][cams], xyz=xyz[points]))
-        pose_const = np.zeros(len(images), np.uint8)
-        pose_const[np.bincount(obs_image, minlength=len(images)) == 0] = 1          # an image all of whose observations were filtered
-        pose_const[img_new[st["init"][0]]] = 1
-        tvec_mask = np.zeros(len(images), np.uint8)
-        tvec_mask[img_new[st["init"][1]]] = 1 << st["gauge"]
-        cam_mask = np.zeros(len(cams), np.uint16)
-        for k, c in enumerate(cams):
-            _, n_params, focal, _, _ = CAMERA_MODELS[int(st["cam_model"][c])]
-            mask = (1 << n_params) - 1
-            if self.conf['ba_refine_focal_length']:
-                for a in focal:
-                    mask &= ~(1 << a)
-            cam_mask[k] = mask
-        opts = lm_options(max_iterations=int(self.conf['ba_max_num_iterations']), linear_solver=linear_solver_for(len(images)))
-        t0 = time.perf_counter()
-        summ = ba.solve(make_loss("trivial", []), pose_const, tvec_mask, cam_mask, np.zeros(len(points), np.uint8), options=opts)
-        st["ms"]["bundle_adjustment_wall"] += 1e3 * (time.perf_counter() - t0)
-        q, t, k, _ = ba.params()
-        st["qvec"][images], st["tvec"][images] = q, t
-        st["cam_params"][cams] = k[:, :st["cam_params"].shape[1]]
-        return ba, summ, dict(sel=sel, obs_track=obs_track, images=images, points=points)
-
+    # -- the stages of a round that are the mapper's own (the shared ones are the module's functions above) ------------------
     def _register(self, st, registered, trials, d_xyz, d_status):
         """Visibility of the unregistered images that have trials left, then one absolute-pose launch over the candidates.
         Returns (number of candidates, indices of the newly registered images)."""
@@ -229,7 +272,7 @@ class IncrementalMapper:
             registered = np.zeros(n, bool); registered[[a, b]] = True
             st["qvec"][:], st["tvec"][:] = [1.0, 0.0, 0.0, 0.0], 0.0
             st["qvec"][b], st["tvec"][b] = np.asarray(g["qvec"], dtype=np.float64), t / np.linalg.norm(t)
-            tri = self._triangulate(st, registered)
+            tri = triangulate_registered(self.conf, st, registered)
             if tri is None:
                 continue
             d_xyz, d_status = tri[2][0], tri[2][1]
@@ -276,10 +319,10 @@ class IncrementalMapper:
         trials = np.zeros(n, np.int64)
         while True:
             before, t0 = dict(st["ms"]), time.perf_counter()
-            prob, r, out = self._triangulate(st, registered)
-            done = self._bundle_adjust(st, registered, r, out)
+            prob, r, out = triangulate_registered(self.conf, st, registered)
+            done = bundle_adjust(self.conf, st, registered, r, out)
             if done is not None:
-                out = self._retriangulate(st, prob)
+                out = retriangulate(self.conf, st, prob)
             n_points = int((out[1].download() == 0).sum())
             n_cand, new = self._register(st, registered, trials, out[0], out[1])
             ms = {k: st["ms"][k] - before[k] for k in before}
@@ -288,38 +331,6 @@ class IncrementalMapper:
                                           ba=None if done is None else done[1], ms=ms))
             if not new:
                 break
-        # -- finish: triangulate, adjust, filter -----------------------------------------------------------------------------
-        prob, r, out = self._triangulate(st, registered)
-        done = self._bundle_adjust(st, registered, r, out)
-        rec = Reconstruction()
-        for k, c in enumerate(flat["camera_ids"]):
-            cam = skeleton.cameras[c]
-            rec.add_camera(Camera(c, int(cam.model_id), cam.width, cam.height, st["cam_params"][k, :len(cam.params)].copy()))
-        for k in np.flatnonzero(registered):
-            im = skeleton.images[flat["image_ids"][k]]
-            kp = np.asarray(keypoints[im.name], dtype=np.float64).reshape(-1, 2)
-            rec.add_image(Image(im.image_id, im.name, im.camera_id, st["qvec"][k].copy(), st["tvec"][k].copy(), [Point2D(xy) for xy in kp]))
-        if done is not None:
-            ba, summ, ix = done
-            err = ba.reprojection_errors()
-            xyz = ba.params()[3]
-            keep = err <= float(self.conf['filter_max_reproj_error'])
-            point_of_obs = np.searchsorted(ix["points"], ix["obs_track"][ix["sel"]])
-            length = np.bincount(point_of_obs[keep], minlength=len(ix["points"]))
-            obs_full = r["obs_index"][ix["sel"]]
-            pid_of_point = np.full(len(ix["points"]), -1, np.int64)
-            for j in np.flatnonzero(length >= 2):
-                pid_of_point[j] = len(rec.points3D) + 1
-                rec.add_point3D(int(pid_of_point[j]), Point3D(xyz[j], Track()))
-            for o, j in zip(obs_full[keep], point_of_obs[keep]):
-                if pid_of_point[j] < 0:
-                    continue
-                image_id, f = flat["image_ids"][flat["obs_image"][o]], int(flat["obs_feature"][o])
-                rec.points3D[int(pid_of_point[j])].track.add_element(image_id, f)
-                rec.images[image_id].points2D[f].point3D_id = int(pid_of_point[j])
-            kept = keep & (pid_of_point[point_of_obs] >= 0)
-            summary.update(final_ba=summ, num_filtered_observations=int((~keep).sum()),
-                           mean_reprojection_error=float(err[kept].mean()) if kept.any() else float("nan"))
-        summary.update(num_reg_images=int(registered.sum()), unregistered=[names[k] for k in np.flatnonzero(~registered)],
-                       num_points3D=len(rec.points3D))
+        rec = finish(self.conf, st, skeleton, flat, keypoints, registered, summary)
+        summary.update(unregistered=[names[k] for k in np.flatnonzero(~registered)])
         return rec, summary

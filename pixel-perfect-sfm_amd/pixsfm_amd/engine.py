@@ -899,6 +899,125 @@ class TriangulationProblem:
         return d_xyz, d_status, d_ninl, d_inl, d_err
 
 
+def rotavg_options(l1_iterations=20, max_iterations=40, min_angle=1e-3, sigma=5.0, tolerance=1e-10):
+    """pxr_rotavg_options: iterations of the L1 phase and in all, the floor of the angle in the L1 weights (radians), the Cauchy
+    scale after it (degrees), the step below which the iteration stops (radians)."""
+    return _lib.RotavgOptions(int(l1_iterations), int(max_iterations), float(min_angle), float(sigma), float(tolerance))
+
+
+class RotationAveragingProblem:
+    """Device-resident view graph of pxr_rotation_averaging: pair_image (n_pairs x 2) indices into the n_images images, pair_qvec
+    (n_pairs x 4) the rotation of the second image relative to the first, pair_weight (n_pairs) >= 0."""
+
+    def __init__(self, ctx, n_images, pair_image, pair_qvec, pair_weight):
+        self.ctx = ctx
+        self.n_images = int(n_images)
+        pair_image = np.ascontiguousarray(pair_image, dtype=np.int32).reshape(-1, 2)
+        self.n_pairs = len(pair_image)
+        pair_qvec = np.ascontiguousarray(pair_qvec, dtype=np.float64).reshape(-1, 4)
+        pair_weight = np.ascontiguousarray(pair_weight, dtype=np.float64).reshape(-1)
+        if len(pair_qvec) != self.n_pairs or len(pair_weight) != self.n_pairs:
+            raise ValueError("pair_qvec and pair_weight must hold one row per pair")
+        rows = max(self.n_pairs, 1)        # (an empty graph still gets buffers)
+        self.d = {"pair_image": ctx.zeros((rows, 2), np.int32), "pair_qvec": ctx.zeros((rows, 4), np.float64),
+                  "pair_weight": ctx.zeros((rows,), np.float64)}
+        if self.n_pairs:
+            self.d["pair_image"].upload(pair_image)
+            self.d["pair_qvec"].upload(pair_qvec)
+            self.d["pair_weight"].upload(pair_weight)
+        self.kernel_ms = None
+
+    def solve(self, timed=False, **options):
+        """Run pxr_rotation_averaging with rotavg_options(**options).  Returns (qvec device array (n_images, 4), root, iterations,
+        pair_angle device array (n_pairs,) in radians).  timed: self.kernel_ms {"residuals", "assembly", "solve"} summed over
+        the iterations."""
+        ctx, d = self.ctx, self.d
+        opts = rotavg_options(**options)
+        d_q = ctx.to_device(np.full((self.n_images, 4), np.nan), np.float64)
+        d_angle = ctx.to_device(np.full((max(self.n_pairs, 1),), np.nan), np.float64)
+        root, iterations = C.c_int32(-1), C.c_int32(-1)
+        args = (ctx.handle, self.n_images, self.n_pairs, d["pair_image"].ptr, d["pair_qvec"].ptr, d["pair_weight"].ptr, C.byref(opts),
+                d_q.ptr, C.byref(root), C.byref(iterations), d_angle.ptr)
+        self.kernel_ms = _launch(ctx, "pxr_rotation_averaging", args, ("residuals", "assembly", "solve"), timed) or self.kernel_ms
+        return d_q, int(root.value), int(iterations.value), d_angle
+
+
+def globalpos_options(iterations=8, cheirality_from=2, sigma_obs=1.0, sigma_pair=3.0, min_det=1e-12):
+    """pxr_globalpos_options: rounds, the first round (from 0) that rejects what lies behind its camera, the Cauchy scales of the
+    observations and the pairs (degrees), the determinant a track's 3 x 3 matrix must exceed."""
+    return _lib.GlobalposOptions(int(iterations), int(cheirality_from), float(sigma_obs), float(sigma_pair), float(min_det))
+
+
+class GlobalPositioningProblem:
+    """Device-resident arrays of pxr_global_positioning.
+
+    problem: dict as for TriangulationProblem (track_offsets, obs_image, obs_xy, image_camera, qvec = the averaged rotations,
+    cam_model, cam_params; a tvec is ignored); pair_image (n_pairs x 2), pair_dir (n_pairs x 3) the unit baseline directions in
+    the world, pair_weight (n_pairs) >= 0; root: the image at the origin."""
+
+    def __init__(self, ctx, problem, pair_image, pair_dir, pair_weight, root):
+        self.ctx = ctx
+        g = problem
+        offsets = _csr_offsets(g["track_offsets"], "track_offsets", "n_tracks")
+        self.n_tracks = len(offsets) - 1
+        self.n_obs = len(g["obs_image"])
+        self.n_images = len(g["image_camera"])
+        self.n_cameras = len(g["cam_model"])
+        self.root = int(root)
+        obs_xy = np.ascontiguousarray(g["obs_xy"], dtype=np.float64).reshape(-1, 2)
+        if len(obs_xy) != self.n_obs:
+            raise ValueError("obs_xy must hold one keypoint per observation")
+        pair_image = np.ascontiguousarray(pair_image, dtype=np.int32).reshape(-1, 2)
+        self.n_pairs = len(pair_image)
+        pair_dir = np.ascontiguousarray(pair_dir, dtype=np.float64).reshape(-1, 3)
+        pair_weight = np.ascontiguousarray(pair_weight, dtype=np.float64).reshape(-1)
+        if len(pair_dir) != self.n_pairs or len(pair_weight) != self.n_pairs:
+            raise ValueError("pair_dir and pair_weight must hold one row per pair")
+        rows, obs = max(self.n_pairs, 1), max(self.n_obs, 1)
+        self.d = {
+            "track_offsets": ctx.to_device(offsets, np.int64),
+            "obs_image": ctx.zeros((obs,), np.int32), "obs_xy": ctx.zeros((obs, 2), np.float64),
+            "image_camera": ctx.to_device(g["image_camera"], np.int32),
+            "qvec": ctx.to_device(np.asarray(g["qvec"], dtype=np.float64).reshape(-1, 4), np.float64),
+            "cam_model": ctx.to_device(g["cam_model"], np.int32),
+            "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
+            "pair_image": ctx.zeros((rows, 2), np.int32), "pair_dir": ctx.zeros((rows, 3), np.float64),
+            "pair_weight": ctx.zeros((rows,), np.float64),
+        }
+        d = self.d
+        if self.n_obs:
+            d["obs_image"].upload(np.asarray(g["obs_image"]).reshape(-1))
+            d["obs_xy"].upload(obs_xy)
+        if self.n_pairs:
+            d["pair_image"].upload(pair_image)
+            d["pair_dir"].upload(pair_dir)
+            d["pair_weight"].upload(pair_weight)
+        self.view = _lib.TriView(self.n_tracks, d["track_offsets"].ptr, self.n_obs, d["obs_image"].ptr, d["obs_xy"].ptr,
+                                 self.n_images, d["image_camera"].ptr, d["qvec"].ptr, None, self.n_cameras,
+                                 d["cam_model"].ptr, d["cam_params"].ptr)
+        self.kernel_ms = None
+
+    def solve(self, timed=False, **options):
+        """Run pxr_global_positioning with globalpos_options(**options).  Returns a dict of device arrays centre (n_images, 3), xyz
+        (n_tracks, 3; NaN where track_status is 1), track_status (n_tracks,) int32, obs_weight (n_obs,), pair_weight (n_pairs,),
+        and the host values status (0 = ok, 1 = degenerate) and rounds.  timed: self.kernel_ms {"tracks", "contraction", "gauge_pack",
+        "cholesky", "update"} summed over the rounds."""
+        ctx, d = self.ctx, self.d
+        opts = globalpos_options(**options)
+        out = dict(centre=ctx.to_device(np.full((self.n_images, 3), np.nan), np.float64),
+                   xyz=ctx.to_device(np.full((max(self.n_tracks, 1), 3), np.nan), np.float64),
+                   track_status=ctx.to_device(np.full((max(self.n_tracks, 1),), -1), np.int32),
+                   obs_weight=ctx.zeros((max(self.n_obs, 1),), np.float64), pair_weight=ctx.zeros((max(self.n_pairs, 1),), np.float64))
+        status, rounds = C.c_int32(-1), C.c_int32(-1)
+        args = (ctx.handle, C.byref(self.view), self.n_pairs, d["pair_image"].ptr, d["pair_dir"].ptr, d["pair_weight"].ptr, self.root,
+                C.byref(opts), out["centre"].ptr, out["xyz"].ptr, out["track_status"].ptr, out["obs_weight"].ptr, out["pair_weight"].ptr,
+                C.byref(status), C.byref(rounds))
+        stages = ("tracks", "contraction", "gauge_pack", "cholesky", "update")
+        self.kernel_ms = _launch(ctx, "pxr_global_positioning", args, stages, timed) or self.kernel_ms
+        out.update(status=int(status.value), rounds=int(rounds.value))
+        return out
+
+
 def abspose_options(max_error=12.0, min_inlier_ratio=0.01, min_num_inliers=4, confidence=0.99999, min_num_trials=64,
                     max_num_trials=4096, round_size=64, seed=0, refine_max_iterations=100, refine_loss_scale=1.0, lo_rounds=4):
     """pxr_abspose_options: pycolmap 0.x / COLMAP 3.8's AbsolutePoseEstimationOptions and AbsolutePoseRefinementOptions values
