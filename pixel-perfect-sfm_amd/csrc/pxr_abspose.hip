@@ -520,38 +520,31 @@ static int absolute_pose(pxr_ctx* ctx, int32_t n_queries, const int64_t* d_query
   };
   if (int rc = batch_order(ctx, {fn, "query_offsets", "query", "n_corr"}, false, d_query_offsets, T, N, off, order, camera_in_range)) return rc;
 
-  Carver cv;
-  const size_t o_rec = cv.take((size_t)N * ABS_REC, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
-  const size_t o_ma = cv.take((size_t)N, 1), o_mb = cv.take((size_t)N, 1), o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4), o_win = cv.take((size_t)T * 3, 4);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  double* rec = (double*)(ws + o_rec);
-  uint8_t* valid = (uint8_t*)(ws + o_valid);
-  int32_t* pos = (int32_t*)(ws + o_pos);
-  int32_t* n_valid = (int32_t*)(ws + o_nv);
-  int32_t* d_order = (int32_t*)(ws + o_order);
+  AbsArgs a;
+  double* rec; uint8_t* valid; int32_t *pos, *n_valid, *d_order;
+  Workspace ws;
+  ws.take(rec, (size_t)N * ABS_REC); ws.take(valid, (size_t)N); ws.take(pos, (size_t)N);
+  ws.take(a.mask_a, (size_t)N); ws.take(a.mask_b, (size_t)N); ws.take(n_valid, (size_t)T); ws.take(d_order, (size_t)T); ws.take(a.winner, (size_t)T * 3);
+  if (int rc = ws.commit(ctx)) return rc;
 
   StageTimer<5> timer(st, h_ms);                         // bearings | compact | hypotheses | refine
   if (int rc = timer.create(fn)) return rc;
 
-  auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
   int rc = hip_check(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (`order` may go out of scope)
   if (rc != PXR_OK) return rc;
   timer.mark(0);
   if (N > 0)
-    hipLaunchKernelGGL(k_abs_bearings, blocks(N, ABS_THREADS), dim3(ABS_THREADS), 0, st, N, n_queries, d_query_offsets, d_query_camera,
+    hipLaunchKernelGGL(k_abs_bearings, blocks_for(N, ABS_THREADS), dim3(ABS_THREADS), 0, st, N, n_queries, d_query_offsets, d_query_camera,
                        d_cam_model, d_cam_params, d_xy, d_xyz, rec, valid, d_inlier, d_err);
   timer.mark(1);
-  hipLaunchKernelGGL(k_compact_records<ABS_REC>, blocks(T, ABS_THREADS), dim3(ABS_THREADS), 0, st, T, d_query_offsets, rec, valid, pos, n_valid);
+  hipLaunchKernelGGL(k_compact_records<ABS_REC>, blocks_for(T, ABS_THREADS), dim3(ABS_THREADS), 0, st, T, d_query_offsets, rec, valid, pos, n_valid);
   timer.mark(2);
-  AbsArgs a;
   a.offsets = d_query_offsets; a.query_camera = d_query_camera; a.cam_model = d_cam_model; a.cam_params = d_cam_params; a.xy = d_xy;
-  a.order = d_order; a.rec = rec; a.pos = pos; a.n_valid = n_valid; a.mask_a = (uint8_t*)(ws + o_ma); a.mask_b = (uint8_t*)(ws + o_mb);
+  a.order = d_order; a.rec = rec; a.pos = pos; a.n_valid = n_valid;
   a.o = *o;
   a.max_trials = (int32_t)(((int64_t)o->max_num_trials + o->round_size - 1) / o->round_size * o->round_size);
   a.qvec = d_qvec; a.tvec = d_tvec; a.status = d_status; a.n_inliers = d_n_inliers; a.n_trials = d_n_trials; a.inlier = d_inlier; a.err = d_err;
-  a.winner = (int32_t*)(ws + o_win);
   hipLaunchKernelGGL(k_abs_hypotheses, dim3((unsigned)T), dim3(ABS_THREADS), 0, st, a);
   timer.mark(3);
   hipLaunchKernelGGL(k_abs_refine, dim3((unsigned)T), dim3(ABS_THREADS), 0, st, a);

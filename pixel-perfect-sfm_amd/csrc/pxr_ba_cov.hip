@@ -206,12 +206,12 @@ extern "C" int pxr_ba_covariance(pxr_ctx* ctx, const pxr_ba_view* view, const do
       // the diagonal of the scaled S, copied before the factorisation updates the tiles it lives in: what the pivots are held against
       DevBuf<double> sdiag;
       RC(sdiag.alloc((size_t)n_c));
-      hipLaunchKernelGGL(k_cov_diag, dim3(nblk(n_c)), dim3(256), 0, st, n_c, (const double*)sys.aug, n_c + 1, sdiag.p);
+      hipLaunchKernelGGL(k_cov_diag, blocks_for(n_c, 256), dim3(256), 0, st, n_c, (const double*)sys.aug, n_c + 1, sdiag.p);
       RC(chol_factor_solve(st, sys.aug, n_c, sys.d_info, sys.linv, sys.xsol, /*zero_info=*/true));
       const int N = (n_c + 63) / 64;
       int h_info[2] = {0, INT_MAX};
       PXR_HIP(hipMemcpyAsync(first_bad.p, &h_info[1], sizeof(int), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_cov_pivot_check, dim3(nblk(n_c)), dim3(256), 0, st, n_c, (const double*)(sys.linv + (size_t)(N + 1) * 4096),
+      hipLaunchKernelGGL(k_cov_pivot_check, blocks_for(n_c, 256), dim3(256), 0, st, n_c, (const double*)(sys.linv + (size_t)(N + 1) * 4096),
                          (const double*)sdiag.p, 64.0 * n_c * kUnit, first_bad.p);
       LAUNCH_CHECK("pivot check");
       PXR_HIP(hipMemcpyAsync(&h_info[0], sys.d_info, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -228,19 +228,19 @@ extern "C" int pxr_ba_covariance(pxr_ctx* ctx, const pxr_ba_view* view, const do
     }
     if (d_cov_points) {
       const int64_t groups = view->n_points;
-      hipLaunchKernelGGL(k_cov_points, dim3(nblk(groups * COV_G)), dim3(256), 0, st, sys.dv, sys.pt_ptr, sys.pt_obs, sys.W, sys.T,
+      hipLaunchKernelGGL(k_cov_points, blocks_for(groups * COV_G, 256), dim3(256), 0, st, sys.dv, sys.pt_ptr, sys.pt_obs, sys.W, sys.T,
                          (const int*)singular.p, sig, d_cov_points);
     }
     if (d_cov_pose) {
-      if (n_c > 0) hipLaunchKernelGGL(k_cov_pose, dim3(nblk(view->n_images)), dim3(256), 0, st, sys.dv, sig, d_cov_pose);
+      if (n_c > 0) hipLaunchKernelGGL(k_cov_pose, blocks_for(view->n_images, 256), dim3(256), 0, st, sys.dv, sig, d_cov_pose);
       else PXR_HIP(hipMemsetAsync(d_cov_pose, 0, sizeof(double) * 36 * (size_t)view->n_images, st));
     }
     if (d_cov_intrinsics) {
-      if (n_c > 0) hipLaunchKernelGGL(k_cov_intr, dim3(nblk(view->n_cameras)), dim3(256), 0, st, sys.dv, sig, d_cov_intrinsics);
+      if (n_c > 0) hipLaunchKernelGGL(k_cov_intr, blocks_for(view->n_cameras, 256), dim3(256), 0, st, sys.dv, sig, d_cov_intrinsics);
       else PXR_HIP(hipMemsetAsync(d_cov_intrinsics, 0, sizeof(double) * PXR_KPAD * PXR_KPAD * (size_t)view->n_cameras, st));
     }
     if (d_cov_cameras && n_c > 0)
-      hipLaunchKernelGGL(k_cov_dense, dim3(nblk((int64_t)n_c * n_c)), dim3(256), 0, st, n_c, sig, (const double*)sys.dv.scale_c, d_cov_cameras);
+      hipLaunchKernelGGL(k_cov_dense, blocks_for((int64_t)n_c * n_c, 256), dim3(256), 0, st, n_c, sig, (const double*)sys.dv.scale_c, d_cov_cameras);
     LAUNCH_CHECK("covariance kernels");
     PXR_HIP(hipStreamSynchronize(st));
     summary->ms_points = ms_since(t);

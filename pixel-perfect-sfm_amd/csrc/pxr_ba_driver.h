@@ -8,7 +8,6 @@
 
 namespace pxr {
 
-static inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
 #define RC(call) do { int _rc = (call); if (_rc != PXR_OK) return _rc; } while (0)
 #define LAUNCH_CHECK(name) RC(pxr::hip_check(hipGetLastError(), name))

@@ -235,7 +235,7 @@ int build_structure(pxr_ctx* ctx, const pxr_ba_view* view, const uint8_t* h_pose
                        (const uint8_t*)s.d_pt_const.p, s.d_pt_ptr.p, s.d_pt_var.p, d_pt_cnt + n_pts + 1);
     PXR_HIP(hipMemcpyAsync(&h_n_pvar, d_pt_cnt + n_pts + 1, sizeof(h_n_pvar), hipMemcpyDeviceToHost, st));
     RC(s.d_img_obs.alloc(n_obs)); RC(s.d_pt_obs.alloc(n_obs));
-    hipLaunchKernelGGL(k_iota, dim3(nblk(n_obs)), dim3(256), 0, st, n_obs, s.d_pt_obs.p);     // ordered by point already
+    hipLaunchKernelGGL(k_iota, blocks_for(n_obs, 256), dim3(256), 0, st, n_obs, s.d_pt_obs.p);     // ordered by point already
     DevBuf<int64_t> d_img_ptr;
     DevBuf<int> d_hist;
     const int n_chunks = (int)((n_obs + SORT_CHUNK - 1) / SORT_CHUNK);
@@ -256,7 +256,7 @@ int build_structure(pxr_ctx* ctx, const pxr_ba_view* view, const uint8_t* h_pose
   }
   RC(s.d_schur_chunks.upload(s.schur_chunks, st));
   RC(s.d_obs_cols.alloc(n_obs)); RC(s.d_so.alloc(n_obs)); RC(s.d_part_obs.alloc(n_obs));
-  hipLaunchKernelGGL(k_build_descriptors, dim3(nblk(n_obs)), dim3(256), 0, st, n_obs, view->d_obs_image, view->d_obs_point,
+  hipLaunchKernelGGL(k_build_descriptors, blocks_for(n_obs, 256), dim3(256), 0, st, n_obs, view->d_obs_image, view->d_obs_point,
                      view->d_image_camera, s.d_pt_obs.p, s.d_img_obs.p, s.d_pt_ptr.p, s.d_pt_var.p, s.d_pose_off.p, s.d_pose_dim.p,
                      s.d_intr_off.p, s.d_intr_dim.p, s.d_obs_cols.p, s.d_part_obs.p, s.d_so.p);
   LAUNCH_CHECK("k_build_descriptors");

@@ -29,7 +29,6 @@
 
 namespace pxr {
 
-static inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
 // device-resident control block of the conjugate-gradient loop (doubles, right behind the eight scalars of `cgs`): the loop's
 // stopping decisions are taken ON the device (k_cg_decide) and every kernel of an iteration returns at once when STOP is
@@ -484,11 +483,11 @@ int pcg_solve(PcgArgs& a, double inv_radius, const pxr_lm_options* opt, const st
   // Deterministic mode (a.det): every sum that floating-point atomics would form in arrival order -- a chunk's part of W u or of an
   // image's block into the image's slots, several images' parts into the columns of a shared camera -- is formed from per-chunk
   // partials in a fixed order instead (k_col_finish, k_mloc_finish, k_pre_assemble_det): the same bits on every run.
-  const dim3 col_grid(nblk((int64_t)n * 64));
+  const dim3 col_grid = blocks_for((int64_t)n * 64, 256);
   PXR_HIP(hipMemsetAsync(a.b, 0, sizeof(double) * n, st));
   launch_by_g(DC, [&](auto G) {
     constexpr int GG = decltype(G)::value;
-    hipLaunchKernelGGL(k_pt_u<GG>, dim3(nblk(n_pts * GG)), dim3(256), 0, st, d, a.pt_ptr, a.part_obs, a.obs_cols, a.W, a.T,
+    hipLaunchKernelGGL(k_pt_u<GG>, blocks_for(n_pts * GG, 256), dim3(256), 0, st, d, a.pt_ptr, a.part_obs, a.obs_cols, a.W, a.T,
                        (const double*)nullptr, a.gp, a.u, (const double*)nullptr);
   });
   if (a.n_chunks > 0)
@@ -508,25 +507,25 @@ int pcg_solve(PcgArgs& a, double inv_radius, const pxr_lm_options* opt, const st
                          a.det ? a.mpart : (double*)nullptr);
     });
   if (a.det) {
-    hipLaunchKernelGGL(k_mloc_finish, dim3(nblk((int64_t)n_img * DC * DC)), dim3(256), 0, st, d, a.chunk_ptr, (const double*)a.mpart, a.Ublk, a.Mloc);
-    hipLaunchKernelGGL(k_pre_assemble_det, dim3(nblk((int64_t)a.n_groups * PCG_GS * PCG_GS)), dim3(256), 0, st, d, a.n_groups, a.group_size,
+    hipLaunchKernelGGL(k_mloc_finish, blocks_for((int64_t)n_img * DC * DC, 256), dim3(256), 0, st, d, a.chunk_ptr, (const double*)a.mpart, a.Ublk, a.Mloc);
+    hipLaunchKernelGGL(k_pre_assemble_det, blocks_for((int64_t)a.n_groups * PCG_GS * PCG_GS, 256), dim3(256), 0, st, d, a.n_groups, a.group_size,
                        a.group_cols, a.col_ent_ptr, a.col_ent, (const double*)a.Mloc, a.Gm);
   } else {
     PXR_HIP(hipMemsetAsync(a.Gm, 0, sizeof(double) * (size_t)a.n_groups * PCG_GS * PCG_GS, st));
-    hipLaunchKernelGGL(k_pre_assemble, dim3(nblk((int64_t)n_img * DC * DC)), dim3(256), 0, st, d, a.col_group, a.Mloc, a.Gm);
+    hipLaunchKernelGGL(k_pre_assemble, blocks_for((int64_t)n_img * DC * DC, 256), dim3(256), 0, st, d, a.col_group, a.Mloc, a.Gm);
   }
   RC(hip_check(hipGetLastError(), "pcg set-up kernels"));
   RC(ar(a.b, n));
   RC(ar(a.Gm, (int64_t)a.n_groups * PCG_GS * PCG_GS));
-  hipLaunchKernelGGL(k_vec_add, dim3(nblk(n)), dim3(256), 0, st, n, a.gc, a.b);
+  hipLaunchKernelGGL(k_vec_add, blocks_for(n, 256), dim3(256), 0, st, n, a.gc, a.b);
   PXR_HIP(hipMemsetAsync(a.d_fail, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_pre_invert, dim3(nblk((int64_t)a.n_groups * 64)), dim3(256), 0, st, a.n_groups, a.group_size, a.group_cols,
+  hipLaunchKernelGGL(k_pre_invert, blocks_for((int64_t)a.n_groups * 64, 256), dim3(256), 0, st, a.n_groups, a.group_size, a.group_cols,
                      a.damp_c, inv_radius, a.Gm, a.d_fail);
   // ---- x = 0, r = b ------------------------------------------------------------------------------------------
   PXR_HIP(hipMemsetAsync(a.x, 0, sizeof(double) * n, st));
   PXR_HIP(hipMemcpyAsync(a.r, a.b, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
   PXR_HIP(hipMemsetAsync(a.cgs, 0, sizeof(double) * (8 + CTL_SIZE), st));
-  const int nb = (int)nblk(n);
+  const int nb = (int)blocks_for(n, 256).x;
   double* ctl = a.cgs + 8;
   hipLaunchKernelGGL(k_dot, dim3(nb), dim3(256), 0, st, n, a.b, a.b, a.cg_part, 6);
   hipLaunchKernelGGL(k_cg_finalize, dim3(1), dim3(64), 0, st, a.cg_part, nb, 1u << 6, a.cgs);
@@ -541,10 +540,10 @@ int pcg_solve(PcgArgs& a, double inv_radius, const pxr_lm_options* opt, const st
     hipLaunchKernelGGL(k_pre_apply, dim3(nb), dim3(256), 0, st, n, a.col_group, a.group_size, a.group_cols, a.Gm, a.r, a.z, a.cg_part, ctl);
     hipLaunchKernelGGL(k_cg_p_update, dim3(nb), dim3(256), 0, st, n, it == 1 ? 1 : 0, a.z, a.p, a.q, a.cg_part, nb, a.cgs, ctl);
     // q = S p (partial over this rank's points)
-    if (!a.det) hipLaunchKernelGGL(k_ublk_matvec, dim3(nblk((int64_t)n_img * DC)), dim3(256), 0, st, d, a.Ublk, a.p, a.q, ctl);
+    if (!a.det) hipLaunchKernelGGL(k_ublk_matvec, blocks_for((int64_t)n_img * DC, 256), dim3(256), 0, st, d, a.Ublk, a.p, a.q, ctl);
     launch_by_g(DC, [&](auto G) {
       constexpr int GG = decltype(G)::value;
-      hipLaunchKernelGGL(k_pt_u<GG>, dim3(nblk(n_pts * GG)), dim3(256), 0, st, d, a.pt_ptr, a.part_obs, a.obs_cols, a.W, a.T, a.p,
+      hipLaunchKernelGGL(k_pt_u<GG>, blocks_for(n_pts * GG, 256), dim3(256), 0, st, d, a.pt_ptr, a.part_obs, a.obs_cols, a.W, a.T, a.p,
                          (const double*)nullptr, a.u, ctl);
     });
     if (a.n_chunks > 0)
@@ -627,13 +626,13 @@ __global__ __launch_bounds__(256) void k_col_gather(const SolveDev d, const int*
 
 int pcg_blocks_from_partials(hipStream_t st, const SolveDev& d, const int* kchunk_ptr, const double* kpart, int ne_max, double* Ublk,
                              double* gimg, const int* col_ent_ptr, const int2* col_ent, double* diag, double* gc) {
-  hipLaunchKernelGGL(k_img_finish, dim3(nblk((int64_t)d.v.n_images * ne_max)), dim3(256), 0, st, d, kchunk_ptr, kpart, ne_max, Ublk, gimg);
-  hipLaunchKernelGGL(k_col_gather, dim3(nblk((int64_t)d.n_c * 64)), dim3(256), 0, st, d, col_ent_ptr, col_ent, (const double*)gimg, (const double*)Ublk, gc, diag);
+  hipLaunchKernelGGL(k_img_finish, blocks_for((int64_t)d.v.n_images * ne_max, 256), dim3(256), 0, st, d, kchunk_ptr, kpart, ne_max, Ublk, gimg);
+  hipLaunchKernelGGL(k_col_gather, blocks_for((int64_t)d.n_c * 64, 256), dim3(256), 0, st, d, col_ent_ptr, col_ent, (const double*)gimg, (const double*)Ublk, gc, diag);
   return hip_check(hipGetLastError(), "deterministic block linearisation");
 }
 
 int pcg_diag_from_blocks(hipStream_t st, const SolveDev& d, const double* Ublk, double* diag) {
-  hipLaunchKernelGGL(k_diag_from_blocks, dim3(nblk((int64_t)d.v.n_images * d.DC)), dim3(256), 0, st, d, Ublk, diag);
+  hipLaunchKernelGGL(k_diag_from_blocks, blocks_for((int64_t)d.v.n_images * d.DC, 256), dim3(256), 0, st, d, Ublk, diag);
   return hip_check(hipGetLastError(), "k_diag_from_blocks");
 }
 

@@ -1285,15 +1285,15 @@ int LmSolve::ar(double* buf, int64_t count) {
 }
 int LmSolve::from_rank0(double* buf, int64_t count) {
   if (!m.bcast) return PXR_OK;
-  if (ctx->rank != 0) hipLaunchKernelGGL(k_zero, dim3(nblk(count)), dim3(256), 0, st, count, buf);
+  if (ctx->rank != 0) hipLaunchKernelGGL(k_zero, blocks_for(count, 256), dim3(256), 0, st, count, buf);
   return ar(buf, count);
 }
 int LmSolve::ar_i64(long long* buf, int64_t count) {    // in-place integer all-reduce(sum)
   if (!m.multi || count <= 0) return PXR_OK;
   if (m.native_i64) return comm_allreduce_sum_i64(ctx, buf, count);
-  hipLaunchKernelGGL(k_i64_split, dim3(nblk(count)), dim3(256), 0, st, count, (const long long*)buf, ws.i64_halves.p);
+  hipLaunchKernelGGL(k_i64_split, blocks_for(count, 256), dim3(256), 0, st, count, (const long long*)buf, ws.i64_halves.p);
   RC(ar(ws.i64_halves.p, 2 * count));
-  hipLaunchKernelGGL(k_i64_join, dim3(nblk(count)), dim3(256), 0, st, count, (const double*)ws.i64_halves.p, buf);
+  hipLaunchKernelGGL(k_i64_join, blocks_for(count, 256), dim3(256), 0, st, count, (const double*)ws.i64_halves.p, buf);
   return PXR_OK;
 }
 int LmSolve::zero_scalars() {
@@ -1338,7 +1338,7 @@ int LmSolve::evaluate(const pxr_ba_view& v, double* rec) {   // rec + cost into 
 int LmSolve::linearize(const double* rec) {
   hipLaunchKernelGGL(k_jac, dim3((unsigned)((n_obs + JAC_THREADS - 1) / JAC_THREADS)), dim3(JAC_THREADS),
                      sizeof(double) * (JAC_THREADS / 64) * 64 * (LS + 3 * DC + 1), st, dv, rec, *loss, ws.L.p, ws.W.p);
-  hipLaunchKernelGGL(k_point, dim3(nblk(n_pts)), dim3(256), 0, st, dv, sx.d_pt_ptr.p, sx.d_pt_obs.p, ws.L.p, ws.V.p, ws.gp.p);
+  hipLaunchKernelGGL(k_point, blocks_for(n_pts, 256), dim3(256), 0, st, dv, sx.d_pt_ptr.p, sx.d_pt_obs.p, ws.L.p, ws.V.p, ws.gp.p);
   PXR_HIP(hipMemsetAsync(ws.U.p, 0, sizeof(double) * ws.U.n, st));
   PXR_HIP(hipMemsetAsync(ws.gcd.p, 0, sizeof(double) * ws.gcd.n, st));
   if (n_c > 0 && !sx.chunks.empty()) {
@@ -1363,7 +1363,7 @@ int LmSolve::linearize(const double* rec) {
       return PXR_OK;
     }
     if (m.iterative) RC(pcg_diag_from_blocks(st, dv, ws.U.p, diagU));
-    else hipLaunchKernelGGL(k_extract_diag, dim3(nblk(n_c)), dim3(256), 0, st, n_c, ws.U.p, diagU);
+    else hipLaunchKernelGGL(k_extract_diag, blocks_for(n_c, 256), dim3(256), 0, st, n_c, ws.U.p, diagU);
   }
   LAUNCH_CHECK("linearize kernels");
   RC(ar(ws.gcd.p, 2 * (int64_t)nc1));   // global diag(U) and g_c
@@ -1408,7 +1408,7 @@ int LmSolve::linearize_checked(const double* rec, double md_guess, double cost_n
 // see at all shows up in the second.  cols_pow2: it happened (from then on the columns are kept there: move_columns)
 // every column into [1/4, 1) by the diagonal of the newest linearisation (diagU); a linearisation must follow
 int LmSolve::move_columns() {
-  hipLaunchKernelGGL(k_column_pow2, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, (const double*)diagU, 0.0, 1, ws.scale_c.p, ws.pow_c.p, ws.damp_c.p,
+  hipLaunchKernelGGL(k_column_pow2, blocks_for(n_c, 256), dim3(256), 0, st, (int64_t)n_c, (const double*)diagU, 0.0, 1, ws.scale_c.p, ws.pow_c.p, ws.damp_c.p,
                      ws.col_count.p);
   LAUNCH_CHECK("k_column_pow2");
   return PXR_OK;
@@ -1418,7 +1418,7 @@ int LmSolve::resolve_small_columns(const double* rec) {
   for (int pass = 0; pass < 4; ++pass) {
     double h = 0.0;
     PXR_HIP(hipMemsetAsync(ws.col_count.p, 0, sizeof(double), st));
-    hipLaunchKernelGGL(k_column_pow2, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, (const double*)diagU, 65536.0 / lin_scale, 0,
+    hipLaunchKernelGGL(k_column_pow2, blocks_for(n_c, 256), dim3(256), 0, st, (int64_t)n_c, (const double*)diagU, 65536.0 / lin_scale, 0,
                        ws.scale_c.p, ws.pow_c.p, ws.damp_c.p, ws.col_count.p);
     PXR_HIP(hipMemcpyAsync(&h, ws.col_count.p, sizeof(double), hipMemcpyDeviceToHost, st));
     PXR_HIP(hipStreamSynchronize(st));
@@ -1439,9 +1439,9 @@ int LmSolve::resolve_small_columns(const double* rec) {
   return PXR_OK;
 }
 int LmSolve::refresh_damping() {  // LevenbergMarquardtStrategy: diagonal clamped to [min, max]
-  if (n_c > 0) hipLaunchKernelGGL(k_clamp_pow, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, diagU, ws.pow_c.p, opt->min_lm_diagonal, opt->max_lm_diagonal, ws.damp_c.p);
-  hipLaunchKernelGGL(k_point_diag, dim3(nblk(n_pts)), dim3(256), 0, st, n_pts, ws.V.p, ws.Vd0.p);
-  hipLaunchKernelGGL(k_clamp, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, ws.Vd0.p, opt->min_lm_diagonal, opt->max_lm_diagonal, ws.Vd0.p);
+  if (n_c > 0) hipLaunchKernelGGL(k_clamp_pow, blocks_for(n_c, 256), dim3(256), 0, st, (int64_t)n_c, diagU, ws.pow_c.p, opt->min_lm_diagonal, opt->max_lm_diagonal, ws.damp_c.p);
+  hipLaunchKernelGGL(k_point_diag, blocks_for(n_pts, 256), dim3(256), 0, st, n_pts, ws.V.p, ws.Vd0.p);
+  hipLaunchKernelGGL(k_clamp, blocks_for(n_pts * 3, 256), dim3(256), 0, st, n_pts * 3, ws.Vd0.p, opt->min_lm_diagonal, opt->max_lm_diagonal, ws.Vd0.p);
   LAUNCH_CHECK("damping kernels");
   return PXR_OK;
 }
@@ -1449,9 +1449,9 @@ int LmSolve::refresh_damping() {  // LevenbergMarquardtStrategy: diagonal clampe
 int LmSolve::gradient_below_tolerance(bool* below) {
   double h[kScalSlots];
   RC(zero_scalars());
-  if (n_c > 0) hipLaunchKernelGGL(k_count_above, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, gc, ws.scale_c.p, opt->gradient_tolerance, ws.scal.p + SCAL_GRAD_COUNT_CAM,
+  if (n_c > 0) hipLaunchKernelGGL(k_count_above, blocks_for(n_c, 256), dim3(256), 0, st, (int64_t)n_c, gc, ws.scale_c.p, opt->gradient_tolerance, ws.scal.p + SCAL_GRAD_COUNT_CAM,
                                   m.det ? slimb + SCAL_GRAD_COUNT_CAM * PXR_LIMBS : (long long*)nullptr);
-  hipLaunchKernelGGL(k_count_above, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, ws.gp.p, ws.scale_p.p, opt->gradient_tolerance, ws.scal.p + SCAL_GRAD_COUNT_PT,
+  hipLaunchKernelGGL(k_count_above, blocks_for(n_pts * 3, 256), dim3(256), 0, st, n_pts * 3, ws.gp.p, ws.scale_p.p, opt->gradient_tolerance, ws.scal.p + SCAL_GRAD_COUNT_PT,
                      m.det ? slimb + SCAL_GRAD_COUNT_PT * PXR_LIMBS : (long long*)nullptr);
   RC(read_scalars(h));
   *below = h[SCAL_GRAD_COUNT_PT] == 0.0 && h[SCAL_GRAD_COUNT_CAM] == 0.0;
@@ -1520,7 +1520,7 @@ int LmSolve::setup() {
 
   cur_q = const_cast<double*>(view->d_qvec); cur_t = const_cast<double*>(view->d_tvec);
   cur_k = const_cast<double*>(view->d_cam_params); cur_X = const_cast<double*>(view->d_xyz);
-  if (!records_only) hipLaunchKernelGGL(k_normalize_q, dim3(nblk(n_img)), dim3(256), 0, st, n_img, cur_q);
+  if (!records_only) hipLaunchKernelGGL(k_normalize_q, blocks_for(n_img, 256), dim3(256), 0, st, n_img, cur_q);
 
   dv.v = *view;
   dv.pose_off = sx.d_pose_off.p; dv.pose_dim = sx.d_pose_dim.p; dv.tmask = sx.d_tmask.p;
@@ -1616,19 +1616,19 @@ int LmSolve::reduced_step_iterative(double inv_radius, bool* ok, double* inexact
   // e = b - S x:  model cost change = delta.(D^2 delta - g) / 2 + x.e / 2
   *inexact_correction = 0.5 * pr.x_dot_r;
   PXR_HIP(hipMemsetAsync(d_info, 0, sizeof(int), st));    // (the CG loop's failure flag lives in the info word: reported through pr.ok)
-  hipLaunchKernelGGL(k_finish_camera_step, dim3(nblk(n_c)), dim3(256), 0, st, n_c, ws.xsol.p, gc, ws.damp_c.p, inv_radius, ws.delta_c.p, scal_rep, limb_arg);
+  hipLaunchKernelGGL(k_finish_camera_step, blocks_for(n_c, 256), dim3(256), 0, st, n_c, ws.xsol.p, gc, ws.damp_c.p, inv_radius, ws.delta_c.p, scal_rep, limb_arg);
   return from_rank0(ws.delta_c.p, n_c);
 }
 // Schur complement (dense): [S + D_c / radius | rhs] in ws.S ...
 int LmSolve::reduced_system_direct(double inv_radius) {
   const double schur_scale = m.det_fixed ? lin_scale : 0.0;    // the SAME grid as U's: re-quantising the finished U is exact
-  hipLaunchKernelGGL(k_copy_upper_add_diag, dim3(nblk((int64_t)n_c * ldS)), dim3(256), 0, st, n_c, ws.U.p, (const double*)nullptr, 0.0, (const double*)nullptr, ws.S.p, 1, schur_scale);
+  hipLaunchKernelGGL(k_copy_upper_add_diag, blocks_for((int64_t)n_c * ldS, 256), dim3(256), 0, st, n_c, ws.U.p, (const double*)nullptr, 0.0, (const double*)nullptr, ws.S.p, 1, schur_scale);
   if (knobs.schur_lds) {
     const SchurLdsKernel kern = schur_lds_kernel(DC);
     hipLaunchKernelGGL(kern, dim3((unsigned)sx.schur_chunks.size(), (unsigned)n_ctiles), dim3(1024), schur_shmem, st, dv,
                        sx.d_schur_chunks.p, sx.d_so.p, sx.d_part_obs.p, sx.d_obs_cols.p, ws.W.p, ws.T.p, ws.gp.p, CT, ws.S.p, rhs, schur_scale);
   } else {
-    hipLaunchKernelGGL(k_schur, dim3(nblk(n_obs * DC)), dim3(256), 0, st, dv, sx.d_pt_ptr.p, sx.d_pt_obs.p, ws.W.p, ws.T.p, ws.gp.p, ws.S.p, rhs, schur_scale);
+    hipLaunchKernelGGL(k_schur, blocks_for(n_obs * DC, 256), dim3(256), 0, st, dv, sx.d_pt_ptr.p, sx.d_pt_obs.p, ws.W.p, ws.T.p, ws.gp.p, ws.S.p, rhs, schur_scale);
   }
   LAUNCH_CHECK("schur kernels");
   phase(0);
@@ -1641,7 +1641,7 @@ int LmSolve::reduced_system_direct(double inv_radius) {
   }
   phase(1);
   // the fixed-point slots back to doubles (deterministic mode), rhs += g_c (global), S += D_c / radius: one pass
-  hipLaunchKernelGGL(k_copy_upper_add_diag, dim3(nblk((int64_t)n_c * ldS)), dim3(256), 0, st, n_c, ws.U.p, ws.damp_c.p, inv_radius, gc, ws.S.p, 0, schur_scale);
+  hipLaunchKernelGGL(k_copy_upper_add_diag, blocks_for((int64_t)n_c * ldS, 256), dim3(256), 0, st, n_c, ws.U.p, ws.damp_c.p, inv_radius, gc, ws.S.p, 0, schur_scale);
   return PXR_OK;
 }
 // ... + Cholesky
@@ -1651,7 +1651,7 @@ int LmSolve::reduced_step_direct(double inv_radius) {
   // this attempt (no extra host synchronisation): a failed factorisation = invalid step.
   RC(chol_factor_solve(st, ws.S.p, n_c, d_info, ws.linv.p, ws.xsol.p, /*zero_info=*/false));     // (the attempt's first kernel cleared the info word)
   phase(2);
-  hipLaunchKernelGGL(k_finish_camera_step, dim3(nblk(n_c)), dim3(256), 0, st, n_c, ws.xsol.p, gc, ws.damp_c.p, inv_radius, ws.delta_c.p, scal_rep, limb_arg);
+  hipLaunchKernelGGL(k_finish_camera_step, blocks_for(n_c, 256), dim3(256), 0, st, n_c, ws.xsol.p, gc, ws.damp_c.p, inv_radius, ws.delta_c.p, scal_rep, limb_arg);
   return from_rank0(ws.delta_c.p, n_c);
 }
 
@@ -1659,10 +1659,10 @@ int LmSolve::reduced_step_direct(double inv_radius) {
 int LmSolve::candidate(double inv_radius, double inexact_correction, Candidate* c) {
   const int G = lane_group(DC);
   const BacksubKernel backsub = backsub_kernel(DC);
-  hipLaunchKernelGGL(backsub, dim3(nblk((n_pts * G + BACKSUB_PPG - 1) / BACKSUB_PPG)), dim3(256), 0, st, dv, sx.d_pt_ptr.p, sx.d_part_obs.p, sx.d_obs_cols.p,
+  hipLaunchKernelGGL(backsub, blocks_for((n_pts * G + BACKSUB_PPG - 1) / BACKSUB_PPG, 256), dim3(256), 0, st, dv, sx.d_pt_ptr.p, sx.d_part_obs.p, sx.d_obs_cols.p,
                      ws.W.p, ws.T.p, ws.gp.p, ws.delta_c.p, ws.Vd0.p, inv_radius, ws.delta_p.p, scal_sum, limb_arg);
   ParamPtrs out{ws.q1.p, ws.t1.p, ws.k1.p, ws.X1.p};
-  const int64_t upd_blocks = nblk(((int64_t)n_img + n_cam + n_pts + UPDATE_IPT - 1) / UPDATE_IPT);
+  const int64_t upd_blocks = blocks_for(((int64_t)n_img + n_cam + n_pts + UPDATE_IPT - 1) / UPDATE_IPT, 256).x;
   hipLaunchKernelGGL(k_update, dim3((unsigned)upd_blocks), dim3(256), 0, st, dv, ws.delta_c.p, ws.delta_p.p, out, scal_rep, scal_sum, limb_arg);
   LAUNCH_CHECK("step kernels");
   const bool do_inner = inner_enabled;
@@ -1680,7 +1680,7 @@ int LmSolve::candidate(double inv_radius, double inexact_correction, Candidate* 
     hipLaunchKernelGGL(k_limb_accumulate, dim3(256), dim3(256), 0, st, (const double*)ws.det_part.p, n_pts, slimb + SCAL_COST_BEFORE_INNER * PXR_LIMBS);
     PXR_HIP(hipMemsetAsync(scal_sum + SCAL_STEP2_PT, 0, sizeof(double), st));   // point part of |x - candidate|^2 after refinement
     PXR_HIP(hipMemsetAsync(slimb + SCAL_STEP2_PT * PXR_LIMBS, 0, sizeof(long long) * PXR_LIMBS, st));
-    hipLaunchKernelGGL(k_point_step_norm, dim3(nblk(n_pts)), dim3(256), 0, st, n_pts, sx.d_pt_var.p, cur_X, ws.X1.p, scal_sum + SCAL_STEP2_PT,
+    hipLaunchKernelGGL(k_point_step_norm, blocks_for(n_pts, 256), dim3(256), 0, st, n_pts, sx.d_pt_var.p, cur_X, ws.X1.p, scal_sum + SCAL_STEP2_PT,
                        m.det ? slimb + SCAL_STEP2_PT * PXR_LIMBS : (long long*)nullptr);
     LAUNCH_CHECK("inner iteration kernels");
   }
@@ -1767,9 +1767,9 @@ int LmSolve::run() {
   cost = hs[SCAL_COST];
   sum->initial_cost = cost;
   if (!std::isfinite(cost)) return finish(PXR_TERM_FAILURE);   // [upstream] "Initial residual and Jacobian evaluation failed" (e.g. check_bounds)
-  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.scale_c.p);
-  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.pow_c.p);
-  hipLaunchKernelGGL(k_fill, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, 1.0, ws.scale_p.p);
+  hipLaunchKernelGGL(k_fill, blocks_for(nc1, 256), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.scale_c.p);
+  hipLaunchKernelGGL(k_fill, blocks_for(nc1, 256), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.pow_c.p);
+  hipLaunchKernelGGL(k_fill, blocks_for(n_pts * 3, 256), dim3(256), 0, st, n_pts * 3, 1.0, ws.scale_p.p);
   // (deterministic mode: the UNSCALED pass only yields diag(U) for the Jacobi scaling and has no a-priori bound: a first guess
   //  of 2^32 for its diagonal -- unit-norm descriptors give 1e3 .. 1e6 -- and the checked retry from the measured trace otherwise)
   RC(linearize_checked(rec_cur, std::ldexp(1.0, 32), cost, !opt->jacobi_scaling));
@@ -1779,10 +1779,10 @@ int LmSolve::run() {
       RC(resolve_small_columns(rec_cur));
       if (lin_not_finite) return finish(PXR_TERM_FAILURE, opt->initial_radius);
     }
-    if (n_c > 0 && cols_pow2) hipLaunchKernelGGL(k_jacobi_scale_pow2, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, diagU, ws.scale_c.p, ws.pow_c.p);
-    else if (n_c > 0) hipLaunchKernelGGL(k_jacobi_scale, dim3(nblk(n_c)), dim3(256), 0, st, (int64_t)n_c, diagU, ws.scale_c.p);
-    hipLaunchKernelGGL(k_point_diag, dim3(nblk(n_pts)), dim3(256), 0, st, n_pts, ws.V.p, ws.Vd0.p);
-    hipLaunchKernelGGL(k_jacobi_scale, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, ws.Vd0.p, ws.scale_p.p);
+    if (n_c > 0 && cols_pow2) hipLaunchKernelGGL(k_jacobi_scale_pow2, blocks_for(n_c, 256), dim3(256), 0, st, (int64_t)n_c, diagU, ws.scale_c.p, ws.pow_c.p);
+    else if (n_c > 0) hipLaunchKernelGGL(k_jacobi_scale, blocks_for(n_c, 256), dim3(256), 0, st, (int64_t)n_c, diagU, ws.scale_c.p);
+    hipLaunchKernelGGL(k_point_diag, blocks_for(n_pts, 256), dim3(256), 0, st, n_pts, ws.V.p, ws.Vd0.p);
+    hipLaunchKernelGGL(k_jacobi_scale, blocks_for(n_pts * 3, 256), dim3(256), 0, st, n_pts * 3, ws.Vd0.p, ws.scale_p.p);
     RC(linearize_checked(rec_cur, 1.0 / 8.0, cost));      // scaled columns have norm < 1: diag(U) < 1 = 8 x 1/8
     if (lin_not_finite) return finish(PXR_TERM_FAILURE, opt->initial_radius);
   }
@@ -1818,7 +1818,7 @@ int LmSolve::run() {
     if (!reuse_diag) RC(refresh_damping());
     const double inv_radius = 1.0 / radius;
     // point elimination (+ the side job of the attempt's first kernel: clear the attempt's scalars), reduced camera system
-    hipLaunchKernelGGL(k_pinv, dim3(nblk(n_pts)), dim3(256), 0, st, n_pts, sx.d_pt_var.p, ws.V.p, ws.Vd0.p, inv_radius, ws.T.p, ws.scal.p, kScalZeroed);
+    hipLaunchKernelGGL(k_pinv, blocks_for(n_pts, 256), dim3(256), 0, st, n_pts, sx.d_pt_var.p, ws.V.p, ws.Vd0.p, inv_radius, ws.T.p, ws.scal.p, kScalZeroed);
     if (n_pts == 0) RC(zero_scalars());
     Candidate c;
     double inexact_correction = 0.0;
@@ -1851,7 +1851,7 @@ int LmSolve::run() {
       // the accepted candidate becomes the current point
       Copy4 c4{{ws.q1.p, ws.t1.p, ws.k1.p, ws.X1.p}, {cur_q, cur_t, cur_k, cur_X},
                {(int64_t)4 * n_img, (int64_t)3 * n_img, (int64_t)PXR_KPAD * n_cam, (int64_t)3 * n_pts}};
-      hipLaunchKernelGGL(k_copy4, dim3((unsigned)std::min<int64_t>(1024, nblk(3 * n_pts + 1))), dim3(256), 0, st, c4);
+      hipLaunchKernelGGL(k_copy4, dim3((unsigned)std::min<int64_t>(1024, blocks_for(3 * n_pts + 1, 256).x)), dim3(256), 0, st, c4);
       std::swap(rec_cur, rec_cand);
       cost = c.cost;
       cur_is_exact = false;
@@ -1897,10 +1897,10 @@ int LmSolve::covariance_system(const double* rec, int* singular, unsigned long l
   RC(read_scalars(hs));
   cost = hs[SCAL_COST];
   PXR_REQUIRE(std::isfinite(cost), "pxr_ba_covariance: the records do not give a finite cost");
-  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.scale_c.p);
-  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.pow_c.p);
-  hipLaunchKernelGGL(k_fill, dim3(nblk(nc1)), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.damp_c.p);
-  hipLaunchKernelGGL(k_fill, dim3(nblk(n_pts * 3)), dim3(256), 0, st, n_pts * 3, 1.0, ws.scale_p.p);
+  hipLaunchKernelGGL(k_fill, blocks_for(nc1, 256), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.scale_c.p);
+  hipLaunchKernelGGL(k_fill, blocks_for(nc1, 256), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.pow_c.p);
+  hipLaunchKernelGGL(k_fill, blocks_for(nc1, 256), dim3(256), 0, st, (int64_t)nc1, 1.0, ws.damp_c.p);
+  hipLaunchKernelGGL(k_fill, blocks_for(n_pts * 3, 256), dim3(256), 0, st, n_pts * 3, 1.0, ws.scale_p.p);
   RC(linearize_checked(rec, std::ldexp(1.0, 32), cost));
   if (n_c > 0 && !lin_not_finite) {
     if (m.det_fixed) RC(resolve_small_columns(rec));
@@ -1912,7 +1912,7 @@ int LmSolve::covariance_system(const double* rec, int* singular, unsigned long l
   PXR_REQUIRE(!lin_not_finite, "pxr_ba_covariance: the Jacobian at these parameters is not finite");
   RC(zero_scalars());
   PXR_HIP(hipMemsetAsync(n_singular, 0, sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_pinv_checked, dim3(nblk(n_pts)), dim3(256), 0, st, n_pts, sx.d_pt_var.p, ws.V.p, ws.T.p, singular, n_singular);
+  hipLaunchKernelGGL(k_pinv_checked, blocks_for(n_pts, 256), dim3(256), 0, st, n_pts, sx.d_pt_var.p, ws.V.p, ws.T.p, singular, n_singular);
   LAUNCH_CHECK("k_pinv_checked");
   if (n_c > 0) RC(reduced_system_direct(0.0));
   out->dv = dv; out->n_c = n_c; out->DC = DC;

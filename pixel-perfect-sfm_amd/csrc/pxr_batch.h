@@ -40,10 +40,30 @@ inline int batch_order(pxr_ctx* ctx, const OffsetNames& nm, bool first_may_be_po
   return PXR_OK;
 }
 
-// the layout of a workspace: every array begins at a multiple of 256 bytes
-struct Carver {
-  size_t bytes = 0;
-  size_t take(size_t count, size_t elem) { const size_t at = bytes; bytes += (count * elem + 255) & ~(size_t)255; return at; }
+// The layout of the context's workspace as typed device arrays.  take(p, count) books `count` elements of p's pointee type at
+// the next multiple of 256 bytes (a count of 0 takes no room) and remembers where p lives; commit() grows the workspace to the
+// total and only then fills every p, so no pointer into the block exists before the block has its final address.  commit()
+// leaves the layout empty: a driver that lays out twice in one call takes and commits again, from offset 0, and keeps no pointer
+// of the first layout (growing loses the contents).  release_caches: see grow_block.
+class Workspace {
+ public:
+  template <class T>
+  void take(T*& p, size_t count) {
+    slots_.push_back({&p, bytes_, [](void* at, char* base) { *static_cast<T**>(at) = reinterpret_cast<T*>(base); }});
+    bytes_ += (count * sizeof(T) + 255) & ~(size_t)255;
+  }
+  int commit(pxr_ctx* ctx, bool release_caches = false) {
+    if (int rc = grow_workspace(ctx, bytes_, release_caches)) return rc;
+    for (const Slot& s : slots_) s.fill(s.at, static_cast<char*>(ctx->d_workspace) + s.offset);
+    slots_.clear();
+    bytes_ = 0;
+    return PXR_OK;
+  }
+
+ private:
+  struct Slot { void* at; size_t offset; void (*fill)(void* at, char* base); };
+  std::vector<Slot> slots_;
+  size_t bytes_ = 0;
 };
 
 // The events of a *_timed call.  Without h_ms nothing is created and mark() does nothing; the destructor destroys what create()
@@ -70,6 +90,16 @@ class StageTimer {
       h_ms_[k] = ms;
     }
     return rc;
+  }
+  // For a driver whose stages repeat: h_ms[k] += milliseconds between marks k and k + 1 of one round, k < MARKS - 1.  The driver
+  // zeroes h_ms when the call starts and adds after the round's own synchronisation (it waits for the round's info word anyway)
+  int add() {
+    for (int k = 0; k + 1 < n_; ++k) {
+      float ms = 0.f;
+      if (int rc = hip_check(hipEventElapsedTime(&ms, ev_[k], ev_[k + 1]), "hipEventElapsedTime")) return rc;
+      h_ms_[k] += ms;
+    }
+    return PXR_OK;
   }
 
  private:

@@ -255,8 +255,6 @@ unsigned long long table_size(int64_t n) {
   return s;
 }
 
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + CL_THREADS - 1) / CL_THREADS); }
-
 int cloud_nearest(pxr_ctx* ctx, int64_t n_ref, const double* d_ref, int64_t n_query, const double* d_query, double max_dist,
                   int32_t* d_nn_index, double* d_nn_dist2, double* h_ms) {
   const char* fn = "pxr_cloud_nearest";
@@ -277,33 +275,29 @@ int cloud_nearest(pxr_ctx* ctx, int64_t n_ref, const double* d_ref, int64_t n_qu
   const double h = std::isfinite(m2) ? std::max(max_dist, 0x1p-400) * (1.0 + 0x1p-20) : std::numeric_limits<double>::infinity();
   const unsigned long long buckets = table_size(n_ref);
   const int64_t n_chunks = (int64_t)((buckets + SCAN_CHUNK - 1) / SCAN_CHUNK);
-  Carver cv;
-  const size_t o_bucket = cv.take((size_t)buckets, 4), o_partial = cv.take((size_t)n_chunks, 4);
-  const size_t o_xyz = cv.take((size_t)n_ref * 3, 8), o_idx = cv.take((size_t)n_ref, 4);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-
   GridArgs g;
-  g.ref = d_ref; g.n_ref = n_ref; g.h = h; g.mask = buckets - 1; g.bucket = (uint32_t*)(ws + o_bucket);
-  g.sorted_xyz = (double*)(ws + o_xyz); g.sorted_idx = (int32_t*)(ws + o_idx);
-  uint32_t* partial = (uint32_t*)(ws + o_partial);
+  g.ref = d_ref; g.n_ref = n_ref; g.h = h; g.mask = buckets - 1;
+  uint32_t* partial;
+  Workspace ws;
+  ws.take(g.bucket, (size_t)buckets); ws.take(partial, (size_t)n_chunks); ws.take(g.sorted_xyz, (size_t)n_ref * 3); ws.take(g.sorted_idx, (size_t)n_ref);
+  if (int rc = ws.commit(ctx)) return rc;
 
   StageTimer<3> timer(st, h_ms);                                     // grid | query
   if (int rc = timer.create(fn)) return rc;
   timer.mark(0);
   if (n_ref > 0) {
     PXR_HIP(hipMemsetAsync(g.bucket, 0, sizeof(uint32_t) * (size_t)buckets, st));
-    hipLaunchKernelGGL(k_cloud_grid<false>, dim3(blocks_of(n_ref)), dim3(CL_THREADS), 0, st, g);
+    hipLaunchKernelGGL(k_cloud_grid<false>, blocks_for(n_ref, CL_THREADS), dim3(CL_THREADS), 0, st, g);
     hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)n_chunks), dim3(CL_THREADS), 0, st, (const uint32_t*)g.bucket, (int64_t)buckets, partial);
     hipLaunchKernelGGL((k_exclusive_scan<CL_THREADS, uint32_t, uint32_t>), dim3(1), dim3(CL_THREADS), 0, st, n_chunks, (const uint32_t*)partial, partial, 0);
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)n_chunks), dim3(CL_THREADS), 0, st, g.bucket, (int64_t)buckets, (const uint32_t*)partial);
-    hipLaunchKernelGGL(k_cloud_grid<true>, dim3(blocks_of(n_ref)), dim3(CL_THREADS), 0, st, g);
+    hipLaunchKernelGGL(k_cloud_grid<true>, blocks_for(n_ref, CL_THREADS), dim3(CL_THREADS), 0, st, g);
   }
   timer.mark(1);
   QueryArgs q;
   q.query = d_query; q.n_query = n_query; q.n_ref = n_ref; q.h = h; q.m2 = m2; q.mask = g.mask; q.bucket_end = g.bucket;
   q.sorted_xyz = g.sorted_xyz; q.sorted_idx = g.sorted_idx; q.nn_index = d_nn_index; q.nn_dist2 = d_nn_dist2;
-  hipLaunchKernelGGL(k_cloud_query, dim3(blocks_of(n_query)), dim3(CL_THREADS), 0, st, q);
+  hipLaunchKernelGGL(k_cloud_query, blocks_for(n_query, CL_THREADS), dim3(CL_THREADS), 0, st, q);
   timer.mark(2);
   const int rc = hip_check(hipGetLastError(), "k_cloud_query launch");
   const int from[2] = {0, 1};
@@ -326,14 +320,12 @@ int cloud_voxel_fractions(pxr_ctx* ctx, int64_t n, const double* d_xyz, const do
 
   const bool table = voxel_size > 0.0 && n > 0;
   const unsigned long long slots = table ? table_size(n) : 0;
-  Carver cv;
-  const size_t o_res = cv.take(RES_WORDS, 8), o_keys = cv.take((size_t)slots, 8), o_counts = cv.take((size_t)slots * (1 + n_tol), 4);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
   VoxelArgs a;
   a.xyz = d_xyz; a.dist2 = d_dist2; a.n = n; a.v = voxel_size; a.n_tol = n_tol; a.mask = slots - 1;
   for (int t = 0; t < PXR_CLOUD_MAX_TOLERANCES; ++t) a.tt[t] = t < n_tol ? h_tol[t] * h_tol[t] : 0.0;
-  a.keys = (unsigned long long*)(ws + o_keys); a.counts = (uint32_t*)(ws + o_counts); a.res = (unsigned long long*)(ws + o_res);
+  Workspace ws;
+  ws.take(a.res, RES_WORDS); ws.take(a.keys, (size_t)slots); ws.take(a.counts, (size_t)slots * (1 + n_tol));
+  if (int rc = ws.commit(ctx)) return rc;
 
   StageTimer<3> timer(st, h_ms);                                     // insert | reduce
   if (int rc = timer.create(fn)) return rc;
@@ -342,12 +334,12 @@ int cloud_voxel_fractions(pxr_ctx* ctx, int64_t n, const double* d_xyz, const do
   if (table) {
     PXR_HIP(hipMemsetAsync(a.keys, 0xff, sizeof(unsigned long long) * (size_t)slots, st));
     PXR_HIP(hipMemsetAsync(a.counts, 0, sizeof(uint32_t) * (size_t)slots * (1 + n_tol), st));
-    hipLaunchKernelGGL(k_voxel_insert, dim3(blocks_of(n)), dim3(CL_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_voxel_insert, blocks_for(n, CL_THREADS), dim3(CL_THREADS), 0, st, a);
   }
   timer.mark(1);
   if (n > 0) {
     const int64_t items = table ? (int64_t)slots : n;
-    const unsigned grid = (unsigned)std::min<int64_t>(blocks_of(items), (int64_t)std::max(ctx->num_cus, 1) * 8);
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(items, CL_THREADS).x, (int64_t)std::max(ctx->num_cus, 1) * 8);
     const int64_t stride = (int64_t)grid * CL_THREADS;
     if (table) hipLaunchKernelGGL(k_voxel_reduce, dim3(grid), dim3(CL_THREADS), 0, st, a, stride);
     else hipLaunchKernelGGL(k_voxel_plain, dim3(grid), dim3(CL_THREADS), 0, st, a, stride);

@@ -22,7 +22,7 @@
 
 #include "pxr_device.h"
 #include "pxr_dispatch.h"
-#include "pxr_internal.h"
+#include "pxr_batch.h"
 #include "pxr_scan.h"
 
 namespace pxr {
@@ -168,22 +168,15 @@ extern "C" int pxr_arena_extract(pxr_ctx* ctx, pxr_arena* a, int64_t first, int6
   const int* d_order = nullptr;
   const int tiles_x = (w + 15) / 16, n_tiles = tiles_x * ((h + 15) / 16);
   if (n >= 4096 && n < ((int64_t)1 << 31)) {
-    const size_t bytes = sizeof(int) * (2 * (size_t)n + n_tiles) + 768;
-    if (bytes > ctx->workspace_bytes) {
-      PXR_HIP(hipStreamSynchronize(ctx->stream));
-      if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
-      PXR_HIP(hipMalloc(&ctx->d_workspace, bytes));
-      ctx->workspace_bytes = bytes;
-    }
-    int* tile_of = static_cast<int*>(ctx->d_workspace);
-    int* order = tile_of + n;
-    int* hist = order + n;
+    int *tile_of, *order, *hist;
+    Workspace ws;
+    ws.take(tile_of, (size_t)n); ws.take(order, (size_t)n); ws.take(hist, (size_t)n_tiles);
+    if (int rc = ws.commit(ctx)) return rc;
     PXR_HIP(hipMemsetAsync(hist, 0, sizeof(int) * n_tiles, ctx->stream));
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ex_tile_count, dim3(nb), dim3(256), 0, ctx->stream, n, d_keypoints, sx, sy, a->H, w, h, tiles_x, tile_of, hist);
+    hipLaunchKernelGGL(ex_tile_count, blocks_for(n, 256), dim3(256), 0, ctx->stream, n, d_keypoints, sx, sy, a->H, w, h, tiles_x, tile_of, hist);
     hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, ctx->stream, (int64_t)n_tiles, (const int*)hist, hist,
                        0);   // counts -> first slots in place; hist has n_tiles entries: no total
-    hipLaunchKernelGGL(ex_tile_scatter, dim3(nb), dim3(256), 0, ctx->stream, n, tile_of, hist, order);
+    hipLaunchKernelGGL(ex_tile_scatter, blocks_for(n, 256), dim3(256), 0, ctx->stream, n, tile_of, hist, order);
     d_order = order;
   }
   bool ok = false;

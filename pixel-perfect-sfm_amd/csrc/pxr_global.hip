@@ -94,36 +94,35 @@ __device__ __forceinline__ double group_sum(double v) {         // over the 16 l
   return v;
 }
 
-// the events of a timed call whose stages repeat: marks 0 .. STAGES of one round, read and added up after every round (the host
-// waits for the round's info word anyway)
-template <int STAGES>
-class RoundTimer {
- public:
-  RoundTimer(hipStream_t st, double* h_ms) : st_(st), h_ms_(h_ms) { if (h_ms) for (int k = 0; k < STAGES; ++k) h_ms[k] = 0.0; }
-  RoundTimer(const RoundTimer&) = delete;
-  RoundTimer& operator=(const RoundTimer&) = delete;
-  ~RoundTimer() { for (int k = 0; k <= STAGES; ++k) if (ev_[k]) (void)hipEventDestroy(ev_[k]); }
-  int create(const char* fn) {
-    if (h_ms_) for (int k = 0; k <= STAGES; ++k) if (hipEventCreate(&ev_[k]) != hipSuccess) return set_error(PXR_EHIP, "%s: hipEventCreate failed", fn);
-    return PXR_OK;
+// The pair list of both drivers on the host.  pair_image and the weights are downloaded and the stream synchronised (a download
+// the driver queued before the call has arrived too); every pair is checked -- its images in range, no self pair, a finite
+// non-negative weight -- and then by check_pair(p, i, j), the driver's own check of pair p = (i, j) (PXR_OK or its error); the
+// images' adjacency (adj_off / adj_pair) lists each image's pairs in ascending pair index.
+template <class CheckPair>
+static int pair_list(pxr_ctx* ctx, const char* fn, int n, int P, const int32_t* d_pair_image, const double* d_pair_weight,
+                     std::vector<int32_t>& pim, std::vector<double>& pw, std::vector<int32_t>& adj_off, std::vector<int32_t>& adj_pair,
+                     CheckPair check_pair) {
+  pim.resize((size_t)2 * P); pw.resize((size_t)P);
+  if (P > 0) {
+    PXR_HIP(hipMemcpyAsync(pim.data(), d_pair_image, sizeof(int32_t) * 2 * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    PXR_HIP(hipMemcpyAsync(pw.data(), d_pair_weight, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
   }
-  void mark(int k) { if (h_ms_) (void)hipEventRecord(ev_[k], st_); }
-  int add() {                                                     // after the stream was synchronised
-    for (int k = 0; h_ms_ && k < STAGES; ++k) {
-      float ms = 0.f;
-      if (int rc = hip_check(hipEventElapsedTime(&ms, ev_[k], ev_[k + 1]), "hipEventElapsedTime")) return rc;
-      h_ms_[k] += ms;
-    }
-    return PXR_OK;
+  PXR_HIP(hipStreamSynchronize(ctx->stream));
+  adj_off.assign((size_t)n + 1, 0);
+  for (int p = 0; p < P; ++p) {
+    const int i = pim[2 * p], j = pim[2 * p + 1];
+    PXR_REQUIRE(i >= 0 && i < n && j >= 0 && j < n, "%s: pair %d names an image outside [0, n_images = %d)", fn, p, n);
+    PXR_REQUIRE(i != j, "%s: pair %d joins image %d to itself", fn, p, i);
+    PXR_REQUIRE(std::isfinite(pw[p]) && pw[p] >= 0.0, "%s: the weight of pair %d is negative or not finite", fn, p);
+    if (int rc = check_pair(p, i, j)) return rc;
+    ++adj_off[i + 1]; ++adj_off[j + 1];
   }
-
- private:
-  hipStream_t st_;
-  double* h_ms_;
-  hipEvent_t ev_[STAGES + 1] = {};
-};
-
-inline dim3 gm_blocks(int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
+  for (int k = 0; k < n; ++k) adj_off[k + 1] += adj_off[k];
+  adj_pair.resize((size_t)2 * P);
+  std::vector<int32_t> fill(adj_off.begin(), adj_off.end() - 1);
+  for (int p = 0; p < P; ++p) { adj_pair[fill[pim[2 * p]]++] = p; adj_pair[fill[pim[2 * p + 1]]++] = p; }
+  return PXR_OK;
+}
 
 // ================================================================================================================================
 // rotation averaging
@@ -222,33 +221,20 @@ static int rotation_averaging(pxr_ctx* ctx, int32_t n_images, int32_t n_pairs, c
   const int n = n_images, P = n_pairs, m = n - 1;
 
   // ---- host: validation, root, spanning tree, adjacency ------------------------------------------------------------------------
-  std::vector<int32_t> pim((size_t)2 * P);
-  std::vector<double> pq((size_t)4 * P), pw((size_t)P);
-  if (P > 0) {
-    PXR_HIP(hipMemcpyAsync(pim.data(), d_pair_image, sizeof(int32_t) * 2 * (size_t)P, hipMemcpyDeviceToHost, st));
-    PXR_HIP(hipMemcpyAsync(pq.data(), d_pair_qvec, sizeof(double) * 4 * (size_t)P, hipMemcpyDeviceToHost, st));
-    PXR_HIP(hipMemcpyAsync(pw.data(), d_pair_weight, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
-  }
-  PXR_HIP(hipStreamSynchronize(st));
-  std::vector<double> sum_w((size_t)n, 0.0);
-  std::vector<int32_t> adj_off((size_t)n + 1, 0);
-  for (int p = 0; p < P; ++p) {
-    const int i = pim[2 * p], j = pim[2 * p + 1];
-    PXR_REQUIRE(i >= 0 && i < n && j >= 0 && j < n, "%s: pair %d names an image outside [0, n_images = %d)", fn, p, n);
-    PXR_REQUIRE(i != j, "%s: pair %d joins image %d to itself", fn, p, i);
-    PXR_REQUIRE(std::isfinite(pw[p]) && pw[p] >= 0.0, "%s: the weight of pair %d is negative or not finite", fn, p);
+  std::vector<int32_t> pim, adj_off, adj_pair;
+  std::vector<double> pq((size_t)4 * P), pw, sum_w((size_t)n, 0.0);
+  if (P > 0) PXR_HIP(hipMemcpyAsync(pq.data(), d_pair_qvec, sizeof(double) * 4 * (size_t)P, hipMemcpyDeviceToHost, st));
+  const auto unit_qvec = [&](int p, int i, int j) {
     double* q = &pq[4 * (size_t)p];
     const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     PXR_REQUIRE(std::isfinite(nq) && nq > 0.0, "%s: the qvec of pair %d is zero or not finite", fn, p);
     for (int c = 0; c < 4; ++c) q[c] /= nq;
     sum_w[i] += pw[p]; sum_w[j] += pw[p];
-    ++adj_off[i + 1]; ++adj_off[j + 1];
-  }
+    return (int)PXR_OK;
+  };
+  if (int rc = pair_list(ctx, fn, n, P, d_pair_image, d_pair_weight, pim, pw, adj_off, adj_pair, unit_qvec)) return rc;
   int root = 0;
   for (int k = 1; k < n; ++k) if (sum_w[k] > sum_w[root]) root = k;
-  for (int k = 0; k < n; ++k) adj_off[k + 1] += adj_off[k];
-  std::vector<int32_t> adj_pair((size_t)2 * P), fill(adj_off.begin(), adj_off.end() - 1);
-  for (int p = 0; p < P; ++p) { adj_pair[fill[pim[2 * p]]++] = p; adj_pair[fill[pim[2 * p + 1]]++] = p; }
   // Prim from the root over the pairs of positive weight: the heaviest pair that leaves the tree, the lower index of equals
   std::vector<double> q0((size_t)4 * n, 0.0);
   std::vector<char> in_tree((size_t)n, 0);
@@ -274,20 +260,16 @@ static int rotation_averaging(pxr_ctx* ctx, int32_t n_images, int32_t n_pairs, c
   }
 
   // ---- device ---------------------------------------------------------------------------------------------------------------------
-  Carver cv;
-  const size_t o_stat = cv.take(2, 8), o_info = cv.take(4, 4), o_pq = cv.take((size_t)4 * P, 8), o_e = cv.take((size_t)3 * P, 8);
-  const size_t o_rho = cv.take((size_t)P, 8), o_ang = cv.take((size_t)P, 8), o_off = cv.take((size_t)n + 1, 4), o_adj = cv.take((size_t)2 * P, 4);
   const size_t n_aug = (size_t)(m + 1) * (m + 1);
-  const size_t o_aug = cv.take(n_aug, 8), o_linv = cv.take(chol_workspace_doubles(std::max(m, 1)), 8), o_om = cv.take((size_t)3 * std::max(m, 1), 8);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  double* stat = (double*)(ws + o_stat);
-  int* info = (int*)(ws + o_info);
-  double *d_pq = (double*)(ws + o_pq), *e = (double*)(ws + o_e), *rho = (double*)(ws + o_rho), *ang = (double*)(ws + o_ang);
-  int32_t *d_off = (int32_t*)(ws + o_off), *d_adj = (int32_t*)(ws + o_adj);
-  double *aug = (double*)(ws + o_aug), *linv = (double*)(ws + o_linv), *omega = (double*)(ws + o_om);
+  double *stat, *d_pq, *e, *rho, *ang, *aug, *linv, *omega; int* info; int32_t *d_off, *d_adj;
+  Workspace ws;
+  ws.take(stat, 2); ws.take(info, 4); ws.take(d_pq, (size_t)4 * P); ws.take(e, (size_t)3 * P);
+  ws.take(rho, (size_t)P); ws.take(ang, (size_t)P); ws.take(d_off, (size_t)n + 1); ws.take(d_adj, (size_t)2 * P);
+  ws.take(aug, n_aug); ws.take(linv, chol_workspace_doubles(std::max(m, 1))); ws.take(omega, (size_t)3 * std::max(m, 1));
+  if (int rc = ws.commit(ctx)) return rc;
 
-  RoundTimer<3> timer(st, h_ms);                                  // residuals | assembly | solves (+ update)
+  if (h_ms) h_ms[0] = h_ms[1] = h_ms[2] = 0.0;
+  StageTimer<4> timer(st, h_ms);                                  // residuals | assembly | solves (+ update)
   if (int rc = timer.create(fn)) return rc;
   PXR_HIP(hipMemcpyAsync(d_qvec, q0.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, st));
   PXR_HIP(hipMemcpyAsync(d_off, adj_off.data(), sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
@@ -300,14 +282,14 @@ static int rotation_averaging(pxr_ctx* ctx, int32_t n_images, int32_t n_pairs, c
   const double sigma = o->sigma * GM_DEG;
   for (int it = 0; m > 0 && it < o->max_iterations; ++it) {
     timer.mark(0);
-    hipLaunchKernelGGL(k_ra_residual, gm_blocks(P, GM_THREADS), dim3(GM_THREADS), 0, st, P, d_pair_image, d_pq, d_qvec, d_pair_weight,
+    hipLaunchKernelGGL(k_ra_residual, blocks_for(P, GM_THREADS), dim3(GM_THREADS), 0, st, P, d_pair_image, d_pq, d_qvec, d_pair_weight,
                        it < o->l1_iterations ? 1 : 0, o->min_angle, sigma, e, rho, ang);
     timer.mark(1);
     // the three coordinates share the matrix; the factorisation overwrites it, so it is assembled three times.  The assembly
     // is timed with the solves it alternates with
     for (int coord = 0; coord < 3; ++coord) {
       PXR_HIP(hipMemsetAsync(aug, 0, sizeof(double) * n_aug, st));
-      hipLaunchKernelGGL(k_ra_assemble, gm_blocks(n, GM_THREADS), dim3(GM_THREADS), 0, st, n, root, coord, d_off, d_adj, d_pair_image, e, rho, aug);
+      hipLaunchKernelGGL(k_ra_assemble, blocks_for(n, GM_THREADS), dim3(GM_THREADS), 0, st, n, root, coord, d_off, d_adj, d_pair_image, e, rho, aug);
       if (coord == 0) timer.mark(2);
       if (int rc = chol_factor_solve(st, aug, m, info, linv, omega + (size_t)coord * m, coord == 0)) return rc;
     }
@@ -325,7 +307,7 @@ static int rotation_averaging(pxr_ctx* ctx, int32_t n_images, int32_t n_pairs, c
     if (it >= o->l1_iterations && h_max < o->tolerance) break;
   }
   if (P > 0)
-    hipLaunchKernelGGL(k_ra_residual, gm_blocks(P, GM_THREADS), dim3(GM_THREADS), 0, st, P, d_pair_image, d_pq, d_qvec, d_pair_weight, 0,
+    hipLaunchKernelGGL(k_ra_residual, blocks_for(P, GM_THREADS), dim3(GM_THREADS), 0, st, P, d_pair_image, d_pq, d_qvec, d_pair_weight, 0,
                        o->min_angle, sigma, e, rho, d_pair_angle);
   if (int rc = hip_check(hipGetLastError(), "k_ra_residual launch")) return rc;
   return hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
@@ -641,20 +623,13 @@ static int global_positioning(pxr_ctx* ctx, const pxr_tri_view* v, int32_t n_pai
 
   // ---- host: validation, the tracks' order, the adjacency, the fixed-point scale -------------------------------------------------
   std::vector<int64_t> off(1, 0);
-  std::vector<int32_t> order;
-  if (T > 0)
+  std::vector<int32_t> order, oim((size_t)N), icam((size_t)n);
+  if (T > 0) {                                                    // (batch_order waits for the two downloads too)
+    if (N > 0) PXR_HIP(hipMemcpyAsync(oim.data(), v->d_obs_image, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost, st));
+    if (v->d_image_camera) PXR_HIP(hipMemcpyAsync(icam.data(), v->d_image_camera, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
     if (int rc = batch_order(ctx, {fn, "track_offsets", "track", "n_obs"}, false, v->d_track_offsets, T, N, off, order, [](int64_t) { return (int)PXR_OK; }))
       return rc;
-  std::vector<int32_t> oim((size_t)N), icam((size_t)n), pim((size_t)2 * P);
-  std::vector<double> pdir((size_t)3 * P), pw((size_t)P);
-  if (N > 0) PXR_HIP(hipMemcpyAsync(oim.data(), v->d_obs_image, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost, st));
-  if (v->d_image_camera) PXR_HIP(hipMemcpyAsync(icam.data(), v->d_image_camera, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-  if (P > 0) {
-    PXR_HIP(hipMemcpyAsync(pim.data(), d_pair_image, sizeof(int32_t) * 2 * (size_t)P, hipMemcpyDeviceToHost, st));
-    PXR_HIP(hipMemcpyAsync(pdir.data(), d_pair_dir, sizeof(double) * 3 * (size_t)P, hipMemcpyDeviceToHost, st));
-    PXR_HIP(hipMemcpyAsync(pw.data(), d_pair_weight, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
   }
-  PXR_HIP(hipStreamSynchronize(st));
   std::vector<int64_t> addends((size_t)n, 0);                     // M_i of the fixed-point bound (k_gp_contract)
   for (int64_t t = 0; t < T; ++t)
     for (int64_t x = off[t]; x < off[t + 1]; ++x) {
@@ -664,23 +639,19 @@ static int global_positioning(pxr_ctx* ctx, const pxr_tri_view* v, int32_t n_pai
   if (N > 0)
     for (int k = 0; k < n; ++k)
       PXR_REQUIRE(icam[k] >= 0 && icam[k] < v->n_cameras, "%s: an image names a camera outside [0, n_cameras = %d)", fn, (int)v->n_cameras);
-  std::vector<int32_t> adj_off((size_t)n + 1, 0);
+  std::vector<int32_t> pim, adj_off, adj_pair;
+  std::vector<double> pdir((size_t)3 * P), pw;
+  if (P > 0) PXR_HIP(hipMemcpyAsync(pdir.data(), d_pair_dir, sizeof(double) * 3 * (size_t)P, hipMemcpyDeviceToHost, st));
   double w_max = 0.0;
-  for (int p = 0; p < P; ++p) {
-    const int i = pim[2 * p], j = pim[2 * p + 1];
-    PXR_REQUIRE(i >= 0 && i < n && j >= 0 && j < n, "%s: pair %d names an image outside [0, n_images = %d)", fn, p, n);
-    PXR_REQUIRE(i != j, "%s: pair %d joins image %d to itself", fn, p, i);
-    PXR_REQUIRE(std::isfinite(pw[p]) && pw[p] >= 0.0, "%s: the weight of pair %d is negative or not finite", fn, p);
+  const auto unit_direction = [&](int p, int i, int j) {
     const double* b = &pdir[3 * (size_t)p];
     const double nb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
     PXR_REQUIRE(std::isfinite(nb) && std::fabs(nb - 1.0) <= 1e-9, "%s: the direction of pair %d is not a finite unit vector", fn, p);
     w_max = std::max(w_max, pw[p]);
-    ++adj_off[i + 1]; ++adj_off[j + 1];
     ++addends[i]; ++addends[j];
-  }
-  for (int k = 0; k < n; ++k) adj_off[k + 1] += adj_off[k];
-  std::vector<int32_t> adj_pair((size_t)2 * P), fill(adj_off.begin(), adj_off.end() - 1);
-  for (int p = 0; p < P; ++p) { adj_pair[fill[pim[2 * p]]++] = p; adj_pair[fill[pim[2 * p + 1]]++] = p; }
+    return (int)PXR_OK;
+  };
+  if (int rc = pair_list(ctx, fn, n, P, d_pair_image, d_pair_weight, pim, pw, adj_off, adj_pair, unit_direction)) return rc;
   for (int p = 0; p < P; ++p) pw[p] = w_max > 0.0 ? pw[p] / w_max : 0.0;
   int64_t M = 1;
   for (int k = 0; k < n; ++k) M = std::max(M, addends[k]);
@@ -689,24 +660,20 @@ static int global_positioning(pxr_ctx* ctx, const pxr_tri_view* v, int32_t n_pai
   const double scale = std::ldexp(1.0, std::min(61 - bits, 60));
 
   // ---- device ---------------------------------------------------------------------------------------------------------------------
-  Carver cv;
   const size_t n_aug = (size_t)(m + 1) * (m + 1), n_S = 9 * (size_t)n * n;
-  const size_t o_stat = cv.take(2, 8), o_info = cv.take(4, 4), o_flag = cv.take(4, 4);
-  const size_t o_rays = cv.take((size_t)3 * N, 8), o_ok = cv.take((size_t)N, 1), o_order = cv.take((size_t)T, 4);
-  const size_t o_ainv = cv.take((size_t)6 * T, 8), o_valid = cv.take((size_t)T, 1);
-  const size_t o_w0 = cv.take((size_t)P, 8), o_rob = cv.take((size_t)P, 8), o_off = cv.take((size_t)n + 1, 4), o_adj = cv.take((size_t)2 * P, 4);
-  const size_t o_g = cv.take((size_t)3 * n, 8), o_S = cv.take(n_S, 8), o_aug = cv.take(n_aug, 8);
-  const size_t o_linv = cv.take(chol_workspace_doubles(std::max(m, 1)), 8), o_y = cv.take((size_t)std::max(m, 1), 8);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  double* stat = (double*)(ws + o_stat);
-  int *info = (int*)(ws + o_info), *flag = (int*)(ws + o_flag);
-  int32_t *d_order = (int32_t*)(ws + o_order), *d_off = (int32_t*)(ws + o_off), *d_adj = (int32_t*)(ws + o_adj);
-  double *w0 = (double*)(ws + o_w0), *robust = (double*)(ws + o_rob), *g = (double*)(ws + o_g);
-  unsigned long long* S = (unsigned long long*)(ws + o_S);
-  double *aug = (double*)(ws + o_aug), *linv = (double*)(ws + o_linv), *y = (double*)(ws + o_y);
+  GpArgs a;
+  double *stat, *rays, *w0, *robust, *g, *aug, *linv, *y; int *info, *flag; uint8_t* ok; int32_t *d_order, *d_off, *d_adj; unsigned long long* S;
+  Workspace ws;
+  ws.take(stat, 2); ws.take(info, 4); ws.take(flag, 4);
+  ws.take(rays, (size_t)3 * N); ws.take(ok, (size_t)N); ws.take(d_order, (size_t)T);
+  ws.take(a.ainv, (size_t)6 * T); ws.take(a.valid, (size_t)T);
+  ws.take(w0, (size_t)P); ws.take(robust, (size_t)P); ws.take(d_off, (size_t)n + 1); ws.take(d_adj, (size_t)2 * P);
+  ws.take(g, (size_t)3 * n); ws.take(S, n_S); ws.take(aug, n_aug);
+  ws.take(linv, chol_workspace_doubles(std::max(m, 1))); ws.take(y, (size_t)std::max(m, 1));
+  if (int rc = ws.commit(ctx)) return rc;
 
-  RoundTimer<5> timer(st, h_ms);                                  // tracks | contraction (+ pairs) | gauge + pack | Cholesky | scale + updates
+  if (h_ms) for (int k = 0; k < 5; ++k) h_ms[k] = 0.0;
+  StageTimer<6> timer(st, h_ms);                                  // tracks | contraction (+ pairs) | gauge + pack | Cholesky | scale + updates
   if (int rc = timer.create(fn)) return rc;
   if (T > 0) PXR_HIP(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st));
   PXR_HIP(hipMemcpyAsync(d_off, adj_off.data(), sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
@@ -720,34 +687,32 @@ static int global_positioning(pxr_ctx* ctx, const pxr_tri_view* v, int32_t n_pai
   PXR_HIP(hipMemsetAsync(flag, 0, 16, st));
   PXR_HIP(hipMemsetAsync(d_centre, 0, sizeof(double) * 3 * (size_t)n, st));
 
-  GpArgs a;
   a.n_tracks = T; a.track_offsets = v->d_track_offsets; a.order = d_order; a.obs_image = v->d_obs_image;
-  a.rays = (double*)(ws + o_rays); a.ok = (uint8_t*)(ws + o_ok); a.w = d_obs_weight; a.ainv = (double*)(ws + o_ainv);
-  a.valid = (uint8_t*)(ws + o_valid); a.n_images = n; a.root = root; a.S = S; a.scale = scale; a.min_det = o->min_det;
+  a.rays = rays; a.ok = ok; a.w = d_obs_weight; a.n_images = n; a.root = root; a.S = S; a.scale = scale; a.min_det = o->min_det;
   a.sigma_obs = o->sigma_obs * GM_DEG; a.centre = d_centre; a.cheirality = 0; a.final_round = 0; a.xyz = d_xyz; a.status = d_track_status;
   GpPairArgs b;
   b.n_pairs = P; b.n_images = n; b.root = root; b.pair_image = d_pair_image; b.pair_dir = d_pair_dir; b.w0 = w0; b.robust = robust;
   b.adj_off = d_off; b.adj_pair = d_adj; b.S = S; b.scale = scale; b.g = g; b.stat = stat; b.centre = d_centre;
   b.sigma_pair = o->sigma_pair * GM_DEG; b.cheirality = 0; b.weight_out = d_pair_weight_out;
 
-  if (N > 0) hipLaunchKernelGGL(k_gp_rays, gm_blocks(N, GM_THREADS), dim3(GM_THREADS), 0, st, *v, (double*)(ws + o_rays), (uint8_t*)(ws + o_ok), d_obs_weight);
+  if (N > 0) hipLaunchKernelGGL(k_gp_rays, blocks_for(N, GM_THREADS), dim3(GM_THREADS), 0, st, *v, rays, ok, d_obs_weight);
   *h_status = 0;
   *h_rounds = 0;
   for (int it = 0; it < o->iterations; ++it) {
     a.cheirality = b.cheirality = it >= o->cheirality_from ? 1 : 0;
     a.final_round = it == o->iterations - 1 ? 1 : 0;
     timer.mark(0);
-    if (T > 0) hipLaunchKernelGGL(k_gp_tracks, gm_blocks(T, GM_TPW), dim3(64), 0, st, a);
+    if (T > 0) hipLaunchKernelGGL(k_gp_tracks, blocks_for(T, GM_TPW), dim3(64), 0, st, a);
     timer.mark(1);
     if (m > 0) {
       PXR_HIP(hipMemsetAsync(S, 0, sizeof(unsigned long long) * n_S, st));
-      if (T > 0) hipLaunchKernelGGL(k_gp_contract, gm_blocks(T, GM_TPW), dim3(64), 0, st, a);
-      if (P > 0) hipLaunchKernelGGL(k_gp_pairs, gm_blocks(P, GM_THREADS), dim3(GM_THREADS), 0, st, b);
+      if (T > 0) hipLaunchKernelGGL(k_gp_contract, blocks_for(T, GM_TPW), dim3(64), 0, st, a);
+      if (P > 0) hipLaunchKernelGGL(k_gp_pairs, blocks_for(P, GM_THREADS), dim3(GM_THREADS), 0, st, b);
     }
     timer.mark(2);
     if (m > 0) {
       hipLaunchKernelGGL(k_gp_gauge, dim3(1), dim3(GM_THREADS), 0, st, b);
-      hipLaunchKernelGGL(k_gp_pack, gm_blocks((int64_t)n_aug, GM_THREADS), dim3(GM_THREADS), 0, st, n, root, S, 1.0 / scale, g, aug);
+      hipLaunchKernelGGL(k_gp_pack, blocks_for((int64_t)n_aug, GM_THREADS), dim3(GM_THREADS), 0, st, n, root, S, 1.0 / scale, g, aug);
     }
     timer.mark(3);
     if (m > 0)
@@ -761,8 +726,8 @@ static int global_positioning(pxr_ctx* ctx, const pxr_tri_view* v, int32_t n_pai
       PXR_HIP(hipStreamSynchronize(st));
     }
     if (h_flag) { *h_status = 1; break; }
-    if (T > 0) hipLaunchKernelGGL(k_gp_update, gm_blocks(T, GM_TPW), dim3(64), 0, st, a);
-    if (P > 0) hipLaunchKernelGGL(k_gp_pair_update, gm_blocks(P, GM_THREADS), dim3(GM_THREADS), 0, st, b);
+    if (T > 0) hipLaunchKernelGGL(k_gp_update, blocks_for(T, GM_TPW), dim3(64), 0, st, a);
+    if (P > 0) hipLaunchKernelGGL(k_gp_pair_update, blocks_for(P, GM_THREADS), dim3(GM_THREADS), 0, st, b);
     timer.mark(5);
     *h_rounds = it + 1;
     if (h_ms) {

@@ -20,13 +20,11 @@
 // grow-only workspace.
 #include <hip/hip_runtime.h>
 
-#include "pxr_internal.h"
+#include "pxr_batch.h"
 #include "pxr_scan.h"
 
 namespace pxr {
 namespace {
-
-inline unsigned gblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
 __global__ void g_iota(int n, int* __restrict__ a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -224,51 +222,40 @@ extern "C" int pxr_graph_labels_device(pxr_ctx* ctx, int64_t n_nodes, const int3
   const int64_t m = n_edges;
   // scratch (ints): comp n | ptr n+1 | cursor n+1 | bucket m | sorted m | parent n | next n | tail n | tsize n | flag 2
   //                 optr n+1 | iptr n+1 | ilist m | best_idx n ; + best keys (u64) n
-  size_t off = 0;
-  auto carve = [&](size_t count, size_t elem) { const size_t o = off; off += (count * elem + 255) & ~(size_t)255; return o; };
-  const size_t o_comp = carve(n, 4), o_ptr = carve(n + 1, 4), o_cur = carve(n + 1, 4), o_bucket = carve(m, 4), o_sorted = carve(m, 4);
-  const size_t o_parent = carve(n, 4), o_next = carve(n, 4), o_tail = carve(n, 4), o_tsize = carve(n, 4), o_flag = carve(4, 4);
-  const size_t o_optr = carve(n + 1, 4), o_iptr = carve(n + 1, 4), o_ilist = carve(m, 4), o_bidx = carve(n, 4), o_best = carve(n, 8);
-  if (off > ctx->workspace_bytes) {
-    PXR_HIP(hipStreamSynchronize(st));
-    if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
-    PXR_HIP(hipMalloc(&ctx->d_workspace, off));
-    ctx->workspace_bytes = off;
-  }
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  int* comp = (int*)(ws + o_comp); int* ptr = (int*)(ws + o_ptr); int* cursor = (int*)(ws + o_cur);
-  int* bucket = (int*)(ws + o_bucket); int* sorted = (int*)(ws + o_sorted);
-  int* parent = (int*)(ws + o_parent); int* next = (int*)(ws + o_next); int* tail = (int*)(ws + o_tail); int* tsize = (int*)(ws + o_tsize);
-  int* flag = (int*)(ws + o_flag);
-  int* optr = (int*)(ws + o_optr); int* iptr = (int*)(ws + o_iptr); int* ilist = (int*)(ws + o_ilist); int* best_idx = (int*)(ws + o_bidx);
-  unsigned long long* best = (unsigned long long*)(ws + o_best);
+  int *comp, *ptr, *cursor, *bucket, *sorted, *parent, *next, *tail, *tsize, *flag, *optr, *iptr, *ilist, *best_idx;
+  unsigned long long* best;
+  Workspace ws;
+  ws.take(comp, n); ws.take(ptr, n + 1); ws.take(cursor, n + 1); ws.take(bucket, m); ws.take(sorted, m);
+  ws.take(parent, n); ws.take(next, n); ws.take(tail, n); ws.take(tsize, n); ws.take(flag, 4);
+  ws.take(optr, n + 1); ws.take(iptr, n + 1); ws.take(ilist, m); ws.take(best_idx, n); ws.take(best, n);
+  if (int rc = ws.commit(ctx)) return rc;
 
   int h_flag[2] = {0, 0};
   PXR_HIP(hipMemsetAsync(flag, 0, 16, st));
-  if (m > 0) hipLaunchKernelGGL(g_check, dim3(gblk(m)), dim3(256), 0, st, m, n, d_edge_src, d_edge_dst, flag);
+  if (m > 0) hipLaunchKernelGGL(g_check, blocks_for(m, 256), dim3(256), 0, st, m, n, d_edge_src, d_edge_dst, flag);
   PXR_HIP(hipMemcpyAsync(h_flag, flag, 4, hipMemcpyDeviceToHost, st));
   PXR_HIP(hipStreamSynchronize(st));
   PXR_REQUIRE(!(h_flag[0] & 1), "pxr_graph_labels_device: a match references a node out of range");
   PXR_REQUIRE(!(h_flag[0] & 2), "pxr_graph_labels_device: matches must be in Graph order (grouped by ascending source node)");
   // 1. components
-  hipLaunchKernelGGL(g_iota, dim3(gblk(n)), dim3(256), 0, st, n, comp);
+  hipLaunchKernelGGL(g_iota, blocks_for(n, 256), dim3(256), 0, st, n, comp);
   for (int64_t round = 0; m > 0; ++round) {             // until no label moves (hook + full pointer jumping: O(log n) rounds)
     PXR_REQUIRE(round <= (int64_t)n + 1, "pxr_graph_labels_device: the component labelling did not converge");
     PXR_HIP(hipMemsetAsync(flag + 1, 0, 4, st));
-    hipLaunchKernelGGL(g_hook, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_src, d_edge_dst, comp, flag + 1);
-    hipLaunchKernelGGL(g_jump, dim3(gblk(n)), dim3(256), 0, st, n, comp, flag + 1);
+    hipLaunchKernelGGL(g_hook, blocks_for(m, 256), dim3(256), 0, st, m, d_edge_src, d_edge_dst, comp, flag + 1);
+    hipLaunchKernelGGL(g_jump, blocks_for(n, 256), dim3(256), 0, st, n, comp, flag + 1);
     PXR_HIP(hipMemcpyAsync(h_flag + 1, flag + 1, 4, hipMemcpyDeviceToHost, st));
     PXR_HIP(hipStreamSynchronize(st));
     if (!h_flag[1]) break;
   }
   // 2. buckets of edges per component (keyed by the component of the source node)
   PXR_HIP(hipMemsetAsync(ptr, 0, sizeof(int) * ((size_t)n + 1), st));
-  if (m > 0) hipLaunchKernelGGL(g_count, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_src, (const int*)comp, ptr);
+  if (m > 0) hipLaunchKernelGGL(g_count, blocks_for(m, 256), dim3(256), 0, st, m, d_edge_src, (const int*)comp, ptr);
   if (m > 0) {
     // g_component orders a component's matches with an O(m_c^2) rank sort in ONE wavefront: fine for tracks-sized
     // components, quadratic when bad matches chain a scene into one giant component -- refuse those (the caller
     // falls back to the host labelling, pxr_graph_track_labels) instead of running a single wave for minutes
-    hipLaunchKernelGGL(g_max, dim3(gblk(n)), dim3(256), 0, st, n, (const int*)ptr, flag + 2);
+    hipLaunchKernelGGL(g_max, blocks_for(n, 256), dim3(256), 0, st, n, (const int*)ptr, flag + 2);
     PXR_HIP(hipMemcpyAsync(h_flag, flag + 2, 4, hipMemcpyDeviceToHost, st));
     PXR_HIP(hipStreamSynchronize(st));
     if (h_flag[0] > kMaxComponentMatches)
@@ -277,42 +264,42 @@ extern "C" int pxr_graph_labels_device(pxr_ctx* ctx, int64_t n_nodes, const int3
   }
   hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, st, (int64_t)n, (const int*)ptr, ptr, 1);
   PXR_HIP(hipMemcpyAsync(cursor, ptr, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToDevice, st));
-  if (m > 0) hipLaunchKernelGGL(g_scatter, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_src, (const int*)comp, cursor, bucket);
+  if (m > 0) hipLaunchKernelGGL(g_scatter, blocks_for(m, 256), dim3(256), 0, st, m, d_edge_src, (const int*)comp, cursor, bucket);
   // 3. constrained merges, one wavefront per component
-  hipLaunchKernelGGL(g_fill, dim3(gblk(n)), dim3(256), 0, st, (int64_t)n, -1, parent);
-  hipLaunchKernelGGL(g_fill, dim3(gblk(n)), dim3(256), 0, st, (int64_t)n, -1, next);
-  hipLaunchKernelGGL(g_iota, dim3(gblk(n)), dim3(256), 0, st, n, tail);
-  hipLaunchKernelGGL(g_fill, dim3(gblk(n)), dim3(256), 0, st, (int64_t)n, 1, tsize);
+  hipLaunchKernelGGL(g_fill, blocks_for(n, 256), dim3(256), 0, st, (int64_t)n, -1, parent);
+  hipLaunchKernelGGL(g_fill, blocks_for(n, 256), dim3(256), 0, st, (int64_t)n, -1, next);
+  hipLaunchKernelGGL(g_iota, blocks_for(n, 256), dim3(256), 0, st, n, tail);
+  hipLaunchKernelGGL(g_fill, blocks_for(n, 256), dim3(256), 0, st, (int64_t)n, 1, tsize);
   if (m > 0)
-    hipLaunchKernelGGL(g_component, dim3(gblk(n, 4)), dim3(256), 0, st, n, (const int*)comp, (const int*)ptr, (const int*)bucket, sorted,
+    hipLaunchKernelGGL(g_component, blocks_for(n, 4), dim3(256), 0, st, n, (const int*)comp, (const int*)ptr, (const int*)bucket, sorted,
                        d_edge_src, d_edge_dst, d_edge_sim, d_node_image, parent, next, tail, tsize);
   // 4. track ids in node order
-  hipLaunchKernelGGL(g_root_flags, dim3(gblk(n)), dim3(256), 0, st, n, (const int*)parent, cursor);
+  hipLaunchKernelGGL(g_root_flags, blocks_for(n, 256), dim3(256), 0, st, n, (const int*)parent, cursor);
   hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, st, (int64_t)n, (const int*)cursor, cursor, 1);
-  hipLaunchKernelGGL(g_assign, dim3(gblk(n)), dim3(256), 0, st, n, (const int*)parent, (const int*)cursor, d_track_labels);
+  hipLaunchKernelGGL(g_assign, blocks_for(n, 256), dim3(256), 0, st, n, (const int*)parent, (const int*)cursor, d_track_labels);
   int h_tracks = 0;
   PXR_HIP(hipMemcpyAsync(&h_tracks, cursor + n, 4, hipMemcpyDeviceToHost, st));
   if (d_scores) {
     PXR_HIP(hipMemsetAsync(optr, 0, sizeof(int) * ((size_t)n + 1), st));
     PXR_HIP(hipMemsetAsync(iptr, 0, sizeof(int) * ((size_t)n + 1), st));
     if (m > 0) {
-      hipLaunchKernelGGL(g_count, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_src, (const int*)nullptr, optr);
-      hipLaunchKernelGGL(g_count, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_dst, (const int*)nullptr, iptr);
+      hipLaunchKernelGGL(g_count, blocks_for(m, 256), dim3(256), 0, st, m, d_edge_src, (const int*)nullptr, optr);
+      hipLaunchKernelGGL(g_count, blocks_for(m, 256), dim3(256), 0, st, m, d_edge_dst, (const int*)nullptr, iptr);
     }
     hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, st, (int64_t)n, (const int*)optr, optr, 1);
     hipLaunchKernelGGL((k_exclusive_scan<1024, int, int>), dim3(1), dim3(1024), 0, st, (int64_t)n, (const int*)iptr, iptr, 1);
     PXR_HIP(hipMemcpyAsync(comp, iptr, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, st));     // comp is free now: cursor of the in-lists
-    if (m > 0) hipLaunchKernelGGL(g_scatter, dim3(gblk(m)), dim3(256), 0, st, m, d_edge_dst, (const int*)nullptr, comp, ilist);
-    hipLaunchKernelGGL(g_scores, dim3(gblk(n)), dim3(256), 0, st, n, (const int*)optr, (const int*)iptr, ilist, d_edge_src, d_edge_dst,
+    if (m > 0) hipLaunchKernelGGL(g_scatter, blocks_for(m, 256), dim3(256), 0, st, m, d_edge_dst, (const int*)nullptr, comp, ilist);
+    hipLaunchKernelGGL(g_scores, blocks_for(n, 256), dim3(256), 0, st, n, (const int*)optr, (const int*)iptr, ilist, d_edge_src, d_edge_dst,
                        d_edge_sim, (const int64_t*)d_track_labels, d_scores);
   }
   if (d_is_root) {
     PXR_HIP(hipMemsetAsync(best, 0, sizeof(unsigned long long) * (size_t)n, st));
-    hipLaunchKernelGGL(g_fill, dim3(gblk(n)), dim3(256), 0, st, (int64_t)n, -1, best_idx);
-    hipLaunchKernelGGL(g_best_score, dim3(gblk(n)), dim3(256), 0, st, n, (const int64_t*)d_track_labels, (const double*)d_scores, best);
-    hipLaunchKernelGGL(g_best_index, dim3(gblk(n)), dim3(256), 0, st, n, (const int64_t*)d_track_labels, (const double*)d_scores,
+    hipLaunchKernelGGL(g_fill, blocks_for(n, 256), dim3(256), 0, st, (int64_t)n, -1, best_idx);
+    hipLaunchKernelGGL(g_best_score, blocks_for(n, 256), dim3(256), 0, st, n, (const int64_t*)d_track_labels, (const double*)d_scores, best);
+    hipLaunchKernelGGL(g_best_index, blocks_for(n, 256), dim3(256), 0, st, n, (const int64_t*)d_track_labels, (const double*)d_scores,
                        (const unsigned long long*)best, best_idx);
-    hipLaunchKernelGGL(g_mark_roots, dim3(gblk(n)), dim3(256), 0, st, n, (const int64_t*)d_track_labels, (const int*)best_idx, d_is_root);
+    hipLaunchKernelGGL(g_mark_roots, blocks_for(n, 256), dim3(256), 0, st, n, (const int64_t*)d_track_labels, (const int*)best_idx, d_is_root);
   }
   PXR_HIP(hipGetLastError());
   PXR_HIP(hipStreamSynchronize(st));

@@ -114,14 +114,31 @@ int gram_build_flagged(pxr_ctx* ctx, pxr_arena* arena, const pxr_ba_view* v, con
   } while (0)
 
 namespace pxr {
-// at least `bytes` of ctx->d_workspace (grow-only; growing waits for the stream, frees the old block and loses its contents).
-// Inline, so that a driver's translation unit is complete without pxr_runtime.cpp: the lane-emulation tests compile one alone.
-inline int grow_workspace(pxr_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->workspace_bytes) return PXR_OK;
+// the grid of a launch over n items: the blocks of `per` items that cover them
+inline dim3 blocks_for(int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
+
+// The one rule for a grow-only device block of the context (*block of *have bytes): at least `want` bytes afterwards.  Growing
+// waits for the stream, frees the old block and loses its contents.  release_caches: when hipMalloc fails, the BA solver's
+// Gram-matrix cache and its solve arena, which stay on the context between solves (grow-only, 1.4 GB at 1M observations), are
+// given back and the allocation is tried once more before giving up.  Inline, so that a driver's translation unit is
+// complete without pxr_runtime.cpp: the lane-emulation tests compile one alone.
+inline int grow_block(pxr_ctx* ctx, void** block, size_t* have, size_t want, bool release_caches) {
+  if (want <= *have) return PXR_OK;
   PXR_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_workspace) { PXR_HIP(hipFree(ctx->d_workspace)); ctx->d_workspace = nullptr; ctx->workspace_bytes = 0; }
-  PXR_HIP(hipMalloc(&ctx->d_workspace, bytes));
-  ctx->workspace_bytes = bytes;
+  if (*block) { PXR_HIP(hipFree(*block)); *block = nullptr; *have = 0; }
+  if (!release_caches) {
+    PXR_HIP(hipMalloc(block, want));
+  } else if (hipMalloc(block, want) != hipSuccess) {
+    (void)hipGetLastError();
+    if (ctx->d_gram) { (void)hipFree(ctx->d_gram); ctx->d_gram = nullptr; ctx->gram_bytes = 0; }
+    if (ctx->d_solve_arena) { (void)hipFree(ctx->d_solve_arena); ctx->d_solve_arena = nullptr; ctx->solve_arena_bytes = 0; }
+    PXR_HIP(hipMalloc(block, want));
+  }
+  *have = want;
   return PXR_OK;
+}
+// at least `bytes` of ctx->d_workspace
+inline int grow_workspace(pxr_ctx* ctx, size_t bytes, bool release_caches = false) {
+  return grow_block(ctx, &ctx->d_workspace, &ctx->workspace_bytes, bytes, release_caches);
 }
 }  // namespace pxr

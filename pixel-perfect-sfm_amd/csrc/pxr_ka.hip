@@ -34,7 +34,7 @@
 #include "pxr_device.h"
 #include "pxr_dispatch.h"
 #include "pxr_interp.h"
-#include "pxr_internal.h"
+#include "pxr_batch.h"
 #include "pxr_scan.h"
 
 namespace pxr {
@@ -1460,38 +1460,25 @@ struct KaKnobs {
   }
 };
 
-// the scratch of a solve, carved out of the context's grow-only workspace (no hipMalloc per call once it has reached its
-// high-water mark): the offsets and the pointers that go with them
+// The scratch of a solve, laid out in the context's grow-only workspace (no hipMalloc per call once it has reached its
+// high-water mark).  Most of it goes straight into KaArgs; kept here is what the host itself writes or hands to a kernel next
+// to KaArgs.  The workspace may release the BA solver's caches to grow (grow_block).
 struct KaWorkspace {
-  size_t desc, cand, vec, var, label, ipos, irow, comp, used, hptr, sum, info, pscale, pdone, pstate, order, heavy, gfirst, gsize, gpart, gcnt;
-  size_t bytes = 0;
-  KaWorkspace(size_t nn, size_t np, int C) {
-    auto carve = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
-    desc = carve(sizeof(double) * nn * 3 * C); cand = carve(sizeof(double) * nn * 2);
-    vec = carve(sizeof(double) * nn * 2 * 9);
-    var = carve(sizeof(int) * nn); label = carve(sizeof(int) * nn); ipos = carve(sizeof(int) * nn * 4);
-    irow = carve(sizeof(int) * nn * 6); comp = carve(sizeof(int) * nn); used = carve(nn);
-    hptr = carve(sizeof(int64_t) * (np + 1)); sum = carve(sizeof(pxr_lm_summary) * np);
-    info = carve(sizeof(KaInfo) * np);
-    pscale = carve(sizeof(double) * np); pdone = carve(np);
-    pstate = carve(sizeof(double) * KA_STATE * np);
-    order = carve(sizeof(int) * np); heavy = carve(np);
-    gfirst = carve(sizeof(int) * np); gsize = carve(sizeof(int) * np);
-    gpart = carve(sizeof(double) * 2 * 4 * np); gcnt = carve(sizeof(unsigned) * KA_GRP_CNT_STRIDE * np);
-  }
-  // what the host itself writes or hands to a kernel next to KaArgs
   int64_t* d_hptr = nullptr; KaInfo* d_info = nullptr; int* d_order = nullptr; int *d_gfirst = nullptr, *d_gsize = nullptr;
-  void wire(char* ws, bool grouped, KaArgs& a) {
-    a.desc = (double*)(ws + desc); a.kp_cand = (double*)(ws + cand); a.vec = (double*)(ws + vec);
-    a.var_of_node = (int*)(ws + var); a.label = (int*)(ws + label); a.ipos = (int*)(ws + ipos);
-    a.irow = (int*)(ws + irow); a.comp_v0 = (int*)(ws + comp); a.used = (uint8_t*)(ws + used);
-    d_hptr = (int64_t*)(ws + hptr); a.prob_h_ptr = d_hptr; a.summaries = (pxr_lm_summary*)(ws + sum);
-    d_info = (KaInfo*)(ws + info);
-    a.prob_scale = (double*)(ws + pscale); a.prob_done = (uint8_t*)(ws + pdone);
-    a.prob_state = (double*)(ws + pstate);
-    d_order = (int*)(ws + order); a.prob_heavy = (uint8_t*)(ws + heavy);
-    d_gfirst = (int*)(ws + gfirst); d_gsize = (int*)(ws + gsize);
-    if (grouped) { a.grp_first = d_gfirst; a.grp_size = d_gsize; a.grp_part = (double*)(ws + gpart); a.grp_cnt = (unsigned*)(ws + gcnt); }
+  double* d_gpart = nullptr; unsigned* d_gcnt = nullptr;
+  int wire(pxr_ctx* ctx, size_t nn, size_t np, int C, bool grouped, KaArgs& a) {
+    Workspace ws;
+    ws.take(a.desc, nn * 3 * C); ws.take(a.kp_cand, nn * 2); ws.take(a.vec, nn * 2 * 9);
+    ws.take(a.var_of_node, nn); ws.take(a.label, nn); ws.take(a.ipos, nn * 4);
+    ws.take(a.irow, nn * 6); ws.take(a.comp_v0, nn); ws.take(a.used, nn);
+    ws.take(d_hptr, np + 1); ws.take(a.summaries, np); ws.take(d_info, np);
+    ws.take(a.prob_scale, np); ws.take(a.prob_done, np); ws.take(a.prob_state, KA_STATE * np);
+    ws.take(d_order, np); ws.take(a.prob_heavy, np);
+    ws.take(d_gfirst, np); ws.take(d_gsize, np); ws.take(d_gpart, 2 * 4 * np); ws.take(d_gcnt, KA_GRP_CNT_STRIDE * np);
+    if (int rc = ws.commit(ctx, true)) return rc;
+    a.prob_h_ptr = d_hptr;
+    if (grouped) { a.grp_first = d_gfirst; a.grp_size = d_gsize; a.grp_part = d_gpart; a.grp_cnt = d_gcnt; }
+    return PXR_OK;
   }
 };
 
@@ -1577,21 +1564,6 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
     PXR_REQUIRE(nmax >= 0 && nmax < 46000, "pxr_ka_solve: sub-problem too large (< 23000 nodes each)");
   }
   const auto t0 = std::chrono::steady_clock::now();
-  auto grow = [&](void** buf, size_t* have, size_t want) -> int {
-    if (want <= *have) return PXR_OK;
-    PXR_HIP(hipStreamSynchronize(st));
-    if (*buf) { PXR_HIP(hipFree(*buf)); *buf = nullptr; *have = 0; }
-    if (hipMalloc(buf, want) != hipSuccess) {
-      // the BA solver's Gram-matrix cache stays on the context between solves (grow-only, 1.4 GB at 1M observations): give it
-      // back before giving up
-      (void)hipGetLastError();
-      if (ctx->d_gram) { (void)hipFree(ctx->d_gram); ctx->d_gram = nullptr; ctx->gram_bytes = 0; }
-      if (ctx->d_solve_arena) { (void)hipFree(ctx->d_solve_arena); ctx->d_solve_arena = nullptr; ctx->solve_arena_bytes = 0; }   // ... and the BA solver's buffers
-      PXR_HIP(hipMalloc(buf, want));
-    }
-    *have = want;
-    return PXR_OK;
-  };
   // label groups spanning several workgroups (pxr_ka_view.d_prob_group)
   std::vector<int> grp_first, grp_size;
   int grp_max = 1;
@@ -1609,11 +1581,10 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
       i = j;
     }
   }
-  KaWorkspace w((size_t)view->n_nodes, (size_t)np, arena->C);
-  if (int rc = grow(&ctx->d_workspace, &ctx->workspace_bytes, w.bytes)) return rc;
   KaArgs a{};
   fill_args(arena, view, cfg, loss, a);
-  w.wire(static_cast<char*>(ctx->d_workspace), grp_max > 1, a);
+  KaWorkspace w;
+  if (int rc = w.wire(ctx, (size_t)view->n_nodes, (size_t)np, arena->C, grp_max > 1, a)) return rc;
   a.bound = bound; a.opt = *options;
   PXR_HIP(hipMemsetAsync(a.used, 0, (size_t)view->n_nodes, st));
   PXR_HIP(hipMemsetAsync(a.prob_state, 0, sizeof(double) * KA_STATE * np, st));
@@ -1646,9 +1617,9 @@ extern "C" int pxr_ka_solve(pxr_ctx* ctx, pxr_arena* arena, const pxr_ka_view* v
   const int lds_elems = (int)std::min<int64_t>(largest, (int64_t)KA_NLDS * KA_NLDS);
   const bool need_aglob = largest > lds_elems;
   const size_t hbytes = (sizeof(double) * (size_t)h_ptr[np] + 255) & ~(size_t)255;
-  if (int rc = grow(&ctx->d_workspace_mat, &ctx->workspace_mat_bytes, hbytes * (need_aglob ? 2 : 1) + 256)) return rc;
-  a.Hbuf = (double*)ctx->d_workspace_mat;
-  a.Abuf = need_aglob ? (double*)((char*)ctx->d_workspace_mat + hbytes) : a.Hbuf;
+  if (int rc = grow_block(ctx, &ctx->d_workspace_mat, &ctx->workspace_mat_bytes, hbytes * (need_aglob ? 2 : 1) + 256, true)) return rc;
+  a.Hbuf = static_cast<double*>(ctx->d_workspace_mat);
+  a.Abuf = need_aglob ? a.Hbuf + hbytes / sizeof(double) : a.Hbuf;
   a.lds_elems = lds_elems;
   // the whole LM state in LDS when EVERY sub-problem fits next to the static metadata caches at two workgroups per CU
   int n_max = 1;

@@ -178,12 +178,10 @@ static int mapper_visibility(pxr_ctx* ctx, const pxr_tri_view* v, const int64_t*
     return hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
   }
 
-  Carver cv;
-  const size_t o_flag = cv.take(4, 4), o_order = cv.take((size_t)I, 4);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  int* flag = (int*)(ws + o_flag);
-  int32_t* d_order = (int32_t*)(ws + o_order);
+  int* flag; int32_t* d_order;
+  Workspace ws;
+  ws.take(flag, 4); ws.take(d_order, (size_t)I);
+  if (int rc = ws.commit(ctx)) return rc;
 
   MapArgs a;
   a.v = *v; a.obs_track = d_obs_track; a.image_obs_offsets = d_image_obs_offsets; a.image_obs = d_image_obs; a.xyz = d_xyz;

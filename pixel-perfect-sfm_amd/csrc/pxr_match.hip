@@ -446,19 +446,15 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
   }
   const bool mutual = o->do_mutual_check != 0;
 
-  Carver cv;
-  const size_t o_pairs = cv.take(hp.size(), sizeof(MatchPair)), o_items = cv.take(items.size(), sizeof(MatchItem));
-  const size_t o_colp = cv.take(col_prefix.size(), 8), o_m1 = cv.take((size_t)cols, 4);
-  const size_t o_s1 = cv.take((size_t)parts, 4), o_i1 = cv.take((size_t)parts, 4), o_s2 = cv.take((size_t)parts, 4);
-  const size_t o_rrow = cv.take(gd ? (size_t)rows * 4 : 0, 8), o_rcol = cv.take(gd ? (size_t)cols * 4 : 0, 8);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-
   GuidedMatchArgs a{};
   a.desc = d_desc;
-  a.pairs = (const MatchPair*)(ws + o_pairs); a.items = (const MatchItem*)(ws + o_items); a.col_prefix = (const int64_t*)(ws + o_colp);
-  a.part_s1 = (float*)(ws + o_s1); a.part_i1 = (int32_t*)(ws + o_i1); a.part_s2 = (float*)(ws + o_s2);
-  a.m1 = (int32_t*)(ws + o_m1);
+  MatchPair* d_hp; MatchItem* d_items; int64_t* d_col_prefix;      // (the host fills these three; the kernels only read them)
+  Workspace ws;
+  ws.take(d_hp, hp.size()); ws.take(d_items, items.size()); ws.take(d_col_prefix, col_prefix.size()); ws.take(a.m1, (size_t)cols);
+  ws.take(a.part_s1, (size_t)parts); ws.take(a.part_i1, (size_t)parts); ws.take(a.part_s2, (size_t)parts);
+  ws.take(a.rec_row, gd ? (size_t)rows * 4 : 0); ws.take(a.rec_col, gd ? (size_t)cols * 4 : 0);
+  if (int rc = ws.commit(ctx)) return rc;
+  a.pairs = d_hp; a.items = d_items; a.col_prefix = d_col_prefix;
   a.matches0 = d_matches0; a.scores0 = d_scores0; a.n_matches = d_n_matches;
   a.n_cols = cols; a.n_pairs = n_pairs; a.dim = dim;
   a.kp = ((dim + 1) / 2 + MT_KSTEP - 1) / MT_KSTEP * MT_KSTEP;
@@ -467,16 +463,16 @@ int match_descriptors(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_off
   a.use_ratio = o->ratio_threshold > 0.0; a.use_dist = o->distance_threshold > 0.0; a.mutual = mutual;
   if (gd) {
     a.row_prefix = d_pair_offsets; a.xy = gd->d_xy; a.kind = gd->d_kind; a.model = gd->d_model; a.thr = gd->d_thr;
-    a.rec_row = (double*)(ws + o_rrow); a.rec_col = (double*)(ws + o_rcol); a.n_rows = rows;
+    a.n_rows = rows;
   }
   const MatchArgs& au = a;                               // what the unguided kernels take
 
   StageTimer<5> timer(st, h_ms);                         // records (with a gate) | tiles | columns | mutual
   if (int rc = timer.create(fn)) return rc;
 
-  int rc = hip_check(hipMemcpyAsync(ws + o_pairs, hp.data(), sizeof(MatchPair) * hp.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-  if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(ws + o_items, items.data(), sizeof(MatchItem) * items.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
-  if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(ws + o_colp, col_prefix.data(), 8 * col_prefix.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  int rc = hip_check(hipMemcpyAsync(d_hp, hp.data(), sizeof(MatchPair) * hp.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(d_items, items.data(), sizeof(MatchItem) * items.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  if (rc == PXR_OK) rc = hip_check(hipMemcpyAsync(d_col_prefix, col_prefix.data(), 8 * col_prefix.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipMemsetAsync(d_n_matches, 0, sizeof(int32_t) * (size_t)n_pairs, st), "hipMemsetAsync");
   if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (the host vectors may go out of scope)
   if (rc != PXR_OK) return rc;

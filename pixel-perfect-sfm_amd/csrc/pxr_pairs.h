@@ -207,31 +207,26 @@ inline int open_pair_batch(const PairCall& c, bool own_outputs, const char* own_
   };
   if (int rc = batch_order(ctx, {fn, "pair_offsets", "pair", "n_matches"}, false, c.d_pair_offsets, T, N, off, order, cameras_in_range)) return rc;
 
-  Carver cv;
-  const size_t o_rec = cv.take((size_t)N * PAIR_REC, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
-  const size_t o_ma = cv.take((size_t)N, 1), o_mb = cv.take((size_t)N, 1), o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4);
-  const size_t o_win = cv.take((size_t)T * winner_ints, 4), o_model = cv.take((size_t)T * 9, 8);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  uint8_t* valid = (uint8_t*)(ws + o_valid);
-  b.rec = (double*)(ws + o_rec); b.pos = (int32_t*)(ws + o_pos); b.n_valid = (int32_t*)(ws + o_nv); b.order = (int32_t*)(ws + o_order);
-  b.mask_a = (uint8_t*)(ws + o_ma); b.mask_b = (uint8_t*)(ws + o_mb);
-  b.winner = (int32_t*)(ws + o_win); b.winner_model = (double*)(ws + o_model);
+  uint8_t* valid;
+  Workspace ws;
+  ws.take(b.rec, (size_t)N * PAIR_REC); ws.take(valid, (size_t)N); ws.take(b.pos, (size_t)N);
+  ws.take(b.mask_a, (size_t)N); ws.take(b.mask_b, (size_t)N); ws.take(b.n_valid, (size_t)T); ws.take(b.order, (size_t)T);
+  ws.take(b.winner, (size_t)T * winner_ints); ws.take(b.winner_model, (size_t)T * 9);
+  if (int rc = ws.commit(ctx)) return rc;
   b.max_trials = (int32_t)(((int64_t)o->max_num_trials + o->round_size - 1) / o->round_size * o->round_size);
 
   StageTimer<5>& timer = b.timer.emplace(st, c.h_ms);
   if (int rc = timer.create(fn)) return rc;
 
-  auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
   int rc = hip_check(hipMemcpyAsync(b.order, order.data(), sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (rc == PXR_OK) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");      // (`order` goes out of scope)
   if (rc != PXR_OK) return rc;
   timer.mark(0);
   if (N > 0)
-    hipLaunchKernelGGL(k_pair_records<PAIR_THREADS>, blocks(N, PAIR_THREADS), dim3(PAIR_THREADS), 0, st, N, c.n_pairs, c.d_pair_offsets,
+    hipLaunchKernelGGL(k_pair_records<PAIR_THREADS>, blocks_for(N, PAIR_THREADS), dim3(PAIR_THREADS), 0, st, N, c.n_pairs, c.d_pair_offsets,
                        c.d_pair_camera, c.d_cam_model, c.d_cam_params, c.d_xy1, c.d_xy2, b.rec, valid, c.d_inlier, c.d_err);
   timer.mark(1);
-  hipLaunchKernelGGL(k_compact_records<PAIR_REC>, blocks(T, PAIR_THREADS), dim3(PAIR_THREADS), 0, st, T, c.d_pair_offsets, b.rec, valid, b.pos,
+  hipLaunchKernelGGL(k_compact_records<PAIR_REC>, blocks_for(T, PAIR_THREADS), dim3(PAIR_THREADS), 0, st, T, c.d_pair_offsets, b.rec, valid, b.pos,
                      b.n_valid);
   timer.mark(2);
   return PXR_OK;

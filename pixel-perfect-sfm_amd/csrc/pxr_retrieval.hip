@@ -408,17 +408,12 @@ int vocab_train(pxr_ctx* ctx, int64_t n_total, int32_t dim, const float* d_desc,
   // one group: chunks small enough that every CU gets two (the merge costs K dim global atomics per chunk)
   push_items(off, 0, 1, std::min<int64_t>(ACC_ROWS, std::max<int64_t>(256, (n_train + 2 * ctx->num_cus - 1) / (2 * std::max(ctx->num_cus, 1)))), items);
   const bool gather = n_train < n_total;
-  Carver cv;
-  const size_t o_train = cv.take(gather ? (size_t)n_train * dim : 0, 4), o_assign = cv.take((size_t)n_train, 4);
-  const size_t o_S = cv.take((size_t)K * dim, 8), o_items = cv.take(items.size(), sizeof(AccItem));
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  float* train = gather ? (float*)(ws + o_train) : nullptr;
+  float* train; int32_t* assign; unsigned long long* S; AccItem* d_items;
+  Workspace ws;
+  ws.take(train, gather ? (size_t)n_train * dim : 0); ws.take(assign, (size_t)n_train); ws.take(S, (size_t)K * dim); ws.take(d_items, items.size());
+  if (int rc = ws.commit(ctx)) return rc;
   const float* rows = gather ? train : d_desc;
-  int32_t* assign = (int32_t*)(ws + o_assign);
-  unsigned long long* S = (unsigned long long*)(ws + o_S);
-  const AccItem* d_items = (const AccItem*)(ws + o_items);
-  PXR_HIP(hipMemcpyAsync(ws + o_items, items.data(), sizeof(AccItem) * items.size(), hipMemcpyHostToDevice, st));
+  PXR_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(AccItem) * items.size(), hipMemcpyHostToDevice, st));
   PXR_HIP(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * (size_t)K, st));     // (`items` outlives the copy: the counts are read back below)
 
   {
@@ -486,17 +481,14 @@ int vlad_aggregate(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offset
   }
   first_item.push_back((int64_t)items.size());
 
-  Carver cv;
-  const size_t o_assign = cv.take(d_assign ? 0 : (size_t)n_total, 4), o_cnt = cv.take(d_counts ? 0 : (size_t)n_images * K, 4);
-  const size_t o_S = cv.take((size_t)batch * per_image, 8), o_b2 = cv.take((size_t)batch * K, 8);
-  const size_t o_items = cv.take(items.size(), sizeof(AccItem));
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  int32_t* assign = d_assign ? d_assign : (int32_t*)(ws + o_assign);
-  int32_t* cnt = d_counts ? d_counts : (int32_t*)(ws + o_cnt);
-  unsigned long long* S = (unsigned long long*)(ws + o_S);
-  const AccItem* d_items = (const AccItem*)(ws + o_items);
-  if (!items.empty()) PXR_HIP(hipMemcpyAsync(ws + o_items, items.data(), sizeof(AccItem) * items.size(), hipMemcpyHostToDevice, st));
+  int32_t *ws_assign, *ws_cnt; unsigned long long* S; double* b2; AccItem* d_items;
+  Workspace ws;
+  ws.take(ws_assign, d_assign ? 0 : (size_t)n_total); ws.take(ws_cnt, d_counts ? 0 : (size_t)n_images * K);
+  ws.take(S, (size_t)batch * per_image); ws.take(b2, (size_t)batch * K); ws.take(d_items, items.size());
+  if (int rc = ws.commit(ctx)) return rc;
+  int32_t* assign = d_assign ? d_assign : ws_assign;
+  int32_t* cnt = d_counts ? d_counts : ws_cnt;
+  if (!items.empty()) PXR_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(AccItem) * items.size(), hipMemcpyHostToDevice, st));
   PXR_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)n_images * K, st));
   PXR_HIP(hipStreamSynchronize(st));                                 // an untimed call waits for nothing after this: the copy out of `items` must be over before it returns
 
@@ -519,7 +511,7 @@ int vlad_aggregate(pxr_ctx* ctx, int32_t n_images, const int64_t* d_image_offset
     launch_accumulate(ctx, d_desc, assign, d_items + first_item[b], first_item[b + 1] - first_item[b], m0, dim, K, S, cnt);
     timer.mark(1);
     VladArgs v;
-    v.S = (const long long*)S; v.cnt = cnt; v.C = d_centroids; v.b2 = (double*)(ws + o_b2); v.G = d_global;
+    v.S = (const long long*)S; v.cnt = cnt; v.C = d_centroids; v.b2 = b2; v.G = d_global;
     v.m0 = m0; v.n_batch = nb; v.K = K; v.dim = dim;
     const dim3 grid((unsigned)(((int64_t)nb * K + 63) / 64));
     hipLaunchKernelGGL(k_vlad_norms, grid, dim3(64), 0, st, v);
@@ -548,10 +540,10 @@ int retrieval_topk(pxr_ctx* ctx, int32_t n_query, int32_t n_db, int32_t dim, con
   if (n_query == 0) return PXR_OK;
   PXR_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  Carver cv;
-  const size_t o_sim = cv.take((size_t)n_query * n_db, 4);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  float* sim = (float*)(static_cast<char*>(ctx->d_workspace) + o_sim);
+  float* sim;
+  Workspace ws;
+  ws.take(sim, (size_t)n_query * n_db);
+  if (int rc = ws.commit(ctx)) return rc;
 
   StageTimer<3> timer(st, h_ms);                                     // similarity | select
   if (int rc = timer.create(fn)) return rc;

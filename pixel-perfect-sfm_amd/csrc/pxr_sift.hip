@@ -514,8 +514,6 @@ static void sift_blur(hipStream_t st, const float* src, float* tmp, float* dst, 
   hipLaunchKernelGGL(k_sift_blur<1>, dim3(tiles_x * (unsigned)((h + SIFT_COL_TILE - 1) / SIFT_COL_TILE)), dim3(SIFT_THREADS), 0, st, (const float*)tmp, dst, h, w, t);
 }
 
-static unsigned sift_blocks(int64_t n) { return (unsigned)((n + SIFT_THREADS - 1) / SIFT_THREADS); }
-
 static int sift_pyramid(pxr_ctx* ctx, const void* d_image, int dtype, int h, int w, const pxr_sift_options* o, float* d_pyramid, double* h_ms) {
   const char* fn = "pxr_sift_pyramid";
   PXR_REQUIRE(ctx && d_image && d_pyramid, "%s: NULL argument", fn);
@@ -533,22 +531,20 @@ static int sift_pyramid(pxr_ctx* ctx, const void* d_image, int dtype, int h, int
   PXR_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int64_t n0 = (int64_t)L.h[0] * L.w[0];
-  Carver cv;
-  const size_t o_img = cv.take((size_t)n0, 4), o_tmp = cv.take((size_t)n0, 4);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  float* img = (float*)(ws + o_img);
-  float* tmp = (float*)(ws + o_tmp);
+  float *img, *tmp;
+  Workspace ws;
+  ws.take(img, (size_t)n0); ws.take(tmp, (size_t)n0);
+  if (int rc = ws.commit(ctx)) return rc;
   StageTimer<2> timer(st, h_ms);
   if (int rc = timer.create(fn)) return rc;
   timer.mark(0);
-  hipLaunchKernelGGL(k_sift_upsample, dim3(sift_blocks(n0)), dim3(SIFT_THREADS), 0, st, d_image, dtype, h, w, o->first_octave < 0 ? 1 : 0, img);
+  hipLaunchKernelGGL(k_sift_upsample, blocks_for(n0, SIFT_THREADS), dim3(SIFT_THREADS), 0, st, d_image, dtype, h, w, o->first_octave < 0 ? 1 : 0, img);
   for (int k = 0; k < L.n_oct; ++k) {
     const int ho = L.h[k], wo = L.w[k];
     const size_t plane = (size_t)ho * wo;
     float* G = d_pyramid + L.off[k];
     if (k == 0) sift_blur(st, img, tmp, G, ho, wo, first);
-    else hipLaunchKernelGGL(k_sift_half, dim3(sift_blocks((int64_t)plane)), dim3(SIFT_THREADS), 0, st,
+    else hipLaunchKernelGGL(k_sift_half, blocks_for((int64_t)plane, SIFT_THREADS), dim3(SIFT_THREADS), 0, st,
                             (const float*)(d_pyramid + L.off[k - 1] + (size_t)S * L.h[k - 1] * L.w[k - 1]), L.w[k - 1], G, ho, wo);
     for (int s = 1; s <= S + 2; ++s) sift_blur(st, G + (size_t)(s - 1) * plane, tmp, G + (size_t)s * plane, ho, wo, inc[s - 1]);
   }
@@ -586,22 +582,19 @@ static int sift_detect(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const
   // The keypoints are staged in the workspace, whose size must be known before the count is: a first guess, and when the count
   // exceeds it the workspace grows (which loses its contents) and count and scan run again.
   int64_t kp_cap = std::max<int64_t>(capacity, 4096), n_kp = 0;
-  size_t o_cnt, o_off, o_kp, o_rec, o_resp, o_nor, o_theta, o_foff;
-  char* ws = nullptr;
+  int64_t *block_off, *feat_off; int32_t* n_orient; double* theta;
   for (int attempt = 0;; ++attempt) {
-    Carver cv;
-    o_cnt = cv.take((size_t)n_blocks, 4); o_off = cv.take((size_t)n_blocks + 1, 8);
-    o_kp = cv.take((size_t)kp_cap * 4, 8); o_rec = cv.take((size_t)kp_cap * 4, 4); o_resp = cv.take((size_t)kp_cap, 8);
-    o_nor = cv.take((size_t)kp_cap, 4); o_theta = cv.take((size_t)kp_cap * 4, 8); o_foff = cv.take((size_t)kp_cap + 1, 8);
-    if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-    ws = static_cast<char*>(ctx->d_workspace);
-    a.block_count = (int32_t*)(ws + o_cnt); a.block_off = (const int64_t*)(ws + o_off);
-    a.kp = (double*)(ws + o_kp); a.rec = (int32_t*)(ws + o_rec); a.resp = (double*)(ws + o_resp); a.kp_cap = kp_cap;
+    Workspace ws;                                       // (a second attempt lays out again: no pointer of the first is kept)
+    ws.take(a.block_count, (size_t)n_blocks); ws.take(block_off, (size_t)n_blocks + 1);
+    ws.take(a.kp, (size_t)kp_cap * 4); ws.take(a.rec, (size_t)kp_cap * 4); ws.take(a.resp, (size_t)kp_cap);
+    ws.take(n_orient, (size_t)kp_cap); ws.take(theta, (size_t)kp_cap * 4); ws.take(feat_off, (size_t)kp_cap + 1);
+    if (int rc = ws.commit(ctx)) return rc;
+    a.block_off = block_off; a.kp_cap = kp_cap;
     timer.mark(0);
     hipLaunchKernelGGL(k_sift_detect<false>, dim3((unsigned)n_blocks), dim3(SIFT_THREADS), 0, st, a);
     timer.mark(1);
     hipLaunchKernelGGL((k_exclusive_scan<SIFT_THREADS, int32_t, int64_t>), dim3(1), dim3(SIFT_THREADS), 0, st, n_blocks, (const int32_t*)a.block_count,
-                       (int64_t*)(ws + o_off), 1);
+                       block_off, 1);
     timer.mark(2);
     if (int rc = hip_check(hipGetLastError(), "k_sift_detect launch")) return rc;
     PXR_HIP(hipMemcpyAsync(&n_kp, a.block_off + n_blocks, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -612,9 +605,6 @@ static int sift_detect(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const
   }
   int64_t total = 0;
   if (n_kp > 0) {
-    int32_t* n_orient = (int32_t*)(ws + o_nor);
-    double* theta = (double*)(ws + o_theta);
-    int64_t* feat_off = (int64_t*)(ws + o_foff);
     hipLaunchKernelGGL(k_sift_detect<true>, dim3((unsigned)n_blocks), dim3(SIFT_THREADS), 0, st, a);
     timer.mark(3);
     const int grid = (int)std::min<int64_t>(n_kp, SIFT_MAX_GRID);
@@ -622,7 +612,7 @@ static int sift_detect(pxr_ctx* ctx, const float* d_pyramid, int h, int w, const
                        (int)o->max_num_orientations, (const double*)a.kp, (const int32_t*)a.rec, n_orient, theta);
     timer.mark(4);
     hipLaunchKernelGGL((k_exclusive_scan<SIFT_THREADS, int32_t, int64_t>), dim3(1), dim3(SIFT_THREADS), 0, st, n_kp, (const int32_t*)n_orient, feat_off, 1);
-    const int egrid = (int)std::min<int64_t>(sift_blocks(n_kp), SIFT_MAX_GRID);
+    const int egrid = (int)std::min<int64_t>(blocks_for(n_kp, SIFT_THREADS).x, SIFT_MAX_GRID);
     if (capacity > 0)
       hipLaunchKernelGGL(k_sift_emit, dim3((unsigned)egrid), dim3(SIFT_THREADS), 0, st, n_kp, egrid, capacity, (const double*)a.kp,
                          (const int32_t*)a.rec, (const double*)a.resp, (const int32_t*)n_orient, (const double*)theta,
@@ -716,7 +706,7 @@ extern "C" int pxr_sift_gather(pxr_ctx* ctx, int64_t n, int64_t n_in, const int6
   PXR_REQUIRE(std::isfinite(offset), "pxr_sift_gather: offset is not finite");
   if (n == 0) return PXR_OK;
   PXR_HIP(hipSetDevice(ctx->device));
-  const int grid = (int)std::min<int64_t>(pxr::sift_blocks(n), pxr::SIFT_MAX_GRID);
+  const int grid = (int)std::min<int64_t>(pxr::blocks_for(n, pxr::SIFT_THREADS).x, pxr::SIFT_MAX_GRID);
   hipLaunchKernelGGL(pxr::k_sift_gather, dim3((unsigned)grid), dim3(pxr::SIFT_THREADS), 0, ctx->stream, n, grid, n_in, d_index, d_keypoints, d_response,
                      offset, d_keypoints_out, d_xy, d_scales, d_orientations, d_scores);
   return pxr::hip_check(hipGetLastError(), "k_sift_gather launch");

@@ -353,29 +353,22 @@ static int triangulate(pxr_ctx* ctx, const pxr_tri_view* v, const pxr_tri_option
   if (int rc = batch_order(ctx, {fn, "track_offsets", "track", "n_obs"}, true, v->d_track_offsets, T, N, off, order, [](int64_t) { return (int)PXR_OK; }))
     return rc;
 
-  Carver cv;
-  const size_t o_flag = cv.take(4, 4), o_rays = cv.take((size_t)N * TRI_RAY, 8), o_valid = cv.take((size_t)N, 1), o_pos = cv.take((size_t)N, 4);
-  const size_t o_nv = cv.take((size_t)T, 4), o_order = cv.take((size_t)T, 4);
-  if (int rc = grow_workspace(ctx, cv.bytes)) return rc;
-  char* ws = static_cast<char*>(ctx->d_workspace);
-  int* flag = (int*)(ws + o_flag);
-  double* rays = (double*)(ws + o_rays);
-  uint8_t* valid = (uint8_t*)(ws + o_valid);
-  int32_t* pos = (int32_t*)(ws + o_pos);
-  int32_t* n_valid = (int32_t*)(ws + o_nv);
-  int32_t* d_order = (int32_t*)(ws + o_order);
+  int* flag; double* rays; uint8_t* valid; int32_t *pos, *n_valid, *d_order;
+  Workspace ws;
+  ws.take(flag, 4); ws.take(rays, (size_t)N * TRI_RAY); ws.take(valid, (size_t)N); ws.take(pos, (size_t)N);
+  ws.take(n_valid, (size_t)T); ws.take(d_order, (size_t)T);
+  if (int rc = ws.commit(ctx)) return rc;
 
   StageTimer<6> timer(st, h_ms);                         // check | (the flag's read-back) | rays | compact | tracks
   if (int rc = timer.create(fn)) return rc;
 
-  auto blocks = [](int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); };
   int h_flag = 0;
   int rc = hip_check(hipMemsetAsync(flag, 0, 16, st), "hipMemsetAsync");
   if (rc == PXR_OK) {
     timer.mark(0);
     const int64_t n_check = std::max<int64_t>(N, v->n_images);
     if (n_check > 0)
-      hipLaunchKernelGGL(k_tri_check, blocks(n_check, TRI_THREADS), dim3(TRI_THREADS), 0, st, N, v->d_obs_image, v->n_images,
+      hipLaunchKernelGGL(k_tri_check, blocks_for(n_check, TRI_THREADS), dim3(TRI_THREADS), 0, st, N, v->d_obs_image, v->n_images,
                          v->d_image_camera, v->n_cameras, flag);
     timer.mark(1);
     rc = hip_check(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
@@ -389,9 +382,9 @@ static int triangulate(pxr_ctx* ctx, const pxr_tri_view* v, const pxr_tri_option
   }
 
   timer.mark(2);
-  if (N > 0) hipLaunchKernelGGL(k_tri_rays, blocks(N, TRI_THREADS), dim3(TRI_THREADS), 0, st, *v, rays, valid, d_obs_inlier, d_obs_err);
+  if (N > 0) hipLaunchKernelGGL(k_tri_rays, blocks_for(N, TRI_THREADS), dim3(TRI_THREADS), 0, st, *v, rays, valid, d_obs_inlier, d_obs_err);
   timer.mark(3);
-  hipLaunchKernelGGL(k_compact_records<TRI_RAY>, blocks(T, TRI_THREADS), dim3(TRI_THREADS), 0, st, T, v->d_track_offsets, rays, valid, pos, n_valid);
+  hipLaunchKernelGGL(k_compact_records<TRI_RAY>, blocks_for(T, TRI_THREADS), dim3(TRI_THREADS), 0, st, T, v->d_track_offsets, rays, valid, pos, n_valid);
   timer.mark(4);
   TriArgs a;
   a.v = *v; a.order = d_order; a.rays = rays; a.pos = pos; a.n_valid = n_valid;
@@ -399,7 +392,7 @@ static int triangulate(pxr_ctx* ctx, const pxr_tri_view* v, const pxr_tri_option
   a.cos_min_tri = std::cos(o->min_tri_angle * rad); a.cos_max_err = std::cos(o->max_angle_error * rad);
   a.max_reproj = o->max_reproj_error; a.min_len = o->min_track_len; a.max_hyp = o->max_hypotheses;
   a.xyz = d_xyz; a.status = d_status; a.n_inliers = d_n_inliers; a.obs_inlier = d_obs_inlier; a.obs_err = d_obs_err;
-  hipLaunchKernelGGL(k_tri_tracks, blocks(T, TRI_TPW), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_tri_tracks, blocks_for(T, TRI_TPW), dim3(64), 0, st, a);
   timer.mark(5);
   rc = hip_check(hipGetLastError(), "k_tri_tracks launch");
   const int from[4] = {0, 2, 3, 4};

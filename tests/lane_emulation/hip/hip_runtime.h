@@ -50,7 +50,13 @@ inline hipError_t hipGetLastError() { return 0; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, int, hipStream_t) { memcpy(d, s, n); return 0; }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return 0; }
-inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return 0; }
+inline int emu_malloc_calls = 0, emu_malloc_failures = 0;    // hipMalloc calls so far; how many of the next ones fail (workspace_on_host.cpp)
+inline hipError_t hipMalloc(void** p, size_t n) {
+  ++emu_malloc_calls;
+  if (emu_malloc_failures > 0) { --emu_malloc_failures; *p = nullptr; return 2; }
+  *p = malloc(n);
+  return 0;
+}
 inline hipError_t hipFree(void* p) { free(p); return 0; }
 inline hipError_t hipEventCreate(hipEvent_t* e) { *e = (void*)1; return 0; }
 inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
