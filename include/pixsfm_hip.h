@@ -621,8 +621,15 @@ void pxr_abspose_default_options(pxr_abspose_options* options);
  *   2. sample h = 0, 1, ... is three distinct indices: draw d = mix(mix(seed + G (h + 1)) + G (d + 1)) mod n, d = 0, 1, ..., with
  *      mix = the output function of splitmix64 and G = 0x9E3779B97F4A7C15 (64-bit wrap-around), a repeated index drawn again;
  *      the three are used in ascending order.  Neither q nor the batch enters.
- *   3. P3P (Grunert's quartic, Ferrari's real roots in the order (+,+) (+,-) (-,+) (-,-), three Newton steps each) gives up to four
- *      poses with positive distances; a degenerate sample gives none.  Each is scored over all n in the normalised image plane:
+ *   3. P3P (Grunert's quartic in v = s3 / s1, or the same coefficients reversed -- the quartic in 1 / v -- where |A0| > |A4|;
+ *      Ferrari's real roots in the order (+,+) (+,-) (-,+) (-,-), a discriminant counting as zero down to -1e-7 of its terms;
+ *      three Newton steps on the quartic each, a step kept only where |f| does not grow) gives up to four poses with positive
+ *      distances; a degenerate sample gives none.  u = s2 / s1 = N(v) / D(v), except for a root with another root within 1e-3
+ *      of it and |D(v)| <= 1e-3 (|D0| + |D1 v|), where N / D tends to 0 / 0: there u = cos(gamma) +- sqrt(cos^2(gamma) - 1 +
+ *      (c^2 / b^2) (1 + v^2 - 2 v cos(beta))), + for the root with the smaller index of the two.  Then three Newton steps on
+ *      the three equations (s_i - s_j)^2 + 2 s_i s_j (1 - cos) = side^2 in (s1, s2, s3), with 1 - cos = |f_i - f_j|^2 / 2 and each
+ *      3 x 3 system by Cramer's rule (a step skipped where the determinant vanishes or the step is not finite); the pose from
+ *      the polished distances.  Each is scored over all n in the normalised image plane:
  *      err = |(u, v) - (X/Z, Y/Z)|^2, inlier iff Z > 0 and err <= (max_error / mean focal)^2; the largest key
  *      (inlier count, -sum min(err, thr^2), -h, -root) wins.
  *   4. after each round of round_size samples: stop once samples done >= clamp(log(1 - confidence) / log(1 - w^3),
@@ -698,7 +705,13 @@ void pxr_two_view_default_options(pxr_two_view_options* options);
  *      with every remainder scaled to a largest coefficient of 1 (a leading coefficient <= 1e-12 after that is dropped); the k-th
  *      real root by 64 bisection steps on the sign-change count from (-bound, bound), then 4 Newton steps, each kept only inside
  *      the last interval; roots ascending, at most ten; (x, y, 1) = the cross product of the two rows of B(z) with the largest third
- *      component.  No hypothesis (and no NaN) from a sample with a pivot <= 1e-12 of its system's largest entry, a leading
+ *      component; then Gauss-Newton steps over (x, y, z), until one is no larger than 1e-10 max(1, |x|, |y|, |z|) and eight at the
+ *      most, on the ten cubic constraints evaluated on the 3 x 3 matrix E itself (the 3 x 3 normal equations by the adjugate; a
+ *      step skipped where their determinant vanishes or the step is not finite, and then ends the iteration), which returns the
+ *      digits that the elimination loses.  Hypotheses are accurate to 600 kappa u (kappa: the norm of d E / d sample, u = 2^-53)
+ *      at a baseline of at least 0.1 of the median depth and on planar scenes, forward motion, small rotations, wide and narrow
+ *      fields (FIVE_POINT_MIN_PARALLAX of tests/twoview_cases.py); below that baseline the elimination loses whole roots, which no
+ *      polish returns.  No hypothesis (and no NaN) from a sample with a pivot <= 1e-12 of its system's largest entry, a leading
  *      coefficient <= 1e-9 of the largest, or any value that is not finite.
  *   4. each E is scored over all n in the normalised image plane by the squared Sampson error err = (x2^t E x1)^2 / ((E x1)_0^2 +
  *      (E x1)_1^2 + (E^t x2)_0^2 + (E^t x2)_1^2); inlier iff err <= thr^2, thr = (max_error / f1 + max_error / f2) / 2 with f the

@@ -17,6 +17,11 @@
 // perspective pose estimation problem", IJCV 1994, section 2): with unit bearings f_i, distances s_i, s_2 = u s_1, s_3 = v s_1
 // the law of cosines gives u = N(v) / D(v) and one quartic in v, whose coefficients are formed here as polynomial products
 // N^2 - 2 cos(gamma) N D + D^2 M; real roots by Ferrari's factorisation into two quadratics, polished by Newton on the quartic.
+// Where the quartic's constant coefficient outweighs its leading one the quartic of 1 / v is solved instead (a leading coefficient
+// near zero is a root near infinity, which costs Ferrari's shift the other three).  Of two roots that nearly coincide while D(v)
+// nearly vanishes -- N / D tends to 0 / 0, as in front of a triangle of equal sides -- u comes from the law of cosines, one of its
+// two roots for each.  The three distances are then polished by Newton on the three cosine-law equations themselves, which are
+// well conditioned where the quartic is not.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +43,11 @@ constexpr int ABS_LDS_CORR = PXR_ABSPOSE_LDS_CORR;     // records of a query sta
 constexpr int ABS_ACC = 28;                            // the refinement's sums: H (21, upper triangle by rows), g (6), cost
 constexpr int ABS_CHUNK = 7;                           // of which this many cross the workgroup at a time (ABS_THREADS x ABS_CHUNK doubles of LDS)
 constexpr int ABS_NEWTON = 3;                          // Newton steps on every quartic root
+constexpr int ABS_DISTANCE_NEWTON = 3;                 // Newton steps on the three cosine-law equations in the distances
+constexpr double ABS_LEAD_TOL = 1e-12;                 // the quartic's leading coefficient counts as zero below this fraction of the sum of magnitudes
+constexpr double ABS_DISC_TOL = 1e-7;                  // a quadratic factor's discriminant counts as zero down to minus this fraction of its terms
+constexpr double ABS_PAIR_TOL = 1e-3;                  // two roots are a close pair within this fraction of their size
+constexpr double ABS_SMALL_D = 1e-3;                   // of a close pair, u is not N / D where |D(v)| is below this fraction of its terms
 constexpr double ABS_STEP_TOL = 1e-12;                 // the refinement stops at a step of this norm
 constexpr double ABS_COST_SLACK = 1e-12;               // a step is kept unless the cost grows by more than this fraction: below it the
                                                        // comparison is rounding noise, and refusing would stall short of the minimum
@@ -45,19 +55,27 @@ constexpr double ABS_COST_SLACK = 1e-12;               // a step is kept unless 
 // ---- P3P -------------------------------------------------------------------------------------------------------------------------
 struct P3P {
   double f1[3], f2[3], f3[3], P1[3], w1[3], w2[3], w3[3];   // unit bearings; first point; orthonormal triad of the three points
-  double b2, cb, N0, N1, N2, D0, D1;
-  double v0, v1, v2, v3;                                    // the roots (NaN: none)
+  double a2, b2, c2, cb, cg, ha, hb, hg, N0, N1, N2, D0, D1;   // squared sides; cos beta, cos gamma; 1 - cos of the three angles
+  double v0, v1, v2, v3;                                    // the roots (NaN: none), of the quartic in 1 / v where rev
+  bool rev;
 };
 
 __device__ __forceinline__ void abs_bearing(const double* r, double f[3]) {
   const double inv = 1.0 / sqrt(r[0] * r[0] + r[1] * r[1] + 1.0);
   f[0] = r[0] * inv; f[1] = r[1] * inv; f[2] = inv;
 }
+// Newton on the monic quartic; a step is kept only where it does not raise |f|: at a double root f' vanishes with f, and an unguarded
+// step can land anywhere
 __device__ __forceinline__ double abs_polish(double v, double B, double C, double D, double E) {
+  double fv = (((v + B) * v + C) * v + D) * v + E;
 #pragma unroll
   for (int it = 0; it < ABS_NEWTON; ++it) {
-    const double fv = (((v + B) * v + C) * v + D) * v + E, dv = ((4.0 * v + 3.0 * B) * v + 2.0 * C) * v + D;
-    if (dv != 0.0) v -= fv / dv;
+    const double dv = ((4.0 * v + 3.0 * B) * v + 2.0 * C) * v + D;
+    if (dv == 0.0) break;
+    const double vn = v - fv / dv;
+    const double fn = (((vn + B) * vn + C) * vn + D) * vn + E;
+    if (!(fabs(fn) <= fabs(fv))) break;
+    v = vn; fv = fn;
   }
   return v;
 }
@@ -81,15 +99,22 @@ __device__ __forceinline__ bool p3p_setup(const double* r1, const double* r2, co
   const double k1 = (a2 - c2) / b2, k2 = c2 / b2;
   const double N0 = k1 + 1.0, N1 = -2.0 * k1 * cb, N2 = k1 - 1.0, D0 = 2.0 * cg, D1 = -2.0 * ca;
   const double M0 = 1.0 - k2, M1 = 2.0 * k2 * cb, M2 = -k2;
-  s.b2 = b2; s.cb = cb; s.N0 = N0; s.N1 = N1; s.N2 = N2; s.D0 = D0; s.D1 = D1;
+  // 1 - cos = |f_i - f_j|^2 / 2: a narrow field of view has cosines that round away what separates them from 1
+  double da[3], db[3], dg[3];
+#pragma unroll
+  for (int m = 0; m < 3; ++m) { da[m] = s.f2[m] - s.f3[m]; db[m] = s.f1[m] - s.f3[m]; dg[m] = s.f1[m] - s.f2[m]; }
+  s.ha = 0.5 * dot3(da, da); s.hb = 0.5 * dot3(db, db); s.hg = 0.5 * dot3(dg, dg);
+  s.a2 = a2; s.b2 = b2; s.c2 = c2; s.cb = cb; s.cg = cg; s.N0 = N0; s.N1 = N1; s.N2 = N2; s.D0 = D0; s.D1 = D1;
   // N^2 - 2 cg N D + D^2 M, ascending powers of v
-  const double A0 = N0 * N0 - 2.0 * cg * (N0 * D0) + D0 * D0 * M0;
-  const double A1 = 2.0 * N0 * N1 - 2.0 * cg * (N0 * D1 + N1 * D0) + (D0 * D0 * M1 + 2.0 * D0 * D1 * M0);
+  double A0 = N0 * N0 - 2.0 * cg * (N0 * D0) + D0 * D0 * M0;
+  double A1 = 2.0 * N0 * N1 - 2.0 * cg * (N0 * D1 + N1 * D0) + (D0 * D0 * M1 + 2.0 * D0 * D1 * M0);
   const double A2 = (N1 * N1 + 2.0 * N0 * N2) - 2.0 * cg * (N1 * D1 + N2 * D0) + (D0 * D0 * M2 + 2.0 * D0 * D1 * M1 + D1 * D1 * M0);
-  const double A3 = 2.0 * N1 * N2 - 2.0 * cg * (N2 * D1) + (2.0 * D0 * D1 * M2 + D1 * D1 * M1);
-  const double A4 = N2 * N2 + D1 * D1 * M2;
+  double A3 = 2.0 * N1 * N2 - 2.0 * cg * (N2 * D1) + (2.0 * D0 * D1 * M2 + D1 * D1 * M1);
+  double A4 = N2 * N2 + D1 * D1 * M2;
   const double scale = fabs(A0) + fabs(A1) + fabs(A2) + fabs(A3) + fabs(A4);
-  if (!(fabs(A4) > 1e-12 * scale) || !isfinite(scale)) return false;
+  s.rev = fabs(A0) > fabs(A4);                          // the quartic of 1 / v: the same coefficients in reverse
+  if (s.rev) { double x = A0; A0 = A4; A4 = x; x = A1; A1 = A3; A3 = x; }
+  if (!(fabs(A4) > ABS_LEAD_TOL * scale) || !isfinite(scale)) return false;
   const double B = A3 / A4, C = A2 / A4, D = A1 / A4, E = A0 / A4;
   // Ferrari: v = y - B / 4, y^4 + p y^2 + q y + r = 0; m = the largest real root of m^3 + p m^2 + (p^2 / 4 - r) m - q^2 / 8
   const double B2 = B * B;
@@ -115,24 +140,56 @@ __device__ __forceinline__ bool p3p_setup(const double* r1, const double* r2, co
   const double sq = sqrt(2.0 * m), tq = q / (2.0 * sq);
   if (!isfinite(tq)) return false;
   const double d1 = -2.0 * m - 2.0 * p - 4.0 * tq, d2 = -2.0 * m - 2.0 * p + 4.0 * tq, off = 0.25 * B;
-  if (d1 >= 0.0) {
-    const double sd = sqrt(d1);
+  const double low = -ABS_DISC_TOL * (2.0 * m + 2.0 * fabs(p) + 4.0 * fabs(tq));   // a double root's discriminant may round below zero
+  if (d1 >= low) {
+    const double sd = sqrt(fmax(d1, 0.0));
     s.v0 = abs_polish(0.5 * (sq + sd) - off, B, C, D, E); s.v1 = abs_polish(0.5 * (sq - sd) - off, B, C, D, E);
   }
-  if (d2 >= 0.0) {
-    const double sd = sqrt(d2);
+  if (d2 >= low) {
+    const double sd = sqrt(fmax(d2, 0.0));
     s.v2 = abs_polish(0.5 * (-sq + sd) - off, B, C, D, E); s.v3 = abs_polish(0.5 * (-sq - sd) - off, B, C, D, E);
   }
   return true;
 }
 
-// the pose (row-major R, t: camera = R world + t) of root v; false: no root, or a distance that is not positive
-__device__ __forceinline__ bool p3p_pose(const P3P& s, double v, double R[9], double t[3]) {
+__device__ __forceinline__ double p3p_root(const P3P& s, int root) { return root == 0 ? s.v0 : root == 1 ? s.v1 : root == 2 ? s.v2 : s.v3; }
+
+// the pose (row-major R, t: camera = R world + t) of root `root`; false: no root, or a distance that is not positive
+__device__ __forceinline__ bool p3p_pose(const P3P& s, int root, double R[9], double t[3]) {
+  double v = p3p_root(s, root);
   if (!(v > 0.0) || !isfinite(v)) return false;
-  const double u = (s.N0 + (s.N1 + s.N2 * v) * v) / (s.D0 + s.D1 * v);
+  int twin = -1;                                        // the first other root within ABS_PAIR_TOL of this one
+#pragma unroll
+  for (int j = 3; j >= 0; --j)
+    if (j != root && fabs(p3p_root(s, j) - v) <= ABS_PAIR_TOL * v) twin = j;
+  if (s.rev) v = 1.0 / v;
   const double g = 1.0 + v * (v - 2.0 * s.cb);
+  const double den = s.D0 + s.D1 * v;
+  double u;
+  if (twin < 0 || fabs(den) > ABS_SMALL_D * (fabs(s.D0) + fabs(s.D1 * v))) {
+    u = (s.N0 + (s.N1 + s.N2 * v) * v) / den;
+  } else {                                              // N / D tends to 0 / 0: both roots of the cosine law in u are solutions
+    const double h = sqrt(fmax(s.cg * s.cg - 1.0 + (s.c2 / s.b2) * g, 0.0));
+    u = root < twin ? s.cg + h : s.cg - h;
+  }
   if (!(u > 0.0) || !isfinite(u) || !(g > 0.0)) return false;
-  const double s1 = sqrt(s.b2 / g), s2 = u * s1, s3 = v * s1;
+  double s1 = sqrt(s.b2 / g), s2 = u * s1, s3 = v * s1;
+#pragma unroll
+  for (int it = 0; it < ABS_DISTANCE_NEWTON; ++it) {    // Newton on (s_i - s_j)^2 + 2 s_i s_j (1 - cos) = side^2, each 3 x 3 system by Cramer's rule
+    const double d23 = s2 - s3, d13 = s1 - s3, d12 = s1 - s2;
+    const double F1 = d23 * d23 + 2.0 * s2 * s3 * s.ha - s.a2;
+    const double F2 = d13 * d13 + 2.0 * s1 * s3 * s.hb - s.b2;
+    const double F3 = d12 * d12 + 2.0 * s1 * s2 * s.hg - s.c2;
+    const double j12 = 2.0 * (d23 + s3 * s.ha), j13 = 2.0 * (s2 * s.ha - d23);
+    const double j21 = 2.0 * (d13 + s3 * s.hb), j23 = 2.0 * (s1 * s.hb - d13);
+    const double j31 = 2.0 * (d12 + s2 * s.hg), j32 = 2.0 * (s1 * s.hg - d12);
+    const double det = j12 * j23 * j31 + j13 * j21 * j32;
+    const double d1 = (j12 * j23 * F3 + j13 * j32 * F2 - j23 * j32 * F1) / det;
+    const double d2 = (j23 * j31 * F1 + j13 * j21 * F3 - j13 * j31 * F2) / det;
+    const double d3 = (j12 * j31 * F2 + j21 * j32 * F1 - j12 * j21 * F3) / det;
+    if (det != 0.0 && isfinite(d1) && isfinite(d2) && isfinite(d3)) { s1 -= d1; s2 -= d2; s3 -= d3; }
+  }
+  if (!(s1 > 0.0 && s2 > 0.0 && s3 > 0.0)) return false;
   double Q1[3], g1[3], g2[3], cr[3], c1[3], c2[3], c3[3];
 #pragma unroll
   for (int m = 0; m < 3; ++m) { Q1[m] = s1 * s.f1[m]; g1[m] = s2 * s.f2[m] - Q1[m]; g2[m] = s3 * s.f3[m] - Q1[m]; }
@@ -152,8 +209,6 @@ __device__ __forceinline__ bool p3p_pose(const P3P& s, double v, double R[9], do
   }
   return ok;
 }
-
-__device__ __forceinline__ double p3p_root(const P3P& s, int root) { return root == 0 ? s.v0 : root == 1 ? s.v1 : root == 2 ? s.v2 : s.v3; }
 
 // ---- kernel A: records -----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(ABS_THREADS) void k_abs_bearings(int64_t n_corr, int32_t n_queries, const int64_t* __restrict__ offsets,
@@ -361,7 +416,7 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_hypotheses(const AbsArgs a)
         if (!p3p_setup(Q.rec(i[0]), Q.rec(i[1]), Q.rec(i[2]), p3)) continue;
         for (int root = 0; root < 4; ++root) {
           double R[9], t[3];
-          if (!p3p_pose(p3, p3p_root(p3, root), R, t)) continue;
+          if (!p3p_pose(p3, root, R, t)) continue;
           int cnt = 0;
           double sum = 0.0;
           for (int j = 0; j < n; ++j) {
@@ -416,7 +471,7 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_refine(const AbsArgs a) {
     P3P p3;
     double R[9];
     p3p_setup(Q.rec(i[0]), Q.rec(i[1]), Q.rec(i[2]), p3);
-    p3p_pose(p3, p3p_root(p3, best.root), R, t);
+    p3p_pose(p3, best.root, R, t);
     rotation_to_quat(R, q);
     for (int j = tid; j < n; j += ABS_THREADS) {
       const double* r = Q.rec(j);

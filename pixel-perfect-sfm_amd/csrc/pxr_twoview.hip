@@ -38,6 +38,8 @@ constexpr int TV_CHUNK = 7;                            // of which this many cro
 constexpr int TV_DEG = 10;                             // degree of the polynomial in z
 constexpr int TV_BISECT = 64;                          // bisection steps per root
 constexpr int TV_NEWTON = 4;                           // Newton steps per root, each kept only inside the bisection's last interval
+constexpr int TV_POLISH = 8;                           // at most this many Gauss-Newton steps per hypothesis on the ten cubic constraints over (x, y, z)
+constexpr double TV_POLISH_TOL = 1e-10;                // the last step: one of at most this size relative to max(1, |x|, |y|, |z|)
 constexpr double TV_PIVOT_TOL = 1e-12;                 // a pivot counts as zero below this fraction of the system's largest entry
 constexpr double TV_LEAD_TOL = 1e-9;                   // the leading coefficient counts as zero below this fraction of the largest one
 constexpr double TV_TRIM_TOL = 1e-12;                  // so does the leading coefficient of a rescaled Sturm remainder
@@ -320,9 +322,83 @@ __device__ inline double tv_root(const TvSolver& s, int k) {
   return z;
 }
 
+// the cofactor matrix of the row-major 3 x 3 matrix E: d det(E) / dE
+__device__ __forceinline__ void tv_cofactors(const double* E, double* c) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      c[3 * i + j] = E[3 * i1 + j1] * E[3 * i2 + j2] - E[3 * i1 + j2] * E[3 * i2 + j1];
+    }
+}
+
+// Up to TV_POLISH Gauss-Newton steps (until one is no larger than TV_POLISH_TOL: convergence is quadratic, what is left is
+// rounding; a root that the elimination misplaced by the matrix's own size needs six) on 2 E E^t E - tr(E E^t) E = 0, det E = 0 of E = x N0 + y N1 + z N2 + N3 over (x, y, z): the
+// constraints are evaluated on the 3 x 3 matrix itself, which is well conditioned where the elimination to det B(z) is not (the
+// elimination loses up to eleven digits on ordinary samples and whole roots at low parallax).  The 3 x 3
+// normal equations of a step by the adjugate; a step is skipped where their determinant vanishes or the step is not finite.
+__device__ inline void tv_polish(const TvSolver& s, double& x, double& y, double& z) {
+  for (int it = 0; it < TV_POLISH; ++it) {
+    double E[9], M[9], G[9], ME[9], cof[9], r[10], J[3][10];
+    for (int m = 0; m < 9; ++m) E[m] = ((x * s.basis[m][0] + y * s.basis[m][1]) + z * s.basis[m][2]) + s.basis[m][3];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        double m = 0.0, g = 0.0;
+        for (int k = 0; k < 3; ++k) { m += E[3 * i + k] * E[3 * j + k]; g += E[3 * k + i] * E[3 * k + j]; }
+        M[3 * i + j] = m; G[3 * i + j] = g;
+      }
+    const double tr = M[0] + M[4] + M[8];
+    tv_cofactors(E, cof);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        double v = 0.0;
+        for (int k = 0; k < 3; ++k) v += M[3 * i + k] * E[3 * k + j];
+        ME[3 * i + j] = v;
+        r[3 * i + j] = 2.0 * v - tr * E[3 * i + j];
+      }
+    r[9] = E[0] * cof[0] + E[1] * cof[1] + E[2] * cof[2];
+    for (int c = 0; c < 3; ++c) {                        // the derivative along N_c: D = basis[.][c]
+      double ED = 0.0, cD = 0.0, DtE[9];
+      for (int m = 0; m < 9; ++m) { ED += E[m] * s.basis[m][c]; cD += cof[m] * s.basis[m][c]; }
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+          double v = 0.0;
+          for (int k = 0; k < 3; ++k) v += s.basis[3 * k + i][c] * E[3 * k + j];
+          DtE[3 * i + j] = v;
+        }
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+          double dg = 0.0, ede = 0.0, md = 0.0;
+          for (int k = 0; k < 3; ++k) {
+            dg += s.basis[3 * i + k][c] * G[3 * k + j]; ede += E[3 * i + k] * DtE[3 * k + j]; md += M[3 * i + k] * s.basis[3 * k + j][c];
+          }
+          J[c][3 * i + j] = 2.0 * ((dg + ede) + md) - 2.0 * ED * E[3 * i + j] - tr * s.basis[3 * i + j][c];
+        }
+      J[c][9] = cD;
+    }
+    double A[9], g[3], adj[9];
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) {
+        double v = 0.0;
+        for (int m = 0; m < 10; ++m) v += J[a][m] * J[b][m];
+        A[3 * a + b] = v;
+      }
+      double v = 0.0;
+      for (int m = 0; m < 10; ++m) v += J[a][m] * r[m];
+      g[a] = v;
+    }
+    tv_cofactors(A, adj);                                // A is symmetric: its cofactor matrix is its adjugate
+    const double dA = A[0] * adj[0] + A[1] * adj[1] + A[2] * adj[2];
+    const double d0 = (adj[0] * g[0] + adj[1] * g[1] + adj[2] * g[2]) / dA, d1 = (adj[3] * g[0] + adj[4] * g[1] + adj[5] * g[2]) / dA,
+                 d2 = (adj[6] * g[0] + adj[7] * g[1] + adj[8] * g[2]) / dA;
+    if (!(dA != 0.0 && isfinite(d0) && isfinite(d1) && isfinite(d2))) break;      // (a skipped step would only repeat itself)
+    x -= d0; y -= d1; z -= d2;
+    if (fmax(fmax(fabs(d0), fabs(d1)), fabs(d2)) <= TV_POLISH_TOL * fmax(fmax(1.0, fabs(x)), fmax(fabs(y), fabs(z)))) break;
+  }
+}
+
 // E (row-major) of root z: (x, y, 1) spans the null space of B(z) -- the cross product of two of its rows, the pair with the
 // largest third component.  false: none, or a value that is not finite.
-__device__ inline bool tv_essential(const TvSolver& s, double z, double E[9]) {
+__device__ inline bool tv_essential(const TvSolver& s, double z, double E[9]) {   // (z: a copy, polished with x and y)
   double B[3][3];
   for (int r = 0; r < 3; ++r) {
     B[r][0] = ((s.bx[r][3] * z + s.bx[r][2]) * z + s.bx[r][1]) * z + s.bx[r][0];
@@ -338,8 +414,9 @@ __device__ inline bool tv_essential(const TvSolver& s, double z, double E[9]) {
       }
     }
   if (!(fabs(best[2]) > 0.0)) return false;
-  const double x = best[0] / best[2], y = best[1] / best[2];
+  double x = best[0] / best[2], y = best[1] / best[2];
   bool ok = isfinite(x) && isfinite(y);
+  if (ok) tv_polish(s, x, y, z);
   for (int m = 0; m < 9; ++m) {
     E[m] = ((x * s.basis[m][0] + y * s.basis[m][1]) + z * s.basis[m][2]) + s.basis[m][3];
     ok = ok && isfinite(E[m]);

@@ -3,8 +3,10 @@ specification (include/pixsfm_hip.h) and not from the kern
 
     samples   draw d of sample h = mix(mix(seed + G (h + 1)) + G (d + 1)) mod n (splitmix64's output function, 64-bit wrap-around),
               repeated indices drawn again, the three used in ascending order
-    P3P       Grunert: s_2 = u s_1, s_3 = v s_1, u = N(v) / D(v), quartic N^2 - 2 cos(gamma) N D + D^2 M = 0; Ferrari's real roots
-              in the order (+,+) (+,-) (-,+) (-,-), three Newton steps each; poses with positive distances only
+    P3P       Grunert: s_2 = u s_1, s_3 = v s_1, u = N(v) / D(v), quartic N^2 - 2 cos(gamma) N D + D^2 M = 0 (in 1 / v where its
+              constant coefficient outweighs the leading one); Ferrari's real roots in the order (+,+) (+,-) (-,+) (-,-), three
+              guarded Newton steps each; u from the cosine law for a close pair of roots where N / D tends to 0 / 0; three Newton
+              steps on the three cosine-law equations in the distances; poses with positive distances only
     score     err = |(u, v) - (X/Z, Y/Z)|^2, inlier iff Z > 0 and err <= (max_error / mean focal)^2;
               key (count, -sum min(err, thr^2), -h, -root)
     stop      after every round: samples done >= clamp(log(1 - confidence) / log(1 - w^3), min_num_trials, max_num_trials)
@@ -128,15 +130,54 @@ def mean_focal(model, k):
 
 # ---- P3P -------------------------------------------------------------------------------------------------------------------------
 def _polish(v, B, C, D, E):
+    """Three Newton steps on the monic quartic, each kept only where it does not raise |f| (at a double root f' vanishes with f and
+    an unguarded step can land anywhere)."""
+    f = (((v + B) * v + C) * v + D) * v + E
     for _ in range(3):
-        f, d = (((v + B) * v + C) * v + D) * v + E, ((4.0 * v + 3.0 * B) * v + 2.0 * C) * v + D
-        if d != 0.0:
-            v -= f / d
+        d = ((4.0 * v + 3.0 * B) * v + 2.0 * C) * v + D
+        if d == 0.0:
+            break
+        vn = v - f / d
+        fn = (((vn + B) * vn + C) * vn + D) * vn + E
+        if not abs(fn) <= abs(f):
+            break
+        v, f = vn, fn
     return v
 
 
-def p3p(uv, X):
-    """The poses [(root, R, t)] of three correspondences (uv (3, 2) normalised image points, X (3, 3))."""
+LEAD_TOL = 1e-12       # the quartic's leading coefficient counts as zero below this fraction of the sum of the coefficients' magnitudes
+PAIR_TOL = 1e-3        # two roots of the quartic are a close pair within this fraction of their size
+SMALL_D = 1e-3         # of a close pair, u is taken from the cosine law and not from N(v) / D(v) where |D(v)| is below this fraction of its terms
+DISC_TOL = 1e-7        # a quadratic factor's discriminant counts as zero down to minus this fraction of its terms
+DISTANCE_NEWTON = 3    # Newton steps on the three cosine-law equations in the distances (ABS_DISTANCE_NEWTON)
+
+
+def polish_distances(s, ha, hb, hg, a2, b2, c2):
+    """DISTANCE_NEWTON Newton steps on the three cosine-law equations (s2 - s3)^2 + 2 s2 s3 (1 - cos alpha) = a^2, (s1 - s3)^2 +
+    2 s1 s3 (1 - cos beta) = b^2, (s1 - s2)^2 + 2 s1 s2 (1 - cos gamma) = c^2 from s = (s1, s2, s3), with ha = 1 - cos alpha = |f2 -
+    f3|^2 / 2 and so on (a narrow field of view has cosines that round away what separates them from 1): the 3 x 3 system of
+    each step by Cramer's rule, a step skipped where the determinant vanishes or the step is not finite."""
+    s1, s2, s3 = s
+    for _ in range(DISTANCE_NEWTON):
+        d23, d13, d12 = s2 - s3, s1 - s3, s1 - s2
+        F1 = d23 * d23 + 2.0 * s2 * s3 * ha - a2
+        F2 = d13 * d13 + 2.0 * s1 * s3 * hb - b2
+        F3 = d12 * d12 + 2.0 * s1 * s2 * hg - c2
+        j12, j13 = 2.0 * (d23 + s3 * ha), 2.0 * (s2 * ha - d23)
+        j21, j23 = 2.0 * (d13 + s3 * hb), 2.0 * (s1 * hb - d13)
+        j31, j32 = 2.0 * (d12 + s2 * hg), 2.0 * (s1 * hg - d12)
+        det = j12 * j23 * j31 + j13 * j21 * j32
+        d1 = (j12 * j23 * F3 + j13 * j32 * F2 - j23 * j32 * F1) / det
+        d2 = (j23 * j31 * F1 + j13 * j21 * F3 - j13 * j31 * F2) / det
+        d3 = (j12 * j31 * F2 + j21 * j32 * F1 - j12 * j21 * F3) / det
+        if det != 0.0 and np.isfinite(d1) and np.isfinite(d2) and np.isfinite(d3):
+            s1, s2, s3 = s1 - d1, s2 - d2, s3 - d3
+    return s1, s2, s3
+
+
+def p3p(uv, X, details=None):
+    """The poses [(root, R, t)] of three correspondences (uv (3, 2) normalised image points, X (3, 3)).  details: a dict that
+    receives the quartic's ascending coefficients A."""
     with np.errstate(all="ignore"):
         f = np.concatenate([uv, np.ones((3, 1))], 1)
         f = f / np.sqrt(uv[:, :1] ** 2 + uv[:, 1:] ** 2 + 1.0)
@@ -149,13 +190,20 @@ def p3p(uv, X):
         w1, w3 = e1 / np.sqrt(c2), cr / np.sqrt(cr2)
         w2 = np.cross(w3, w1)
         ca, cb, cg = f[1] @ f[2], f[0] @ f[2], f[0] @ f[1]
+        da, db, dg = f[1] - f[2], f[0] - f[2], f[0] - f[1]
+        ha, hb, hg = 0.5 * (da @ da), 0.5 * (db @ db), 0.5 * (dg @ dg)
         k1, k2 = (a2 - c2) / b2, c2 / b2
         N = np.array([k1 + 1.0, -2.0 * k1 * cb, k1 - 1.0])
         D = np.array([2.0 * cg, -2.0 * ca])
         M = np.array([1.0 - k2, 2.0 * k2 * cb, -k2])
         A = np.convolve(N, N) - 2.0 * cg * np.append(np.convolve(N, D), 0.0) + np.convolve(np.convolve(D, D), M)
         scale = np.abs(A).sum()
-        if not (abs(A[4]) > 1e-12 * scale) or not np.isfinite(scale):
+        if details is not None:
+            details["A"] = A
+        rev = abs(A[0]) > abs(A[4])               # the quartic of w = 1 / v has the larger leading coefficient
+        if rev:
+            A = A[::-1]
+        if not (abs(A[4]) > LEAD_TOL * scale) or not np.isfinite(scale):
             return []
         B, C, Dq, E = A[3] / A[4], A[2] / A[4], A[1] / A[4], A[0] / A[4]
         p = C - 0.375 * B * B
@@ -180,23 +228,38 @@ def p3p(uv, X):
             return []
         d1, d2, off = -2.0 * m - 2.0 * p - 4.0 * tq, -2.0 * m - 2.0 * p + 4.0 * tq, 0.25 * B
         roots = [np.nan] * 4
-        if d1 >= 0.0:
-            roots[0], roots[1] = 0.5 * (sq + np.sqrt(d1)) - off, 0.5 * (sq - np.sqrt(d1)) - off
-        if d2 >= 0.0:
-            roots[2], roots[3] = 0.5 * (-sq + np.sqrt(d2)) - off, 0.5 * (-sq - np.sqrt(d2)) - off
+        low = -DISC_TOL * (2.0 * m + 2.0 * abs(p) + 4.0 * abs(tq))         # a double root's discriminant may round below zero
+        if d1 >= low:
+            sd = np.sqrt(max(d1, 0.0))
+            roots[0], roots[1] = 0.5 * (sq + sd) - off, 0.5 * (sq - sd) - off
+        if d2 >= low:
+            sd = np.sqrt(max(d2, 0.0))
+            roots[2], roots[3] = 0.5 * (-sq + sd) - off, 0.5 * (-sq - sd) - off
+        roots = [_polish(v, B, C, Dq, E) if np.isfinite(v) else np.nan for v in roots]
         out = []
         for root, v in enumerate(roots):
-            if not np.isfinite(v):
-                continue
-            v = _polish(v, B, C, Dq, E)
             if not (v > 0.0) or not np.isfinite(v):
                 continue
-            u = (N[0] + (N[1] + N[2] * v) * v) / (D[0] + D[1] * v)
+            twin = -1                             # the first other root within PAIR_TOL of this one
+            for j in range(3, -1, -1):
+                if j != root and abs(roots[j] - v) <= PAIR_TOL * v:
+                    twin = j
+            if rev:
+                v = 1.0 / v
             g = 1.0 + v * (v - 2.0 * cb)
+            den = D[0] + D[1] * v
+            if twin < 0 or abs(den) > SMALL_D * (abs(D[0]) + abs(D[1] * v)):
+                u = (N[0] + (N[1] + N[2] * v) * v) / den
+            else:     # a close pair where N / D tends to 0 / 0: both roots of the cosine law in u are solutions, one for each of the pair
+                h = np.sqrt(max(cg * cg - 1.0 + k2 * g, 0.0))
+                u = cg + h if root < twin else cg - h
             if not (u > 0.0) or not np.isfinite(u) or not (g > 0.0):
                 continue
             s1 = np.sqrt(b2 / g)
-            Q1, Q2, Q3 = s1 * f[0], u * s1 * f[1], v * s1 * f[2]
+            s1, s2, s3 = polish_distances((s1, u * s1, v * s1), ha, hb, hg, a2, b2, c2)
+            if not (s1 > 0.0 and s2 > 0.0 and s3 > 0.0):
+                continue
+            Q1, Q2, Q3 = s1 * f[0], s2 * f[1], s3 * f[2]
             g1, g2 = Q2 - Q1, Q3 - Q1
             crc = np.cross(g1, g2)
             n1, n3 = np.sqrt(g1 @ g1), np.sqrt(crc @ crc)
@@ -491,6 +554,98 @@ def eleven_models_queries():
                  query_camera=np.arange(len(models), dtype=np.int32), cam_model=np.array(models, np.int32),
                  cam_params=tc.pad_params([tc.MODEL_PARAMS[m] for m in models]))
     return batch, gq, gt
+
+
+# ---- hard families of minimal samples (tests/test_minimal_solvers_*.py) ---------------------------------------------------------
+def _from_camera_points(rng, P):
+    """A noise-free sample whose points sit at P (3, 3) in the camera's frame, under a random pose: (uv, X, R, t)."""
+    q, t = random_pose(rng)
+    R = synthetic.qvec_to_rotmat(q)
+    return P[:, :2] / P[:, 2:], (P - t) @ R, R, t
+
+
+def _points(rng, half_field=0.4, depth=(2.0, 20.0)):
+    return np.concatenate([rng.uniform(-half_field, half_field, (3, 2)), np.ones((3, 1))], 1) * rng.uniform(*depth, (3, 1))
+
+
+def _nearly_collinear(rng, off):
+    uv = rng.uniform(-0.4, 0.4, (3, 2))
+    d = uv[1] - uv[0]
+    uv[2] = uv[0] + rng.uniform(0.2, 0.8) * d + off * np.array([-d[1], d[0]]) / np.linalg.norm(d)
+    return np.concatenate([uv, np.ones((3, 1))], 1) * rng.uniform(2.0, 20.0, (3, 1))
+
+
+def _equilateral(rng, jitter):
+    """A triangle with equal sides in a plane facing the camera, its centre on the optical axis; every coordinate moved by up to jitter."""
+    r, d, th = rng.uniform(0.5, 2.0), rng.uniform(4.0, 10.0), rng.uniform(0, 2 * np.pi) + 2 * np.pi / 3 * np.arange(3)
+    return np.stack([r * np.cos(th), r * np.sin(th), np.full(3, d)], 1) + jitter * rng.uniform(-1, 1, (3, 3))
+
+
+def _two_equal_distances(rng):
+    f = np.concatenate([rng.uniform(-0.4, 0.4, (3, 2)), np.ones((3, 1))], 1)
+    f /= np.linalg.norm(f, axis=1, keepdims=True)
+    s = rng.uniform(2.0, 20.0)
+    return f * np.array([s, s, rng.uniform(2.0, 20.0)])[:, None]
+
+
+def _leading_ratio(P):
+    det = {}
+    p3p(P[:, :2] / P[:, 2:], P, det)
+    return det["A"][4] / np.abs(det["A"]).sum()
+
+
+def _small_leading_coefficient(rng, target):
+    """Points whose quartic has A4 = target x (sum of |A_k|), to a few per cent: A4 is 4 c^2 / b^2 (cos^2 of the triangle's angle at
+    point 1 - cos^2 alpha), so the first point slides along its ray until that angle meets the angle of view of the other two."""
+    while True:
+        P = _points(rng)
+        ray, grid = P[0] / P[0, 2], np.linspace(1.0, 40.0, 100)
+        val = np.array([_leading_ratio(np.vstack([ray * z, P[1:]])) for z in grid]) - target
+        k = np.flatnonzero(np.sign(val[:-1]) * np.sign(val[1:]) < 0)
+        if not len(k):
+            continue
+        lo, hi = grid[k[0]], grid[k[0] + 1]
+        for _ in range(60):
+            mid = 0.5 * (lo + hi)
+            same = np.sign(_leading_ratio(np.vstack([ray * mid, P[1:]])) - target) == np.sign(val[k[0]])
+            lo, hi = (mid, hi) if same else (lo, mid)
+        P = np.vstack([ray * lo, P[1:]])
+        if abs(_leading_ratio(P) / target - 1.0) < 0.1:
+            return P
+
+
+HARD_FAMILIES = {
+    "generic": _points,
+    "distant": lambda rng: _points(rng, depth=(1000.0, 1001.0)),
+    "narrow field": lambda rng: _points(rng, half_field=0.005),
+    "nearly collinear 1e-3": lambda rng: _nearly_collinear(rng, 1e-3),
+    "nearly collinear 1e-5": lambda rng: _nearly_collinear(rng, 1e-5),
+    "nearly collinear 1e-7": lambda rng: _nearly_collinear(rng, 1e-7),
+    "equilateral": lambda rng: _equilateral(rng, 0.0),
+    "equilateral 1e-3": lambda rng: _equilateral(rng, 1e-3),
+    "equilateral 1e-6": lambda rng: _equilateral(rng, 1e-6),
+    "equilateral 1e-9": lambda rng: _equilateral(rng, 1e-9),
+    "two equal distances": _two_equal_distances,
+    "A4 above LEAD_TOL": lambda rng: _small_leading_coefficient(rng, rng.choice([-1.0, 1.0]) * rng.uniform(1.5, 10.0) * LEAD_TOL),
+    "A4 below LEAD_TOL": lambda rng: _small_leading_coefficient(rng, rng.choice([-1.0, 1.0]) * rng.uniform(0.1, 0.7) * LEAD_TOL),
+}
+# (both A4 families are solved: where |A0| > |A4| the quartic of 1 / v is the one that LEAD_TOL applies to)
+
+
+def hard_family(name, seed, B=64):
+    """B noise-free samples of a family of HARD_FAMILIES: (uv (B, 3, 2), X (B, 3, 3), R (B, 3, 3), t (B, 3))."""
+    rng = np.random.default_rng(seed)
+    parts = [_from_camera_points(rng, HARD_FAMILIES[name](rng)) for _ in range(B)]
+    return tuple(np.array([p[k] for p in parts]) for k in range(4))
+
+
+def degenerate_samples(seed=0):
+    """(uv (3, 3, 2), X (3, 3, 3)): two coincident correspondences, three world points on one line, a coordinate that is not a number."""
+    uv, X, _, _ = hard_family("generic", seed, 3)
+    uv[0, 1], X[0, 1] = uv[0, 0], X[0, 0]
+    X[1, 2] = X[1, 0] + 0.75 * (X[1, 1] - X[1, 0])
+    X[2, 0, 1] = np.nan
+    return uv, X
 
 
 # ---- the batch the lane emulation and the GPU are both held to ------------------------------------------------------------------

@@ -466,6 +466,105 @@ def noise_free_samples(B, seed, focal_scale=(0.7, 1.0, 1.4)):
     return rec, Fs
 
 
+# ---- hard families of minimal samples (tests/test_minimal_solvers_*.py) ---------------------------------------------------------
+def _sample(rng, n=7, focal=1.0, half_field=0.4, depth=(2.0, 20.0), parallax=None):
+    """n noise-free matches of a random relative pose seen through a focal length stated `focal` times too long: (rec (n, 4), F (9,)).
+    parallax: the baseline as a fraction of the median depth (None: random_relative_pose's 1-3 units)."""
+    q, t = tv.random_relative_pose(rng)
+    R = synthetic.qvec_to_rotmat(q)
+    x1 = rng.uniform(-half_field, half_field, (n, 2))
+    d = rng.uniform(*depth, (n, 1))
+    if parallax is not None:
+        t = t / np.linalg.norm(t) * parallax * np.median(d)
+    X2 = (np.concatenate([x1, np.ones((n, 1))], 1) * d) @ R.T + t
+    K = np.diag([focal, focal, 1.0])
+    Fm = (K @ tv.essential_of_pose(R, t) @ K).reshape(9)
+    return np.concatenate([x1, X2[:, :2] / X2[:, 2:]], 1) / focal, signed(Fm / np.linalg.norm(Fm))
+
+
+def _slide(rng, crossing):
+    """A generic sample whose first match is slid along x2 to a sign change of crossing(rec (B, 7, 4)) -> (B,): (lo, hi, at) with
+    at(lo) and at(hi) the samples on either side, one rounding apart."""
+    while True:
+        rec, _ = _sample(rng)
+
+        def at(lam):
+            r = rec.copy()
+            r[0, 2] += lam
+            return r
+
+        grid = np.linspace(-0.2, 0.2, 81)
+        val = crossing(np.array([at(lam) for lam in grid]))
+        k = np.flatnonzero(np.sign(val[:-1]) * np.sign(val[1:]) < 0)
+        if not len(k):
+            continue
+        lo, hi = grid[k[0]], grid[k[0] + 1]
+        for _ in range(60):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if np.sign(crossing(at(mid)[None])[0]) == np.sign(val[k[0]]) else (lo, mid)
+        return lo, hi, at
+
+
+DOUBLE_ROOT_MARGIN = 1e-8
+
+
+def _double_root(rng):
+    """A sample DOUBLE_ROOT_MARGIN (in the slid coordinate) from where two of the cubic's three real roots merge, on the side that
+    has three: the pair is about 1e-4 apart, real beyond doubt and ill-conditioned, the third root is an ordinary one."""
+    count = lambda r: seven_point(r, details=True)[2]["n_roots"].astype(np.float64)
+    lo, hi, at = _slide(rng, lambda r: count(r) - 2.0)
+    lam = lo - DOUBLE_ROOT_MARGIN if count(at(lo)[None])[0] == 3 else hi + DOUBLE_ROOT_MARGIN
+    return at(lam), np.full(9, np.nan)
+
+
+def _small_leading_coefficient(rng, target):
+    """A sample whose scaled cubic has the leading coefficient `target` to a few per cent (one root of det(x A + B) runs off to infinity)."""
+    lead = lambda r: seven_point(r, details=True)[2]["c"][:, 3]
+    while True:
+        lo, _, at = _slide(rng, lambda r: lead(r) - target)
+        if abs(lead(at(lo)[None])[0] / target - 1.0) < 0.1:
+            return at(lo), np.full(9, np.nan)
+
+
+HARD_FAMILIES = {
+    "generic, focal x 0.7": lambda rng: _sample(rng, focal=0.7),
+    "generic, focal x 1": lambda rng: _sample(rng, focal=1.0),
+    "generic, focal x 1.4": lambda rng: _sample(rng, focal=1.4),
+    "parallax 1e-1": lambda rng: _sample(rng, parallax=1e-1),
+    "parallax 1e-2": lambda rng: _sample(rng, parallax=1e-2),
+    "parallax 1e-3": lambda rng: _sample(rng, parallax=1e-3),
+    "parallax 1e-4": lambda rng: _sample(rng, parallax=1e-4),
+    # depth spread 1e-3: kappa of F grows with 1 / spread, and at 1e-4 13 % of the solutions lie beyond the 1e-7 cap on C kappa u
+    "near-planar": lambda rng: _sample(rng, depth=(8.0 * (1.0 - 1e-3), 8.0 * (1.0 + 1e-3))),
+    "narrow field": lambda rng: _sample(rng, half_field=0.008),
+    "double root": _double_root,
+    "leading coefficient above LEAD_TOL": lambda rng: _small_leading_coefficient(rng, rng.choice([-1.0, 1.0]) * rng.uniform(1.5, 10.0) * LEAD_TOL),
+    "leading coefficient below LEAD_TOL": lambda rng: _small_leading_coefficient(rng, rng.choice([-1.0, 1.0]) * rng.uniform(0.1, 0.7) * LEAD_TOL),
+}
+# families that the solver's own rule declares degenerate: no hypothesis by specification, whatever the problem's conditioning
+REFUSED_FAMILIES = ("leading coefficient below LEAD_TOL",)
+
+
+def hard_family(name, seed, B=64):
+    """B samples of a family of HARD_FAMILIES: (rec (B, 7, 4), F (B, 9) the generating matrix, NaN where the family has none)."""
+    rng = np.random.default_rng(seed)
+    parts = [HARD_FAMILIES[name](rng) for _ in range(B)]
+    return np.array([p[0] for p in parts]), np.array([p[1] for p in parts])
+
+
+def degenerate_samples(seed=0):
+    """(rec (4, 7, 4)): a repeated match, seven copies of one match, a coordinate that is not a number, a pure rotation."""
+    rng = np.random.default_rng(seed)
+    rec = np.array([_sample(rng)[0] for _ in range(4)])
+    rec[0, 1] = rec[0, 0]
+    rec[1, :] = rec[1, 0]
+    rec[2, 0, 2] = np.nan
+    R = synthetic.qvec_to_rotmat(tv.random_relative_pose(rng)[0])
+    X2 = np.concatenate([rec[3, :, :2], np.ones((7, 1))], 1) @ R.T
+    rec[3, :, 2:] = X2[:, :2] / X2[:, 2:]
+    return rec
+
+
 def eleven_models_pairs():
     """tv.eleven_models_pairs: (batch, F (11, 9)) -- one noise-free pair of 40 matches per camera model, and its true F."""
     batch, gq, gt = tv.eleven_models_pairs()

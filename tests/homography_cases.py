@@ -438,6 +438,68 @@ def noise_free_samples(B, seed):
     return rec, Hs
 
 
+# ---- hard families of minimal samples (tests/test_minimal_solvers_*.py) ---------------------------------------------------------
+def _sample(rng, x1=None, half_field=0.4, baseline=None, affine=False):
+    """Four noise-free matches of a plane: (rec (4, 4), H (9,) unit norm, positive third component on the points).  baseline: the
+    length of the translation (None: random_relative_pose's); affine: no rotation out of the image plane, a plane facing the
+    camera and a translation within it, so that the last row of H is (0, 0, 1) up to 1e-6."""
+    q, t = tv.random_relative_pose(rng)
+    nrm = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), 1.0])
+    if affine:
+        ang = rng.uniform(0.02, 0.25)
+        q = np.array([np.cos(0.5 * ang), 1e-6 * rng.uniform(-1, 1), 1e-6 * rng.uniform(-1, 1), np.sin(0.5 * ang)])
+        q /= np.linalg.norm(q)
+        nrm, t = np.array([0.0, 0.0, 1.0]), t * np.array([1.0, 1.0, 1e-6])
+    if baseline is not None:
+        t = t / np.linalg.norm(t) * baseline
+    nrm = nrm / np.linalg.norm(nrm)
+    Hm = synthetic.qvec_to_rotmat(q) + np.outer(t, nrm) / (rng.uniform(5.0, 7.0) * nrm[2])
+    if x1 is None:
+        x1 = rng.uniform(-half_field, half_field, (4, 2))
+    p = np.concatenate([x1, np.ones((4, 1))], 1) @ Hm.T
+    return np.concatenate([x1, p[:, :2] / p[:, 2:]], 1), (Hm / np.linalg.norm(Hm)).reshape(9)
+
+
+def _sliver(rng, off):
+    """A quadrilateral whose fourth corner sits `off` from the side of the first two."""
+    x1 = rng.uniform(-0.4, 0.4, (4, 2))
+    d = x1[1] - x1[0]
+    x1[3] = x1[0] + rng.uniform(0.2, 0.8) * d + off * np.array([-d[1], d[0]]) / np.linalg.norm(d)
+    return x1
+
+
+# (No sliver at 1e-7: kappa of H is about 4 / off there, 4e7, which puts 63 of 64 samples beyond the 1e-7 cap on C kappa u; no draw of
+# such a quadrilateral keeps it under, so the family would pass with nothing judged.)
+HARD_FAMILIES = {
+    "generic": _sample,
+    "narrow field": lambda rng: _sample(rng, half_field=0.005),
+    "translation 1e-4": lambda rng: _sample(rng, baseline=1e-4),
+    "sliver 1e-3": lambda rng: _sample(rng, x1=_sliver(rng, 1e-3)),
+    "sliver 1e-5": lambda rng: _sample(rng, x1=_sliver(rng, 1e-5)),
+    "near-affine": lambda rng: _sample(rng, affine=True),
+}
+
+
+def hard_family(name, seed, B=64):
+    """B noise-free samples of a family of HARD_FAMILIES: (rec (B, 4, 4), H (B, 9))."""
+    rng = np.random.default_rng(seed)
+    parts = [HARD_FAMILIES[name](rng) for _ in range(B)]
+    return np.array([p[0] for p in parts]), np.array([p[1] for p in parts])
+
+
+def degenerate_samples(seed=0):
+    """(rec (4, 4, 4)): a repeated match, four points on one line, a coordinate that is not a number, three points on one line."""
+    rng = np.random.default_rng(seed)
+    rec = np.array([_sample(rng)[0] for _ in range(4)])
+    rec[0, 1] = rec[0, 0]
+    rec[1, :, 1] = rec[1, :, 0]
+    rec[1, :, 2:] = rec[1, :, :2]
+    rec[2, 0, 2] = np.nan
+    rec[3, 2, :2] = 0.5 * (rec[3, 0, :2] + rec[3, 1, :2])
+    rec[3, 2, 2:] = 0.5 * (rec[3, 0, 2:] + rec[3, 1, 2:])
+    return rec
+
+
 def eleven_models_pairs():
     """(batch, gt_H): one noise-free planar pair of 40 matches per camera model, its second camera the next model."""
     models = sorted(tc.MODEL_PARAMS)

@@ -47,3 +47,31 @@ int main(int argc, char** argv) {
   return 0;
 }
 #endif
+
+// the seven-point solver alone (tests/test_minimal_solvers_cpu.py): n samples of seven records (x1, y1, x2, y2) -> F of each real
+// root in ascending order, valid[3 s + k] = 0 where there is none
+extern "C" void emu_seven_point(int n, const double* rec, double* F, uint8_t* valid) {
+  for (int s = 0; s < n; ++s) {
+    const double* r[7];
+    for (int m = 0; m < 7; ++m) r[m] = rec + ((size_t)s * 7 + m) * 4;
+    pxr::FmSolver sol;
+    const bool ok = pxr::fm_solver_setup(r, sol);
+    for (int k = 0; k < 3; ++k)
+      valid[3 * s + k] = ok && k < sol.n_roots && pxr::fm_fundamental(sol, pxr::fm_root(sol, k), F + (size_t)(3 * s + k) * 9) ? 1 : 0;
+  }
+}
+
+// the root stage alone: the scaled cubic (4 ascending coefficients), its count of real roots and the roots as fm_root returns
+// them, n_roots[s] = -1 where the sample gives no cubic
+extern "C" void emu_seven_point_roots(int n, const double* rec, double* c, int32_t* n_roots, double* roots) {
+  for (int s = 0; s < n; ++s) {
+    const double* r[7];
+    for (int m = 0; m < 7; ++m) r[m] = rec + ((size_t)s * 7 + m) * 4;
+    pxr::FmSolver sol;
+    n_roots[s] = -1;
+    if (!pxr::fm_solver_setup(r, sol)) continue;
+    n_roots[s] = sol.n_roots;
+    for (int k = 0; k <= pxr::FM_DEG; ++k) c[(size_t)s * 4 + k] = sol.c[k];
+    for (int k = 0; k < sol.n_roots; ++k) roots[(size_t)s * 3 + k] = pxr::fm_root(sol, k);
+  }
+}

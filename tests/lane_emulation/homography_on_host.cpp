@@ -44,3 +44,13 @@ int main(int argc, char** argv) {
   return 0;
 }
 #endif
+
+// the four-point solver alone (tests/test_minimal_solvers_cpu.py): n samples of four records (x1, y1, x2, y2) -> H, valid[s] = 0
+// where there is none
+extern "C" void emu_four_point(int n, const double* rec, double* H, uint8_t* valid) {
+  for (int s = 0; s < n; ++s) {
+    const double* r[4];
+    for (int m = 0; m < 4; ++m) r[m] = rec + ((size_t)s * 4 + m) * 4;
+    valid[s] = pxr::hg_four_point(r, H + (size_t)s * 9) ? 1 : 0;
+  }
+}

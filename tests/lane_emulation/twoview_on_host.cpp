@@ -47,3 +47,31 @@ int main(int argc, char** argv) {
   return 0;
 }
 #endif
+
+// the five-point solver alone (tests/test_minimal_solvers_cpu.py): n samples of five records (x1, y1, x2, y2) -> E of each real
+// root in ascending order, valid[10 s + k] = 0 where there is none
+extern "C" void emu_five_point(int n, const double* rec, double* E, uint8_t* valid) {
+  for (int s = 0; s < n; ++s) {
+    const double* r[5];
+    for (int m = 0; m < 5; ++m) r[m] = rec + ((size_t)s * 5 + m) * 4;
+    pxr::TvSolver sol;
+    const bool ok = pxr::tv_solver_setup(r, sol);
+    for (int k = 0; k < 10; ++k)
+      valid[10 * s + k] = ok && k < sol.n_roots && pxr::tv_essential(sol, pxr::tv_root(sol, k), E + (size_t)(10 * s + k) * 9) ? 1 : 0;
+  }
+}
+
+// the root stage alone: the scaled polynomial det B(z) (11 ascending coefficients), its count of real roots and the roots as
+// tv_root returns them (before any polish), n_roots[s] = -1 where the sample gives no polynomial
+extern "C" void emu_five_point_roots(int n, const double* rec, double* c, int32_t* n_roots, double* roots) {
+  for (int s = 0; s < n; ++s) {
+    const double* r[5];
+    for (int m = 0; m < 5; ++m) r[m] = rec + ((size_t)s * 5 + m) * 4;
+    pxr::TvSolver sol;
+    n_roots[s] = -1;
+    if (!pxr::tv_solver_setup(r, sol)) continue;
+    n_roots[s] = sol.n_roots;
+    for (int k = 0; k <= pxr::TV_DEG; ++k) c[(size_t)s * 11 + k] = sol.c[k];
+    for (int k = 0; k < sol.n_roots; ++k) roots[(size_t)s * 10 + k] = pxr::tv_root(sol, k);
+  }
+}

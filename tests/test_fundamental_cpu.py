@@ -10,7 +10,9 @@ import fundamental_cases as fc
 def test_seven_point_solver_recovers_the_fundamental_matrix():
     """256 noise-free samples of seven matches, a third each through a focal length stated x 0.7, x 1 and x 1.4.  Measured: largest
     |det F| 6.3e-17, largest |x2^t F x1| on a sample's own seven points 2.4e-15, largest distance of the closest root from the true
-    F 4.6e-13; the bounds are 100 x these."""
+    F 4.6e-13; the bounds are 100 x these.  Against the mp reference of tests/test_minimal_solvers_cpu.py the same generator
+    gives err <= 14 kappa u with kappa (the norm of d F / d sample) up to 1e4: the 4.6e-13 is the problem's conditioning times
+    rounding, and the solver's own share is within a factor 10 of a Newton-polished solution's."""
     rec, Ft = fc.noise_free_samples(256, seed=1)
     F, valid, det = fc.seven_point(rec, details=True)
     assert det["ok"].all() and (det["n_roots"] >= 1).all() and set(det["n_roots"]) == {1, 3}

@@ -12,7 +12,9 @@ def test_four_point_solver_recovers_the_homography():
     """256 noise-free samples of four points of a plane, spread over 0.8 of the normalised plane.  The null vector of the 8 x 9
     system moves by about eps / (its smallest singular value / its largest); four random points leave that ratio above 1e-5
     unless three of them are collinear to 1e-5 of their spread, which 256 draws do not meet: 1e-9 holds with two decades to
-    spare, and the transfer error of the four points themselves is rounding."""
+    spare, and the transfer error of the four points themselves is rounding.  Measured against the mp reference
+    (tests/test_minimal_solvers_cpu.py, the same generator): err <= 0.53 kappa u with kappa (the norm of d H / d sample) up to
+    5e3, so the largest |H - H_true| of about 1e-13 here is conditioning times rounding and 1e-9 leaves four decades."""
     rec, Ht = hc.noise_free_samples(256, seed=1)
     H, ok = hc.four_point(rec)
     assert ok.all()

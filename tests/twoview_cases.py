@@ -4,7 +4,8 @@ specification (include/pixsfm_hip.h) and not from the kern
     samples   draw d of sample h = mix(mix(seed + G (h + 1)) + G (d + 1)) mod n (the hash of section 19), repeated indices drawn
               again, the five used in ascending order
     solver    Nister's five-point: null space by Gauss-Jordan (orthonormalised, mixed), the ten cubics as polynomial products, Gauss-Jordan, det B(z) of
-              degree 10, Sturm chain + bisection + Newton with + - x / only, E by back-substitution
+              degree 10, Sturm chain + bisection + Newton with + - x / only, E by back-substitution, then Gauss-Newton
+              steps to convergence (at most eight) over (x, y, z) on the ten cubic constraints of the 3 x 3 matrix itself
     score     squared Sampson error in the normalised plane, inlier iff err <= thr^2; key (count, -sum min(err, thr^2), -h, -root)
     stop      after every round: samples done >= clamp(log(1 - confidence) / log(1 - w^5), min_num_trials, max_num_trials)
     pose      Horn's closed form, the pose of four with the most inliers in front of both cameras
@@ -28,6 +29,8 @@ LDS_MATCHES = 1024     # PXR_TWOVIEW_LDS_MATCHES: the staged-in-LDS capacity S o
 IMAGE = ac.IMAGE
 PIVOT_TOL, LEAD_TOL, TRIM_TOL = 1e-12, 1e-9, 1e-12
 BISECT, NEWTON = 64, 4
+POLISH = 8             # at most this many Gauss-Newton steps on the ten cubic constraints over (x, y, z), per hypothesis (TV_POLISH)
+POLISH_TOL = 1e-10     # the last step: one of at most this size, relative to max(1, |x|, |y|, |z|) (quadratic convergence: what is left is rounding)
 
 # ---- samples and the stop rule: ac's, for samples of five --------------------------------------------------------------------------
 sample = functools.partial(ac.sample, k=5)
@@ -169,9 +172,54 @@ def sign_changes(chain, x):
     return changes
 
 
-def five_point(rec, details=False):
+def _cofactors(E):
+    """The cofactor matrix of E (.., 3, 3): d det(E) / dE."""
+    c = np.zeros_like(E)
+    for i in range(3):
+        for j in range(3):
+            i1, i2, j1, j2 = (i + 1) % 3, (i + 2) % 3, (j + 1) % 3, (j + 2) % 3
+            c[..., i, j] = E[..., i1, j1] * E[..., i2, j2] - E[..., i1, j2] * E[..., i2, j1]
+    return c
+
+
+def polish_essential(x, y, z, basis):
+    """Up to POLISH Gauss-Newton steps (until one is no larger than POLISH_TOL) on the ten cubic constraints 2 E E^t E - tr(E E^t) E = 0, det E = 0 of E = x N0 + y N1 + z N2 + N3
+    over (x, y, z) (.., each), basis (.., 9, 4): the constraints are evaluated on the 3 x 3 matrix itself, which is well
+    conditioned where the elimination to the polynomial in z is not.  The 3 x 3 normal equations of a step by the adjugate; a
+    step is skipped where their determinant vanishes or the step is not finite."""
+    b = basis.reshape(basis.shape[:-2] + (3, 3, 4))
+    T = lambda A: np.swapaxes(A, -1, -2)
+    live = np.ones(np.broadcast(x, y, z).shape, bool)
+    for _ in range(POLISH):
+        E = ((x[..., None, None] * b[..., 0] + y[..., None, None] * b[..., 1]) + z[..., None, None] * b[..., 2]) + b[..., 3]
+        M, G = E @ T(E), T(E) @ E
+        tr = (M[..., 0, 0] + M[..., 1, 1] + M[..., 2, 2])[..., None, None]
+        cof = _cofactors(E)
+        det = (E[..., 0, :] * cof[..., 0, :]).sum(-1)
+        r = np.concatenate([(2.0 * (M @ E) - tr * E).reshape(E.shape[:-2] + (9,)), det[..., None]], -1)
+        cols = []
+        for k in range(3):
+            D = np.broadcast_to(b[..., k], E.shape)
+            dC = 2.0 * ((D @ G + E @ T(D) @ E) + M @ D) - 2.0 * (E * D).sum((-1, -2))[..., None, None] * E - tr * D
+            cols.append(np.concatenate([dC.reshape(E.shape[:-2] + (9,)), (cof * D).sum((-1, -2))[..., None]], -1))
+        J = np.stack(cols, -1)
+        A, g = T(J) @ J, (T(J) @ r[..., None])[..., 0]
+        adj = T(_cofactors(A))
+        dA = (A[..., 0, :] * T(adj)[..., 0, :]).sum(-1)
+        d = (adj @ g[..., None])[..., 0] / dA[..., None]
+        ok = live & (dA != 0.0) & np.isfinite(d).all(-1)
+        x, y, z = np.where(ok, x - d[..., 0], x), np.where(ok, y - d[..., 1], y), np.where(ok, z - d[..., 2], z)
+        size = np.maximum(np.maximum(np.abs(d[..., 0]), np.abs(d[..., 1])), np.abs(d[..., 2]))
+        scale = np.maximum(np.maximum(1.0, np.abs(x)), np.maximum(np.abs(y), np.abs(z)))
+        live = ok & ~(size <= POLISH_TOL * scale)                 # (a skipped step would only repeat itself)
+    return x, y, z
+
+
+def five_point(rec, details=False, exact=None):
     """rec (B, 5, 4): the records (u1, v1, u2, v2) of B samples.  Returns (E (B, 10, 9), valid (B, 10)): the essential matrix of
-    every real root, roots ascending.  details: also a dict with c (B, 11), roots (B, 10), n_roots (B,), ok (B,)."""
+    every real root, roots ascending.  details: also a dict with c (B, 11) (zero where a sample is refused; c_scaled: not), roots (B, 10), n_roots (B,), ok (B,).  exact: a dict
+    that replaces a stage's result by one computed elsewhere (tools/five_point_stages.py locates a loss of accuracy with
+    it): basis (B, 9, 4), rows (B, 10, 20) the constraints before elimination, c (B, 11) the polynomial before scaling."""
     rec = np.asarray(rec, dtype=np.float64)
     B = len(rec)
     with np.errstate(all="ignore"):
@@ -185,6 +233,8 @@ def five_point(rec, details=False):
         basis[:, :, 1] = 0.5 * (((u[:, 0] - u[:, 1]) + u[:, 2]) - u[:, 3])
         basis[:, :, 2] = 0.5 * (((u[:, 0] + u[:, 1]) - u[:, 2]) - u[:, 3])
         basis[:, :, 3] = 0.5 * (((u[:, 0] - u[:, 1]) - u[:, 2]) + u[:, 3])
+        if exact and "basis" in exact:
+            basis = np.array(exact["basis"], dtype=np.float64)
         # the ten cubic constraints
         M = np.zeros((B, 10, 20))
         EEt = {}
@@ -206,6 +256,8 @@ def five_point(rec, details=False):
             mul11(basis[:, 3 + b], basis[:, 6 + c], pos)
             mul11(basis[:, 3 + c], basis[:, 6 + b], neg)
             mul21(pos - neg, basis[:, a], M[:, 9])
+        if exact and "rows" in exact:
+            M = np.array(exact["rows"], dtype=np.float64)
         ok &= gauss_jordan(M)
         bx, by, bw = np.zeros((B, 3, 4)), np.zeros((B, 3, 4)), np.zeros((B, 3, 5))
         for r in range(3):
@@ -227,6 +279,8 @@ def five_point(rec, details=False):
         for i in range(5):
             for j in range(7):
                 c[:, i + j] += bw[:, 0, i] * m2[:, j]
+        if exact and "c" in exact:
+            c = np.array(exact["c"], dtype=np.float64)
         big = np.abs(c).max(1)
         ok &= (big > 0.0) & np.isfinite(big)
         c = c / big[:, None]
@@ -237,6 +291,7 @@ def five_point(rec, details=False):
             chain[s], good = sturm_chain([float(v) for v in c[s]])
             ok[s] &= good
         bound = np.where(ok, bound, 1.0)
+        c_scaled = c
         c = np.where(ok[:, None], c, 0.0)
         v_low = sign_changes(chain, -bound[:, None])[:, 0]
         n_roots = np.clip(v_low - sign_changes(chain, bound[:, None])[:, 0], 0, 10)
@@ -270,10 +325,14 @@ def five_point(rec, details=False):
             best = np.where((np.abs(w) > np.abs(best[:, :, 2]))[:, :, None], cr, best)
         valid &= np.abs(best[:, :, 2]) > 0.0
         x, y = best[:, :, 0] / best[:, :, 2], best[:, :, 1] / best[:, :, 2]
+        start = valid & np.isfinite(x) & np.isfinite(y)
+        x, y, zp = polish_essential(np.where(start, x, 0.0), np.where(start, y, 0.0), np.where(start, z, 0.0), basis[:, None])
+        z_poly = z
+        x, y, z = np.where(start, x, np.nan), np.where(start, y, np.nan), np.where(start, zp, z)
         E = ((x[:, :, None] * basis[:, None, :, 0] + y[:, :, None] * basis[:, None, :, 1]) + z[:, :, None] * basis[:, None, :, 2]) + basis[:, None, :, 3]
         valid &= np.isfinite(x) & np.isfinite(y) & np.isfinite(E).all(2)
     if details:
-        return E, valid, dict(c=c, roots=z, n_roots=n_roots, ok=ok)
+        return E, valid, dict(c=c, c_scaled=c_scaled, roots=z_poly, n_roots=n_roots, ok=ok)           # (the polynomial's roots, before the polish)
     return E, valid
 
 
@@ -650,6 +709,130 @@ def noise_free_samples(B, seed):
         rec[b] = np.concatenate([x1, X2[:, :2] / X2[:, 2:]], 1)
         Rs[b], ts[b] = R, t / np.linalg.norm(t)
     return rec, Rs, ts
+
+
+# ---- hard families of minimal samples (tests/test_minimal_solvers_*.py) ---------------------------------------------------------
+def unit_essential(R, t):
+    """[t]x R as 9 numbers of unit norm, its entry of largest magnitude positive (fundamental_cases.signed)."""
+    E = essential_of_pose(R, t).reshape(9)
+    E = E / np.linalg.norm(E)
+    return -E if E[int(np.argmax(np.abs(E)))] < 0.0 else E
+
+
+def _sample(rng, n=5, half_field=0.4, depth=(2.0, 20.0), parallax=None, planar=False, motion=None, angle=None):
+    """n noise-free matches of a relative pose in the normalised planes: (rec (n, 4), E (9,)).  parallax: the baseline as a
+    fraction of the median depth (None: random_relative_pose's 1-3 units); planar: the points on one random plane; motion:
+    "forward" (the baseline along the optical axis) or "sideways" (along x, no rotation); angle: the rotation angle in radians."""
+    q, t = random_relative_pose(rng)
+    if angle is not None:
+        axis = q[1:] / np.linalg.norm(q[1:])
+        q = np.concatenate([[np.cos(0.5 * angle)], np.sin(0.5 * angle) * axis])
+    if motion == "forward":
+        t = np.array([0.0, 0.0, np.linalg.norm(t)])
+    if motion == "sideways":
+        q, t = np.array([1.0, 0.0, 0.0, 0.0]), np.array([np.linalg.norm(t), 0.0, 0.0])
+    R = synthetic.qvec_to_rotmat(q)
+    x1 = np.concatenate([rng.uniform(-half_field, half_field, (n, 2)), np.ones((n, 1))], 1)
+    d = rng.uniform(*depth, (n, 1))
+    if planar:
+        nrm = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), 1.0])
+        d = rng.uniform(*depth) / (x1 @ nrm)[:, None]
+    if parallax is not None:
+        t = t / np.linalg.norm(t) * parallax * np.median(d)
+    X2 = (x1 * d) @ R.T + t
+    return np.concatenate([x1[:, :2], X2[:, :2] / X2[:, 2:]], 1), unit_essential(R, t)
+
+
+def _slide(rng, value, level):
+    """A generic sample whose first match is slid along x2 to where value(rec (B, 5, 4)) -> (B,) crosses `level` (a number, or a
+    function of the values on the grid that first brackets the crossing): (lo, hi, at) with at(lo) and at(hi) the samples on
+    either side, one rounding apart."""
+    while True:
+        rec, _ = _sample(rng)
+
+        def at(lam):
+            r = rec.copy()
+            r[0, 2] += lam
+            return r
+
+        grid = np.linspace(-0.2, 0.2, 81)
+        val = value(np.array([at(lam) for lam in grid]))
+        lev = level(val) if callable(level) else level
+        k = np.flatnonzero(np.sign(val[:-1] - lev) * np.sign(val[1:] - lev) < 0)
+        if not len(k):
+            continue
+        lo, hi = grid[k[0]], grid[k[0] + 1]
+        for _ in range(60):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if np.sign(value(at(mid)[None])[0] - lev) == np.sign(val[k[0]] - lev) else (lo, mid)
+        return lo, hi, at
+
+
+DOUBLE_ROOT_MARGIN = 1e-8
+
+
+def _double_root(rng):
+    """A sample DOUBLE_ROOT_MARGIN (in the slid coordinate) from where two real roots of the polynomial merge, on the side that
+    has them: the pair is about 1e-4 apart, real beyond doubt and ill-conditioned, the other roots are ordinary ones."""
+    count = lambda r: five_point(r, details=True)[2]["n_roots"].astype(np.float64)
+    lo, hi, at = _slide(rng, count, lambda val: val.min() + 1.0)        # (a sample has 0, 2, .. 10 real roots)
+    lam = lo - DOUBLE_ROOT_MARGIN if count(at(lo)[None])[0] > count(at(hi)[None])[0] else hi + DOUBLE_ROOT_MARGIN
+    return at(lam), np.full(9, np.nan)
+
+
+def _small_leading_coefficient(rng, target):
+    """A sample whose scaled polynomial has the leading coefficient `target` to a few per cent (one root in z runs off to infinity)."""
+    lead = lambda r: five_point(r, details=True)[2]["c_scaled"][:, 10]
+    while True:
+        lo, _, at = _slide(rng, lead, target)
+        if abs(lead(at(lo)[None])[0] / target - 1.0) < 0.1:
+            return at(lo), np.full(9, np.nan)
+
+
+HARD_FAMILIES = {
+    "generic": _sample,
+    "parallax 1e-1": lambda rng: _sample(rng, parallax=1e-1),
+    "parallax 1e-2": lambda rng: _sample(rng, parallax=1e-2),
+    "parallax 1e-3": lambda rng: _sample(rng, parallax=1e-3),
+    "parallax 1e-4": lambda rng: _sample(rng, parallax=1e-4),
+    "planar scene": lambda rng: _sample(rng, planar=True),
+    "forward motion": lambda rng: _sample(rng, motion="forward"),
+    "sideways, no rotation": lambda rng: _sample(rng, motion="sideways"),
+    "rotation 1e-4": lambda rng: _sample(rng, angle=1e-4),
+    "wide field": lambda rng: _sample(rng, half_field=2.0),
+    "narrow field": lambda rng: _sample(rng, half_field=0.01),
+    "double root": _double_root,
+    "leading coefficient above LEAD_TOL": lambda rng: _small_leading_coefficient(rng, rng.choice([-1.0, 1.0]) * rng.uniform(1.5, 10.0) * LEAD_TOL),
+    "leading coefficient below LEAD_TOL": lambda rng: _small_leading_coefficient(rng, rng.choice([-1.0, 1.0]) * rng.uniform(0.1, 0.7) * LEAD_TOL),
+}
+PARALLAX_FAMILIES = {"parallax 1e-1": 1e-1, "parallax 1e-2": 1e-2, "parallax 1e-3": 1e-3, "parallax 1e-4": 1e-4}
+# The smallest tested parallax (baseline / median depth) at and above which every well-conditioned solution of every sample is
+# returned within the bound of tests/test_minimal_solvers_cpu.py.  Measured there (64 samples per decade, after the Gauss-Newton
+# polish): at 1e-1 all 322 solutions are met; at 1e-2 the elimination to det B(z) loses 4 of 328, at 1e-3 64 of 328, at 1e-4
+# 174 of 318 -- whole roots, which no polish of the roots that are found returns.
+FIVE_POINT_MIN_PARALLAX = 1e-1
+# families that the solver's own rule declares degenerate: no hypothesis by specification, whatever the problem's conditioning
+REFUSED_FAMILIES = ("leading coefficient below LEAD_TOL",)
+
+
+def hard_family(name, seed, B=64):
+    """B samples of a family of HARD_FAMILIES: (rec (B, 5, 4), E (B, 9) the generating matrix, NaN where the family has none)."""
+    rng = np.random.default_rng(seed)
+    parts = [HARD_FAMILIES[name](rng) for _ in range(B)]
+    return np.array([p[0] for p in parts]), np.array([p[1] for p in parts])
+
+
+def degenerate_samples(seed=0):
+    """(rec (4, 5, 4)): a repeated match, five copies of one match, a coordinate that is not a number, a pure rotation."""
+    rng = np.random.default_rng(seed)
+    rec = np.array([_sample(rng)[0] for _ in range(4)])
+    rec[0, 1] = rec[0, 0]
+    rec[1, :] = rec[1, 0]
+    rec[2, 0, 2] = np.nan
+    R = synthetic.qvec_to_rotmat(random_relative_pose(rng)[0])
+    X2 = np.concatenate([rec[3, :, :2], np.ones((5, 1))], 1) @ R.T
+    rec[3, :, 2:] = X2[:, :2] / X2[:, 2:]
+    return rec
 
 
 def eleven_models_pairs():
