@@ -1107,6 +1107,88 @@ int pxr_mapper_visibility_timed(pxr_ctx* ctx, const pxr_tri_view* view, const in
                                 int64_t* d_corr_obs, double* d_corr_xy, double* d_corr_xyz, int64_t* h_n_corr,
                                 double* h_kernel_ms);
 
+/* ---- batched map localization: covisibility, clusters, 2D-3D pairs (a map and retrieved images in, pxr_absolute_pose's input out) ----
+ * The glue of the reference's second entry point, pixsfm/localize.py:main, which takes it from hloc: pairs_from_covisibility (as
+ * pixsfm/eval/eth3d/utils.py:73 calls it), localize_sfm.do_covisibility_clustering and the gathering of
+ * localize_sfm.pose_from_cluster -- as remembered, parity unpinned; the definitions below are the
+ * specification.  All arrays are device pointers unless named h_.  Every output is an integer or a copied double: two calls give
+ * the same bits.  PXR_EINVAL always means: nothing was launched on the outputs, which stay untouched.  Every entry point
+ * synchronises the context's stream (offsets are validated on host copies, index ranges by a kernel whose flag is read back). */
+#define PXR_MAX_COVIS_IMAGES 8192 /* the count matrix is dense: 256 MB of int32 at this limit */
+#define PXR_MAX_COVIS_MATCHED 256 /* partners per image */
+#define PXR_MAX_LOC_ENTRIES 64    /* retrieved images of a query, entries of a problem: one wavefront, one 64-bit mask */
+
+/* Covisibility counts of a map whose tracks are given as in pxr_tri_view (d_track_offsets [n_tracks + 1], d_obs_image [n_obs]);
+ * d_track_mask [n_tracks] uint8 or NULL (= all tracks).
+ *   d_count [n_images][n_images] int32, zeroed by the call: for every track whose mask is non-zero and every ORDERED pair (a, b)
+ *   of its observations with image(a) != image(b), count[image(a)][image(b)] += 1.  The diagonal stays 0 and the matrix is
+ *   symmetric.  This is hloc's count -- for every keypoint of image i that has a point, every element of that point's track in
+ *   another image j adds one -- so an image that sees a track twice counts twice.
+ *   d_topk_index, d_topk_count [n_images][num_matched] int32, d_n_topk [n_images] int32: row i holds the n = min(num_matched,
+ *   number of j with count[i][j] > 0) images of largest count in the order (count descending, image index ascending) -- hloc
+ *   leaves ties to argpartition, here they are defined -- with their counts; d_n_topk[i] = n; the entries from n on are -1
+ *   (index) and 0 (count).  All three may be NULL: then only the counts are written and num_matched is ignored.
+ * Limits: n_images <= PXR_MAX_COVIS_IMAGES, 1 <= num_matched <= PXR_MAX_COVIS_MATCHED, n_obs < 2^31.  A count is an int32 sum
+ * that is not checked: an entry wraps around once two images share 2^31 ordered pairs, which takes e.g. one track that both
+ * see 46341 times each -- far from any map, but tracks that long are the caller's to keep out (d_track_mask).
+ * PXR_EINVAL: a limit exceeded; offsets not starting at 0, not monotone or not ending at n_obs; an image index out of range. */
+int pxr_covisibility(pxr_ctx* ctx, int32_t n_images, int64_t n_tracks, const int64_t* d_track_offsets, int64_t n_obs,
+                     const int32_t* d_obs_image, const uint8_t* d_track_mask, int32_t num_matched, int32_t* d_count,
+                     int32_t* d_topk_index, int32_t* d_topk_count, int32_t* d_n_topk);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[3] = validation, count, top-k. */
+int pxr_covisibility_timed(pxr_ctx* ctx, int32_t n_images, int64_t n_tracks, const int64_t* d_track_offsets, int64_t n_obs,
+                           const int32_t* d_obs_image, const uint8_t* d_track_mask, int32_t num_matched, int32_t* d_count,
+                           int32_t* d_topk_index, int32_t* d_topk_count, int32_t* d_n_topk, double* h_kernel_ms);
+
+/* Covisibility clusters of the retrieved images of a batch of queries.  d_count as pxr_covisibility writes it (symmetric; row
+ * i of the entry's own image is what is read); query q owns the entries [d_ret_offsets[q], d_ret_offsets[q+1]) of d_ret [n_ret],
+ * int32 map image indices in retrieval rank order (an image may appear twice).
+ *   Two entries of one query are CONNECTED iff they name the same image or count[i][j] > 0; the clusters are the connected
+ *   components of that relation restricted to the query's list -- hloc's breadth-first search, which only walks through frames
+ *   of the list.  They are numbered by (size descending, rank of their first member ascending), size counting list entries:
+ *   hloc's stable sorted(clusters, key=len, reverse=True) over discovery order.
+ *   d_cluster [n_ret] int32 = the cluster number of every entry; d_n_clusters [n_queries] int32 (0 for a query without entries).
+ * PXR_EINVAL: more than PXR_MAX_LOC_ENTRIES entries in a query; offsets not starting at 0, not monotone or not ending at n_ret;
+ * an image index out of range; n_images > PXR_MAX_COVIS_IMAGES. */
+int pxr_covisibility_clusters(pxr_ctx* ctx, int32_t n_images, const int32_t* d_count, int32_t n_queries, const int64_t* d_ret_offsets,
+                              int64_t n_ret, const int32_t* d_ret, int32_t* d_cluster, int32_t* d_n_clusters);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[2] = validation, clusters. */
+int pxr_covisibility_clusters_timed(pxr_ctx* ctx, int32_t n_images, const int32_t* d_count, int32_t n_queries,
+                                    const int64_t* d_ret_offsets, int64_t n_ret, const int32_t* d_ret, int32_t* d_cluster,
+                                    int32_t* d_n_clusters, double* h_kernel_ms);
+
+/* The 2D-3D pairs of a batch of localization problems, out of the matcher's device output: the device form of the gathering of
+ * pose_from_cluster.  A PROBLEM is one (query, cluster), or one query with its whole list; problem p owns the entries
+ * [d_problem_offsets[p], d_problem_offsets[p+1]) of d_problem_pair [n_entries], int32 indices into the matcher's pair list in
+ * visiting (retrieval rank) order.
+ *   from pxr_match_descriptors: n_pairs, d_pairs [n_pairs][2] (first image = the query, second = the database image, indices
+ *   into the descriptor set), d_pair_offsets [n_pairs + 1], d_matches0 [n_rows] (per query keypoint the database keypoint or
+ *   a negative value), n_set_images, d_image_offsets [n_set_images + 1] ending at n_total
+ *   per keypoint of the set: d_kp_xy [n_total][2]; d_kp_point [n_total] int64, the row of d_xyz [n_points][3] (negative: no point)
+ * Per problem and per query keypoint k, ascending, the entries j are visited in order: m = matches0[pair_offsets[pair_j] + k],
+ * and for m >= 0, pid = kp_point[image_offsets[db_j] + m].  The pair (k, pid) is emitted iff pid >= 0, xyz[pid] and the keypoint
+ * kp_xy[image_offsets[query] + k] are finite, and no earlier entry j' < j of the problem gave the same pid for k: within a
+ * keypoint the order is first appearance.
+ * Outputs: d_corr_offsets [n_problems + 1] int64; per emitted pair d_corr_kp int32 (k), d_corr_point int64 (pid), d_corr_xy
+ * (the keypoint), d_corr_xyz (the point), each with room for the sum over the entries of their pair's rows; *h_n_corr their
+ * number.  (n_problems, d_corr_offsets, *h_n_corr, d_corr_xy, d_corr_xyz) is an argument set of pxr_absolute_pose.
+ * PXR_EINVAL: any offsets array not starting at 0, not monotone or not ending at its total; a pair, image, keypoint (a match
+ * beyond the database image's keypoints) or point index out of range; entries of one problem that do not share their first
+ * image; more than PXR_MAX_LOC_ENTRIES entries in a problem; a pair whose rows differ from its first image's keypoint count. */
+int pxr_localization_pairs(pxr_ctx* ctx, int32_t n_problems, const int64_t* d_problem_offsets, int64_t n_entries,
+                           const int32_t* d_problem_pair, int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets,
+                           int64_t n_rows, const int32_t* d_matches0, int32_t n_set_images, const int64_t* d_image_offsets,
+                           int64_t n_total, const double* d_kp_xy, const int64_t* d_kp_point, int64_t n_points, const double* d_xyz,
+                           int64_t* d_corr_offsets, int32_t* d_corr_kp, int64_t* d_corr_point, double* d_corr_xy, double* d_corr_xyz,
+                           int64_t* h_n_corr);
+/* The same, and the HIP-event times of its kernels in milliseconds: h_kernel_ms[3] = count (with the index checks), scan, write. */
+int pxr_localization_pairs_timed(pxr_ctx* ctx, int32_t n_problems, const int64_t* d_problem_offsets, int64_t n_entries,
+                                 const int32_t* d_problem_pair, int32_t n_pairs, const int32_t* d_pairs, const int64_t* d_pair_offsets,
+                                 int64_t n_rows, const int32_t* d_matches0, int32_t n_set_images, const int64_t* d_image_offsets,
+                                 int64_t n_total, const double* d_kp_xy, const int64_t* d_kp_point, int64_t n_points,
+                                 const double* d_xyz, int64_t* d_corr_offsets, int32_t* d_corr_kp, int64_t* d_corr_point,
+                                 double* d_corr_xy, double* d_corr_xyz, int64_t* h_n_corr, double* h_kernel_ms);
+
 /* ---- BA reference extraction -----------------------------------------------------------
  * Replaces ReferenceExtractor::Run (bundle_adjustment/src/reference_extractor.h:125-318) +
  * RobustMeanIRLS (base/src/irls_optim.h:24-71) for N_NODES = 1: per point, descriptors of all

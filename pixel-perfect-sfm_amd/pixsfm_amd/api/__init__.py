@@ -32,6 +32,8 @@ from .sift import SiftExtractor  # noqa: F401,E402
 from . import retrieval  # noqa: F401,E402
 from .retrieval import (GlobalDescriptorExtractor, pairs_from_exhaustive, pairs_from_retrieval,  # noqa: F401,E402
                         unique_pairs)
+from . import map_localization  # noqa: F401,E402
+from .map_localization import MapLocalizer, covisibility_clustering, pairs_from_covisibility  # noqa: F401,E402
 from . import covariance  # noqa: F401,E402
 from .covariance import BACovariance, estimate_ba_covariance  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402

@@ -1439,6 +1439,126 @@ class MapperScene:
         return out
 
 
+# ---- batched map localization ----------------------------------------------------------------------------------------------------
+def _on_device(ctx, array, dtype, shape):
+    """`array` as a DeviceArray of `dtype` and `shape` (-1: any): a DeviceArray is used in place, a host array is uploaded."""
+    if not isinstance(array, DeviceArray):
+        array = ctx.to_device(np.ascontiguousarray(array, dtype=dtype).reshape(shape), dtype)
+    if array.dtype != np.dtype(dtype) or len(array.shape) != len(shape) or any(s >= 0 and s != t for s, t in zip(shape, array.shape)):
+        raise ValueError("expected a %s array of shape %s, not %s %s" % (np.dtype(dtype), shape, array.dtype, array.shape))
+    return array
+
+
+class CovisibilityGraph:
+    """The covisibility counts of a map on the device (pxr_covisibility): count[i][j] = over the tracks, the ordered pairs of
+    observations in images i != j -- hloc's count, symmetric, diagonal 0.
+
+    track_offsets (n_tracks + 1), obs_image (n_obs): the tracks as TriangulationProblem takes them; track_mask (n_tracks) or None:
+    the tracks that count.  At most _lib.MAX_COVIS_IMAGES images (the matrix is dense).
+    timed keeps the kernels' HIP-event times in self.kernel_ms {"check", "count", "topk"} (milliseconds)."""
+
+    def __init__(self, ctx, track_offsets, obs_image, n_images, track_mask=None, timed=False):
+        self.ctx = ctx
+        offsets = _csr_offsets(track_offsets, "track_offsets", "n_tracks")
+        self.n_tracks, self.n_images = len(offsets) - 1, int(n_images)
+        obs_image = np.ascontiguousarray(np.asarray(obs_image).reshape(-1), dtype=np.int32)
+        self.n_obs = len(obs_image)
+        self.d_track_offsets, self.d_obs_image = ctx.to_device(offsets, np.int64), ctx.to_device(obs_image, np.int32)
+        self.d_track_mask = None
+        if track_mask is not None:
+            mask = np.ascontiguousarray(track_mask, dtype=np.uint8).reshape(-1)
+            if len(mask) != self.n_tracks:
+                raise ValueError("track_mask must hold one entry per track")
+            self.d_track_mask = ctx.to_device(mask, np.uint8)
+        if self.n_images > _lib.MAX_COVIS_IMAGES:
+            raise ValueError("%d map images, more than %d: the covisibility matrix is dense" % (self.n_images, _lib.MAX_COVIS_IMAGES))
+        self.d_count = ctx.empty((self.n_images, self.n_images), np.int32)
+        self.kernel_ms = None
+        self._run(1, None, None, None, timed)
+
+    def _run(self, num_matched, d_index, d_count, d_n, timed):
+        ctx = self.ctx
+        ptr = lambda a: None if a is None else a.ptr                                           # noqa: E731
+        args = (ctx.handle, self.n_images, self.n_tracks, self.d_track_offsets.ptr, self.n_obs, self.d_obs_image.ptr, ptr(self.d_track_mask),
+                int(num_matched), self.d_count.ptr, ptr(d_index), ptr(d_count), ptr(d_n))
+        self.kernel_ms = _launch(ctx, "pxr_covisibility", args, ("check", "count", "topk"), timed) or self.kernel_ms
+
+    def counts(self):
+        """The (n_images, n_images) int32 matrix, downloaded."""
+        return self.d_count.download()
+
+    def topk(self, num_matched, timed=False):
+        """Per image its min(num_matched, partners with a positive count) best partners by (count descending, index ascending).
+        Returns the device arrays (index (n_images, num_matched) int32, -1 where a row ends; count, the same shape, 0 there;
+        n (n_images,) int32).  The counts are computed again by the same call: they come out the same."""
+        ctx, K = self.ctx, int(num_matched)
+        if not 1 <= K <= _lib.MAX_COVIS_MATCHED:
+            raise ValueError("num_matched = %d outside [1, %d]" % (K, _lib.MAX_COVIS_MATCHED))
+        out = ctx.empty((self.n_images, K), np.int32), ctx.empty((self.n_images, K), np.int32), ctx.empty((self.n_images,), np.int32)
+        self._run(K, *out, timed)
+        return out
+
+    def clusters(self, ret_offsets, ret, timed=False):
+        """The covisibility clusters of every query's retrieved images (pxr_covisibility_clusters): query q owns
+        ret[ret_offsets[q]:ret_offsets[q + 1]], map image indices in retrieval rank order, at most _lib.MAX_LOC_ENTRIES of them.
+        Returns the device arrays (cluster (n_ret,) int32: the number of every entry's cluster, clusters numbered by (size
+        descending, first member ascending); n_clusters (n_queries,) int32).  timed keeps self.kernel_ms {"check", "clusters"}."""
+        ctx = self.ctx
+        offsets = _csr_offsets(ret_offsets, "ret_offsets", "n_queries")
+        ret = np.ascontiguousarray(np.asarray(ret).reshape(-1), dtype=np.int32)
+        n_q = len(offsets) - 1
+        d_off, d_ret = ctx.to_device(offsets, np.int64), ctx.to_device(ret, np.int32)
+        d_cluster, d_n = ctx.empty((len(ret),), np.int32), ctx.empty((n_q,), np.int32)
+        args = (ctx.handle, self.n_images, self.d_count.ptr, n_q, d_off.ptr, len(ret), d_ret.ptr, d_cluster.ptr, d_n.ptr)
+        self.kernel_ms = _launch(ctx, "pxr_covisibility_clusters", args, ("check", "clusters"), timed) or self.kernel_ms
+        return d_cluster, d_n
+
+
+class LocalizationPairs:
+    """The gather between matching and absolute pose for a batch of localization problems (pxr_localization_pairs).
+
+    match: the MatchProblem whose pairs are (query, database image) -- its pair list, pair offsets and image offsets are used
+    where they live on the device.  kp_xy (n_total, 2) float64: the keypoint of every descriptor row; kp_point (n_total,) int64:
+    the row of xyz that keypoint observes, negative = none; xyz (n_points, 3).  Each a host array or a DeviceArray (used in place).
+    """
+
+    def __init__(self, ctx, match, kp_xy, kp_point, xyz):
+        self.ctx, self.match = ctx, match
+        self.d_kp_xy = _on_device(ctx, kp_xy, np.float64, (match.n_total, 2))
+        self.d_kp_point = _on_device(ctx, kp_point, np.int64, (match.n_total,))
+        self.d_xyz = _on_device(ctx, xyz, np.float64, (-1, 3))
+        self.n_points = int(self.d_xyz.shape[0])
+        self.kernel_ms = None
+
+    def gather(self, matches0, problem_offsets, problem_pair, timed=False, out=None):
+        """matches0: the device array MatchProblem.run returned.  Problem p owns the entries problem_pair[problem_offsets[p]:
+        problem_offsets[p + 1]], indices into the match's pair list in visiting order, all of one query, at most
+        _lib.MAX_LOC_ENTRIES.  Returns a dict of device arrays: corr_offsets (n_problems + 1,) int64, corr_kp (capacity,) int32,
+        corr_point (capacity,) int64, corr_xy (capacity, 2), corr_xyz (capacity, 3) -- the first n_corr rows are written, per
+        problem by ascending query keypoint and, within a keypoint, by first appearance -- and n_corr (int).  corr_offsets, n_corr,
+        corr_xy and corr_xyz go into AbsolutePoseProblem.from_device as they are.  out: a dict of the five arrays to write into.
+        timed keeps the kernels' HIP-event times in self.kernel_ms {"count", "scan", "write"} (milliseconds)."""
+        ctx, m = self.ctx, self.match
+        offsets = _csr_offsets(problem_offsets, "problem_offsets", "n_problems")
+        entries = np.ascontiguousarray(np.asarray(problem_pair).reshape(-1), dtype=np.int32)
+        n_p = len(offsets) - 1
+        rows = np.diff(m.pair_offsets)
+        ok = (entries >= 0) & (entries < m.n_pairs)              # an index out of range is the library's to report
+        cap = max(int(rows[entries[ok]].sum()), 1)
+        out = dict(out) if out is not None else dict(
+            corr_offsets=ctx.empty((n_p + 1,), np.int64), corr_kp=ctx.empty((cap,), np.int32), corr_point=ctx.empty((cap,), np.int64),
+            corr_xy=ctx.empty((cap, 2), np.float64), corr_xyz=ctx.empty((cap, 3), np.float64))
+        d_off, d_ent = ctx.to_device(offsets, np.int64), ctx.to_device(entries, np.int32)
+        n_corr = C.c_int64()
+        args = (ctx.handle, n_p, d_off.ptr, len(entries), d_ent.ptr, m.n_pairs, m.d_pairs.ptr, m.d_pair_offsets.ptr,
+                int(m.pair_offsets[-1]), matches0.ptr, m.n_images, m.d_offsets.ptr, m.n_total, self.d_kp_xy.ptr, self.d_kp_point.ptr,
+                self.n_points, self.d_xyz.ptr, out["corr_offsets"].ptr, out["corr_kp"].ptr, out["corr_point"].ptr, out["corr_xy"].ptr,
+                out["corr_xyz"].ptr, C.byref(n_corr))
+        self.kernel_ms = _launch(ctx, "pxr_localization_pairs", args, ("count", "scan", "write"), timed) or self.kernel_ms
+        out["n_corr"] = int(n_corr.value)
+        return out
+
+
 # ---- SIFT ------------------------------------------------------------------------------------------------------------------------
 def sift_options(**options):
     """pxr_sift_options: the library's defaults (pxr_sift_default_options) with `options` over them.  peak_threshold < 0 (the
