@@ -5,6 +5,8 @@ places.  MapLocalizer.localize_queries matches all queries against their lists i
 device and estimates all poses in one launch -- once over each query's whole list, once per covisibility cluster of the list
 (pixsfm/localize.py with covisibility_clustering) -- next to the per-query loop over DescriptorMatcher.match_pairs,
 pairs_2d3d_from_matches and absolute_pose_estimation.  Prints pairs_from_covisibility's first pairs, the clusters and the pose errors.
+Then the pixel-perfect half on a scene with feature patches: QueryLocalizer.localize per query next to
+QueryLocalizer.localize_batch (keypoint adjustment, PnP and query bundle adjustment one launch each over all queries).
 
     python examples/localize_queries.py          # needs an MI355X and the built libpixsfm_hip.so
 """
@@ -64,6 +66,31 @@ def main():
         rot, centre = pose_error(r["qvec"], r["tvec"], scene["poses"][q])
         print("  %s: %d inliers of %d pairs, rotation %.4f deg, centre %.5f (%.1f ms)"
               % (q, r["num_inliers"], len(p2d), rot, centre, 1e3 * (time.perf_counter() - t0)))
+
+    batched_refinement()
+
+
+def batched_refinement():
+    """The pixel-perfect half on a scene that has feature patches (three held-out images of a synthetic map, a fifth of the 2D-3D
+    pairs wrong): QueryLocalizer.localize per query, and QueryLocalizer.localize_batch -- keypoint adjustment, PnP and the query
+    bundle adjustment one launch each over all queries."""
+    from copy import deepcopy
+
+    import test_query_ba_gpu as tq                                                 # the scene of the tests
+    from pixsfm_amd.api.keypoint_adjustment import default_context
+    s = tq.make_scene(default_context())
+    loc, qs = s["localizer"], s["queries"]
+    for name, run in (("localize() per query", lambda: [loc.localize(q["keypoints"].copy(), q["kp_idx"], q["p3d_id"], deepcopy(s["camera"]),
+                                                                      query_fmaps=[q["fmap"]]) for q in qs]),
+                      ("localize_batch()", lambda: loc.localize_batch([tq._as_dict(s, q) for q in qs]))):
+        run()                                                                      # the first call loads the kernels
+        t0 = time.perf_counter()
+        res = run()
+        print("\n%s: %.1f ms for %d queries" % (name, 1e3 * (time.perf_counter() - t0), len(qs)))
+        for q, r in zip(qs, res):
+            ang, centre = tq._pose_error(q, r)
+            print("  %d inliers of %d pairs (%d wrong ones among the pairs, %d among the inliers), rotation %.3e rad, centre %.3e"
+                  % (r["num_inliers"], len(q["kp_idx"]), int(q["wrong"].sum()), int(np.array(r["inliers"])[q["wrong"]].sum()), ang, centre))
 
 
 if __name__ == "__main__":

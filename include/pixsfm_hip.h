@@ -1189,6 +1189,53 @@ int pxr_localization_pairs_timed(pxr_ctx* ctx, int32_t n_problems, const int64_t
                                  const double* d_xyz, int64_t* d_corr_offsets, int32_t* d_corr_kp, int64_t* d_corr_point,
                                  double* d_corr_xy, double* d_corr_xyz, int64_t* h_n_corr, double* h_kernel_ms);
 
+/* ---- batched query bundle adjustment (QBA: localization/src/single_query_bundle_optimizer.h:91-222, query_bundle_optimizer.h:
+ * 114-151) -- the poses of a whole batch of queries refined in ONE launch, a workgroup per query, the trust-region loop inside
+ * the kernel.  Per query it is the problem pxr_ba_solve solves for one image whose points are all constant
+ * and whose intrinsics are constant: FeatureReferenceCostFunctor blocks, the pose on the quaternion manifold plus the
+ * translation, six tangent unknowns.  All arrays are device pointers unless named h_.
+ *   queries: n_queries, d_query_offsets [n_queries + 1] int64 into the residual-block arrays (a query may be empty)
+ *   per residual block, n_obs in total: d_obs_patch int64 (arena index), d_xyz [n_obs][3] (the block's constant point),
+ *     d_refs [n_obs][C] (its reference descriptor).  One row per (correspondence, reference descriptor): a correspondence with two
+ *     references is two rows with the same patch and point.
+ *   cameras: d_query_camera [n_queries] int32, n_cameras, d_cam_model [n_cameras], d_cam_params [n_cameras][PXR_KPAD]; constant
+ *   poses: d_qvec [n_queries][4] (w first; normalised by the call), d_tvec [n_queries][3], refined IN PLACE
+ * Cost per block: exactly pxr_ba_eval's -- the bicubic descriptor at WorldToPixel (use_float_simd as there), L2 normalisation
+ * with its chain rule when cfg->l2_normalize, minus the reference; cfg->check_bounds as there, i.e. without effect, because every
+ * block has a reference descriptor (see pxr_interp_cfg).
+ * Loop: [upstream Ceres 2.1] trust-region Levenberg-Marquardt as pxr_ba_solve states it (oracle/pxo_solve.c with one image and
+ * every point constant): Jacobi scaling from the initial linearisation when options->jacobi_scaling, the LM diagonal clamped to
+ * [min_lm_diagonal, max_lm_diagonal], the robustifier's corrector, a 6 x 6 Cholesky step, acceptance by min_relative_decrease,
+ * the radius update (initial_radius, min_radius, max_radius), max_consecutive_invalid_steps, the function / gradient / parameter
+ * tolerances and max_iterations.  A trial pose whose cost is not finite is a rejected step.  IGNORED fields of pxr_lm_options:
+ * use_inner_iterations, inner_iteration_tolerance (no point moves), linear_solver, max_linear_solver_iterations, eta,
+ * linear_r_tolerance (the system is 6 x 6).  Iteration callbacks are NOT called: the loop runs inside the kernel, as in
+ * pxr_ka_solve.
+ * h_summaries [n_queries] (host): iterations, num_successful, termination, num_camera_unknowns = 6, num_point_unknowns = 0,
+ * initial_cost, final_cost, final_radius, accumulation = 2 (ordered sums), total_ms = the HIP-event time of the solve kernel (the
+ * same value for every query); the other fields are 0.
+ *   an empty query keeps its pose: iterations = 0, PXR_TERM_CONVERGENCE, costs 0
+ *   a query whose initial cost is not finite keeps its pose: iterations = 0, PXR_TERM_FAILURE
+ * A query's outputs -- pose and summary except total_ms -- are a function of that query's own blocks, camera, pose and the options
+ * alone: the same bits alone, in any batch, at any position of it and on every run (fixed-order sums; the lanes a block runs on
+ * depend on nothing but its position in the query).
+ * Storage and channels: fp16 / fp32 / fp64 arenas with C = 128 or 64 (what pxr_ba_eval dispatches beyond the cost maps); anything
+ * else returns PXR_EUNSUPPORTED.
+ * PXR_EINVAL (every output untouched, the summaries included): a NULL argument, offsets not starting at 0, not monotone or not
+ * ending at n_obs, a camera index out of range (both checked on host copies), a patch index outside the arena (checked by a kernel
+ * whose flag is read back before the solve starts), an arena with an upsampling factor, n_obs >= 2^31.
+ * Synchronises the context's stream. */
+int pxr_query_ba_solve(pxr_ctx* ctx, pxr_arena* arena, int32_t n_queries, const int64_t* d_query_offsets, int64_t n_obs,
+                       const int64_t* d_obs_patch, const double* d_xyz, const double* d_refs, const int32_t* d_query_camera,
+                       int32_t n_cameras, const int32_t* d_cam_model, const double* d_cam_params, double* d_qvec, double* d_tvec,
+                       const pxr_interp_cfg* cfg, const pxr_loss* loss, const pxr_lm_options* options, pxr_lm_summary* h_summaries);
+/* The same, and the HIP-event time of the solve kernel in milliseconds: h_kernel_ms[1]. */
+int pxr_query_ba_solve_timed(pxr_ctx* ctx, pxr_arena* arena, int32_t n_queries, const int64_t* d_query_offsets, int64_t n_obs,
+                             const int64_t* d_obs_patch, const double* d_xyz, const double* d_refs, const int32_t* d_query_camera,
+                             int32_t n_cameras, const int32_t* d_cam_model, const double* d_cam_params, double* d_qvec, double* d_tvec,
+                             const pxr_interp_cfg* cfg, const pxr_loss* loss, const pxr_lm_options* options,
+                             pxr_lm_summary* h_summaries, double* h_kernel_ms);
+
 /* ---- BA reference extraction -----------------------------------------------------------
  * Replaces ReferenceExtractor::Run (bundle_adjustment/src/reference_extractor.h:125-318) +
  * RobustMeanIRLS (base/src/irls_optim.h:24-71) for N_NODES = 1: per point, descriptors of all

@@ -250,6 +250,9 @@ _SIGNATURES = {
     "pxr_localization_pairs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "pxr_query_ba_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(InterpCfg), C.POINTER(Loss),
+                                     C.POINTER(LMOptions), C.c_void_p]),
     "pxr_rotavg_default_options": (None, [C.POINTER(RotavgOptions)]),
     "pxr_rotation_averaging": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RotavgOptions),
                                          C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
@@ -310,7 +313,7 @@ for _name in ("pxr_triangulate_tracks", "pxr_absolute_pose", "pxr_two_view_geome
               "pxr_match_descriptors", "pxr_match_guided", "pxr_mapper_visibility", "pxr_sift_pyramid", "pxr_sift_detect", "pxr_sift_describe",
               "pxr_vocab_train", "pxr_vlad_aggregate", "pxr_retrieval_topk", "pxr_cloud_nearest", "pxr_cloud_voxel_fractions",
               "pxr_rotation_averaging", "pxr_global_positioning", "pxr_covisibility", "pxr_covisibility_clusters",
-              "pxr_localization_pairs"):
+              "pxr_localization_pairs", "pxr_query_ba_solve"):
     _SIGNATURES[_name + "_timed"] = (_SIGNATURES[_name][0], _SIGNATURES[_name][1] + [C.POINTER(C.c_double)])
 LINEAR_AUTO, LINEAR_DIRECT, LINEAR_ITERATIVE = 0, 1, 2
 GUIDE_EPIPOLAR, GUIDE_HOMOGRAPHY = 0, 1      # PXR_GUIDE_*: the kind of a pair's model in pxr_match_guided

@@ -362,10 +362,11 @@ class QueryBundleOptimizer:
         self.interpolation = ic if isinstance(ic, base.InterpolationConfig) else base.InterpolationConfig(ic)
         self.ctx = ctx
         self.last_summary = None
+        self.last_summaries = None
+        self.last_batch_path = None
 
-    def _problem(self, qvec, tvec, camera, points3D, fmap, references, inliers, patch_idxs):
-        """The QBA problem at (qvec, tvec, camera): (BAProblem, arena, camera mask, number of residual blocks), or None when no
-        residual is added -- one image, every point constant."""
+    @staticmethod
+    def _check(qvec, tvec, points3D, references, inliers, patch_idxs):
         n = len(points3D)
         if len(references) != n:
             raise ValueError("references.size() != points3D.size()")          # THROW_CHECK_EQ, :100 / :141 / :183
@@ -376,6 +377,11 @@ class QueryBundleOptimizer:
         for name, v, k in (("qvec", qvec, 4), ("tvec", tvec, 3)):
             if not isinstance(v, np.ndarray) or v.dtype != np.float64 or v.size != k:
                 raise ValueError("%s must be a float64 numpy array of %d values (refined in place)" % (name, k))
+
+    def _problem(self, qvec, tvec, camera, points3D, fmap, references, inliers, patch_idxs):
+        """The QBA problem at (qvec, tvec, camera): (BAProblem, arena, camera mask, number of residual blocks), or None when no
+        residual is added -- one image, every point constant."""
+        self._check(qvec, tvec, points3D, references, inliers, patch_idxs)
         rows, patches, xyz, refs = _qba_observations(points3D, fmap, references, inliers, patch_idxs)
         if not patches:
             return None
@@ -421,6 +427,87 @@ class QueryBundleOptimizer:
         self.last_summary = summary
         arena.close()
         return True
+
+    def batch_fallback_reason(self):
+        """Why run_batch would call run() per query whatever the patches are, or None: the batch kernel keeps the intrinsics
+        constant and calls nothing back (pxr_query_ba_solve)."""
+        o = self.options
+        if o['refine_focal_length'] or o['refine_principal_point'] or o['refine_extra_params']:
+            return "the batch kernel keeps the intrinsics constant (refine_focal_length / refine_principal_point / refine_extra_params)"
+        if list(o['solver'].get('callbacks') or []):
+            return "the batch kernel runs its loop on the device and calls no iteration callbacks"
+        return None
+
+    def run_batch(self, queries):
+        """Many queries in ONE launch (pxr_query_ba_solve: a workgroup per query, the trust-region loop inside the kernel):
+        `queries` is a list of (qvec, tvec, camera, points3D, fmap, references, inliers | None, patch_idxs | None) tuples with
+        run()'s meaning and checks.  Every qvec / tvec is refined in place; returns the list of run()'s booleans, the per-query
+        summaries in self.last_summaries (None for a query without residuals).  All queries share one arena upload.
+        With a refine_* option, with iteration callbacks, or with patches the batch kernel does not take (anything but fp16 /
+        fp32 / fp64 patches of 128 or 64 channels and one shape) it calls run() per query -- unchanged results;
+        self.last_batch_path says which path ran ("batch" or "per_query") and self.last_batch_reason why."""
+        from ..engine import QueryBAProblem, query_ba_supported
+        qs = []
+        for q in queries:
+            q = tuple(q)
+            if not 6 <= len(q) <= 8:
+                raise ValueError("a query is (qvec, tvec, camera, points3D, fmap, references[, inliers[, patch_idxs]])")
+            q = q + (None,) * (8 - len(q))
+            self._check(q[0], q[1], q[3], q[5], q[6], q[7])
+            qs.append(q)
+        reason = self.batch_fallback_reason()
+        blocks, arena = [], None
+        if reason is None:
+            blocks = [_qba_observations(q[3], q[4], q[5], q[6], q[7]) for q in qs]
+            patches = [p for b in blocks for p in b[1]]
+            if patches:
+                ctx = self.ctx or default_context()
+                try:
+                    arena = features.to_arena(ctx, patches)
+                except ValueError as e:                     # patches of several shapes: no one arena
+                    reason = str(e)
+                if arena is not None and not query_ba_supported(arena):
+                    reason = "no batch kernel for %s patches of %d channels" % (np.dtype(arena.dtype).name, int(arena.C))
+                    arena.close()
+        self.last_batch_reason = reason
+        if reason is not None:
+            self.last_batch_path = "per_query"
+            ok, summaries = [], []
+            for q in qs:
+                ok.append(self.run(q[0], q[1], q[2], q[3], q[4], q[5], inliers=q[6], patch_idxs=q[7]))
+                summaries.append(self.last_summary if ok[-1] else None)
+            self.last_summaries = summaries
+            return ok
+        self.last_batch_path = "batch"
+        ok = [len(b[1]) > 0 for b in blocks]
+        self.last_summaries = [None] * len(qs)
+        live = [i for i, has in enumerate(ok) if has]
+        if not live:
+            return ok
+        o, s = self.options, self.options['solver']
+        off = np.concatenate([[0], np.cumsum([len(blocks[i][1]) for i in live])]).astype(np.int64)
+        params = np.zeros((len(live), 12))
+        for slot, i in enumerate(live):
+            params[slot, :len(qs[i][2].params)] = qs[i][2].params
+        prob = dict(query_offsets=off, obs_patch=arena.index,
+                    xyz=np.array([x for i in live for x in blocks[i][2]]), refs=np.array([r for i in live for r in blocks[i][3]]),
+                    qvec=np.array([qs[i][0].reshape(4) for i in live]), tvec=np.array([qs[i][1].reshape(3) for i in live]),
+                    query_camera=np.arange(len(live), dtype=np.int32),
+                    cam_model=np.array([qs[i][2].model_id for i in live], np.int32), cam_params=params)
+        lm = lm_options(max_iterations=s['max_num_iterations'], function_tolerance=s['function_tolerance'],
+                        gradient_tolerance=s['gradient_tolerance'], parameter_tolerance=s['parameter_tolerance'],
+                        max_consecutive_invalid_steps=s['max_num_consecutive_invalid_steps'], use_inner_iterations=False)
+        try:
+            qba = QueryBAProblem(ctx, arena, prob)
+            per = qba.solve(self.interpolation.to_engine(), make_loss(o['loss']['name'], o['loss']['params']), options=lm)
+            q_out, t_out = qba.poses()
+        finally:
+            arena.close()
+        for slot, i in enumerate(live):
+            qs[i][0].reshape(4)[:] = q_out[slot]
+            qs[i][1].reshape(3)[:] = t_out[slot]
+            self.last_summaries[i] = per[slot]
+        return ok
 
     def covariance(self, qvec, tvec, camera, points3D, fmap, references, inliers=None, patch_idxs=None):
         """The 6 x 6 covariance of the query pose at (qvec, tvec) -- rotation in radians about the camera axes, then the
@@ -473,6 +560,29 @@ class QueryBundleAdjuster:
         for level in resolve_level_indices(self.conf['level_indices'], len(fmaps)):
             self.refine(qvec, tvec, camera, points3D, fmaps[level], references[level], inliers=inliers,
                         point2D_idxs=point2D_idxs)
+
+    def refine_batch(self, queries):
+        """refine() for many queries in one launch: `queries` = [(qvec, tvec, camera, points3D, fmap, references, inliers | None,
+        point2D_idxs | None), ...]; every qvec / tvec is refined in place.  Returns refine()'s booleans
+        (QueryBundleOptimizer.run_batch, which also says when it runs the queries one by one instead)."""
+        return self.solver.run_batch(queries)
+
+    def refine_multilevel_batch(self, queries):
+        """refine_multilevel() for many queries: as refine_batch, with the `fmaps` and `references` of every level in place of
+        fmap and references -- one launch per level over all queries.  Returns the booleans of the last level."""
+        queries = [tuple(q) + (None,) * (8 - len(q)) for q in queries]
+        if not queries:
+            return []
+        n_levels = len(queries[0][4])
+        for q in queries:
+            if len(q) != 8:
+                raise ValueError("a query is (qvec, tvec, camera, points3D, fmaps, references[, inliers[, point2D_idxs]])")
+            if len(q[4]) != len(q[5]) or len(q[4]) != n_levels:
+                raise ValueError("every query needs fmaps and references of the same %d levels" % n_levels)
+        ok = [False] * len(queries)
+        for level in resolve_level_indices(self.conf['level_indices'], n_levels):
+            ok = self.refine_batch([(q[0], q[1], q[2], q[3], q[4][level], q[5][level], q[6], q[7]) for q in queries])
+        return ok
 
     def covariance(self, qvec, tvec, camera, points3D, fmaps, references, inliers=None, point2D_idxs=None):
         """QueryBundleOptimizer.covariance on the LAST level refine_multilevel refines (the finest by default)."""
@@ -760,17 +870,7 @@ class QueryLocalizer:
             return pose_dict
 
         # For QBA we optionally select unique 2D-3D correspondences
-        inliers = pose_dict["inliers"]
-        if conf["unique_inliers"]:                  # None and False: keep all
-            if conf["unique_inliers"] == "random":
-                inliers = find_unique_inliers(pnp_points3D_id, pre_inliers=inliers)
-            elif conf["unique_inliers"] == "min_error":
-                inliers = find_unique_min_reproj_inliers(pnp_points3D_id, pose_dict["qvec"], pose_dict["tvec"], query_camera,
-                                                         pnp_points2D, self.reconstruction, pre_inliers=inliers,
-                                                         point2D_idxs=pnp_point2D_idxs)
-            else:
-                import warnings
-                warnings.warn("Unknown unique_inlier method %s." % (conf["unique_inliers"],))
+        inliers = self._unique_inliers(pose_dict, pnp_points3D_id, query_camera, pnp_points2D, pnp_point2D_idxs)
         self.last_qba_inliers = list(inliers)
 
         # Run QBA
@@ -792,6 +892,117 @@ class QueryLocalizer:
         pose_dict["inliers"] = [bool(err < max_error) for err in errors]
         pose_dict["num_inliers"] = sum(pose_dict["inliers"])
         return pose_dict
+
+    def _unique_inliers(self, pose_dict, pnp_points3D_id, query_camera, pnp_points2D, pnp_point2D_idxs):
+        """The correspondences the QBA takes: PnP's inliers, made unique as conf["unique_inliers"] says (main.py:462-478)."""
+        conf = self.conf
+        inliers = pose_dict["inliers"]
+        if conf["unique_inliers"]:                  # None and False: keep all
+            if conf["unique_inliers"] == "random":
+                inliers = find_unique_inliers(pnp_points3D_id, pre_inliers=inliers)
+            elif conf["unique_inliers"] == "min_error":
+                inliers = find_unique_min_reproj_inliers(pnp_points3D_id, pose_dict["qvec"], pose_dict["tvec"], query_camera,
+                                                         pnp_points2D, self.reconstruction, pre_inliers=inliers,
+                                                         point2D_idxs=pnp_point2D_idxs)
+            else:
+                import warnings
+                warnings.warn("Unknown unique_inlier method %s." % (conf["unique_inliers"],))
+        return inliers
+
+    _BATCH_KEYS = ("keypoints", "pnp_point2D_idxs", "pnp_points3D_id", "query_camera", "image_path", "query_fmaps", "return_covariance")
+
+    def localize_batch(self, queries):
+        """localize() for many queries: `queries` is a list of dicts or tuples of localize()'s arguments (keypoints,
+        pnp_point2D_idxs, pnp_points3D_id, query_camera, image_path=None, query_fmaps=None).  Per level the references of every
+        query as in localize(), then ONE keypoint-adjustment launch over all queries per level, ONE absolute-pose launch, the
+        unique inliers per query on the host, ONE bundle-adjustment launch per level over the queries PnP localized, and the final
+        inlier recount.  Returns the list of localize()'s dicts: {"success": False} for a query without pairs, PnP's dict for one
+        it could not localize.  Stacked correspondences and return_covariance are localize()'s: ValueError here."""
+        conf = self.conf
+        if conf["QKA"]["apply"] and conf["QKA"]["stack_correspondences"]:
+            raise ValueError("localize_batch does not stack correspondences (QKA.stack_correspondences); call localize() per query")
+        require_feats = conf["QKA"]["apply"] or conf["QBA"]["apply"]
+        items = []
+        for q in queries:
+            if isinstance(q, dict):
+                unknown = set(q) - set(self._BATCH_KEYS)
+                if unknown:
+                    raise ValueError("unknown argument(s) %s of a query" % sorted(unknown))
+                a = dict(q)
+            else:
+                q = tuple(q)
+                if not 4 <= len(q) <= len(self._BATCH_KEYS):
+                    raise ValueError("a query is (keypoints, pnp_point2D_idxs, pnp_points3D_id, query_camera[, image_path[, query_fmaps]])")
+                a = dict(zip(self._BATCH_KEYS, q))
+            for k in ("keypoints", "pnp_point2D_idxs", "pnp_points3D_id", "query_camera"):
+                if k not in a:
+                    raise ValueError("a query needs %r" % (k,))
+            if a.get("return_covariance"):
+                raise ValueError("localize_batch does not return covariances (no batched covariance); call localize(..., "
+                                 "return_covariance=True) per query")
+            if len(a["pnp_point2D_idxs"]) != len(a["pnp_points3D_id"]):
+                raise ValueError("pnp_point2D_idxs and pnp_points3D_id must have the same length")
+            if require_feats and a.get("image_path") is None and a.get("query_fmaps") is None and len(a["pnp_point2D_idxs"]):
+                raise ValueError("a query needs image_path or query_fmaps: QKA / QBA work on its features")
+            items.append(a)
+
+        out = [{"success": False} for _ in items]
+        live = []
+        for i, a in enumerate(items):
+            if len(a["pnp_point2D_idxs"]) == 0:
+                continue
+            idxs = [int(k) for k in a["pnp_point2D_idxs"]]
+            ids = list(a["pnp_points3D_id"])
+            keypoints = np.array(a["keypoints"], dtype=np.float64)
+            fmaps = a.get("query_fmaps")
+            if fmaps is None and require_feats:                    # Extract Features
+                if self.extractor is None:
+                    from .extract import FeatureExtractor
+                    self.extractor = FeatureExtractor(conf["dense_features"], ctx=self.ctx)
+                required_kp_ids = list(OrderedDict.fromkeys(idxs))
+                fmaps = self.extractor(a["image_path"], keypoints=keypoints[required_kp_ids], as_dict=False,
+                                       keypoint_ids=required_kp_ids, overwrite_sparse=conf["overwrite_features_sparse"])
+            p2D = keypoints[idxs]
+            refs = None
+            if require_feats:                                      # Get references for this query
+                refs = self.get_query_references(ids, fmaps, p2D, idxs)
+                assert len(fmaps) == len(refs)
+            live.append(dict(i=i, idxs=idxs, ids=ids, p2D=p2D, p3D=[self.reconstruction.points3D[p].xyz for p in ids],
+                             camera=a["query_camera"], fmaps=fmaps, refs=refs))
+        if not live:
+            return out
+
+        if conf["QKA"]["apply"]:                                   # Run QKA: one launch per level
+            n_levels = len(live[0]["fmaps"])
+            if any(len(w["fmaps"]) != n_levels for w in live):
+                raise ValueError("every query needs query_fmaps of the same %d levels" % n_levels)
+            for level in resolve_level_indices(conf["QKA"]["level_indices"], n_levels):
+                self.query_keypoint_adjuster.refine_batch([(w["p2D"], w["fmaps"][level], w["refs"][level], w["idxs"]) for w in live])
+
+        poses = absolute_pose_estimation_batch([(w["p2D"], w["p3D"], w["camera"]) for w in live],       # Run PnP: one launch
+                                               estimation_options=conf["PnP"]["estimation"],
+                                               refinement_options=conf["PnP"]["refinement"], ctx=self.ctx)
+        located = []
+        for w, pose_dict in zip(live, poses):
+            out[w["i"]] = pose_dict
+            if pose_dict["success"]:
+                w["pose"] = pose_dict
+                w["inliers"] = self._unique_inliers(pose_dict, w["ids"], w["camera"], w["p2D"], w["idxs"])
+                located.append(w)
+        self.last_qba_inliers_batch = {w["i"]: list(w["inliers"]) for w in located}
+
+        if conf["QBA"]["apply"] and located:                       # Run QBA: one launch per level
+            self.query_bundle_adjuster.refine_multilevel_batch(
+                [(w["pose"]["qvec"], w["pose"]["tvec"], w["camera"], w["p3D"], w["fmaps"], w["refs"], w["inliers"], w["idxs"])
+                 for w in located])
+
+        max_error = conf["PnP"]["estimation"]["ransac"]["max_error"]
+        for w in located:                                          # We recompute the inliers from the final pose
+            pose_dict = w["pose"]
+            errors = compute_reprojection_errors(w["p2D"], w["p3D"], pose_dict["qvec"], pose_dict["tvec"], w["camera"])
+            pose_dict["inliers"] = [bool(err < max_error) for err in errors]
+            pose_dict["num_inliers"] = sum(pose_dict["inliers"])
+        return out
 
     def get_nearest_references(self, pnp_points3D_id, query_fmaps, pnp_points2D, patch_idxs):
         return [find_nearest_references(query_fmaps[level], refs, pnp_points2D, pnp_points3D_id, self.conf["interpolation"],

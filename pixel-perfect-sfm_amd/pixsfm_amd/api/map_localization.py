@@ -183,17 +183,25 @@ def collect_results(query_names, plan, problems, out, map_poses, point_ids):
     return results
 
 
-def refine_results(results, refine, query_cameras, keypoints, query_fmaps=None):
+def refine_results(results, refine, query_cameras, keypoints, query_fmaps=None, batch=False):
     """conf["refine"]: for every localized query, refine.localize(keypoints (n, 2), point2D_idxs, point3D_ids, camera,
     query_fmaps=query_fmaps[query] or None) on the winning problem's 2D-3D pairs -- QueryLocalizer.localize's arguments, unchanged.
     Where it succeeds, its qvec, tvec, num_inliers and inliers replace the batch's; point2D_idxs / point3D_ids stay, so `inliers`
     must be a mask over the pairs it was given, in their order, which is what QueryLocalizer.localize returns.  Where it fails the
-    batch's pose stays.  In place."""
-    for q, res in results.items():
-        if not res["success"]:
-            continue
-        fine = refine.localize(np.asarray(keypoints[q], dtype=np.float64)[:, :2], list(res["point2D_idxs"]), list(res["point3D_ids"]),
-                               query_cameras[q], query_fmaps=None if query_fmaps is None else query_fmaps[q])
+    batch's pose stays.  In place.
+    batch (conf["refine_batch"]) with a `refine` that has localize_batch: ONE refine.localize_batch call over the localized queries,
+    with the same arguments per query, instead of the loop."""
+    todo = [q for q, res in results.items() if res["success"]]
+    args = [(np.asarray(keypoints[q], dtype=np.float64)[:, :2], list(results[q]["point2D_idxs"]), list(results[q]["point3D_ids"]),
+             query_cameras[q]) for q in todo]
+    fmaps = [None if query_fmaps is None else query_fmaps[q] for q in todo]
+    if batch and hasattr(refine, "localize_batch"):
+        fines = refine.localize_batch([dict(keypoints=a[0], pnp_point2D_idxs=a[1], pnp_points3D_id=a[2], query_camera=a[3], query_fmaps=f)
+                                       for a, f in zip(args, fmaps)]) if todo else []
+    else:
+        fines = (refine.localize(*a, query_fmaps=f) for a, f in zip(args, fmaps))
+    for q, fine in zip(todo, fines):
+        res = results[q]
         if fine.get("success"):
             if len(fine["inliers"]) != len(res["point2D_idxs"]):
                 raise ValueError("refine.localize returned %d inlier flags for the %d pairs of %r" % (len(fine["inliers"]), len(res["point2D_idxs"]), q))
@@ -210,13 +218,16 @@ class MapLocalizer:
     conf: "matcher": a DescriptorMatcher conf (name or dict); "pnp": the options absolute_pose_estimation takes
     ("estimation_options", "refinement_options"; max_error 12 px as in the reference); "covisibility_clustering": localize per
     covisibility cluster of the retrieved images and keep the best (False, as in the reference); "refine": None, or a
-    QueryLocalizer that is called per query, unchanged, on the winning cluster's 2D-3D pairs (QKA / QBA)."""
+    QueryLocalizer that is called per query, unchanged, on the winning cluster's 2D-3D pairs (QKA / QBA); "refine_batch": False,
+    or True to refine all localized queries in one refine.localize_batch call (batched QKA, PnP and QBA launches) when `refine` has
+    that method."""
 
     default_conf = {
         "matcher": "NN-mutual",
         "pnp": {"estimation_options": {"ransac": {"max_error": 12}}, "refinement_options": {}},
         "covisibility_clustering": False,
         "refine": None,
+        "refine_batch": False,
     }
 
     def __init__(self, reconstruction, conf=None, ctx=None):
@@ -311,5 +322,5 @@ class MapLocalizer:
                    corr_kp=corr["corr_kp"].download()[:n_corr], corr_point=corr["corr_point"].download()[:n_corr])
         results = collect_results(query_names, plan, problems, out, self.map_poses, self.map["point_ids"])
         if self.conf["refine"] is not None:
-            refine_results(results, self.conf["refine"], query_cameras, keypoints, query_fmaps)
+            refine_results(results, self.conf["refine"], query_cameras, keypoints, query_fmaps, batch=bool(self.conf["refine_batch"]))
         return results

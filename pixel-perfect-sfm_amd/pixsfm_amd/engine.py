@@ -1094,6 +1094,68 @@ class AbsolutePoseProblem:
         return d_q, d_t, d_status, d_ninl, d_ntr, d_inl, d_err
 
 
+def query_ba_supported(arena):
+    """Whether pxr_query_ba_solve has a kernel for the arena's patches (fp16 / fp32 / fp64 with 128 or 64 channels)."""
+    return np.dtype(arena.dtype) in _NP2DT and int(arena.C) in (128, 64)
+
+
+class QueryBAProblem:
+    """Device-resident flat arrays of a batch of query bundle adjustments (pxr_query_ba_solve): the residual blocks of every
+    query in CSR form, one camera and one pose per query, every point constant.
+
+    problem: dict with query_offsets (n_queries + 1), obs_patch (n_obs, arena indices), xyz (n_obs x 3), refs (n_obs x C),
+    qvec (n_queries x 4), tvec (n_queries x 3), query_camera (n_queries), cam_model, cam_params (n_cams x <= KPAD).
+    """
+
+    def __init__(self, ctx, arena, problem):
+        self.ctx, self.arena = ctx, arena
+        g = problem
+        offsets = _csr_offsets(g["query_offsets"], "query_offsets", "n_queries")
+        self.n_queries = len(offsets) - 1
+        obs_patch = np.ascontiguousarray(g["obs_patch"], dtype=np.int64).reshape(-1)
+        self.n_obs = len(obs_patch)
+        xyz = np.ascontiguousarray(g["xyz"], dtype=np.float64).reshape(-1, 3)
+        refs = np.ascontiguousarray(g["refs"], dtype=np.float64)
+        if len(xyz) != self.n_obs or refs.size % max(self.n_obs, 1) or (self.n_obs == 0 and refs.size):
+            raise ValueError("obs_patch, xyz and refs must hold one row per residual block")
+        refs = refs.reshape(self.n_obs, refs.size // max(self.n_obs, 1))
+        if self.n_obs and refs.shape[1] != int(arena.C):
+            raise ValueError("refs must hold %d channels per residual block" % int(arena.C))
+        self.n_cameras = len(g["cam_model"])
+        qvec = np.ascontiguousarray(g["qvec"], dtype=np.float64).reshape(-1, 4)
+        tvec = np.ascontiguousarray(g["tvec"], dtype=np.float64).reshape(-1, 3)
+        if not len(qvec) == len(tvec) == len(np.asarray(g["query_camera"]).reshape(-1)) == self.n_queries:
+            raise ValueError("qvec, tvec and query_camera must hold one row per query")
+        self.d = {
+            "query_offsets": ctx.to_device(offsets, np.int64),
+            "obs_patch": ctx.to_device(obs_patch, np.int64),
+            "xyz": ctx.to_device(xyz, np.float64),
+            "refs": ctx.to_device(refs, np.float64),
+            "qvec": ctx.to_device(qvec, np.float64),
+            "tvec": ctx.to_device(tvec, np.float64),
+            "query_camera": ctx.to_device(np.asarray(g["query_camera"]).reshape(-1), np.int32),
+            "cam_model": ctx.to_device(g["cam_model"], np.int32),
+            "cam_params": ctx.to_device(_padded_cam_params(g["cam_params"], self.n_cameras), np.float64),
+        }
+        self.kernel_ms = None
+
+    def solve(self, cfg, loss, options=None, timed=False):
+        """Refine every pose in place on the device (pxr_query_ba_solve); returns the per-query summaries as dicts.  timed: also
+        keep the solve kernel's HIP-event time in self.kernel_ms {"solve"} (milliseconds)."""
+        ctx, d = self.ctx, self.d
+        opts = options or lm_options()
+        summaries = (_lib.LMSummary * max(self.n_queries, 1))()
+        args = (ctx.handle, self.arena.handle, self.n_queries, d["query_offsets"].ptr, self.n_obs, d["obs_patch"].ptr, d["xyz"].ptr,
+                d["refs"].ptr, d["query_camera"].ptr, self.n_cameras, d["cam_model"].ptr, d["cam_params"].ptr, d["qvec"].ptr,
+                d["tvec"].ptr, C.byref(cfg), C.byref(loss), C.byref(opts), summaries)
+        self.kernel_ms = _launch(ctx, "pxr_query_ba_solve", args, ("solve",), timed) or self.kernel_ms
+        return [summaries[i].as_dict() for i in range(self.n_queries)]
+
+    def poses(self):
+        """(qvec (n_queries, 4), tvec (n_queries, 3)) as they stand on the device."""
+        return self.d["qvec"].download(), self.d["tvec"].download()
+
+
 def two_view_options(max_error=4.0, min_inlier_ratio=0.25, min_num_inliers=15, confidence=0.999, min_num_trials=64,
                      max_num_trials=10000, round_size=64, seed=0, refine_max_iterations=100, lo_rounds=4):
     """pxr_pair_options, the one struct the header also names pxr_two_view_options, pxr_homography_options and
